@@ -17,7 +17,18 @@ barrier and the max-over-ranks reduction.
           the GPU and never imports torch -- spawns N fresh child processes with those variables set, relays rank 0's JSON
           line and exits non-zero if any child does.  `n_gpus` is the number of ranks that ran.
 
-Besides the contract's fields the JSON line carries
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: it generates and uploads the
+stream, ramps the clocks, runs W untimed and K timed steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = milliseconds of one timed step, the figures derived from them, and null for the blocks below).
+`--full` adds the blocks below; the `--no-*` options leave single blocks out of a `--full` run.
+
+`--dump-outputs DIR` (rank 0) writes, after the timed steps, what the last step left in HBM for a fixed, seeded sample of
+rows (the first and last record batches and 14 others, 4096 rows of each): per column `DIR/<column>.npy`, rows x words,
+the DuckDB vector bytes of each row as little-endian uint32 words in float64 (exact; strings are string_t with
+stream-offset pointers, so equal inputs give equal words), `DIR/<column>_valid.npy` (float32, 1 = valid) and
+`DIR/row_index.npy` (float64, row of the shard).  The input depends only on the arguments, so two builds compare file for file.
+
+With `--full` the JSON line also carries
   roofline           HBM roofline of the dominant kernel, from HIP-event timings taken live (mi_hbm_launch_timed)
   kernels            the same for every kernel class
   reference_shaped   secondary, never `value`: the same scan laid out the way the reference's vectors are (plain
@@ -46,6 +57,53 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec; ~6.3 TB/s achievable copy)
 SHIP_LO, SHIP_HI = 8766, 9131   # config 3: 1994-01-01 <= l_shipdate < 1995-01-01
+DUMP_SEED = 20240917            # --dump-outputs: the row sample is the same for every build and every run
+DUMP_BATCHES, DUMP_ROWS = 16, 4096
+DUMP_BUDGET = 64 << 20          # bytes of .npy payload at most
+
+
+def dump_sample(batch_rows):
+    """The rows --dump-outputs writes: {record batch index: sorted row positions within it}.  The first and the last record
+    batch (a partial one, usually) and seeded others; DUMP_ROWS seeded rows of each."""
+    rng = np.random.default_rng(DUMP_SEED)
+    nb = len(batch_rows)
+    pick = {0, nb - 1} if nb else set()
+    rest = [b for b in range(nb) if b not in pick]
+    pick.update(int(b) for b in rng.choice(rest, size=min(len(rest), DUMP_BATCHES - len(pick)), replace=False))
+    return {b: np.sort(rng.choice(batch_rows[b], size=min(batch_rows[b], DUMP_ROWS), replace=False)) for b in sorted(pick)}
+
+
+def write_outputs(out_dir, batches, sample, batch_first_row):
+    """`batches` as HbmStream.fetch returns them (None where not fetched) -> the .npy files of --dump-outputs; returns the
+    bytes written.  Every column's vector is 4-byte aligned in width (lineitem: 4, 8 and 16), so the words are exact in float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols, valid, rows = {}, {}, []
+    for bi, pos in sample.items():
+        b = batches[bi]
+        rows.append(batch_first_row[bi] + pos)
+        for c in b["columns"]:
+            assert not c["children"] and c["width"] % 4 == 0, (c["name"], c["width"])
+            words = c["data"][: b["nrows"] * c["width"]].view(np.uint32).reshape(b["nrows"], c["width"] // 4)
+            bits = np.unpackbits(c["validity"].view(np.uint8), bitorder="little")[: b["nrows"]]
+            cols.setdefault(c["name"], []).append(words[pos].astype(np.float64))
+            valid.setdefault(c["name"], []).append(bits[pos].astype(np.float32))
+    out = {"row_index": np.concatenate(rows).astype(np.float64) if rows else np.zeros(0)}
+    for name in cols:
+        out[name] = np.concatenate(cols[name])
+        out[name + "_valid"] = np.concatenate(valid[name])
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BUDGET, "dump of %d bytes exceeds the %d-byte budget" % (total, DUMP_BUDGET)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
+def dump_outputs(hs, out_dir, first_row):
+    """--dump-outputs: the sampled rows of what the last launch of `hs` left in HBM, fetched (D2H) and written."""
+    batch_rows = [b["nrows"] for b in hs.layout]
+    sample = dump_sample(batch_rows)
+    batch_first_row = first_row + np.concatenate([[0], np.cumsum(batch_rows, dtype=np.int64)[:-1]]) if batch_rows else []
+    return write_outputs(out_dir, hs.fetch(batches=list(sample)), sample, batch_first_row)
 
 
 def kernel_table(cstats, per_class, pmc, same_workload):
@@ -156,7 +214,7 @@ def run_sf100_child(args, torch):
         pass
     if free_hbm < 210e9 or avail_host < 150e9:
         return {"skipped": "needs 210 GB of free HBM and 150 GB of host memory; free: %.0f GB HBM, %.0f GB host" % (free_hbm / 1e9, avail_host / 1e9)}
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--sf", "100", "--steps", "5", "--warmup", "2", "--no-operator-path",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--sf", "100", "--steps", "5", "--warmup", "2", "--full", "--no-operator-path",
            "--no-cpu-baseline", "--no-encode-leg", "--no-sf100", "--seed", str(args.seed)]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     try:
@@ -195,6 +253,10 @@ def main():
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--shm-dir", default="/dev/shm", help="where the operator-path legs put their files")
     ap.add_argument("--no-sf100", action="store_true", help="skip the SF100 block (N = 1; a child process after the SF10 legs)")
+    ap.add_argument("--full", action="store_true", help="also the secondary blocks: per-kernel rooflines, reference-shaped layout, "
+                                                        "parity vs the oracle, CPU baselines, encode leg, operator path, SF100")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a seeded sample of the last timed step's vectors "
+                                                                         "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -291,6 +353,8 @@ def main():
 
     # ---- timed region: exactly K steps of the fully materialised scan (`value`) ----
     elapsed = timed_steps(hs)
+    if args.dump_outputs and rank == 0:   # before anything else launches on hs: the vectors of the last timed step
+        dump_outputs(hs, args.dump_outputs, first_row)
 
     # ---- per-kernel HIP-event timings (same stream, same launches, outside the timed region) ----
     def per_class_ms(h):
@@ -300,19 +364,20 @@ def main():
             acc += np.array(h.plan.launch_timed(stream))
         return acc / reps
 
-    per_class = per_class_ms(hs)
-    traffic_src = os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")
-    pmc_doc = json.load(open(traffic_src)) if os.path.exists(traffic_src) else {}
-    pmc = pmc_doc.get("traffic_bytes_per_launch", {})
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from kernel_sha import kernel_source_sha
-    traffic_stale = bool(pmc) and pmc_doc.get("kernel_source_sha") != kernel_source_sha()
-    same_workload = args.sf == 10.0 and not args.rows and not args.no_validity
+    if args.full:
+        per_class = per_class_ms(hs)
+        traffic_src = os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")
+        pmc_doc = json.load(open(traffic_src)) if os.path.exists(traffic_src) else {}
+        pmc = pmc_doc.get("traffic_bytes_per_launch", {})
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from kernel_sha import kernel_source_sha
+        traffic_stale = bool(pmc) and pmc_doc.get("kernel_source_sha") != kernel_source_sha()
+        same_workload = args.sf == 10.0 and not args.rows and not args.no_validity
 
     # ---- secondary, never `value`: the reference-shaped layout over the same resident stream -- plain fixed-width columns
     # alias the Arrow buffer in HBM (DirectConversion) and all-valid columns carry no validity words (unset ValidityMask) ----
     ref_shaped = None
-    if world == 1:
+    if args.full and world == 1:
         zs = HbmStream(ctx, buf, zero_copy_direct=True, unset_all_valid=True, share_stream_of=hs)
         dz = timed_steps(zs)
         zst, zcs = zs.stats(), zs.plan.class_stats()
@@ -333,27 +398,28 @@ def main():
 
     # ---- parity of the measured run: sampled batches of EVERY rank's shard vs the oracle ----
     parity = cpu_baseline = cpu_baseline_encode = None
-    from oracle import pyoracle as po
-    msgs = [m for m in po.walk_stream(buf) if m["type"] == po.MSG_RECORD_BATCH]
-    sample = sorted(set([0, len(msgs) // 2, len(msgs) - 1]))
-    got = hs.fetch(batches=sample)
-    ok = True
-    for bi in sample:
-        m = msgs[bi]
-        sub = np.concatenate([buf[: msgs[0]["prefix_off"]], buf[m["prefix_off"]: m["body_off"] + m["body_len"]]])
-        shift = m["prefix_off"] - msgs[0]["prefix_off"]
-        _, want = po.decode_stream(sub, ptr_base_of=lambda i, body_off, boff: body_off + boff + shift)
-        for gc, wc in zip(got[bi]["columns"], want[0]["columns"]):
-            ok = ok and np.array_equal(gc["data"], wc["data"]) and np.array_equal(gc["validity"], wc["validity"])
-    del got
-    ranks_ok = 1 if ok else 0
-    if world > 1:
-        t = torch.tensor([ranks_ok], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t)
-        ranks_ok = int(t.item())
-    parity = {"checked_batches": sample, "bit_exact": bool(ranks_ok == world), "ranks_bit_exact": ranks_ok, "ranks": world}
+    if args.full:
+        from oracle import pyoracle as po
+        msgs = [m for m in po.walk_stream(buf) if m["type"] == po.MSG_RECORD_BATCH]
+        sample = sorted(set([0, len(msgs) // 2, len(msgs) - 1]))
+        got = hs.fetch(batches=sample)
+        ok = True
+        for bi in sample:
+            m = msgs[bi]
+            sub = np.concatenate([buf[: msgs[0]["prefix_off"]], buf[m["prefix_off"]: m["body_off"] + m["body_len"]]])
+            shift = m["prefix_off"] - msgs[0]["prefix_off"]
+            _, want = po.decode_stream(sub, ptr_base_of=lambda i, body_off, boff: body_off + boff + shift)
+            for gc, wc in zip(got[bi]["columns"], want[0]["columns"]):
+                ok = ok and np.array_equal(gc["data"], wc["data"]) and np.array_equal(gc["validity"], wc["validity"])
+        del got
+        ranks_ok = 1 if ok else 0
+        if world > 1:
+            t = torch.tensor([ranks_ok], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
+            dist.all_reduce(t)
+            ranks_ok = int(t.item())
+        parity = {"checked_batches": sample, "bit_exact": bool(ranks_ok == world), "ranks_bit_exact": ranks_ok, "ranks": world}
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # bounded sample: time 2 batches, then as many as fit the budget
             rc, st = po.scan_stream(buf, max_batches=2)
             t1 = time.perf_counter()
@@ -388,7 +454,7 @@ def main():
     # ---- secondary, never `value`: BASELINE config 4 at kernel level -- the K7 encode kernels over the vectors this run has
     # just decoded (DuckDB vectors resident in HBM -> Arrow buffers), one plan for the table, HIP events per kernel class ----
     encode_kernels = None
-    if rank == 0 and world == 1 and not args.no_encode_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_encode_leg:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
         from encode_bench import encode_leg
         from duckdb_arrow_amd import _ffi
@@ -404,7 +470,7 @@ def main():
 
     # ---- secondary, never `value`: the scan OPERATOR over files (BASELINE config 3) ----
     operator_path = None
-    if not args.no_operator_path:
+    if args.full and not args.no_operator_path:
         # one directory per run, the same name on every rank: the self-launcher's run id, else the launcher's rendezvous port
         run_id = os.environ.get("MI_BENCH_RUN_ID") or ("port%s" % os.environ.get("MASTER_PORT", "0") if world > 1 else str(os.getpid()))
         d = os.path.join(args.shm_dir, "mi_bench_%s" % run_id)
@@ -543,14 +609,14 @@ def main():
                     os.rmdir(d)
 
     sf100 = None
-    if rank == 0 and world == 1 and args.sf == 10.0 and not args.rows and not args.no_sf100:
+    if args.full and rank == 0 and world == 1 and args.sf == 10.0 and not args.rows and not args.no_sf100:
         sf100 = run_sf100_child(args, torch)
     if rank == 0:
         total_rows = info["n_rows"] * world
         ms_per_step = elapsed / args.steps * 1e3
         rows_per_s = total_rows * args.steps / elapsed
         alg_bytes = stats["bytes_read"] + stats["bytes_written"]
-        kernels = kernel_table(cstats, per_class, pmc, same_workload)
+        kernels = kernel_table(cstats, per_class, pmc, same_workload) if args.full else None
         out = {
             "metric": "rows/sec + achieved HBM GB/s, TPC-H lineitem.arrows scan at 1/2/4/8 GPUs",
             "value": rows_per_s,
@@ -572,7 +638,8 @@ def main():
                        "sharding": "row groups, no collective"},
             "achieved_hbm_GBps_whole_step": alg_bytes * world / (elapsed / args.steps) / 1e9,
             "algorithmic_bytes_per_row": {"read": stats["bytes_read"] / info["n_rows"], "written": stats["bytes_written"] / info["n_rows"]},
-            "roofline": roofline_of(kernels, alg_bytes, ms_per_step, traffic_stale),
+            "full": args.full,
+            "roofline": roofline_of(kernels, alg_bytes, ms_per_step, traffic_stale) if args.full else None,
             "north_star_read_roofline": read_roofline(rows_per_s / world, stats["bytes_read"] / info["n_rows"], stats["bytes_written"] / info["n_rows"]),
             "kernels": kernels,
             "cpu_baseline": cpu_baseline,

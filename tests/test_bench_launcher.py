@@ -31,7 +31,7 @@ def test_a_failing_rank_fails_the_run():
 def test_self_launcher_runs_two_ranks_on_one_device():
     """Two ranks rehearsed on ONE device over gloo: both shards bit-exact against the oracle, the operator-path table scanned
     exactly once between them (record batch k -> rank k mod 2), n_gpus = the ranks that ran."""
-    run = _bench("--gpus", "2", "--single-device", "--backend", "gloo", "--rows", "300000", "--steps", "2", "--no-cpu-baseline")
+    run = _bench("--gpus", "2", "--single-device", "--backend", "gloo", "--rows", "300000", "--steps", "2", "--full", "--no-cpu-baseline")
     assert run.returncode == 0, run.stderr[-2000:]
     z = json.loads([ln for ln in run.stdout.split("\n") if ln.startswith("{")][-1])
     assert z["n_gpus"] == 2 and z["scaling"] == "weak"

@@ -34,9 +34,9 @@ Context::Context(int device_id) : device(device_id) {
   hipDeviceProp_t prop;
   MI_HIP_CHECK(hipGetDeviceProperties(&prop, device));
   num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  MI_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  MI_HIP_CHECK(hipStreamCreateWithFlags(&h2d_stream, hipStreamNonBlocking));
-  MI_HIP_CHECK(hipStreamCreateWithFlags(&d2h_stream, hipStreamNonBlocking));
+  stream = HipStream::Create();
+  h2d_stream = HipStream::Create();
+  d2h_stream = HipStream::Create();
   // the device's place in the host (best effort: any failure leaves numa_node = -1 and nothing is bound)
   const char* nb = std::getenv("MI_NUMA_BIND");
   char bus[64] = {0};
@@ -84,12 +84,6 @@ Context::PreferNode::PreferNode(const Context* c) {
 }
 Context::PreferNode::~PreferNode() {
   if (on) (void)syscall(SYS_set_mempolicy, saved_mode, saved_mode == 0 ? nullptr : saved_mask, saved_mode == 0 ? 0 : sizeof(saved_mask) * 8);
-}
-
-Context::~Context() {
-  if (stream) (void)hipStreamDestroy(stream);
-  if (h2d_stream) (void)hipStreamDestroy(h2d_stream);
-  if (d2h_stream) (void)hipStreamDestroy(d2h_stream);
 }
 
 void Context::Bind() const { MI_HIP_CHECK(hipSetDevice(device)); }
@@ -271,19 +265,14 @@ Plan::Plan(Context* ctx_p, const mi_col_task* in_tasks, int32_t n_tasks) : ctx(c
 
 Plan::Plan(Context* ctx_p) : ctx(ctx_p), reusable(true) {
   ctx->Bind();
-  MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_status), 64));
-  SyncMemset(d_status, 0, 64);
+  d_status = DeviceBuffer(64);
+  SyncMemset(d_status.get(), 0, 64);
 }
 
+// A device table of `n` elements: the element count at least doubles (64 at least), the outgrown table is freed at once.
 template <typename T>
-static void EnsureDevice(T** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return;
-  if (*p) MI_HIP_CHECK(hipFree(*p));
-  *p = nullptr;
-  size_t n = std::max<size_t>(need, *cap * 2);
-  n = std::max<size_t>(n, 64);
-  MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  *cap = n;
+static void GrowTable(DeviceBuffer& table, size_t n) {
+  Grow(table, n * sizeof(T), std::max<size_t>({n, table.size() / sizeof(T) * 2, 64}) * sizeof(T));
 }
 
 void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_stream) {
@@ -362,84 +351,66 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
     }
   }
   // device tables
-  const size_t old_cap_tasks = cap_tasks, old_cap_tb = cap_tile_begin;
-  EnsureDevice(&d_tasks, &cap_tasks, tasks.size());
-  EnsureDevice(&d_tile_begin, &cap_tile_begin, tile_begin.size());
-  const size_t old_cap_tt = cap_tile_task;
-  EnsureDevice(&d_tile_task, &cap_tile_task, tile_task.size());
+  GrowTable<mi_col_task>(d_tasks, tasks.size());
+  GrowTable<uint32_t>(d_tile_begin, tile_begin.size());
+  GrowTable<uint32_t>(d_tile_task, tile_task.size());
   if (!d_status) {
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_status), 64));
-    SyncMemset(d_status, 0, 64);
+    d_status = DeviceBuffer(64);
+    SyncMemset(d_status.get(), 0, 64);
   }
-  if (class_tiles[device::kClassEncString]) EnsureDevice(&d_tile_sums, &cap_tile_sums, 2 * static_cast<size_t>(class_tiles[device::kClassEncString]) + 1);
-  if (class_tiles[device::kClassGather]) EnsureDevice(&d_gather_bases, &cap_gather_bases, tile_task.size());
+  if (class_tiles[device::kClassEncString]) GrowTable<int64_t>(d_tile_sums, 2 * static_cast<size_t>(class_tiles[device::kClassEncString]) + 1);
+  if (class_tiles[device::kClassGather]) GrowTable<int64_t>(d_gather_bases, tile_task.size());
   if (n_null_counts) {
-    const size_t before = cap_null_counts;
-    EnsureDevice(&d_null_counts, &cap_null_counts, static_cast<size_t>(n_null_counts));
-    if (cap_null_counts != before) SyncMemset(d_null_counts, 0, cap_null_counts * sizeof(int64_t));
+    const size_t before = d_null_counts.size();
+    GrowTable<int64_t>(d_null_counts, static_cast<size_t>(n_null_counts));
+    if (d_null_counts.size() != before) SyncMemset(d_null_counts.get(), 0, d_null_counts.size());
   }
   if (reusable && upload_stream) {
-    if (cap_tasks != old_cap_tasks || !h_tasks) {
-      if (h_tasks) MI_HIP_CHECK(hipHostFree(h_tasks));
-      MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_tasks), cap_tasks * sizeof(mi_col_task), hipHostMallocDefault));
-    }
-    if (cap_tile_begin != old_cap_tb || !h_tile_begin) {
-      if (h_tile_begin) MI_HIP_CHECK(hipHostFree(h_tile_begin));
-      MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_tile_begin), cap_tile_begin * sizeof(uint32_t), hipHostMallocDefault));
-    }
+    // a pinned mirror as large as its device table (a new one whenever the table grew)
+    auto mirror = [](PinnedBuffer& h, const DeviceBuffer& d) {
+      if (h.size() != d.size()) h = PinnedBuffer(d.size());
+    };
+    mirror(h_tasks, d_tasks);
+    mirror(h_tile_begin, d_tile_begin);
     if (!tasks.empty()) {
-      std::memcpy(h_tasks, tasks.data(), tasks.size() * sizeof(mi_col_task));
-      MI_HIP_CHECK(hipMemcpyAsync(d_tasks, h_tasks, tasks.size() * sizeof(mi_col_task), hipMemcpyHostToDevice, upload_stream));
+      std::memcpy(h_tasks.get(), tasks.data(), tasks.size() * sizeof(mi_col_task));
+      MI_HIP_CHECK(hipMemcpyAsync(d_tasks.get(), h_tasks.get(), tasks.size() * sizeof(mi_col_task), hipMemcpyHostToDevice, upload_stream));
     }
-    std::memcpy(h_tile_begin, tile_begin.data(), tile_begin.size() * sizeof(uint32_t));
-    MI_HIP_CHECK(hipMemcpyAsync(d_tile_begin, h_tile_begin, tile_begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice, upload_stream));
-    if (cap_tile_task != old_cap_tt || !h_tile_task) {
-      if (h_tile_task) MI_HIP_CHECK(hipHostFree(h_tile_task));
-      MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_tile_task), cap_tile_task * sizeof(uint32_t), hipHostMallocDefault));
-    }
+    std::memcpy(h_tile_begin.get(), tile_begin.data(), tile_begin.size() * sizeof(uint32_t));
+    MI_HIP_CHECK(hipMemcpyAsync(d_tile_begin.get(), h_tile_begin.get(), tile_begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice, upload_stream));
+    mirror(h_tile_task, d_tile_task);
     if (!tile_task.empty()) {
-      std::memcpy(h_tile_task, tile_task.data(), tile_task.size() * sizeof(uint32_t));
-      MI_HIP_CHECK(hipMemcpyAsync(d_tile_task, h_tile_task, tile_task.size() * sizeof(uint32_t), hipMemcpyHostToDevice, upload_stream));
+      std::memcpy(h_tile_task.get(), tile_task.data(), tile_task.size() * sizeof(uint32_t));
+      MI_HIP_CHECK(hipMemcpyAsync(d_tile_task.get(), h_tile_task.get(), tile_task.size() * sizeof(uint32_t), hipMemcpyHostToDevice, upload_stream));
     }
   } else {
     if (!tasks.empty())
-      MI_HIP_CHECK(hipMemcpy(d_tasks, tasks.data(), tasks.size() * sizeof(mi_col_task), hipMemcpyHostToDevice));
-    MI_HIP_CHECK(hipMemcpy(d_tile_begin, tile_begin.data(), tile_begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      MI_HIP_CHECK(hipMemcpy(d_tasks.get(), tasks.data(), tasks.size() * sizeof(mi_col_task), hipMemcpyHostToDevice));
+    MI_HIP_CHECK(hipMemcpy(d_tile_begin.get(), tile_begin.data(), tile_begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!tile_task.empty())
-      MI_HIP_CHECK(hipMemcpy(d_tile_task, tile_task.data(), tile_task.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      MI_HIP_CHECK(hipMemcpy(d_tile_task.get(), tile_task.data(), tile_task.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
-}
-
-Plan::~Plan() {
-  if (d_tasks) (void)hipFree(d_tasks);
-  if (d_tile_begin) (void)hipFree(d_tile_begin);
-  if (d_status) (void)hipFree(d_status);
-  if (d_tile_sums) (void)hipFree(d_tile_sums);
-  if (d_gather_bases) (void)hipFree(d_gather_bases);
-  if (d_null_counts) (void)hipFree(d_null_counts);
-  if (h_tasks) (void)hipHostFree(h_tasks);
-  if (h_tile_begin) (void)hipHostFree(h_tile_begin);
-  if (d_tile_task) (void)hipFree(d_tile_task);
-  if (h_tile_task) (void)hipHostFree(h_tile_task);
 }
 
 void Plan::LaunchSlice(const ClassSlice& cs, hipStream_t s) {
   if (cs.total_tiles == 0) return;
-  const mi_col_task* t = d_tasks + cs.first_task;
-  const uint32_t* tb = d_tile_begin + cs.tile_begin_at;
-  const uint32_t* tt = d_tile_task + cs.tile_task_at;
+  const mi_col_task* t = d_tasks.get<mi_col_task>() + cs.first_task;
+  const uint32_t* tb = d_tile_begin.get<uint32_t>() + cs.tile_begin_at;
+  const uint32_t* tt = d_tile_task.get<uint32_t>() + cs.tile_task_at;
+  uint32_t* status = d_status.get<uint32_t>();
+  int64_t* null_counts = d_null_counts.get<int64_t>();
   switch (cs.cls) {
     case device::kClassEncFixed:
-      MI_HIP_CHECK(device::LaunchEncodeFixed(t, tb, tt, cs.n_tasks, cs.total_tiles, d_null_counts, s));
+      MI_HIP_CHECK(device::LaunchEncodeFixed(t, tb, tt, cs.n_tasks, cs.total_tiles, null_counts, s));
       break;
     case device::kClassEncString:
-      MI_HIP_CHECK(device::LaunchEncodeString(t, tb, tt, cs.n_tasks, cs.total_tiles, d_tile_sums, d_null_counts, d_status, (cs.misc_groups & 2u) != 0, s));
+      MI_HIP_CHECK(device::LaunchEncodeString(t, tb, tt, cs.n_tasks, cs.total_tiles, d_tile_sums.get<int64_t>(), null_counts, status, (cs.misc_groups & 2u) != 0, s));
       break;
     case device::kClassGather:
-      MI_HIP_CHECK(device::LaunchGather(t, tb, tt, cs.n_tasks, cs.total_tiles, d_gather_bases + cs.tile_task_at, d_status, s));
+      MI_HIP_CHECK(device::LaunchGather(t, tb, tt, cs.n_tasks, cs.total_tiles, d_gather_bases.get<int64_t>() + cs.tile_task_at, status, s));
       break;
     default:
-      MI_HIP_CHECK(device::LaunchTranscode(cs.cls, t, tb, tt, cs.n_tasks, cs.total_tiles, d_status, cs.misc_groups, s));
+      MI_HIP_CHECK(device::LaunchTranscode(cs.cls, t, tb, tt, cs.n_tasks, cs.total_tiles, status, cs.misc_groups, s));
       break;
   }
 }
@@ -477,9 +448,9 @@ uint32_t Plan::Status() {
   hipStream_t s = last_stream ? last_stream : ctx->stream;
   MI_HIP_CHECK(hipStreamSynchronize(s));
   uint32_t bits = 0;
-  MI_HIP_CHECK(hipMemcpy(&bits, d_status, sizeof(bits), hipMemcpyDeviceToHost));
+  MI_HIP_CHECK(hipMemcpy(&bits, d_status.get(), sizeof(bits), hipMemcpyDeviceToHost));
   if (bits) {   // on the plan's own stream: a memset on the null stream is not ordered with the non-blocking streams the plans run on
-    MI_HIP_CHECK(hipMemsetAsync(d_status, 0, sizeof(bits), s));
+    MI_HIP_CHECK(hipMemsetAsync(d_status.get(), 0, sizeof(bits), s));
     MI_HIP_CHECK(hipStreamSynchronize(s));
   }
   return bits;
@@ -491,12 +462,12 @@ std::vector<int64_t> Plan::NullCounts(bool reset) {
   if (n_null_counts) {
     hipStream_t s = last_stream ? last_stream : ctx->stream;
     MI_HIP_CHECK(hipStreamSynchronize(s));
-    MI_HIP_CHECK(hipMemcpy(per_slot.data(), d_null_counts, per_slot.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    MI_HIP_CHECK(hipMemcpy(per_slot.data(), d_null_counts.get(), per_slot.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (reset) {
       // on the plan's own stream and finished before this returns: hipMemset() goes to the null stream, which is not ordered
       // with the non-blocking streams the plans run on -- the next row group's kernels could add their NULLs to the counters
       // BEFORE the memset of this row group cleared them (seen as null_count 0 in a file written by several sink threads)
-      MI_HIP_CHECK(hipMemsetAsync(d_null_counts, 0, per_slot.size() * sizeof(int64_t), s));
+      MI_HIP_CHECK(hipMemsetAsync(d_null_counts.get(), 0, per_slot.size() * sizeof(int64_t), s));
       MI_HIP_CHECK(hipStreamSynchronize(s));
     }
   }

@@ -7,26 +7,18 @@
 #include <string>
 #include <vector>
 
+#include "hip_resources.hpp"
 #include "ipc_format.hpp"
 #include "kernels.hpp"
 
 namespace miarrow {
 
-#define MI_HIP_CHECK(expr)                                                                                  \
-  do {                                                                                                      \
-    hipError_t _e = (expr);                                                                                 \
-    if (_e != hipSuccess) {                                                                                 \
-      throw ::miarrow::Exception(_e == hipErrorOutOfMemory ? MI_ENOMEM : MI_EIO,                            \
-                                 std::string(#expr) + " failed: " + hipGetErrorString(_e));                 \
-    }                                                                                                       \
-  } while (0)
-
 struct Context {
   int device = 0;
   int num_cus = 256;
-  hipStream_t stream = nullptr;       // compute
-  hipStream_t h2d_stream = nullptr;   // pinned host -> HBM
-  hipStream_t d2h_stream = nullptr;   // HBM -> pinned host
+  HipStream stream;       // compute
+  HipStream h2d_stream;   // pinned host -> HBM
+  HipStream d2h_stream;   // HBM -> pinned host
 
   // Where the device hangs in the host: its NUMA node and that node's CPUs (/sys/bus/pci/devices/<bus id>/numa_node and
   // local_cpulist; -1 / empty when the platform does not say).  The library's OWN host threads -- read-ahead producers, the
@@ -48,7 +40,6 @@ struct Context {
   };
 
   explicit Context(int device_id);
-  ~Context();
   void Bind() const;  // hipSetDevice
 };
 
@@ -75,34 +66,27 @@ struct Plan {
   std::vector<uint32_t> tile_begin;
   std::vector<ClassSlice> slices;                 // launch order: depth by depth, class by class
   uint32_t class_tiles[device::kNumClasses] = {0};
-  mi_col_task* d_tasks = nullptr;
-  uint32_t* d_tile_begin = nullptr;
-  uint32_t* d_tile_task = nullptr;   // per class slice: task index (within the slice) of every tile
-  uint32_t* h_tile_task = nullptr;
-  size_t cap_tile_task = 0;
   std::vector<uint32_t> tile_task;
-  uint32_t* d_status = nullptr;
-  int64_t* d_tile_sums = nullptr;    // encode plans with string columns
-  int64_t* d_gather_bases = nullptr; // gather plans: first output row of every window (indexed like tile_task)
-  size_t cap_gather_bases = 0;
-  int64_t* d_null_counts = nullptr;  // encode plans: one counter per task
+  // device tables (mi_col_task / uint32_t / int64_t elements) and the pinned mirrors they are uploaded from (reusable plans)
+  DeviceBuffer d_tasks, d_tile_begin;
+  DeviceBuffer d_tile_task;          // per class slice: task index (within the slice) of every tile
+  DeviceBuffer d_status;             // uint32_t status word
+  DeviceBuffer d_tile_sums;          // encode plans with string columns
+  DeviceBuffer d_gather_bases;       // gather plans: first output row of every window (indexed like tile_task)
+  DeviceBuffer d_null_counts;        // encode plans: one counter per task
+  PinnedBuffer h_tasks, h_tile_begin, h_tile_task;
   int64_t n_null_counts = 0;
   uint32_t total_tiles = 0;
   bool is_encode = false;
   hipStream_t last_stream = nullptr;
   int64_t bytes_read = 0, bytes_written = 0, rows = 0;
-  // capacities + pinned mirrors (reusable plans)
-  size_t cap_tasks = 0, cap_tile_begin = 0, cap_tile_sums = 0, cap_null_counts = 0;
-  mi_col_task* h_tasks = nullptr;
-  uint32_t* h_tile_begin = nullptr;
   bool reusable = false;
 
   Plan(Context* ctx, const mi_col_task* tasks, int32_t n_tasks);
   //! Reusable plan (scan / writer pipelines): tables are re-filled with Set() and uploaded asynchronously from
-  //! pinned host mirrors, so a new record batch costs no hipMalloc and no synchronous copy.
+  //! pinned host mirrors, so a new record batch costs no device allocation and no synchronous copy.
   explicit Plan(Context* ctx);
   void Set(const mi_col_task* tasks, int32_t n_tasks, hipStream_t upload_stream);
-  ~Plan();
   Plan(const Plan&) = delete;
   Plan& operator=(const Plan&) = delete;
   void Launch(hipStream_t stream);

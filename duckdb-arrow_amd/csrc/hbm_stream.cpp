@@ -57,8 +57,8 @@ class HbmStream {
     if (o.device_stream) {
       d_in = static_cast<uint8_t*>(o.device_stream);
     } else {
-      MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_in), static_cast<size_t>(size) + 320));
-      own_in = true;
+      in_buf = DeviceBuffer(static_cast<size_t>(size) + 320);
+      d_in = in_buf.get();
       MI_HIP_CHECK(hipMemcpy(d_in, host, static_cast<size_t>(size), hipMemcpyHostToDevice));
     }
     stream_size = size;
@@ -138,8 +138,8 @@ class HbmStream {
       AllocateArena();
     }
     if (!planner.aux.empty()) {
-      MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_aux), planner.aux.size() * 8));
-      MI_HIP_CHECK(hipMemcpy(d_aux, planner.aux.data(), planner.aux.size() * 8, hipMemcpyHostToDevice));
+      d_aux = DeviceBuffer(planner.aux.size() * 8);
+      MI_HIP_CHECK(hipMemcpy(d_aux.get(), planner.aux.data(), planner.aux.size() * 8, hipMemcpyHostToDevice));
     }
     if (d_out) Finish();
   }
@@ -147,9 +147,6 @@ class HbmStream {
   ~HbmStream() {
     try { ctx->Bind(); } catch (...) {}
     plan.reset();
-    if (own_in && d_in) (void)hipFree(d_in);
-    if (own_out && d_out) (void)hipFree(d_out);
-    if (d_aux) (void)hipFree(d_aux);
   }
 
   void SetArena(void* p, int64_t bytes) {
@@ -200,23 +197,22 @@ class HbmStream {
     return p;
   }
   void AllocateArena() {
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_out), arena_bytes));
-    own_out = true;
+    out_buf = DeviceBuffer(arena_bytes);
+    d_out = out_buf.get();
     // NULL slots of dictionaries and padding between arrays read as zero
     MI_HIP_CHECK(hipMemset(d_out, 0, arena_bytes));
     MI_HIP_CHECK(hipStreamSynchronize(nullptr));   // the null stream is not ordered with the (non-blocking) streams the plans run on
   }
   void Finish() {
-    planner.Rebase(0, d_out, d_aux);
+    planner.Rebase(0, d_out, d_aux.get());
     plan = std::make_unique<Plan>(ctx, planner.tasks.data(), static_cast<int32_t>(planner.tasks.size()));
   }
 
   BatchPlanner planner;
   std::unique_ptr<Plan> plan;
-  uint8_t* d_in = nullptr;
-  uint8_t* d_out = nullptr;
-  uint8_t* d_aux = nullptr;
-  bool own_in = false, own_out = false;
+  uint8_t* d_in = nullptr;    // the stream in HBM: in_buf or the caller's device_stream
+  uint8_t* d_out = nullptr;   // the arena: out_buf or the caller's device_arena
+  DeviceBuffer in_buf, out_buf, d_aux;
   size_t arena_bytes = 0;
   int64_t stream_size = 0, n_rows = 0;
   uint64_t consumer_base = 0;

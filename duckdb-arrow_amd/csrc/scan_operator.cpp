@@ -18,6 +18,12 @@ void EnsureIoThreads(int n);                // ipc_stream_reader.cpp
 namespace {
 constexpr size_t kAlign = 256;
 size_t RoundUp(size_t v, size_t a = kAlign) { return (v + a - 1) / a * a; }
+// a buffer that lives as long as any of the shared pointers to its memory (dictionary versions keep them)
+template <typename Buffer>
+std::shared_ptr<void> Shared(size_t bytes) {
+  auto b = std::make_shared<Buffer>(bytes);
+  return std::shared_ptr<void>(b, b->get());
+}
 
 std::map<std::string, std::string> ParseHive(const std::string& path) {
   // key=value path components (DuckDB's HivePartitioning::Parse behaviour for simple keys)
@@ -92,51 +98,16 @@ ArrowScan::~ArrowScan() {
     ctx->Bind();
   } catch (...) {
   }
+  // The device is done with every buffer before any of them goes (the members, after this body).  The batches in the
+  // slots and in the read-ahead queues hold staging leases, whose release marks the staging buffer free: they go first.
   (void)hipStreamSynchronize(ctx->h2d_stream);
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipStreamSynchronize(ctx->d2h_stream);
-  for (auto& s : slots) {
-    s.batch = DecodedBatch();  // returns the staging lease
-    s.plan.reset();
-    s.gather_plan.reset();
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_status) (void)hipHostFree(s.h_status);
-    if (s.h_counts) (void)hipHostFree(s.h_counts);
-    if (s.h_aux) (void)hipHostFree(s.h_aux);
-    if (s.d_aux) (void)hipFree(s.d_aux);
-    if (s.lz4_stream) (void)hipStreamSynchronize(s.lz4_stream);
-    if (s.d_comp) (void)hipFree(s.d_comp);
-    if (s.d_lz4) (void)hipFree(s.d_lz4);
-    if (s.h_lz4) (void)hipHostFree(s.h_lz4);
-    if (s.h_mirror) (void)hipHostFree(s.h_mirror);
-    if (s.lz4_stream && !s.lz4_stream_shared) (void)hipStreamDestroy(s.lz4_stream);
-    if (s.lz4_done) (void)hipEventDestroy(s.lz4_done);
-    if (s.h2d_done) (void)hipEventDestroy(s.h2d_done);
-    if (s.compute_done) (void)hipEventDestroy(s.compute_done);
-    if (s.d2h_done) (void)hipEventDestroy(s.d2h_done);
-    if (s.filter_done) (void)hipEventDestroy(s.filter_done);
-  }
-  for (void* p : d_in_lists)
-    if (p) (void)hipFree(p);
-  for (void* p : retired_device) (void)hipFree(p);
-  for (void* p : retired_host) (void)hipHostFree(p);
-  dicts.clear();
+  for (auto& s : slots)
+    if (s.lz4_stream) (void)hipStreamSynchronize(s.lz4_stream);   // a borrowed stream: its owner is still alive
+  for (auto& s : slots) s.batch = DecodedBatch();
   fetched.clear();
   extra_readers.clear();
-  for (auto& st : staging)
-    if (st.p) (void)hipHostFree(st.p);
-}
-
-ArrowScan::DictState::~DictState() {
-  decode_plan.reset();
-  if (d_data) (void)hipFree(d_data);
-  if (d_validity) (void)hipFree(d_validity);
-  if (h_data) (void)hipHostFree(h_data);
-  if (h_words) (void)hipHostFree(h_words);   // h_validity is the same memory
-  if (h_status) (void)hipHostFree(h_status);
-  if (uploaded) (void)hipEventDestroy(uploaded);
 }
 
 void ArrowScan::OpenSource(size_t i) {
@@ -306,22 +277,20 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
       }
     }
     // IN-lists live in HBM for the lifetime of the scan
-    for (void* p : d_in_lists)
-      if (p) (void)hipFree(p);
     d_in_lists.clear();
     for (auto& clause : filter)
       for (auto& leaf : clause) {
-        void* p = nullptr;
+        DeviceBuffer list;
         if (leaf.op == device::kLeafIn) {
-          MI_HIP_CHECK(hipMalloc(&p, leaf.in_values.size() * 8));
-          MI_HIP_CHECK(hipMemcpy(p, leaf.in_values.data(), leaf.in_values.size() * 8, hipMemcpyHostToDevice));
+          list = DeviceBuffer(leaf.in_values.size() * 8);
+          MI_HIP_CHECK(hipMemcpy(list.get(), leaf.in_values.data(), leaf.in_values.size() * 8, hipMemcpyHostToDevice));
         } else if ((leaf.op == device::kLeafStrIn || leaf.op == device::kLeafStrRange) && !leaf.str_values.empty()) {
           // 3 words per constant (its string_t image + the device address of its bytes), the bytes behind the table
           const size_t nc = leaf.str_values.size();
           size_t bytes = 0;
           for (auto& v : leaf.str_values) bytes += RoundUp(v.size() + 1, 8);
           std::vector<uint8_t> img(nc * 24 + bytes, 0);
-          MI_HIP_CHECK(hipMalloc(&p, img.size()));
+          list = DeviceBuffer(img.size());
           size_t at = nc * 24;
           for (size_t k = 0; k < nc; k++) {
             const std::string& v = leaf.str_values[k];
@@ -330,16 +299,16 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
             std::memcpy(dw, v.data(), std::min<size_t>(v.size(), v.size() <= 12 ? 12 : 4));
             const uint64_t w0 = static_cast<uint64_t>(v.size()) | (static_cast<uint64_t>(dw[0]) << 32);
             const uint64_t w1 = v.size() <= 12 ? (static_cast<uint64_t>(dw[1]) | (static_cast<uint64_t>(dw[2]) << 32)) : 0;
-            const uint64_t w2 = reinterpret_cast<uint64_t>(static_cast<uint8_t*>(p) + at);
+            const uint64_t w2 = reinterpret_cast<uint64_t>(list.get() + at);
             std::memcpy(&img[k * 24], &w0, 8);
             std::memcpy(&img[k * 24 + 8], &w1, 8);
             std::memcpy(&img[k * 24 + 16], &w2, 8);
             std::memcpy(&img[at], v.data(), v.size());
             at += RoundUp(v.size() + 1, 8);
           }
-          MI_HIP_CHECK(hipMemcpy(p, img.data(), img.size(), hipMemcpyHostToDevice));
+          MI_HIP_CHECK(hipMemcpy(list.get(), img.data(), img.size(), hipMemcpyHostToDevice));
         }
-        d_in_lists.push_back(p);
+        d_in_lists.push_back(std::move(list));
       }
     if (opts.filter_compact) {
       for (auto& c : out_columns) {
@@ -361,14 +330,15 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
 void ArrowScan::InitSlot(Slot& s) {
   if (s.h2d_done) return;
   ctx->Bind();
-  MI_HIP_CHECK(hipEventCreateWithFlags(&s.h2d_done, hipEventDisableTiming));
-  MI_HIP_CHECK(hipEventCreateWithFlags(&s.compute_done, hipEventDisableTiming));
-  MI_HIP_CHECK(hipEventCreateWithFlags(&s.d2h_done, hipEventDisableTiming));
-  MI_HIP_CHECK(hipEventCreateWithFlags(&s.filter_done, hipEventDisableTiming));
+  s.h2d_done = HipEvent::Create();
+  s.compute_done = HipEvent::Create();
+  s.d2h_done = HipEvent::Create();
+  s.filter_done = HipEvent::Create();
   s.plan = std::make_unique<Plan>(ctx);
   s.gather_plan = std::make_unique<Plan>(ctx);
-  MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_status), 64, hipHostMallocDefault));
-  s.h_status[0] = s.h_status[1] = s.h_status[2] = 0;
+  s.h_status = PinnedBuffer(64);
+  uint32_t* st = s.h_status.get<uint32_t>();
+  st[0] = st[1] = st[2] = 0;
 }
 
 // More record batches in flight / held by the caller at once (the COPY pump hands whole batches to several sink threads).
@@ -386,30 +356,11 @@ void ArrowScan::EnsurePipelineDepth(int depth) {
     for (auto& s : slots) InitSlot(s);
 }
 
-void ArrowScan::EnsureSlotBuffers(Slot& s, size_t in_bytes, size_t out_bytes) {
-  ctx->Bind();
-  if (in_bytes > s.d_in_cap) {
-    if (s.d_in) RetireDevice(s.d_in);
-    s.d_in = nullptr;
-    s.d_in_cap = RoundUp(GrowCap(in_bytes, s.d_in_cap), 1 << 16);
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_in), s.d_in_cap));
-  }
-  if (out_bytes > s.d_out_cap) {
-    if (s.d_out) RetireDevice(s.d_out);
-    s.d_out = nullptr;
-    s.d_out_cap = RoundUp(GrowCap(out_bytes, s.d_out_cap), 1 << 16);
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_out), s.d_out_cap));
-  }
-}
-
 void ArrowScan::EnsureHostOut(Slot& s, size_t bytes) {
-  if (opts.device_resident || bytes <= s.h_out_cap) return;
+  if (opts.device_resident || bytes <= s.h_out.size()) return;
   ctx->Bind();
-  if (s.h_out) RetireHost(s.h_out);
-  s.h_out = nullptr;
   Context::PreferNode near_the_gpu(ctx);   // (the caller's thread allocates: only its policy, for the length of this call)
-  s.h_out_cap = RoundUp(GrowCap(bytes, s.h_out_cap), 1 << 16);
-  MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_out), s.h_out_cap, hipHostMallocDefault));
+  Retire(Grow(s.h_out, bytes, GrownCapacity(bytes, s.h_out.size(), 1 << 16)));
 }
 
 ArrowScan::Slot* ArrowScan::FreeSlot() {
@@ -461,27 +412,25 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
   // behind it (the record batches that use the dictionary follow on the same stream), the decode's status word comes back
   // with the first such batch (DictState::h_status, checked in AcquireBatch).  The validity words are built on the host
   // from the Arrow bitmap (the value types admitted above are flat: a value is NULL exactly when its bit says so).
-  MI_HIP_CHECK(hipMalloc(&d->d_data, data_bytes));
-  MI_HIP_CHECK(hipMalloc(&d->d_validity, valid_bytes));
-  MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d->h_words), valid_bytes, hipHostMallocDefault));
-  MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d->h_status), 64, hipHostMallocDefault));
-  d->h_status[0] = 0;
-  MI_HIP_CHECK(hipMemsetAsync(d->d_data, 0, data_bytes, ctx->stream));
+  d->d_data = DeviceBuffer(data_bytes);
+  d->d_validity = DeviceBuffer(valid_bytes);
+  d->h_words = PinnedBuffer(valid_bytes);
+  d->h_status = PinnedBuffer(64);
+  d->h_status.get<uint32_t>()[0] = 0;
+  MI_HIP_CHECK(hipMemsetAsync(d->d_data.get(), 0, data_bytes, ctx->stream));
   uint8_t* heap = nullptr;
   if (b.body_size > 0) {
-    void* p = nullptr;
-    MI_HIP_CHECK(hipMalloc(&p, RoundUp(static_cast<size_t>(b.body_size) + 16)));
-    d->d_heaps.push_back(std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); }));
-    heap = static_cast<uint8_t*>(p);
+    d->d_heaps.push_back(Shared<DeviceBuffer>(RoundUp(static_cast<size_t>(b.body_size) + 16)));
+    heap = static_cast<uint8_t*>(d->d_heaps.back().get());
     // the body is pinned (the read-ahead's allocator for DICTIONARY_BATCH messages) and lives in host_bodies
     MI_HIP_CHECK(hipMemcpyAsync(heap, b.body, static_cast<size_t>(b.body_size), hipMemcpyHostToDevice, ctx->h2d_stream));
-    if (!d->uploaded) MI_HIP_CHECK(hipEventCreateWithFlags(&d->uploaded, hipEventDisableTiming));
+    if (!d->uploaded) d->uploaded = HipEvent::Create();
     MI_HIP_CHECK(hipEventRecord(d->uploaded, ctx->h2d_stream));
     MI_HIP_CHECK(hipStreamWaitEvent(ctx->stream, d->uploaded, 0));
   }
   if (n_old > 0)
-    MI_HIP_CHECK(hipMemcpyAsync(d->d_data, old->d_data, static_cast<size_t>(n_old) * static_cast<size_t>(w), hipMemcpyDeviceToDevice, ctx->stream));
-  uint64_t* words = d->h_words;
+    MI_HIP_CHECK(hipMemcpyAsync(d->d_data.get(), old->d_data.get(), static_cast<size_t>(n_old) * static_cast<size_t>(w), hipMemcpyDeviceToDevice, ctx->stream));
+  uint64_t* words = d->h_words.get<uint64_t>();
   for (size_t i = 0; i < valid_bytes / 8; i++) words[i] = ~0ull;
   auto set_bit = [&](int64_t i, bool v) {
     if (v) words[static_cast<size_t>(i >> 6)] |= 1ull << (i & 63);
@@ -497,9 +446,8 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
   if (n_new > 0) {
     // decode the new values into a tile-aligned scratch vector, then append (the scratch lives as long as the version:
     // freeing it here would wait for the device)
-    void* scratch_data = nullptr;
-    MI_HIP_CHECK(hipMalloc(&scratch_data, RoundUp(static_cast<size_t>(n_new) * static_cast<size_t>(w) + 16)));
-    d->d_heaps.push_back(std::shared_ptr<void>(scratch_data, [](void* q) { (void)hipFree(q); }));
+    d->d_heaps.push_back(Shared<DeviceBuffer>(RoundUp(static_cast<size_t>(n_new) * static_cast<size_t>(w) + 16)));
+    void* scratch_data = d->d_heaps.back().get();
     mi_col_task t;
     std::memset(&t, 0, sizeof(t));
     const mi_buffer_span* sp = &b.buffers[0];
@@ -517,9 +465,9 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
     t.param = param;
     d->decode_plan = std::make_unique<Plan>(ctx, &t, 1);
     d->decode_plan->Launch(ctx->stream);
-    MI_HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t*>(d->d_data) + static_cast<size_t>(n_old) * static_cast<size_t>(w), scratch_data,
+    MI_HIP_CHECK(hipMemcpyAsync(d->d_data.get() + static_cast<size_t>(n_old) * static_cast<size_t>(w), scratch_data,
                                 static_cast<size_t>(n_new) * static_cast<size_t>(w), hipMemcpyDeviceToDevice, ctx->stream));
-    MI_HIP_CHECK(hipMemcpyAsync(d->h_status, d->decode_plan->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP_CHECK(hipMemcpyAsync(d->h_status.get(), d->decode_plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   }
   // string-valued dictionaries keep their values on the host too: pushed-down string predicates are matched against the
   // dictionary once and against the rows by index (the offsets are validated here; the device validates them again)
@@ -553,12 +501,12 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
     }
   }
   set_bit(n, false);  // the extra NULL entry at index dict_len (ColumnArrowToDuckDBDictionary)
-  MI_HIP_CHECK(hipMemcpyAsync(d->d_validity, words, valid_bytes, hipMemcpyHostToDevice, ctx->stream));
+  MI_HIP_CHECK(hipMemcpyAsync(d->d_validity.get(), words, valid_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (!opts.device_resident) {
     // host consumers read the values from pinned memory: the copy rides the compute stream too, and every batch that uses
     // the dictionary is handed out only after its own results have come back behind it
-    MI_HIP_CHECK(hipHostMalloc(&d->h_data, data_bytes, hipHostMallocDefault));
-    MI_HIP_CHECK(hipMemcpyAsync(d->h_data, d->d_data, data_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    d->h_data = PinnedBuffer(data_bytes);
+    MI_HIP_CHECK(hipMemcpyAsync(d->h_data.get(), d->d_data.get(), data_bytes, hipMemcpyDeviceToHost, ctx->stream));
     d->h_validity = words;   // the same pinned words
   }
   dicts[b.dict_id] = d;
@@ -568,15 +516,10 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
 void ArrowScan::UploadAux(Slot& s, const std::vector<uint64_t>& aux) {
   const size_t aux_bytes = aux.size() * 8;
   if (!aux_bytes) return;
-  if (aux_bytes > s.h_aux_cap) {
-    if (s.h_aux) RetireHost(s.h_aux);
-    if (s.d_aux) RetireDevice(s.d_aux);
-    s.h_aux_cap = s.d_aux_cap = RoundUp(aux_bytes * 2, 4096);
-    MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_aux), s.h_aux_cap, hipHostMallocDefault));
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_aux), s.d_aux_cap));
-  }
-  std::memcpy(s.h_aux, aux.data(), aux_bytes);
-  MI_HIP_CHECK(hipMemcpyAsync(s.d_aux, s.h_aux, aux_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
+  Retire(Grow(s.h_aux, aux_bytes, RoundUp(aux_bytes * 2, 4096)));   // the two grow together: twice the need
+  Retire(Grow(s.d_aux, aux_bytes, RoundUp(aux_bytes * 2, 4096)));
+  std::memcpy(s.h_aux.get(), aux.data(), aux_bytes);
+  MI_HIP_CHECK(hipMemcpyAsync(s.d_aux.get(), s.h_aux.get(), aux_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
 }
 
 // Stage A of a record batch: H2D of the body, the full-width decode tasks (every projected column; with compaction only
@@ -592,7 +535,8 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   s.needs_stage_b = false;
   const int64_t n_windows = (n + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
   // d_in must be final before tasks take addresses inside it
-  EnsureSlotBuffers(s, static_cast<size_t>(b.body_size) + 64, 0);
+  const size_t in_bytes = static_cast<size_t>(b.body_size) + 64;
+  Retire(Grow(s.d_in, in_bytes, GrownCapacity(in_bytes, s.d_in.size(), 1 << 16)));
 
   PlannerOptions po;
   po.array_align = kAlign;
@@ -604,12 +548,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   // a host consumer of a body that only exists decompressed in HBM: string_t rows point into a pinned mirror of the body
   const bool mirror = b.deferred && !opts.device_resident;
   po.zero_copy_direct = zero_copy && !agg.on && !s.compact && !mirror;
-  if (mirror && static_cast<size_t>(b.body_size) + 64 > s.h_mirror_cap) {
-    if (s.h_mirror) RetireHost(s.h_mirror);
-    s.h_mirror = nullptr;
-    s.h_mirror_cap = RoundUp(GrowCap(static_cast<size_t>(b.body_size) + 64, s.h_mirror_cap), 1 << 16);
-    MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_mirror), s.h_mirror_cap, hipHostMallocDefault));
-  }
+  if (mirror) Retire(Grow(s.h_mirror, in_bytes, GrownCapacity(in_bytes, s.h_mirror.size(), 1 << 16)));
   po.unset_all_valid = opts.unset_all_valid != 0;
   s.planner.opts = po;
   s.planner.Clear();
@@ -620,9 +559,9 @@ void ArrowScan::EnqueueBatch(Slot& s) {
 
   BatchPlacement where;
   where.batch = &b;
-  where.in_base = s.d_in;
-  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in)
-                                             : reinterpret_cast<uint64_t>(mirror ? s.h_mirror : b.body);
+  where.in_base = s.d_in.get();
+  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in.get())
+                                             : reinterpret_cast<uint64_t>(mirror ? s.h_mirror.get() : b.body);
   where.dict_len = [&](int64_t id) -> int64_t {
     auto it = dicts.find(id);
     if (it == dicts.end()) throw IOException("RecordBatch uses dictionary id " + std::to_string(id) + " before its DictionaryBatch");
@@ -687,18 +626,15 @@ void ArrowScan::EnqueueBatch(Slot& s) {
       if (!c.is_filename && !c.is_hive)
         stage_b_worst += RoundUp(static_cast<size_t>(n) * static_cast<size_t>(std::max(width_of(c), 1)) + 16) + RoundUp(static_cast<size_t>((n + 63) / 64) * 8 + 8);
   }
-  EnsureSlotBuffers(s, static_cast<size_t>(b.body_size) + 64, s.stage_a_bytes + stage_b_worst + 64);
+  const size_t out_bytes = s.stage_a_bytes + stage_b_worst + 64;
+  Retire(Grow(s.d_out, out_bytes, GrownCapacity(out_bytes, s.d_out.size(), 1 << 16)));
   EnsureHostOut(s, s.d2h_bytes + 64);
-  if (static_cast<size_t>(n_windows + 1) * 4 > s.h_counts_cap) {
-    if (s.h_counts) RetireHost(s.h_counts);
-    s.h_counts_cap = RoundUp(static_cast<size_t>(n_windows + 1) * 8, 4096);
-    MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_counts), s.h_counts_cap, hipHostMallocDefault));
-  }
+  Retire(Grow(s.h_counts, static_cast<size_t>(n_windows + 1) * 4, RoundUp(static_cast<size_t>(n_windows + 1) * 8, 4096)));
   UploadAux(s, s.planner.aux);
-  s.planner.Rebase(0, s.d_out, s.d_aux);
+  s.planner.Rebase(0, s.d_out.get(), s.d_aux.get());
 
   stats.record_batches++;
-  s.h_status[2] = 0;
+  s.h_status.get<uint32_t>()[2] = 0;
   if (b.deferred) {
     EnqueueLz4(s);   // compressed body -> HBM -> K8 kernels -> d_in; ctx->stream waits for them
     if (mirror) {    // the payload of every string-like buffer goes back to the host as soon as it is decompressed
@@ -714,7 +650,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
         for (size_t k = first; k < last && k < nd.spans.size(); k++)
           if (nd.spans[k].length > 0)
           {
-            MI_HIP_CHECK(hipMemcpyAsync(s.h_mirror + nd.spans[k].offset, s.d_in + nd.spans[k].offset, static_cast<size_t>(nd.spans[k].length),
+            MI_HIP_CHECK(hipMemcpyAsync(s.h_mirror.get() + nd.spans[k].offset, s.d_in.get() + nd.spans[k].offset, static_cast<size_t>(nd.spans[k].length),
                                         hipMemcpyDeviceToHost, ctx->d2h_stream));
             stats.d2h_bytes += nd.spans[k].length;
           }
@@ -741,7 +677,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     auto flush = [&]() {
       if (lo < 0) return;
       hi = std::min<int64_t>((hi + 63) & ~int64_t(63), b.body_size);
-      MI_HIP_CHECK(hipMemcpyAsync(s.d_in + lo, b.body + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
+      MI_HIP_CHECK(hipMemcpyAsync(s.d_in.get() + lo, b.body + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
       stats.h2d_bytes += hi - lo;
     };
     for (const auto& r : upload) {
@@ -763,13 +699,13 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     for (size_t c = 0; c < out_columns.size(); c++) {
       if (out_columns[c].is_filename || out_columns[c].is_hive) continue;
       if (src.out_to_file_column[c] < 0 && n > 0) {
-        MI_HIP_CHECK(hipMemsetAsync(s.d_out + s.absent[c].first, 0, static_cast<size_t>(n) * static_cast<size_t>(std::max(widths[c], 1)), ctx->stream));
-        MI_HIP_CHECK(hipMemsetAsync(s.d_out + s.absent[c].second, 0, static_cast<size_t>((n + 63) / 64) * 8, ctx->stream));
+        MI_HIP_CHECK(hipMemsetAsync(s.d_out.get() + s.absent[c].first, 0, static_cast<size_t>(n) * static_cast<size_t>(std::max(widths[c], 1)), ctx->stream));
+        MI_HIP_CHECK(hipMemsetAsync(s.d_out.get() + s.absent[c].second, 0, static_cast<size_t>((n + 63) / 64) * 8, ctx->stream));
       }
     }
   }
   s.plan->Set(s.planner.tasks.data(), static_cast<int32_t>(s.planner.tasks.size()), ctx->stream);
-  MI_HIP_CHECK(hipMemsetAsync(s.plan->d_status, 0, sizeof(uint32_t), ctx->stream));
+  MI_HIP_CHECK(hipMemsetAsync(s.plan->d_status.get(), 0, sizeof(uint32_t), ctx->stream));
   s.plan->Launch(ctx->stream);
   if (has_filter && n > 0) {
     device::FilterProgram prog;
@@ -786,7 +722,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
         L.flags = (j + 1 == clause.size() ? device::kLeafEndsClause : 0) | (leaf.negate ? device::kLeafNegate : 0);
         L.lo = leaf.lo;
         L.hi = leaf.hi;
-        L.in_values = static_cast<const int64_t*>(d_in_lists[li]);
+        L.in_values = d_in_lists[li].get<int64_t>();
         L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.in_values.size());
         if (leaf.op == device::kLeafStrRange)
           L.n_in = (leaf.lo_open ? 0 : 1) | (leaf.lo_incl ? 2 : 0) | (leaf.hi_open ? 0 : 4) | (leaf.hi_incl ? 8 : 0);
@@ -802,13 +738,13 @@ void ArrowScan::EnqueueBatch(Slot& s) {
             L.op = device::kLeafRange;
             L.lo = 1;
             L.hi = 0;
-            L.data = s.d_out + s.sel_off;
+            L.data = s.d_out.get() + s.sel_off;
           }
           continue;
         }
         const PlannedNode& pn = s.planner.nodes[static_cast<size_t>(root)];
-        L.data = pn.alias_body_off >= 0 ? static_cast<const void*>(s.d_in + pn.alias_body_off) : static_cast<const void*>(s.d_out + pn.data_off);
-        L.validity = pn.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out + pn.valid_off) : nullptr;
+        L.data = pn.alias_body_off >= 0 ? static_cast<const void*>(s.d_in.get() + pn.alias_body_off) : static_cast<const void*>(s.d_out.get() + pn.data_off);
+        L.validity = pn.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out.get() + pn.valid_off) : nullptr;
         L.width = std::max(pn.width, 1);
         const bool null_test = leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull;
         if (pn.kind == MI_K_DICT && (leaf.is_string || null_test)) {
@@ -841,17 +777,11 @@ void ArrowScan::EnqueueBatch(Slot& s) {
                                               : (leaf.is_string && passes(dict->host_strings[static_cast<size_t>(e)])) ? 1 : 0;
             codes[static_cast<size_t>(dict->dict_len)] = 2;   // the NULL entry rows without a value point at
             // device copy + its pinned source, uploaded on the compute stream in front of the filter kernel that reads it
-            void* p = nullptr;
-            void* hp = nullptr;
-            MI_HIP_CHECK(hipMalloc(&p, RoundUp(codes.size() + 16)));
-            MI_HIP_CHECK(hipHostMalloc(&hp, RoundUp(codes.size() + 16), hipHostMallocDefault));
-            std::shared_ptr<void> keep(p, [hp](void* q) {
-              (void)hipFree(q);
-              (void)hipHostFree(hp);
-            });
-            std::memcpy(hp, codes.data(), codes.size());
-            MI_HIP_CHECK(hipMemcpyAsync(p, hp, codes.size(), hipMemcpyHostToDevice, ctx->stream));
-            it = dict->match_maps.emplace(li, std::move(keep)).first;
+            DeviceBuffer d_map(RoundUp(codes.size() + 16));
+            auto map = std::make_shared<std::pair<DeviceBuffer, PinnedBuffer>>(std::move(d_map), PinnedBuffer(RoundUp(codes.size() + 16)));
+            std::memcpy(map->second.get(), codes.data(), codes.size());
+            MI_HIP_CHECK(hipMemcpyAsync(map->first.get(), map->second.get(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
+            it = dict->match_maps.emplace(li, std::shared_ptr<void>(map, map->first.get())).first;
           }
           L.op = device::kLeafDictMap;
           L.in_values = static_cast<const int64_t*>(it->second.get());
@@ -866,7 +796,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
           // consumer sees it); the kernel reads the bytes from the HBM copy of that buffer
           const DecodedNode& dn = b.nodes[static_cast<size_t>(pn.source_node)];
           const size_t data_span = pn.kind == MI_K_FIXED_BINARY ? 1 : 2;
-          L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(s.d_in + (dn.spans.size() > data_span ? dn.spans[data_span].offset : 0)));
+          L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(s.d_in.get() + (dn.spans.size() > data_span ? dn.spans[data_span].offset : 0)));
           L.hi = static_cast<int64_t>(pn.ptr_base);
           continue;
         }
@@ -890,8 +820,8 @@ void ArrowScan::EnqueueBatch(Slot& s) {
         }
       }
     }
-    MI_HIP_CHECK(device::LaunchFilterProgram(prog, n, reinterpret_cast<mi_sel_t*>(s.d_out + s.sel_off),
-                                             reinterpret_cast<uint32_t*>(s.d_out + s.sel_count_off), ctx->stream));
+    MI_HIP_CHECK(device::LaunchFilterProgram(prog, n, reinterpret_cast<mi_sel_t*>(s.d_out.get() + s.sel_off),
+                                             reinterpret_cast<uint32_t*>(s.d_out.get() + s.sel_count_off), ctx->stream));
   }
   if (agg.on && n > 0) {
     // fused consumer: the decoded vectors are read once more by the aggregate kernel and never leave HBM
@@ -900,8 +830,8 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     auto column = [&](int32_t c, const void** data, const uint64_t** valid, int32_t* width) {
       if (s.col_root[static_cast<size_t>(c)] < 0) throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
       const PlannedNode& o = s.planner.nodes[static_cast<size_t>(s.col_root[static_cast<size_t>(c)])];
-      *data = s.d_out + o.data_off;
-      *valid = o.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out + o.valid_off) : nullptr;
+      *data = s.d_out.get() + o.data_off;
+      *valid = o.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out.get() + o.valid_off) : nullptr;
       *width = o.width;
     };
     a.n_filters = static_cast<int32_t>(agg.filter_cols.size());
@@ -913,13 +843,13 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     column(agg.col_a, &a.a, &a.avalid, &a.awidth);
     column(agg.col_b, &a.b, &a.bvalid, &a.bwidth);
     a.nrows = n;
-    MI_HIP_CHECK(device::LaunchAggSumProduct(a, agg.d_acc, ctx->num_cus, ctx->stream));
+    MI_HIP_CHECK(device::LaunchAggSumProduct(a, agg.d_acc.get<unsigned long long>(), ctx->num_cus, ctx->stream));
     agg.rows_scanned += n;
   }
   MI_HIP_CHECK(hipEventRecord(s.compute_done, ctx->stream));
   MI_HIP_CHECK(hipStreamWaitEvent(ctx->d2h_stream, s.compute_done, 0));
   if (has_filter && n > 0)  // the per-window counts always come back (tiny): chunk sizes, Count(), the stage-B layout
-    MI_HIP_CHECK(hipMemcpyAsync(s.h_counts, s.d_out + s.sel_count_off, static_cast<size_t>(n_windows) * 4, hipMemcpyDeviceToHost, ctx->d2h_stream));
+    MI_HIP_CHECK(hipMemcpyAsync(s.h_counts.get<uint32_t>(), s.d_out.get() + s.sel_count_off, static_cast<size_t>(n_windows) * 4, hipMemcpyDeviceToHost, ctx->d2h_stream));
   if (s.compact) {
     MI_HIP_CHECK(hipEventRecord(s.filter_done, ctx->d2h_stream));
     s.needs_stage_b = true;
@@ -927,14 +857,14 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   }
   s.host_vectors = !opts.device_resident && !agg.on && s.d2h_bytes > 0 && !keep_on_device;
   if (s.host_vectors) {
-    MI_HIP_CHECK(hipMemcpyAsync(s.h_out, s.d_out, s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
+    MI_HIP_CHECK(hipMemcpyAsync(s.h_out.get(), s.d_out.get(), s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
     stats.d2h_bytes += static_cast<int64_t>(s.d2h_bytes);
   }
   for (const auto& nd : s.planner.nodes)
     if (nd.alias_body_off >= 0) stats.aliased_bytes += nd.nrows * nd.width;
   // the device status word travels with the results instead of costing a stream-wide synchronisation
-  MI_HIP_CHECK(hipMemcpyAsync(&s.h_status[0], s.plan->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
-  s.h_status[1] = 0;
+  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>(), s.plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
+  s.h_status.get<uint32_t>()[1] = 0;
   MI_HIP_CHECK(hipEventRecord(s.d2h_done, ctx->d2h_stream));
 }
 
@@ -962,13 +892,12 @@ void ArrowScan::EnqueueLz4(Slot& s) {
     const int idx = static_cast<int>(&s - slots.data());
     if (idx >= kLz4Streams) {
       Slot& owner = slots[static_cast<size_t>(idx % kLz4Streams)];
-      if (!owner.lz4_stream) MI_HIP_CHECK(hipStreamCreateWithFlags(&owner.lz4_stream, hipStreamNonBlocking));
+      if (!owner.lz4_stream) owner.lz4_stream = owner.own_lz4_stream = HipStream::Create();
       s.lz4_stream = owner.lz4_stream;
-      s.lz4_stream_shared = true;
     } else {
-      MI_HIP_CHECK(hipStreamCreateWithFlags(&s.lz4_stream, hipStreamNonBlocking));
+      s.lz4_stream = s.own_lz4_stream = HipStream::Create();
     }
-    MI_HIP_CHECK(hipEventCreateWithFlags(&s.lz4_done, hipEventDisableTiming));
+    s.lz4_done = HipEvent::Create();
   }
   const size_t out_size = static_cast<size_t>(b.body_size);
   const size_t nb = d.blocks.size(), nf = d.buffers.size();
@@ -991,26 +920,11 @@ void ArrowScan::EnqueueLz4(Slot& s) {
   const size_t o_seq = take(static_cast<size_t>(total_seq) * 16), o_seqoff = take(static_cast<size_t>(total_seq) * 4);
   const size_t o_lane_out = take(nb * 256 * 4), o_lane_n = take(nb * 256 * 4), o_rep = take(is_zstd ? nb * 256 * 16 : 0);
   const size_t o_link = take(out_size * 4 + 16), o_skel = take(out_size * 4 + 16);
-  if (at > s.d_lz4_cap) {
-    if (s.d_lz4) RetireDevice(s.d_lz4);
-    s.d_lz4 = nullptr;
-    s.d_lz4_cap = RoundUp(GrowCap(at, s.d_lz4_cap), 1 << 20);
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_lz4), s.d_lz4_cap));
-  }
-  if (comp_need > s.d_comp_cap) {
-    if (s.d_comp) RetireDevice(s.d_comp);
-    s.d_comp = nullptr;
-    s.d_comp_cap = RoundUp(GrowCap(comp_need, s.d_comp_cap), 1 << 16);
-    MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_comp), s.d_comp_cap));
-  }
-  if (tables_bytes > s.h_lz4_cap) {
-    if (s.h_lz4) RetireHost(s.h_lz4);
-    s.h_lz4 = nullptr;
-    s.h_lz4_cap = RoundUp(std::max(tables_bytes, s.h_lz4_cap * 2), 1 << 16);
-    MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_lz4), s.h_lz4_cap, hipHostMallocDefault));
-  }
-  auto* hb = reinterpret_cast<device::Lz4BlockDev*>(s.h_lz4 + o_blocks);
-  auto* hf = reinterpret_cast<device::Lz4BufferDev*>(s.h_lz4 + o_buffers);
+  Retire(Grow(s.d_lz4, at, GrownCapacity(at, s.d_lz4.size(), 1 << 20)));
+  Retire(Grow(s.d_comp, comp_need, GrownCapacity(comp_need, s.d_comp.size(), 1 << 16)));
+  Retire(Grow(s.h_lz4, tables_bytes, RoundUp(std::max(tables_bytes, s.h_lz4.size() * 2), 1 << 16)));   // doubles
+  auto* hb = reinterpret_cast<device::Lz4BlockDev*>(s.h_lz4.get() + o_blocks);
+  auto* hf = reinterpret_cast<device::Lz4BufferDev*>(s.h_lz4.get() + o_buffers);
   uint32_t seq_at = 0;
   for (size_t i = 0; i < nb; i++) {
     const auto& blk = d.blocks[i];
@@ -1023,7 +937,7 @@ void ArrowScan::EnqueueLz4(Slot& s) {
     seq_at += hb[i].seq_cap;
   }
   if (is_zstd) {
-    auto* hz = reinterpret_cast<zstd::BlockInfo*>(s.h_lz4 + o_zblocks);
+    auto* hz = reinterpret_cast<zstd::BlockInfo*>(s.h_lz4.get() + o_zblocks);
     for (size_t i = 0; i < nb; i++) {
       hz[i] = d.zblocks[i];
       const bool in_scratch = hz[i].type == 1 || (hz[i].type == 2 && hz[i].lit_type != 0);
@@ -1052,7 +966,7 @@ void ArrowScan::EnqueueLz4(Slot& s) {
   int64_t lo = -1, hi = -1;
   auto flush = [&]() {
     if (lo < 0) return;
-    MI_HIP_CHECK(hipMemcpyAsync(s.d_comp + lo, d.comp + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
+    MI_HIP_CHECK(hipMemcpyAsync(s.d_comp.get() + lo, d.comp + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
     stats.h2d_bytes += hi - lo;
   };
   if (is_zstd) stats.zstd_batches_on_device++;
@@ -1068,25 +982,25 @@ void ArrowScan::EnqueueLz4(Slot& s) {
     hi = r.first + r.second;
   }
   flush();
-  MI_HIP_CHECK(hipMemcpyAsync(s.d_lz4, s.h_lz4, tables_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
+  MI_HIP_CHECK(hipMemcpyAsync(s.d_lz4.get(), s.h_lz4.get(), tables_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
   MI_HIP_CHECK(hipEventRecord(s.h2d_done, ctx->h2d_stream));
   hipStream_t q = s.lz4_stream;
   MI_HIP_CHECK(hipStreamWaitEvent(q, s.h2d_done, 0));
   // ONE memset per record batch: counters, status, marks.  The link words need none (every word a stage reads was written
   // by the stage before it), nor does the body: the bytes between its buffers are padding nobody reads.
-  MI_HIP_CHECK(hipMemsetAsync(s.d_lz4 + tables_bytes, 0, counters_end - tables_bytes, q));
+  MI_HIP_CHECK(hipMemsetAsync(s.d_lz4.get() + tables_bytes, 0, counters_end - tables_bytes, q));
   for (auto& f : d.buffers)
     if (f.raw && f.out_len > 0)
-      MI_HIP_CHECK(hipMemcpyAsync(s.d_in + f.out_off, s.d_comp + f.comp_off, static_cast<size_t>(f.out_len), hipMemcpyDeviceToDevice, q));
+      MI_HIP_CHECK(hipMemcpyAsync(s.d_in.get() + f.out_off, s.d_comp.get() + f.comp_off, static_cast<size_t>(f.out_len), hipMemcpyDeviceToDevice, q));
   device::Lz4Args a;
   std::memset(&a, 0, sizeof(a));
-  a.comp = s.d_comp;
-  a.out = s.d_in;
+  a.comp = s.d_comp.get();
+  a.out = s.d_in.get();
   a.out_size = out_size;
   a.max_buffer_len = max_len;
   a.max_buffer_blocks = max_blocks;
-  a.blocks = reinterpret_cast<const device::Lz4BlockDev*>(s.d_lz4 + o_blocks);
-  a.buffers = reinterpret_cast<const device::Lz4BufferDev*>(s.d_lz4 + o_buffers);
+  a.blocks = reinterpret_cast<const device::Lz4BlockDev*>(s.d_lz4.get() + o_blocks);
+  a.buffers = reinterpret_cast<const device::Lz4BufferDev*>(s.d_lz4.get() + o_buffers);
   a.n_blocks = static_cast<uint32_t>(nb);
   a.n_buffers = static_cast<uint32_t>(nf);
   a.min_block_comp = 0xFFFFFFFFu;
@@ -1095,31 +1009,31 @@ void ArrowScan::EnqueueLz4(Slot& s) {
       a.max_block_comp = std::max(a.max_block_comp, blk.comp_size);
       a.min_block_comp = std::min(a.min_block_comp, blk.comp_size);
     }
-  a.seq = s.d_lz4 + o_seq;
-  a.seq_off = reinterpret_cast<uint32_t*>(s.d_lz4 + o_seqoff);
-  a.lane_out = reinterpret_cast<uint32_t*>(s.d_lz4 + o_lane_out);
-  a.lane_nseq = reinterpret_cast<uint32_t*>(s.d_lz4 + o_lane_n);
-  a.link = reinterpret_cast<uint32_t*>(s.d_lz4 + o_link);
-  a.block_out_size = reinterpret_cast<uint32_t*>(s.d_lz4 + o_bsize);
-  a.block_nseq = reinterpret_cast<uint32_t*>(s.d_lz4 + o_bnseq);
-  a.block_out_base = reinterpret_cast<uint64_t*>(s.d_lz4 + o_bbase);
-  a.chunk_base = reinterpret_cast<uint32_t*>(s.d_lz4 + o_chunk);
-  a.buffer_ok = reinterpret_cast<uint32_t*>(s.d_lz4 + o_bufok);
-  a.round_left = reinterpret_cast<uint32_t*>(s.d_lz4 + o_round);
-  a.mark = s.d_lz4 + o_mark;
-  a.skel = reinterpret_cast<uint32_t*>(s.d_lz4 + o_skel);
-  a.status = reinterpret_cast<uint32_t*>(s.d_lz4 + o_status);
-  a.zblocks = is_zstd ? s.d_lz4 + o_zblocks : nullptr;
-  a.literals = s.d_comp;
-  a.rep_state = is_zstd ? reinterpret_cast<uint32_t*>(s.d_lz4 + o_rep) : nullptr;
+  a.seq = s.d_lz4.get() + o_seq;
+  a.seq_off = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_seqoff);
+  a.lane_out = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_lane_out);
+  a.lane_nseq = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_lane_n);
+  a.link = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_link);
+  a.block_out_size = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_bsize);
+  a.block_nseq = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_bnseq);
+  a.block_out_base = reinterpret_cast<uint64_t*>(s.d_lz4.get() + o_bbase);
+  a.chunk_base = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_chunk);
+  a.buffer_ok = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_bufok);
+  a.round_left = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_round);
+  a.mark = s.d_lz4.get() + o_mark;
+  a.skel = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_skel);
+  a.status = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_status);
+  a.zblocks = is_zstd ? s.d_lz4.get() + o_zblocks : nullptr;
+  a.literals = s.d_comp.get();
+  a.rep_state = is_zstd ? reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_rep) : nullptr;
   const int64_t t_launch = trace ? TraceNow() : 0;
   MI_HIP_CHECK(device::LaunchLz4Decompress(a, ctx->num_cus, q));
   if (trace) {
     tr_k8_prep_ns += t_launch - t_k8;
     tr_k8_launch_ns += TraceNow() - t_launch;
   }
-  MI_HIP_CHECK(hipMemcpyAsync(&s.h_status[2], a.status, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-  MI_HIP_CHECK(hipMemcpyAsync(&s.h_status[4], a.round_left + 37, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>() + 2, a.status, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>() + 4, a.round_left + 37, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
   s.lz4_counted = false;
   MI_HIP_CHECK(hipEventRecord(s.lz4_done, q));
   MI_HIP_CHECK(hipStreamWaitEvent(ctx->stream, s.lz4_done, 0));
@@ -1136,16 +1050,16 @@ void ArrowScan::EnqueueStageB(Slot& s) {
   const int64_t n = b.length;
   const int64_t n_windows = (n + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
   int64_t total = 0;
-  for (int64_t w = 0; w < n_windows; w++) total += s.h_counts[w];
+  for (int64_t w = 0; w < n_windows; w++) total += s.h_counts.get<uint32_t>()[w];
   s.needs_stage_b = false;
   // a fresh planner pass for the projected columns: arena offsets relative to the compact region behind stage A's arrays
   BatchPlanner cp(s.planner.opts);
   cp.opts.zero_copy_direct = false;
   BatchPlacement where;
   where.batch = &b;
-  where.in_base = s.d_in;
-  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in)
-                                             : reinterpret_cast<uint64_t>(b.deferred ? s.h_mirror : b.body);
+  where.in_base = s.d_in.get();
+  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in.get())
+                                             : reinterpret_cast<uint64_t>(b.deferred ? s.h_mirror.get() : b.body);
   where.alloc_rows = total;
   where.dict_len = [&](int64_t id) -> int64_t {
     auto it = dicts.find(id);
@@ -1168,13 +1082,13 @@ void ArrowScan::EnqueueStageB(Slot& s) {
   }
   s.d2h_bytes = cp.arena_bytes;
   const size_t region_off = RoundUp(s.stage_a_bytes, 4096);
-  if (region_off + cp.arena_bytes + 64 > s.d_out_cap) throw InternalException("compact region exceeds the slot");
-  uint8_t* region = s.d_out + region_off;
+  if (region_off + cp.arena_bytes + 64 > s.d_out.size()) throw InternalException("compact region exceeds the slot");
+  uint8_t* region = s.d_out.get() + region_off;
   EnsureHostOut(s, s.d2h_bytes + 64);
   cp.Rebase(0, region, nullptr);
   for (auto& t : cp.tasks) {
-    t.sel = s.d_out + s.sel_off;
-    t.sel_count = s.d_out + s.sel_count_off;
+    t.sel = s.d_out.get() + s.sel_off;
+    t.sel_count = s.d_out.get() + s.sel_count_off;
   }
   hipStream_t st = ctx->stream;
   // validity words start as all ones (the gather kernel clears the NULLs); absent columns are all NULL
@@ -1189,16 +1103,16 @@ void ArrowScan::EnqueueStageB(Slot& s) {
     if (pn.valid_off >= 0) MI_HIP_CHECK(hipMemsetAsync(region + pn.valid_off, 0xFF, static_cast<size_t>((total + 63) / 64) * 8 + 8, st));
   }
   s.gather_plan->Set(cp.tasks.data(), static_cast<int32_t>(total > 0 ? cp.tasks.size() : 0), st);
-  MI_HIP_CHECK(hipMemsetAsync(s.gather_plan->d_status, 0, sizeof(uint32_t), st));
+  MI_HIP_CHECK(hipMemsetAsync(s.gather_plan->d_status.get(), 0, sizeof(uint32_t), st));
   if (total > 0) s.gather_plan->Launch(st);
   MI_HIP_CHECK(hipEventRecord(s.compute_done, st));
   MI_HIP_CHECK(hipStreamWaitEvent(ctx->d2h_stream, s.compute_done, 0));
   if (!opts.device_resident && s.d2h_bytes > 0 && total > 0) {
-    MI_HIP_CHECK(hipMemcpyAsync(s.h_out, region, s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
+    MI_HIP_CHECK(hipMemcpyAsync(s.h_out.get(), region, s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
     stats.d2h_bytes += static_cast<int64_t>(s.d2h_bytes);
   }
-  MI_HIP_CHECK(hipMemcpyAsync(&s.h_status[0], s.plan->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
-  MI_HIP_CHECK(hipMemcpyAsync(&s.h_status[1], s.gather_plan->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
+  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>(), s.plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
+  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>() + 1, s.gather_plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
   MI_HIP_CHECK(hipEventRecord(s.d2h_done, ctx->d2h_stream));
   // the chunk builder reads the compact layout from here on
   s.node_dict.assign(cp.nodes.size(), nullptr);
@@ -1216,7 +1130,7 @@ void ArrowScan::BuildVector(const Slot& s, int32_t node, size_t window, int64_t 
   const int64_t r0 = compact_rows >= 0 ? static_cast<int64_t>(window) * MI_VECTOR_SIZE : o.win[window];
   const int64_t r1 = compact_rows >= 0 ? r0 + compact_rows : o.win[window + 1];
   if (o.alias_body_off >= 0) {
-    const uint8_t* body = opts.device_resident ? s.d_in : s.batch.body;
+    const uint8_t* body = opts.device_resident ? s.d_in.get() : s.batch.body;
     v->data = const_cast<uint8_t*>(body) + o.alias_body_off + static_cast<size_t>(r0) * static_cast<size_t>(o.width);
     v->validity = nullptr;  // all valid
   } else {
@@ -1235,8 +1149,8 @@ void ArrowScan::BuildVector(const Slot& s, int32_t node, size_t window, int64_t 
   }
   if (o.kind == MI_K_DICT && s.node_dict[static_cast<size_t>(node)]) {
     const DictState& d = *s.node_dict[static_cast<size_t>(node)];
-    v->dictionary = opts.device_resident ? d.d_data : d.h_data;
-    v->dictionary_validity = static_cast<const mi_validity_t*>(opts.device_resident ? d.d_validity : d.h_validity);
+    v->dictionary = opts.device_resident ? d.d_data.get() : d.h_data.get();
+    v->dictionary_validity = static_cast<const mi_validity_t*>(opts.device_resident ? d.d_validity.get() : d.h_validity);
     v->dict_len = d.dict_len;
   }
   if (!o.children.empty()) {
@@ -1311,21 +1225,18 @@ std::shared_ptr<void> ArrowScan::LeaseStaging(size_t bytes, uint8_t** ptr) {
     if (producer_stop) throw IOException("scan closed while reading");
     // prefer a free buffer that is already large enough
     for (auto& x : staging)
-      if (!x.leased && x.cap >= bytes + 64) { st = &x; break; }
+      if (!x.leased && x.buf.size() >= bytes + 64) { st = &x; break; }
     if (!st)
       for (auto& x : staging)
         if (!x.leased) { st = &x; break; }
     st->leased = true;
   }
-  if (bytes + 64 > st->cap) {
+  if (bytes + 64 > st->buf.size()) {
     ctx->Bind();
-    if (st->p) RetireHost(st->p);
-    st->p = nullptr;
-    st->cap = RoundUp(GrowCap(bytes + 64, st->cap), 1 << 16);
-    MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&st->p), st->cap, hipHostMallocDefault));
+    Retire(Grow(st->buf, bytes + 64, GrownCapacity(bytes + 64, st->buf.size(), 1 << 16)));
   }
-  *ptr = st->p;
-  return std::shared_ptr<void>(st->p, [this, st](void*) {
+  *ptr = st->buf.get();
+  return std::shared_ptr<void>(st->buf.get(), [this, st](void*) {
     {
       std::lock_guard<std::mutex> lk(q_mu);
       st->leased = false;
@@ -1386,10 +1297,9 @@ void ArrowScan::ProducerLoop(int p) {
       reader->SetBodyAllocator([this](size_t bytes, MessageType type, uint8_t** ptr) -> std::shared_ptr<void> {
         if (type == MessageType::DICTIONARY_BATCH) {  // lives as long as the dictionary version that points into it
           ctx->Bind();
-          void* q = nullptr;
-          MI_HIP_CHECK(hipHostMalloc(&q, bytes + 64, hipHostMallocDefault));
-          *ptr = static_cast<uint8_t*>(q);
-          return std::shared_ptr<void>(q, [](void* x) { (void)hipHostFree(x); });
+          std::shared_ptr<void> body = Shared<PinnedBuffer>(bytes + 64);
+          *ptr = static_cast<uint8_t*>(body.get());
+          return body;
         }
         return LeaseStaging(bytes, ptr);
       });
@@ -1585,16 +1495,17 @@ bool ArrowScan::AcquireBatch(BatchRef* out) {
   inflight.pop_front();
   if (trace) tr_latency_ns += TraceNow() - s.tr_enqueued_ns;
   try {
+    const uint32_t* st = s.h_status.get<uint32_t>();
     if (s.batch.deferred && !s.lz4_counted) {
       s.lz4_counted = true;
-      stats.lz4_blocks += s.h_status[4];
-      stats.lz4_parse_rounds += s.h_status[6];
-      stats.lz4_parse_rounds_max = std::max<int64_t>(stats.lz4_parse_rounds_max, s.h_status[5]);
+      stats.lz4_blocks += st[4];
+      stats.lz4_parse_rounds += st[6];
+      stats.lz4_parse_rounds_max = std::max<int64_t>(stats.lz4_parse_rounds_max, st[5]);
     }
     uint32_t dict_status = 0;   // the decode of the dictionary versions this batch uses ran in front of it on the same stream
     for (auto& nd : s.node_dict)
-      if (nd && nd->h_status) dict_status |= nd->h_status[0];
-    ThrowForStatus(s.h_status[0] | s.h_status[1] | s.h_status[2] | dict_status);
+      if (nd && nd->h_status) dict_status |= nd->h_status.get<uint32_t>()[0];
+    ThrowForStatus(st[0] | st[1] | st[2] | dict_status);
   } catch (...) {
     s.busy = false;
     s.batch.owner.reset();
@@ -1608,7 +1519,7 @@ bool ArrowScan::AcquireBatch(BatchRef* out) {
   if (has_filter) {
     out->selected = 0;
     const int64_t n_windows = (s.nrows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
-    for (int64_t w = 0; w < n_windows; w++) out->selected += s.h_counts[w];
+    for (int64_t w = 0; w < n_windows; w++) out->selected += s.h_counts.get<uint32_t>()[w];
   }
   out->chunk_rows = s.compact ? out->selected : s.nrows;
   out->n_windows = static_cast<int32_t>((out->chunk_rows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE);
@@ -1625,7 +1536,7 @@ void ArrowScan::EnsureHostVectors(const BatchRef& ref) {
   Slot& s = slots[static_cast<size_t>(ref.slot)];
   if (s.host_vectors || opts.device_resident || s.compact || s.d2h_bytes == 0) return;
   ctx->Bind();
-  MI_HIP_CHECK(hipMemcpy(s.h_out, s.d_out, s.d2h_bytes, hipMemcpyDeviceToHost));
+  MI_HIP_CHECK(hipMemcpy(s.h_out.get(), s.d_out.get(), s.d2h_bytes, hipMemcpyDeviceToHost));
   stats.d2h_bytes += static_cast<int64_t>(s.d2h_bytes);
   s.host_vectors = true;
 }
@@ -1641,13 +1552,13 @@ void ArrowScan::DeviceColumn(const BatchRef& ref, size_t c, DeviceColumnView* ou
   out->kind = pn.kind;
   out->width = pn.width;
   out->null_count = pn.null_count;
-  out->d_data = pn.alias_body_off >= 0 ? s.d_in + pn.alias_body_off : s.d_out + pn.data_off;
-  out->d_validity = (pn.valid_off >= 0 && pn.null_count != 0) ? s.d_out + pn.valid_off : nullptr;
+  out->d_data = pn.alias_body_off >= 0 ? s.d_in.get() + pn.alias_body_off : s.d_out.get() + pn.data_off;
+  out->d_validity = (pn.valid_off >= 0 && pn.null_count != 0) ? s.d_out.get() + pn.valid_off : nullptr;
   if (pn.null_count != 0 && pn.valid_off < 0) return;
   if (pn.kind == MI_K_STR32 || pn.kind == MI_K_STR64) {
     if (dn.spans.size() < 3) return;
     out->offset_width = pn.kind == MI_K_STR64 ? 8 : 4;
-    out->d_heap = s.d_in + dn.spans[2].offset;
+    out->d_heap = s.d_in.get() + dn.spans[2].offset;
     out->ptr_base = pn.ptr_base;
     out->h_offsets = s.batch.body + dn.spans[1].offset;
     out->h_validity = dn.spans[0].length > 0 ? s.batch.body + dn.spans[0].offset : nullptr;
@@ -1662,7 +1573,7 @@ void ArrowScan::BuildChunk(const BatchRef& ref, int32_t window, ChunkStorage* st
   const int64_t row0 = static_cast<int64_t>(window) * MI_VECTOR_SIZE;
   const int64_t n = std::min<int64_t>(MI_VECTOR_SIZE, chunk_rows - row0);
   if (window < 0 || n <= 0) throw InvalidInputException("chunk window outside the record batch");
-  uint8_t* base = opts.device_resident ? (s.compact ? s.compact_region : s.d_out) : s.h_out;
+  uint8_t* base = opts.device_resident ? (s.compact ? s.compact_region : s.d_out.get()) : s.h_out.get();
   st->vectors.assign(out_columns.size(), mi_vector{});
   if (st->child_pool.size() < s.planner.nodes.size() + 1) st->child_pool.resize(s.planner.nodes.size() + 1);
   st->child_pool_used = 0;
@@ -1709,7 +1620,7 @@ void ArrowScan::BuildChunk(const BatchRef& ref, int32_t window, ChunkStorage* st
   out->source_rows = s.compact ? (window == 0 ? s.nrows : 0) : n;
   if (has_filter && !s.compact) {
     out->sel = reinterpret_cast<const mi_sel_t*>(base + s.sel_off) + row0;
-    out->sel_count = s.h_counts[window];
+    out->sel_count = s.h_counts.get<uint32_t>()[window];
   }
 }
 
@@ -1791,8 +1702,8 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
                     (w == 1 || w == 2 || w == 4 || w == 8) && c.field.type != MI_AT_FLOAT;
     if (!ok) throw InvalidInputException("Column '" + name + "' (" + c.field.DuckType() + ") is not a fixed-width integer-like column: the fused aggregate takes integers, DATE, TIME/TIMESTAMP and DECIMAL(<=18)");
   }
-  MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&agg.d_acc), 4 * sizeof(unsigned long long)));
-  MI_HIP_CHECK(hipMemsetAsync(agg.d_acc, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  agg.d_acc = DeviceBuffer(4 * sizeof(unsigned long long));
+  MI_HIP_CHECK(hipMemsetAsync(agg.d_acc.get(), 0, agg.d_acc.size(), ctx->stream));
   agg.on = true;
   agg.rows_scanned = 0;
   try {
@@ -1800,19 +1711,15 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
     while (AcquireBatch(&ref)) ReleaseBatch(ref);   // the pull loop only recycles slots: nothing is copied back
     unsigned long long acc[4] = {0, 0, 0, 0};
     MI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MI_HIP_CHECK(hipMemcpy(acc, agg.d_acc, sizeof(acc), hipMemcpyDeviceToHost));
+    MI_HIP_CHECK(hipMemcpy(acc, agg.d_acc.get(), sizeof(acc), hipMemcpyDeviceToHost));
     out->sum_lo = acc[0];
     out->sum_hi = static_cast<int64_t>(acc[1]);
     out->rows_selected = static_cast<int64_t>(acc[2]);
     out->rows_scanned = agg.rows_scanned;
   } catch (...) {
-    (void)hipFree(agg.d_acc);
-    agg.d_acc = nullptr;
     agg.on = false;
     throw;
   }
-  MI_HIP_CHECK(hipFree(agg.d_acc));
-  agg.d_acc = nullptr;
   agg.on = false;
 }
 

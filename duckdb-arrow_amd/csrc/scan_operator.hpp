@@ -165,13 +165,13 @@ class ArrowScan : public ScanBase {
   //! One immutable version of a decoded dictionary (dict_len + 1 entries, the last one NULL).  Record batches keep the
   //! version they were enqueued with, so a later replacement / delta never changes what an in-flight batch sees.
   struct DictState {
-    void* d_data = nullptr;        // decoded values on the device
-    void* d_validity = nullptr;
-    void* h_data = nullptr;        // pinned host copy (host consumers)
+    DeviceBuffer d_data;           // decoded values on the device
+    DeviceBuffer d_validity;
+    PinnedBuffer h_data;           // pinned host copy (host consumers)
     void* h_validity = nullptr;    // == h_words for host consumers
-    uint64_t* h_words = nullptr;   // pinned: the validity words as built on the host (uploaded from here)
-    uint32_t* h_status = nullptr;  // pinned: status word of the decode of the values, checked with the first batch that uses them
-    hipEvent_t uploaded = nullptr; // the dictionary body is in HBM
+    PinnedBuffer h_words;          // the validity words (uint64_t) as built on the host (uploaded from here)
+    PinnedBuffer h_status;         // status word (uint32_t) of the decode of the values, checked with the first batch that uses them
+    HipEvent uploaded;             // the dictionary body is in HBM
     std::unique_ptr<Plan> decode_plan;   // kept until the version dies: its status word is read asynchronously
     std::vector<std::shared_ptr<void>> d_heaps;      // device copies of the dictionary bodies (long string payload)
     std::vector<std::shared_ptr<void>> host_bodies;  // host bodies: long dictionary strings point into them
@@ -182,18 +182,17 @@ class ArrowScan : public ScanBase {
     std::vector<std::string> host_strings;
     std::vector<char> host_valid;
     std::map<size_t, std::shared_ptr<void>> match_maps;   // filter leaf -> device byte per entry: 0 no, 1 yes, 2 NULL
-    ~DictState();
   };
   struct Slot {
     int64_t tr_enqueued_ns = 0;       // MI_SCAN_TRACE: when the batch was submitted
     // one record batch in flight
-    uint8_t* d_in = nullptr;   size_t d_in_cap = 0;    // body in HBM
-    uint8_t* d_out = nullptr;  size_t d_out_cap = 0;   // decoded vectors in HBM
-    uint8_t* h_out = nullptr;  size_t h_out_cap = 0;   // decoded vectors, pinned
+    DeviceBuffer d_in;                                 // body in HBM
+    DeviceBuffer d_out;                                // decoded vectors in HBM
+    PinnedBuffer h_out;                                // decoded vectors, pinned
     std::unique_ptr<Plan> plan;                        // full-width decode (all columns, or the filter columns when compacting)
     std::unique_ptr<Plan> gather_plan;                 // compaction: every projected column through the selection vector
-    uint32_t* h_status = nullptr;                      // pinned copy of the plans' device status words
-    hipEvent_t h2d_done = nullptr, compute_done = nullptr, d2h_done = nullptr, filter_done = nullptr;
+    PinnedBuffer h_status;                             // uint32_t: copies of the plans' device status words, K8 counters
+    HipEvent h2d_done, compute_done, d2h_done, filter_done;
     bool busy = false;
     DecodedBatch batch;
     int32_t source = 0;
@@ -203,25 +202,25 @@ class ArrowScan : public ScanBase {
     std::vector<int32_t> col_root;                     // per output column: planner node (-1: absent in this file)
     std::vector<std::pair<size_t, size_t>> absent;     // per output column absent in this file: {data_off, valid_off}
     std::vector<std::shared_ptr<DictState>> node_dict; // per planner node: the dictionary version this batch uses
-    uint8_t* h_aux = nullptr;  size_t h_aux_cap = 0;   // pinned: list window tables, string-view buffer tables, filter program
-    uint8_t* d_aux = nullptr;  size_t d_aux_cap = 0;
+    PinnedBuffer h_aux;                                // list window tables, string-view buffer tables, filter program
+    DeviceBuffer d_aux;
     size_t sel_off = 0, sel_count_off = 0;             // filter outputs (arena offsets)
     std::vector<int32_t> filter_root;                  // per filter column: planner node of its full-width decoded vector
-    uint32_t* h_counts = nullptr; size_t h_counts_cap = 0;  // pinned: rows selected per 2048-row window
+    PinnedBuffer h_counts;                             // uint32_t: rows selected per 2048-row window
     size_t d2h_bytes = 0;                              // bytes that travel back to the host
     size_t stage_a_bytes = 0;                          // arena bytes of the full-width arrays (+ sel, counts)
     bool compact = false;                              // chunks hold only the selected rows (dense arrays behind stage A's)
     bool host_vectors = false;                         // h_out holds the decoded vectors
     // K8: a record batch whose LZ4 buffers are decompressed in HBM (kernels_lz4.hip)
-    uint8_t* d_comp = nullptr;  size_t d_comp_cap = 0; // the compressed body
-    uint8_t* d_lz4 = nullptr;   size_t d_lz4_cap = 0;  // block / buffer tables, sequence descriptors, links, counters
-    uint8_t* h_lz4 = nullptr;   size_t h_lz4_cap = 0;  // pinned copy of the tables
-    hipStream_t lz4_stream = nullptr;                  // decompression of this slot overlaps the other slots' copies and kernels
-    hipEvent_t lz4_done = nullptr;
-    uint8_t* h_mirror = nullptr; size_t h_mirror_cap = 0;   // host consumers: pinned image of the decompressed body; only the
-                                                            // string payload buffers are filled (D2H), string_t rows point into it
+    DeviceBuffer d_comp;                               // the compressed body
+    DeviceBuffer d_lz4;                                // block / buffer tables, sequence descriptors, links, counters
+    PinnedBuffer h_lz4;                                // pinned copy of the tables
+    hipStream_t lz4_stream = nullptr;                  // decompression of this slot overlaps the other slots' copies and kernels;
+    HipStream own_lz4_stream;                          // lz4_stream is this one or a lower slot's (borrowed: never destroyed here)
+    HipEvent lz4_done;
+    PinnedBuffer h_mirror;                             // host consumers: pinned image of the decompressed body; only the
+                                                       // string payload buffers are filled (D2H), string_t rows point into it
     bool lz4_counted = true;
-    bool lz4_stream_shared = false;
     bool needs_stage_b = false;                        // compaction: the gather + copy back wait for the counts
     uint8_t* compact_region = nullptr;                 // device address of the dense arrays
   };
@@ -241,8 +240,7 @@ class ArrowScan : public ScanBase {
     std::exception_ptr error;         // raised where the consumer reaches it, after the batches read before it
   };
   struct Staging {                    // pinned body buffers, leased to one record batch at a time
-    uint8_t* p = nullptr;
-    size_t cap = 0;
+    PinnedBuffer buf;
     bool leased = false;
   };
   void StartProducer();
@@ -273,7 +271,6 @@ class ArrowScan : public ScanBase {
   void UploadAux(Slot& s, const std::vector<uint64_t>& aux);
   void BuildVector(const Slot& s, int32_t node, size_t window, int64_t compact_rows, uint8_t* base, ChunkStorage* st, mi_vector* out);
   void DecodeDictionary(Source& src, const DecodedBatch& b);
-  void EnsureSlotBuffers(Slot& s, size_t in_bytes, size_t out_bytes);
   void EnsureHostOut(Slot& s, size_t bytes);
   Slot* FreeSlot();
 
@@ -304,7 +301,7 @@ class ArrowScan : public ScanBase {
     int32_t col_a = -1, col_b = -1;
     std::vector<int32_t> filter_cols;
     std::vector<int64_t> lo, hi;
-    unsigned long long* d_acc = nullptr;   // {sum lo, sum hi, rows selected}
+    DeviceBuffer d_acc;                    // unsigned long long {sum lo, sum hi, rows selected}
     int64_t rows_scanned = 0;
   } agg;
   // constant columns (filename / hive): 2048 string_t each per source, host
@@ -318,15 +315,15 @@ class ArrowScan : public ScanBase {
   FilterCnf filter;
   //! filter column k -> output column (>= 0) or ~index into filter_only_columns (< 0)
   std::vector<int32_t> filter_columns;
-  // Buffers a slot has outgrown.  hipFree / hipHostFree wait for the device to go idle -- with the other slots' record batches
+  // Buffers a slot has outgrown.  Freeing a buffer waits for the device to go idle -- with the other slots' record batches
   // in flight that is a pipeline stall of milliseconds -- so they are kept until the scan closes (growth is geometric: at
   // most twice the final sizes in all).
-  std::vector<void*> retired_device, retired_host;
+  std::vector<DeviceBuffer> retired_device;
+  std::vector<PinnedBuffer> retired_host;
   std::mutex retire_mu;   // the pipeline thread and the producers (staging buffers) both retire
-  void RetireDevice(void* p) { std::lock_guard<std::mutex> lk(retire_mu); retired_device.push_back(p); }
-  void RetireHost(void* p) { std::lock_guard<std::mutex> lk(retire_mu); retired_host.push_back(p); }
-  static size_t GrowCap(size_t need, size_t cap) { return std::max(need + need / 4, cap + cap / 2); }   // record batches of a file differ by a few percent
-  std::vector<void*> d_in_lists;         // per leaf (clause order): its IN-list in HBM, or NULL
+  void Retire(DeviceBuffer b) { if (b) { std::lock_guard<std::mutex> lk(retire_mu); retired_device.push_back(std::move(b)); } }
+  void Retire(PinnedBuffer b) { if (b) { std::lock_guard<std::mutex> lk(retire_mu); retired_host.push_back(std::move(b)); } }
+  std::vector<DeviceBuffer> d_in_lists;  // per leaf (clause order): its IN-list in HBM, or empty
   bool compact = false;
   bool keep_on_device = false;
   mi_scan_stats stats{};

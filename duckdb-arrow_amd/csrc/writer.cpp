@@ -45,28 +45,12 @@ struct ScopedTimer {
 constexpr size_t kBufferAlign = 64;  // Arrow's recommended buffer alignment; any multiple of 8 is valid IPC
 size_t RoundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-template <typename T>
-void GrowPinned(T** p, size_t* cap_bytes, size_t need_bytes, size_t keep_bytes) {
-  if (need_bytes <= *cap_bytes && *p) return;
-  // a quarter of headroom: row groups of one table differ by a few percent, and growing means hipHostFree / hipFree, which
-  // wait for the device to go idle -- with the other sink threads' row groups in flight a stall of milliseconds
-  size_t ncap = RoundUp(std::max(need_bytes + need_bytes / 4, *cap_bytes + *cap_bytes / 2), 1 << 16);
-  void* np = nullptr;
-  MI_HIP_CHECK(hipHostMalloc(&np, ncap, hipHostMallocDefault));
-  if (*p) {
-    std::memcpy(np, *p, std::min(keep_bytes, *cap_bytes));
-    MI_HIP_CHECK(hipHostFree(*p));
-  }
-  *p = static_cast<T*>(np);
-  *cap_bytes = ncap;
-}
-
-void GrowDevice(uint8_t** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return;
-  if (*p) MI_HIP_CHECK(hipFree(*p));
-  *p = nullptr;
-  *cap = RoundUp(std::max(need + need / 4, *cap + *cap / 2), 1 << 16);
-  MI_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), *cap));
+// The sink's buffers grow by GrownCapacity -- a quarter of headroom: row groups of one table differ by a few percent, and
+// the outgrown buffer is freed at once, which waits for the device to go idle (with the other sink threads' row groups in
+// flight a stall of milliseconds).  `keep_bytes`: what the new buffer starts with (pinned buffers).
+template <typename Buffer>
+void Fit(Buffer& buf, size_t need, size_t keep_bytes = 0) {
+  Grow(buf, need, GrownCapacity(need, buf.size(), 1 << 16), keep_bytes);
 }
 
 // DuckDB logical type -> how the vector is laid out and which K7 kernel encodes it
@@ -139,27 +123,15 @@ int32_t ChunkCollection::AddField(const ArrowField& f, int32_t depth) {
   return idx;
 }
 
-ChunkCollection::~ChunkCollection() {
-  for (auto& c : columns) {
-    if (c.data) (void)hipHostFree(c.data);
-    if (c.validity) (void)hipHostFree(c.validity);
-    if (c.heap) (void)hipHostFree(c.heap);
-  }
-}
-
 void ChunkCollection::Reserve(Column& c, int64_t rows, int64_t extra_heap) {
   ctx->Bind();
   if (c.width > 0)
-    GrowPinned(&c.data, &c.data_cap, static_cast<size_t>(rows) * static_cast<size_t>(c.width) + 64,
-               static_cast<size_t>(c.count) * static_cast<size_t>(c.width));
-  const size_t old_vcap = c.validity_cap;
-  GrowPinned(&c.validity, &c.validity_cap, static_cast<size_t>((rows + 63) / 64) * 8 + 16, static_cast<size_t>((c.count + 63) / 64) * 8);
-  if (c.validity_cap != old_vcap) {
-    const size_t used = static_cast<size_t>((c.count + 63) / 64) * 8;
-    std::memset(reinterpret_cast<uint8_t*>(c.validity) + used, 0xFF, c.validity_cap - used);
-  }
-  if (extra_heap > 0)
-    GrowPinned(&c.heap, &c.heap_cap, static_cast<size_t>(c.heap_used + extra_heap) + 64, static_cast<size_t>(c.heap_used));
+    Fit(c.data, static_cast<size_t>(rows) * static_cast<size_t>(c.width) + 64, static_cast<size_t>(c.count) * static_cast<size_t>(c.width));
+  const size_t old_vcap = c.validity.size();
+  const size_t used = static_cast<size_t>((c.count + 63) / 64) * 8;
+  Fit(c.validity, static_cast<size_t>((rows + 63) / 64) * 8 + 16, used);
+  if (c.validity.size() != old_vcap) std::memset(c.validity.get() + used, 0xFF, c.validity.size() - used);
+  if (extra_heap > 0) Fit(c.heap, static_cast<size_t>(c.heap_used + extra_heap) + 64, static_cast<size_t>(c.heap_used));
 }
 
 void ChunkCollection::Append(const mi_data_chunk& chunk) {
@@ -214,7 +186,7 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
   }
   Reserve(columns[static_cast<size_t>(ni)], columns[static_cast<size_t>(ni)].count + n, extra_heap);
   Column& c = columns[static_cast<size_t>(ni)];  // (children are appended after this block: `columns` never grows here)
-  AppendBits(c.validity, c.count, v.validity, vbit, n);
+  AppendBits(c.validity.get<uint64_t>(), c.count, v.validity, vbit, n);
   if (v.validity && !c.has_nulls) {
     for (int64_t i = 0; i < n; i++)
       if (!BitAt(v.validity, vbit + i)) { c.has_nulls = true; break; }
@@ -229,7 +201,7 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
     // the list_entry_t rows are staged as they are (the GPU turns the lengths of the valid rows into Arrow offsets);
     // the child rows of every valid list are gathered here, in list order (ArrowListData::Append)
     const uint64_t* ent = static_cast<const uint64_t*>(v.data) + 2 * start;
-    std::memcpy(c.data + static_cast<size_t>(c.count) * 16, ent, static_cast<size_t>(n) * 16);
+    std::memcpy(c.data.get() + static_cast<size_t>(c.count) * 16, ent, static_cast<size_t>(n) * 16);
     int64_t run_start = 0, run_len = 0;
     const int32_t child = c.children[0];
     c.count += n;
@@ -254,14 +226,14 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
     if (run_len > 0) AppendNode(child, v.children[0], run_start, run_len);
     return;
   }
-  std::memcpy(c.data + static_cast<size_t>(c.count) * static_cast<size_t>(c.width),
+  std::memcpy(c.data.get() + static_cast<size_t>(c.count) * static_cast<size_t>(c.width),
               static_cast<const uint8_t*>(v.data) + static_cast<size_t>(start) * static_cast<size_t>(c.width),
               static_cast<size_t>(n) * static_cast<size_t>(c.width));
   if (c.enc_kind == MI_K_ENC_STR32) {
     c.payload_bytes += payload;
     if (extra_heap > 0) {
-      mi_string_t* dst = reinterpret_cast<mi_string_t*>(c.data) + c.count;
-      if (one_copy) std::memcpy(c.heap + c.heap_used, reinterpret_cast<const void*>(static_cast<uintptr_t>(region_lo)), static_cast<size_t>(extra_heap));
+      mi_string_t* dst = reinterpret_cast<mi_string_t*>(c.data.get()) + c.count;
+      if (one_copy) std::memcpy(c.heap.get() + c.heap_used, reinterpret_cast<const void*>(static_cast<uintptr_t>(region_lo)), static_cast<size_t>(extra_heap));
       int64_t at = c.heap_used;
       for (int64_t i = 0; i < n; i++) {   // the staged rows point at heap offsets
         if (!BitAt(v.validity, vbit + i)) continue;
@@ -271,7 +243,7 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
         if (one_copy) {
           dst[i].value.pointer.ptr = static_cast<uint64_t>(c.heap_used) + (p - region_lo);
         } else {
-          std::memcpy(c.heap + at, reinterpret_cast<const void*>(static_cast<uintptr_t>(p)), len);
+          std::memcpy(c.heap.get() + at, reinterpret_cast<const void*>(static_cast<uintptr_t>(p)), len);
           dst[i].value.pointer.ptr = static_cast<uint64_t>(at);
           at += len;
         }
@@ -291,7 +263,7 @@ void ChunkCollection::Reset() {
     c.ptr_base = 0;
     c.payload_bytes = 0;
     c.has_nulls = false;
-    if (c.validity) std::memset(c.validity, 0xFF, c.validity_cap);
+    if (c.validity) std::memset(c.validity.get(), 0xFF, c.validity.size());
   }
   count = 0;
   size_in_bytes = 0;
@@ -302,19 +274,8 @@ ColumnDataCollectionSerializer::ColumnDataCollectionSerializer(Context* ctx_p, b
   stream = ctx->stream;
   if (own_stream) {
     ctx->Bind();
-    MI_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    owns_stream = true;
+    stream = owned_stream = HipStream::Create();
   }
-}
-
-ColumnDataCollectionSerializer::~ColumnDataCollectionSerializer() {
-  h_bodies[cur_body] = h_body;
-  for (auto* b : h_bodies)
-    if (b) (void)hipHostFree(b);
-  plan.reset();
-  if (d_body) (void)hipFree(d_body);
-  if (d_in) (void)hipFree(d_in);
-  if (owns_stream && stream) (void)hipStreamDestroy(stream);
 }
 
 void ColumnDataCollectionSerializer::Init(const ArrowSchemaModel* schema_p) { schema = schema_p; }
@@ -380,12 +341,13 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
     in_bytes += RoundUp(static_cast<size_t>(c.heap_used) + 16, 256);
   }
   body_size = static_cast<int64_t>(body_off);
-  GrowDevice(&d_in, &d_in_cap, in_bytes + 256);
-  GrowDevice(&d_body, &d_body_cap, body_off + 256);
-  { size_t zero = 0; GrowPinned(&h_body, &h_body_cap, body_off + 256, zero); }
+  Fit(d_in, in_bytes + 256);
+  Fit(d_body, body_off + 256);
+  PinnedBuffer& h_body = bodies[cur_body];
+  Fit(h_body, body_off + 256);
 
   hipStream_t s = stream;
-  MI_HIP_CHECK(hipMemsetAsync(d_body, 0, body_off, s));  // the padding bytes of every buffer are zero
+  MI_HIP_CHECK(hipMemsetAsync(d_body.get(), 0, body_off, s));  // the padding bytes of every buffer are zero
   std::vector<mi_col_task> tasks;
   std::vector<int32_t> validity_task(n_nodes, -1);  // task whose NULL counter belongs to node ci
   for (size_t ci = 0; ci < n_nodes; ci++) {
@@ -395,48 +357,48 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
     const size_t sp = in_off[ci].first_span;
     const int64_t staged_rows = n;
     if (c.width > 0)
-      MI_HIP_CHECK(hipMemcpyAsync(d_in + in_off[ci].data, c.data, static_cast<size_t>(staged_rows) * static_cast<size_t>(c.width), hipMemcpyHostToDevice, s));
+      MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].data, c.data.get(), static_cast<size_t>(staged_rows) * static_cast<size_t>(c.width), hipMemcpyHostToDevice, s));
     if (c.has_nulls)
-      MI_HIP_CHECK(hipMemcpyAsync(d_in + in_off[ci].validity, c.validity, static_cast<size_t>((n + 63) / 64) * 8, hipMemcpyHostToDevice, s));
+      MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].validity, c.validity.get(), static_cast<size_t>((n + 63) / 64) * 8, hipMemcpyHostToDevice, s));
     if (c.heap_used)
-      MI_HIP_CHECK(hipMemcpyAsync(d_in + in_off[ci].heap, c.heap, static_cast<size_t>(c.heap_used), hipMemcpyHostToDevice, s));
+      MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].heap, c.heap.get(), static_cast<size_t>(c.heap_used), hipMemcpyHostToDevice, s));
     mi_col_task t;
     std::memset(&t, 0, sizeof(t));
     t.nrows = n;
-    t.validity = c.has_nulls ? d_in + in_off[ci].validity : nullptr;
-    t.out_validity = d_body + spans[sp].offset;
+    t.validity = c.has_nulls ? d_in.get() + in_off[ci].validity : nullptr;
+    t.out_validity = d_body.get() + spans[sp].offset;
     validity_task[ci] = static_cast<int32_t>(tasks.size());
     if (c.IsGroup()) {
       // struct / fixed_size_list: the node's own bitmap + NULL count
       t.kind = MI_K_ENC_VALIDITY;
-      t.buf1 = d_in + in_off[ci].validity;
-      t.out_data = d_body + spans[sp].offset;
+      t.buf1 = d_in.get() + in_off[ci].validity;
+      t.out_data = d_body.get() + spans[sp].offset;
       tasks.push_back(t);
       continue;
     }
     t.flags = c.large_offsets ? 1 : 0;
     if (c.IsList()) {  // list / map: bitmap + int32 (or int64) offsets from the staged list_entry_t rows
       t.kind = MI_K_ENC_LIST32;
-      t.buf1 = d_in + in_off[ci].data;
-      t.out_data = d_body + spans[sp + 1].offset;
+      t.buf1 = d_in.get() + in_off[ci].data;
+      t.out_data = d_body.get() + spans[sp + 1].offset;
       tasks.push_back(t);
       continue;
     }
     t.kind = c.enc_kind;
     t.param = c.param;
-    t.buf1 = d_in + in_off[ci].data;
-    t.out_data = d_body + spans[sp + 1].offset;
+    t.buf1 = d_in.get() + in_off[ci].data;
+    t.out_data = d_body.get() + spans[sp + 1].offset;
     if (c.enc_kind == MI_K_ENC_STR32) {
-      t.buf2 = d_in + in_off[ci].heap;
+      t.buf2 = d_in.get() + in_off[ci].heap;
       t.buf2_len = c.payload_bytes;
       t.ptr_base = c.ptr_base;
-      t.out_aux = d_body + spans[sp + 2].offset;
+      t.out_aux = d_body.get() + spans[sp + 2].offset;
     }
     tasks.push_back(t);
   }
   plan->Set(tasks.data(), static_cast<int32_t>(tasks.size()), s);
   plan->Launch(s);
-  MI_HIP_CHECK(hipMemcpyAsync(h_body, d_body, body_off, hipMemcpyDeviceToHost, s));
+  MI_HIP_CHECK(hipMemcpyAsync(h_body.get(), d_body.get(), body_off, hipMemcpyDeviceToHost, s));
   ThrowForStatus(plan->Status());  // synchronises the stream
   std::vector<int64_t> null_counts = plan->NullCounts(/*reset*/ true);
   std::vector<std::pair<int64_t, int64_t>> nodes;
@@ -1058,12 +1020,12 @@ void PumpScanParallel(mi_writer* w, ArrowScan* scan, int threads, int64_t* rows_
 // the host path (EnsureHostVectors + ChunkCollection) on the pump thread, so the file is byte-identical to the
 // one-thread file in every case.
 struct FusedEncoder {
-  uint8_t* d_body = nullptr;  size_t d_cap = 0;
-  uint8_t* h_body = nullptr;  size_t h_cap = 0;
-  int64_t* h_nulls = nullptr; size_t h_nulls_cap = 0;   // pinned copy of the plan's NULL counters
-  uint32_t* h_status = nullptr;
+  DeviceBuffer d_body;
+  PinnedBuffer h_body;
+  PinnedBuffer h_nulls;     // int64_t: copy of the plan's NULL counters
+  PinnedBuffer h_status;    // uint32_t
   std::unique_ptr<Plan> plan;
-  hipEvent_t encoded = nullptr, done = nullptr;
+  HipEvent encoded, done;
   bool busy = false;
   // the row group in flight
   int64_t nrows = 0, body_size = 0;
@@ -1091,36 +1053,17 @@ void PumpScanFused(mi_writer* w, ArrowScan* scan, const BatchRef& first, int64_t
   ctx->Bind();
   auto local = MakeLocal(w);             // host path of row groups that straddle record batches
   constexpr int kEncoders = 4;
+  HipStream enc_stream = HipStream::Create();
+  HipStream back_stream = HipStream::Create();
   std::vector<FusedEncoder> enc(kEncoders);
-  hipStream_t enc_stream = nullptr, back_stream = nullptr;
-  // whatever ends this function, the device objects created below go away (the encoders' plans free themselves)
-  struct Cleanup {
-    std::vector<FusedEncoder>& enc;
-    hipStream_t& enc_stream;
-    hipStream_t& back_stream;
-    ~Cleanup() {
-      if (enc_stream) (void)hipStreamSynchronize(enc_stream);
-      if (back_stream) (void)hipStreamSynchronize(back_stream);
-      for (auto& e : enc) {
-        e.plan.reset();
-        if (e.d_body) (void)hipFree(e.d_body);
-        if (e.h_body) (void)hipHostFree(e.h_body);
-        if (e.h_nulls) (void)hipHostFree(e.h_nulls);
-        if (e.h_status) (void)hipHostFree(e.h_status);
-        if (e.encoded) (void)hipEventDestroy(e.encoded);
-        if (e.done) (void)hipEventDestroy(e.done);
-      }
-      if (enc_stream) (void)hipStreamDestroy(enc_stream);
-      if (back_stream) (void)hipStreamDestroy(back_stream);
-    }
-  } cleanup{enc, enc_stream, back_stream};
-  MI_HIP_CHECK(hipStreamCreateWithFlags(&enc_stream, hipStreamNonBlocking));
-  MI_HIP_CHECK(hipStreamCreateWithFlags(&back_stream, hipStreamNonBlocking));
+  // whatever ends this function, the GPU is done with the encoders' buffers before they go
+  struct SyncStreams { hipStream_t a, b; ~SyncStreams() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } };
+  SyncStreams sync_streams{enc_stream, back_stream};
   for (auto& e : enc) {
     e.plan = std::make_unique<Plan>(ctx);
-    MI_HIP_CHECK(hipEventCreateWithFlags(&e.encoded, hipEventDisableTiming));
-    MI_HIP_CHECK(hipEventCreateWithFlags(&e.done, hipEventDisableTiming));
-    MI_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e.h_status), 64, hipHostMallocDefault));
+    e.encoded = HipEvent::Create();
+    e.done = HipEvent::Create();
+    e.h_status = PinnedBuffer(64);
   }
   ChunkStorage storage;
   mi_data_chunk chunk;
@@ -1167,12 +1110,12 @@ void PumpScanFused(mi_writer* w, ArrowScan* scan, const BatchRef& first, int64_t
             }
           }
           cv.notify_all();
-          ThrowForStatus(e.h_status[0]);
-          const std::vector<int64_t> nulls = e.plan->MapNullCounts(e.h_nulls);
+          ThrowForStatus(e.h_status.get<uint32_t>()[0]);
+          const std::vector<int64_t> nulls = e.plan->MapNullCounts(e.h_nulls.get<int64_t>());
           std::vector<std::pair<int64_t, int64_t>> nodes;
           for (size_t c = 0; c < n_cols; c++) nodes.emplace_back(e.nrows, nulls[c]);
           job.header = EncodeRecordBatchMessage(e.nrows, nodes, e.spans, e.body_size);
-          job.body = e.h_body;
+          job.body = e.h_body.get();
           job.body_size = static_cast<size_t>(e.body_size);
         }
         const int64_t at = out.ReserveRowGroup(job.header.size() + job.body_size);
@@ -1287,9 +1230,9 @@ void PumpScanFused(mi_writer* w, ArrowScan* scan, const BatchRef& first, int64_t
       }
     }
     e.body_size = static_cast<int64_t>(body_off);
-    GrowDevice(&e.d_body, &e.d_cap, body_off + 256);
-    { size_t zero = 0; GrowPinned(&e.h_body, &e.h_cap, body_off + 256, zero); }
-    MI_HIP_CHECK(hipMemsetAsync(e.d_body, 0, body_off, enc_stream));
+    Fit(e.d_body, body_off + 256);
+    Fit(e.h_body, body_off + 256);
+    MI_HIP_CHECK(hipMemsetAsync(e.d_body.get(), 0, body_off, enc_stream));
     std::vector<mi_col_task> tasks(n_cols);
     for (size_t c = 0; c < n_cols; c++) {
       const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
@@ -1303,26 +1246,26 @@ void PumpScanFused(mi_writer* w, ArrowScan* scan, const BatchRef& first, int64_t
       t.flags = wc.large_offsets ? 1 : 0;
       t.buf1 = v.d_data + static_cast<size_t>(r0) * static_cast<size_t>(v.width);
       t.validity = v.d_validity ? v.d_validity + static_cast<size_t>(r0 / 64) * 8 : nullptr;   // r0 is a multiple of 2048
-      t.out_validity = e.d_body + e.spans[sp].offset;
-      t.out_data = e.d_body + e.spans[sp + 1].offset;
+      t.out_validity = e.d_body.get() + e.spans[sp].offset;
+      t.out_data = e.d_body.get() + e.spans[sp + 1].offset;
       if (wc.enc_kind == MI_K_ENC_STR32) {
         t.buf2 = v.d_heap;
         t.buf2_len = payload[c];
         t.ptr_base = v.ptr_base;
-        t.out_aux = e.d_body + e.spans[sp + 2].offset;
+        t.out_aux = e.d_body.get() + e.spans[sp + 2].offset;
       }
     }
     e.plan->Set(tasks.data(), static_cast<int32_t>(tasks.size()), enc_stream);
-    MI_HIP_CHECK(hipMemsetAsync(e.plan->d_status, 0, sizeof(uint32_t), enc_stream));
-    if (e.plan->n_null_counts) MI_HIP_CHECK(hipMemsetAsync(e.plan->d_null_counts, 0, static_cast<size_t>(e.plan->n_null_counts) * 8, enc_stream));
+    MI_HIP_CHECK(hipMemsetAsync(e.plan->d_status.get(), 0, sizeof(uint32_t), enc_stream));
+    if (e.plan->n_null_counts) MI_HIP_CHECK(hipMemsetAsync(e.plan->d_null_counts.get(), 0, static_cast<size_t>(e.plan->n_null_counts) * 8, enc_stream));
     e.plan->Launch(enc_stream);
     MI_HIP_CHECK(hipEventRecord(e.encoded, enc_stream));
     MI_HIP_CHECK(hipStreamWaitEvent(back_stream, e.encoded, 0));
-    MI_HIP_CHECK(hipMemcpyAsync(e.h_body, e.d_body, body_off, hipMemcpyDeviceToHost, back_stream));
-    { size_t zero = 0; GrowPinned(&e.h_nulls, &e.h_nulls_cap, static_cast<size_t>(e.plan->n_null_counts + 1) * 8, zero); }
+    MI_HIP_CHECK(hipMemcpyAsync(e.h_body.get(), e.d_body.get(), body_off, hipMemcpyDeviceToHost, back_stream));
+    Fit(e.h_nulls, static_cast<size_t>(e.plan->n_null_counts + 1) * 8);
     if (e.plan->n_null_counts)
-      MI_HIP_CHECK(hipMemcpyAsync(e.h_nulls, e.plan->d_null_counts, static_cast<size_t>(e.plan->n_null_counts) * 8, hipMemcpyDeviceToHost, back_stream));
-    MI_HIP_CHECK(hipMemcpyAsync(e.h_status, e.plan->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, back_stream));
+      MI_HIP_CHECK(hipMemcpyAsync(e.h_nulls.get(), e.plan->d_null_counts.get(), static_cast<size_t>(e.plan->n_null_counts) * 8, hipMemcpyDeviceToHost, back_stream));
+    MI_HIP_CHECK(hipMemcpyAsync(e.h_status.get(), e.plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, back_stream));
     MI_HIP_CHECK(hipEventRecord(e.done, back_stream));
     WriteJob job;
     job.enc = ei;

@@ -37,7 +37,6 @@ class ChunkCollection {
  public:
   //! fields as exported (LargeUtf8 / LargeBinary / LargeList nodes get int64 offsets)
   ChunkCollection(Context* ctx, const std::vector<ArrowField>& fields);
-  ~ChunkCollection();
   void Append(const mi_data_chunk& chunk);
   void Reset();
   int64_t Count() const { return count; }
@@ -50,9 +49,9 @@ class ChunkCollection {
     int32_t width = 0;       // bytes per staged row (list: 16 = one list_entry_t)
     int32_t depth = 0;
     int64_t count = 0;       // rows buffered in this node
-    uint8_t* data = nullptr;      size_t data_cap = 0;       // pinned
-    uint64_t* validity = nullptr; size_t validity_cap = 0;   // pinned words
-    uint8_t* heap = nullptr;      size_t heap_cap = 0;       // pinned payload of long strings (pointer = heap offset)
+    PinnedBuffer data;
+    PinnedBuffer validity;        // uint64_t words
+    PinnedBuffer heap;            // payload of long strings (pointer = heap offset)
     int64_t heap_used = 0;
     int64_t payload_bytes = 0;    // sum of valid string lengths = size of the Arrow data buffer (list: child rows gathered)
     bool has_nulls = false;
@@ -82,42 +81,33 @@ class ColumnDataCollectionSerializer {
  public:
   //! own_stream: the encode runs on a stream of its own (one serializer per sink thread: their H2D / K7 / D2H overlap)
   explicit ColumnDataCollectionSerializer(Context* ctx, bool own_stream = false);
-  ~ColumnDataCollectionSerializer();
   void Init(const ArrowSchemaModel* schema);
   void SerializeSchema();
   //! Serializes the collection as ONE record batch (header + body). Returns the number of messages (0 when empty).
   idx_t Serialize(ChunkCollection& buffer);
   const std::vector<uint8_t>& GetHeader() const { return header; }
-  const uint8_t* GetBody() const { return h_body; }
+  const uint8_t* GetBody() const { return bodies[cur_body].get(); }
   int CurrentBody() const { return cur_body; }
   //! The next Serialize() writes its body into the other pinned buffer (the stream writer hands the current one to its
   //! I/O thread); returns the index of the buffer that was current
   int SwapBody() {
-    const int was = cur_body;
-    h_bodies[cur_body] = h_body;
-    h_body_caps[cur_body] = h_body_cap;
     cur_body ^= 1;
-    h_body = h_bodies[cur_body];
-    h_body_cap = h_body_caps[cur_body];
-    return was;
+    return cur_body ^ 1;
   }
   int64_t GetBodySize() const { return body_size; }
   int64_t LastBytesRead() const { return plan ? plan->bytes_read : 0; }
 
  private:
   Context* ctx;
+  HipStream owned_stream;         // own_stream: the encode runs here, otherwise
+  hipStream_t stream = nullptr;   // on the context's compute stream
   const ArrowSchemaModel* schema = nullptr;
   std::vector<uint8_t> header;
-  uint8_t* h_body = nullptr;  size_t h_body_cap = 0;   // pinned; the current one of two
-  uint8_t* h_bodies[2] = {nullptr, nullptr};
-  size_t h_body_caps[2] = {0, 0};
+  PinnedBuffer bodies[2];         // the current one is bodies[cur_body]
   int cur_body = 0;
-  uint8_t* d_body = nullptr;  size_t d_body_cap = 0;
-  uint8_t* d_in = nullptr;    size_t d_in_cap = 0;
+  DeviceBuffer d_body, d_in;
   int64_t body_size = 0;
   std::unique_ptr<Plan> plan;
-  hipStream_t stream = nullptr;
-  bool owns_stream = false;
 };
 
 class ArrowStreamWriter {

@@ -17,6 +17,7 @@ void BatchPlanner::Clear() {
   aux.clear();
   upload.clear();
   aux_fixups.clear();
+  value_fixups.clear();
   arena_bytes = 0;
 }
 
@@ -70,6 +71,17 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
   if (!nd.field->Plan(&kind, &param, &w, &nb, nd.value_only))
     throw NotImplementedException("Arrow type " + nd.field->Format() + " of field '" + nd.field->name + "' is not decoded by the MI355X scan path");
   const int64_t n = nd.length;
+  if (kind == MI_K_RUN_END) {
+    // a list's child vector is cut into windows per chunk: runs would have to be split at them (DuckDB refuses it too)
+    for (int32_t a = parent; a >= 0; a = nodes[static_cast<size_t>(a)].parent) {
+      const int32_t at = nodes[static_cast<size_t>(a)].arrow_type;
+      if (at == MI_AT_LIST || at == MI_AT_LARGE_LIST || at == MI_AT_MAP || at == MI_AT_FIXED_LIST)
+        throw NotImplementedException("Column '" + nd.field->name + "': run-end encoded arrays inside a list / map / fixed_size_list are not decoded by the MI355X scan path");
+    }
+    if (nd.children.size() != 2) throw InternalException("run-end encoded field without exactly two children");
+  }
+  const DecodedNode* ree_values = kind == MI_K_RUN_END ? &b.nodes[static_cast<size_t>(nd.children[1])] : nullptr;
+  const bool scratch = parent >= 0 && nodes[static_cast<size_t>(parent)].kind == MI_K_RUN_END;  // values of a run-end array
   const int32_t idx = static_cast<int32_t>(nodes.size());
   nodes.emplace_back();
   auto span = [&](size_t k) { return k < nd.spans.size() ? nd.spans[k] : mi_buffer_span{0, 0}; };
@@ -87,12 +99,14 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
     o.source_node = ni;
     // reference behaviour for plain fixed-width columns: the vector aliases the Arrow buffer (DirectConversion) and an
     // array without NULLs leaves the ValidityMask unset
-    if (opts.zero_copy_direct && kind == MI_K_COPY && nd.null_count == 0 && parent_valid_off < 0 && nd.spans.size() > 1 &&
+    if (opts.zero_copy_direct && kind == MI_K_COPY && nd.null_count == 0 && parent_valid_off < 0 && nd.spans.size() > 1 && !scratch &&
         !(where.no_alias && (*where.no_alias)[static_cast<size_t>(ni)]) && extra_rows == 0 && where.alloc_rows < 0) {
       o.alias_body_off = nd.spans[1].offset;
       return idx;
     }
-    const bool all_valid = opts.unset_all_valid && nd.null_count == 0 && parent_valid_off < 0 && extra_rows == 0 && kind != MI_K_NULL;
+    // a run-end array's NULLs are its values' NULLs
+    const int64_t nulls = ree_values ? ree_values->null_count : nd.null_count;
+    const bool all_valid = opts.unset_all_valid && nulls == 0 && parent_valid_off < 0 && extra_rows == 0 && kind != MI_K_NULL;
     Alloc((where.alloc_rows >= 0 && nd.depth == 0 ? where.alloc_rows : n) + extra_rows, w, !all_valid, &o.data_off, &o.valid_off);
   }
   for (const auto& sp : nd.spans)
@@ -140,6 +154,34 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
       t.param2 = where.dict_len(nd.field->dict_id);
       break;
     }
+    case MI_K_RUN_END: {
+      // the values child decodes into a scratch vector of its own row space (one row per run) in an earlier slice of the plan
+      const DecodedNode& re = b.nodes[static_cast<size_t>(nd.children[0])];
+      const int64_t n_runs = re.length;
+      std::vector<int64_t> vwin;
+      for (int64_t r = 0; r < n_runs; r += MI_VECTOR_SIZE) vwin.push_back(r);
+      vwin.push_back(n_runs);
+      const int32_t vi = AddNode(where, nd.children[1], std::move(vwin), true, -1, 0, idx, 0);
+      const PlannedNode& v = nodes[static_cast<size_t>(vi)];
+      for (const auto& sp : re.spans)
+        if (sp.length > 0) upload.emplace_back(sp.offset, sp.length);
+      t.validity = nullptr;
+      t.null_count = 0;
+      if (v.valid_off >= 0 && v.null_count != 0) {
+        t.validity = OffsetHandle(v.valid_off);
+        t.null_count = v.null_count;
+      }
+      t.buf1 = where.in_base + (re.spans.size() > 1 ? re.spans[1].offset : 0);
+      t.buf2 = OffsetHandle(static_cast<int64_t>(v.data_off));
+      t.buf2_len = v.nrows;
+      t.param2 = n_runs;
+      t.ptr_base = v.ptr_base;
+      PlannedNode& o = nodes[static_cast<size_t>(idx)];
+      o.value_kind = v.kind;
+      o.null_count = v.null_count;
+      o.heap_size = v.heap_size;
+      break;
+    }
     case MI_K_LIST32: case MI_K_LIST64: {
       if (nd.children.size() != 1) throw InternalException("list field without exactly one child");
       t.param = b.nodes[static_cast<size_t>(nd.children[0])].length;
@@ -171,11 +213,12 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
     default: break;
   }
   nodes[static_cast<size_t>(idx)].ptr_base = t.ptr_base;
-  nodes[static_cast<size_t>(idx)].heap_size = kind == MI_K_FIXED_BINARY ? span(1).length : t.buf2_len;
+  if (kind != MI_K_RUN_END) nodes[static_cast<size_t>(idx)].heap_size = kind == MI_K_FIXED_BINARY ? span(1).length : t.buf2_len;
   // a struct without NULLs of its own or of a parent has nothing to compute when its validity stays unset
   const bool has_work = n > 0 && !(kind == MI_K_STRUCT && valid_off < 0);
   if (has_work) {
     if (aux_at >= 0) aux_fixups.emplace_back(tasks.size(), static_cast<size_t>(aux_at));
+    if (kind == MI_K_RUN_END) value_fixups.push_back(tasks.size());
     nodes[static_cast<size_t>(idx)].task = static_cast<int32_t>(tasks.size());
     tasks.push_back(t);
   }
@@ -208,6 +251,11 @@ void BatchPlanner::Rebase(size_t first_task, uint8_t* arena_base, const uint8_t*
   }
   for (auto& fx : aux_fixups)
     if (fx.first >= first_task) tasks[fx.first].buf2 = aux_base + fx.second * 8;
+  for (size_t i : value_fixups)
+    if (i >= first_task) {
+      tasks[i].buf2 = addr(const_cast<void*>(tasks[i].buf2));
+      tasks[i].validity = addr(const_cast<void*>(tasks[i].validity));
+    }
 }
 
 }  // namespace miarrow

@@ -35,6 +35,7 @@ struct PlannedNode {
   int64_t heap_size = 0;               //               bytes of that data buffer
   int32_t source_node = -1;            // index into DecodedBatch::nodes
   int32_t task = -1;                   // index into BatchPlanner::tasks (-1: no task -- empty, aliased or nothing to do)
+  int32_t value_kind = 0;              // MI_K_RUN_END: kind of the values child (decoded as scratch, not one of `children`)
 };
 
 struct PlannerOptions {
@@ -83,6 +84,7 @@ class BatchPlanner {
   int32_t AddNode(const BatchPlacement& where, int32_t ni, std::vector<int64_t> win, bool win_is_tiles, int64_t parent_valid_off,
                   int32_t parent_div, int32_t parent, int64_t extra_rows);
   std::vector<std::pair<size_t, size_t>> aux_fixups;      // (task index, first aux word)
+  std::vector<size_t> value_fixups;                       // MI_K_RUN_END tasks: buf2 / validity are arena offsets too
   friend class HbmStream;
 };
 

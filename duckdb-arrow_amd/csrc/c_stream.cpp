@@ -153,6 +153,26 @@ void ValidateNodeFull(const DecodedBatch& b, const DecodedNode& nd, const std::m
     case MI_K_STR64: CheckOffsets<int64_t>(b, nd, nd.spans[2].length, "string"); break;
     case MI_K_LIST32: CheckOffsets<int32_t>(b, nd, b.nodes[static_cast<size_t>(nd.children[0])].length, "list"); break;
     case MI_K_LIST64: CheckOffsets<int64_t>(b, nd, b.nodes[static_cast<size_t>(nd.children[0])].length, "list"); break;
+    case MI_K_RUN_END: {
+      // run ends positive, strictly increasing, the last one at least the array's length (the device checks the same)
+      const DecodedNode& re = b.nodes[static_cast<size_t>(nd.children[0])];
+      const int rw = static_cast<int>(param & 0xFF);
+      const uint8_t* e = b.body + re.spans[1].offset;
+      int64_t prev = 0;
+      bool ok = re.length > 0 || nd.length == 0;
+      for (int64_t i = 0; i < re.length && ok; i++) {
+        int64_t v;
+        if (rw == 2) { int16_t x; std::memcpy(&x, e + 2 * i, 2); v = x; }
+        else if (rw == 4) { int32_t x; std::memcpy(&x, e + 4 * i, 4); v = x; }
+        else std::memcpy(&v, e + 8 * i, 8);
+        ok = v > prev;
+        prev = v;
+      }
+      if (!ok || (re.length > 0 && prev < nd.length))
+        throw IOException("Arrow IPC validation failed: run ends of '" + nd.field->name +
+                          "' are not positive and strictly increasing or end before the array does");
+      break;
+    }
     case MI_K_STRVIEW: {
       const uint8_t* v = b.body + nd.spans[1].offset;
       const uint64_t* valid = nd.spans[0].length ? reinterpret_cast<const uint64_t*>(b.body + nd.spans[0].offset) : nullptr;

@@ -103,6 +103,7 @@ int OutWidth(int32_t kind, int64_t param) {
     case MI_K_STRVIEW: case MI_K_LIST32: case MI_K_LIST64: return 16;
     case MI_K_STRUCT: return 0;
     case MI_K_DICT: return 4;
+    case MI_K_RUN_END: return static_cast<int>((param >> 8) & 0xFF);
     default: return 0;
   }
 }
@@ -111,7 +112,7 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
   auto fail = [&](const std::string& what) {
     throw InvalidInputException("task " + std::to_string(i) + ": " + what);
   };
-  if (device::ClassOfKind(t.kind) < 0) fail("unknown kind " + std::to_string(t.kind));
+  if (t.kind != MI_K_RUN_END && device::ClassOfKind(t.kind) < 0) fail("unknown kind " + std::to_string(t.kind));
   if (t.sel != nullptr) {  // gather mode: decode only the rows a selection vector names, compacted per 2048-row window
     if (!device::KindCanGather(t.kind)) fail("kind " + std::to_string(t.kind) + " cannot be decoded through a selection vector");
     if (t.sel_count == nullptr) fail("gather tasks need sel_count (rows selected per 2048-row window)");
@@ -179,6 +180,16 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
     case MI_K_DURATION:
       if (t.param == 0) fail("duration factor must be non-zero");
       break;
+    case MI_K_RUN_END: {
+      const int64_t rw = t.param & 0xFF, w = (t.param >> 8) & 0xFF;
+      if (rw != 2 && rw != 4 && rw != 8) fail("RUN_END run-end width must be 2,4,8");
+      if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16) fail("RUN_END out width must be 1,2,4,8,16");
+      if (reinterpret_cast<uintptr_t>(t.buf1) % rw != 0) fail("run ends misaligned");
+      if (t.param2 <= 0) fail("RUN_END needs param2 = number of runs > 0");
+      if (t.buf2 == nullptr || reinterpret_cast<uintptr_t>(t.buf2) % 16 != 0) fail("RUN_END needs the decoded values (16-byte aligned) in buf2");
+      if (t.flags > 1) fail("RUN_END parents are structs (flags 0 or 1)");
+      break;
+    }
     case MI_K_ENC_COPY:
       if (t.param != 1 && t.param != 2 && t.param != 4 && t.param != 8 && t.param != 16) fail("ENC_COPY width must be 1,2,4,8,16");
       break;
@@ -198,9 +209,16 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
     fail("encode tasks need out_validity (the bitmap is always emitted; only a bare ENC_COPY of list offsets has none)");
 }
 
+// staging key of run-end tasks in Plan::Set (not a kernel class: they launch transcode_run_end, kernels_run_end.hip)
+constexpr int kRunEndSlot = device::kNumClasses;
+
 static int64_t TaskBytesRead(const mi_col_task& t) {
   const int64_t n = t.nrows;
   int64_t b = 0;
+  if (t.kind == MI_K_RUN_END) {  // run ends + every run's value and validity bit once (+ the parent's words)
+    b = t.param2 * ((t.param & 0xFF) + ((t.param >> 8) & 0xFF)) + (t.validity ? ((t.param2 + 63) / 64) * 8 : 0);
+    return b + (t.out_aux ? ((n + 63) / 64) * 8 : 0);
+  }
   if (t.kind < MI_K_ENC_COPY) {
     if (t.validity && t.null_count != 0) b += (n + 7) / 8;
     switch (t.kind) {
@@ -296,7 +314,9 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
   for (int32_t i = 0; i < n_tasks; i++) {
     ValidateTask(in_tasks[i], static_cast<size_t>(i));
     mi_col_task t = in_tasks[i];
-    const int cls = device::ClassOfTask(t);
+    // run-end expansion lives outside kernels_decode.hip: its bytes count under the misc class, its slices go last
+    const bool run_end = t.kind == MI_K_RUN_END;
+    const int cls = run_end ? static_cast<int>(device::kClassMisc) : device::ClassOfTask(t);
     if (t.kind >= MI_K_ENC_COPY) {
       is_encode = true;
       t.depth = 0;
@@ -310,14 +330,20 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
     class_rows[cls] += t.nrows;
     max_depth = std::max(max_depth, t.depth);
     staged.push_back(t);
-    staged_cls.push_back(cls);
+    staged_cls.push_back(run_end ? kRunEndSlot : cls);
   }
   n_null_counts = null_counter;
   order.assign(static_cast<size_t>(n_tasks), {0, 0});
+  // depth-major, shallow first (a child sees its parent's finished validity); then, in a slice of their own per depth after
+  // every other slice, the run-end expansions: they read the decoded vector of their values child, which is deeper than they are
+  for (int pass = 0; pass < 2; pass++)
   for (int depth = 0; depth <= max_depth; depth++) {
     for (int c = 0; c < device::kNumClasses; c++) {
+      if (pass == 1 && c != device::kClassMisc) continue;
+      const int want = pass == 0 ? c : kRunEndSlot;
       ClassSlice sl;
       sl.cls = c;
+      sl.run_end = pass == 1;
       sl.depth = depth;
       sl.first_task = static_cast<int32_t>(tasks.size());
       sl.tile_begin_at = static_cast<int32_t>(tile_begin.size());
@@ -326,14 +352,14 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
       uint64_t tiles = 0;
       uint32_t local_task = 0;
       for (size_t i = 0; i < staged.size(); i++) {
-        if (staged_cls[i] != c || staged[i].depth != depth) continue;
+        if (staged_cls[i] != want || staged[i].depth != depth) continue;
         const mi_col_task& t = staged[i];
         tile_begin.push_back(static_cast<uint32_t>(tiles));
         const uint64_t nt = static_cast<uint64_t>((t.nrows + tile_rows - 1) / tile_rows);
         tiles += nt;
         if (tiles > 0xFFFFFFF0ull) throw InvalidInputException("plan has too many tiles");
         tile_task.insert(tile_task.end(), static_cast<size_t>(nt), local_task);
-        if (c == device::kClassMisc) sl.misc_groups |= 1u << device::MiscGroupOfKind(t.kind);
+        if (c == device::kClassMisc && !sl.run_end) sl.misc_groups |= 1u << device::MiscGroupOfKind(t.kind);
         if (c == device::kClassDec128 || c == device::kClassString)   // which of the two kernel instances has tiles (device: tile_needs_mask)
           sl.misc_groups |= ((t.validity != nullptr && t.null_count != 0) || t.out_aux != nullptr) ? 2u : 1u;
         if (c == device::kClassEncString && t.kind == MI_K_ENC_LIST32) sl.misc_groups |= 2u;
@@ -399,6 +425,10 @@ void Plan::LaunchSlice(const ClassSlice& cs, hipStream_t s) {
   const uint32_t* tt = d_tile_task.get<uint32_t>() + cs.tile_task_at;
   uint32_t* status = d_status.get<uint32_t>();
   int64_t* null_counts = d_null_counts.get<int64_t>();
+  if (cs.run_end) {
+    MI_HIP_CHECK(device::LaunchRunEnd(t, tb, tt, cs.n_tasks, cs.total_tiles, status, s));
+    return;
+  }
   switch (cs.cls) {
     case device::kClassEncFixed:
       MI_HIP_CHECK(device::LaunchEncodeFixed(t, tb, tt, cs.n_tasks, cs.total_tiles, null_counts, s));
@@ -493,6 +523,8 @@ void ThrowForStatus(uint32_t bits) {
   if (bits & MI_ST_INDEX_RANGE) throw ConversionException("DuckDB only supports indices that fit on an uint32");
   if (bits & MI_ST_DICT_INDEX) throw InternalException("Arrow IPC validation failed: dictionary index out of range");
   if (bits & MI_ST_DECIMAL_RANGE) throw ConversionException("Decimal value does not fit the physical type of its declared precision");
+  if (bits & MI_ST_BAD_RUN_ENDS)
+    throw InternalException("Arrow IPC validation failed: run ends are not positive and strictly increasing or end before the array does");
   if (bits & MI_ST_DECOMPRESS)
     throw IOException("LZ4_FRAME compressed buffer is malformed or does not decompress to its declared size (Expected decompressed size mismatch)");
   if (bits & MI_ST_INTERNAL) throw InternalException("a kernel gave up waiting for another workgroup (bounded spin exceeded)");

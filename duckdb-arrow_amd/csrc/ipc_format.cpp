@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 #include "flatbuf.hpp"
 
@@ -56,6 +57,7 @@ std::string ArrowField::Format() const {
     case MI_AT_STRUCT: return "+s";
     case MI_AT_MAP: return "+m";
     case MI_AT_FIXED_LIST: std::snprintf(tmp, sizeof(tmp), "+w:%d", byte_width); return tmp;
+    case MI_AT_RUN_END: return "+r";
     default: return "?";
   }
 }
@@ -97,6 +99,7 @@ std::string ArrowField::DuckType() const {
         return "MAP(" + children[0].children[0].DuckType() + ", " + children[0].children[1].DuckType() + ")";
       return "MAP(?, ?)";
     }
+    case MI_AT_RUN_END: return children.size() == 2 ? children[1].DuckType() : "?";  // flattened, as DuckDB's Arrow scan reads it
     default: return "?";
   }
 }
@@ -160,6 +163,20 @@ bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, int32_t
     case MI_AT_LARGE_LIST: return set(MI_K_LIST64, 0, 16);
     case MI_AT_STRUCT: *n_buffers = 1; return set(MI_K_STRUCT, 0, 0);
     case MI_AT_FIXED_LIST: *n_buffers = 1; return set(MI_K_STRUCT, byte_width, 0);  // DuckDB ARRAY: validity + one child
+    case MI_AT_RUN_END: {
+      // no buffers of its own: run_ends (signed int16/32/64) and values (a flat kind, not dictionary-encoded) are its children
+      *n_buffers = 0;
+      if (children.size() != 2) return false;
+      const ArrowField& re = children[0];
+      const ArrowField& v = children[1];
+      if (re.type != MI_AT_INT || !re.is_signed || re.has_dictionary || (re.bit_width != 16 && re.bit_width != 32 && re.bit_width != 64))
+        return false;
+      int32_t vk, vw, vnb;
+      int64_t vp;
+      if (v.has_dictionary || !v.Plan(&vk, &vp, &vw, &vnb)) return false;
+      if (vk == MI_K_NULL || vk == MI_K_LIST32 || vk == MI_K_LIST64 || vk == MI_K_STRUCT || vk == MI_K_RUN_END) return false;
+      return set(MI_K_RUN_END, (re.bit_width / 8) | (static_cast<int64_t>(vw) << 8), vw);
+    }
     default: return false;
   }
 }
@@ -172,6 +189,20 @@ bool ArrowField::Supported(std::string* why) const {
     return false;
   }
   if (has_dictionary) return true;
+  if (type == MI_AT_LIST || type == MI_AT_LARGE_LIST || type == MI_AT_MAP || type == MI_AT_FIXED_LIST) {
+    // DuckDB's list vectors are windows of one child vector: a run-end encoded child would need its runs split per window
+    std::function<const ArrowField*(const ArrowField&)> find_ree = [&](const ArrowField& f) -> const ArrowField* {
+      if (f.type == MI_AT_RUN_END) return &f;
+      for (auto& c : f.children)
+        if (const ArrowField* hit = find_ree(c)) return hit;
+      return nullptr;
+    };
+    for (auto& c : children)
+      if (const ArrowField* hit = find_ree(c)) {
+        if (why) *why = "run-end encoded field '" + hit->name + "' inside the list / map / fixed_size_list '" + name + "'";
+        return false;
+      }
+  }
   for (auto& c : children)
     if (!c.Supported(why)) return false;
   return true;
@@ -188,7 +219,7 @@ int64_t ArrowField::CountBuffers() const {
   int64_t own;
   if (has_dictionary) return 2;
   switch (type) {
-    case MI_AT_NULL: own = 0; break;
+    case MI_AT_NULL: case MI_AT_RUN_END: own = 0; break;
     case MI_AT_STRUCT: case MI_AT_FIXED_LIST: own = 1; break;
     case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: own = 3; break;
     case MI_AT_UNION: own = 2; break;  // dense (sparse has 1): unions are outside the path

@@ -192,7 +192,21 @@ bool IPCStreamReader::GetNextBatch(DecodedBatch* out, bool accept_dictionaries, 
   }
   cur_deferred.reset();
   if (meta.compression != -1 && cur_size > 0) DecompressBody(&meta);
-  if (base_schema.endianness == 1 && cur_size > 0) SwapBodyEndianness(meta);
+  if (base_schema.endianness == 1) {
+    // the swap itself would be right (run_ends is an int child), but no test pins big-endian run-end encoded columns yet
+    for (size_t i = 0; i < base_schema.fields.size(); i++) {
+      const bool wanted = !HasProjection() || std::find(projected_columns.begin(), projected_columns.end(), static_cast<int32_t>(i)) != projected_columns.end();
+      std::function<bool(const ArrowField&)> has_ree = [&](const ArrowField& f) {
+        if (f.type == MI_AT_RUN_END) return true;
+        for (auto& c : f.children)
+          if (has_ree(c)) return true;
+        return false;
+      };
+      if (wanted && !meta.is_dictionary && has_ree(base_schema.fields[i]))
+        throw NotImplementedException("Column '" + base_schema.fields[i].name + "': run-end encoded arrays in a big-endian stream are not read");
+    }
+    if (cur_size > 0) SwapBodyEndianness(meta);
+  }
   SliceBatch(meta, out);
   if (cur_deferred) {
     out->deferred = cur_deferred;
@@ -832,7 +846,7 @@ static void SubtreeBufferBounds(const ArrowField& f, const RecordBatchMeta& meta
     return;
   }
   switch (f.type) {
-    case MI_AT_NULL: break;
+    case MI_AT_NULL: case MI_AT_RUN_END: break;  // run-end encoded: run_ends and values are children
     case MI_AT_STRUCT: case MI_AT_FIXED_LIST: out->push_back(bitmap); break;
     case MI_AT_UTF8: case MI_AT_BINARY: out->push_back(bitmap); out->push_back(rows(4, 1)); out->push_back((int64_t(1) << 31) + 64); break;
     case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: out->push_back(bitmap); out->push_back(rows(8, 1)); out->push_back(kLoose); break;
@@ -878,7 +892,7 @@ static bool CountSubtreeBuffers(const ArrowField& f, const RecordBatchMeta& meta
     return true;
   }
   switch (f.type) {
-    case MI_AT_NULL: break;
+    case MI_AT_NULL: case MI_AT_RUN_END: break;
     case MI_AT_STRUCT: case MI_AT_FIXED_LIST: *buffers += 1; break;
     case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: *buffers += 3; break;
     case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {
@@ -1007,7 +1021,7 @@ void SubtreeSwaps(const ArrowField& f, const RecordBatchMeta& meta, size_t* vari
     return;
   }
   switch (f.type) {
-    case MI_AT_NULL: break;
+    case MI_AT_NULL: case MI_AT_RUN_END: break;  // its run_ends child swaps as the int it is
     case MI_AT_STRUCT: case MI_AT_FIXED_LIST: out->push_back(Swap::NONE); break;
     case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LIST: case MI_AT_MAP:
       out->push_back(Swap::NONE);
@@ -1126,6 +1140,21 @@ void IPCStreamReader::SliceBatch(const RecordBatchMeta& meta, DecodedBatch* out)
     if (nulls < -1 || nulls > n) throw InternalException("Field node null_count " + std::to_string(nulls) + " is outside [0, length]");
     if (depth == 0 && !value_only && n != meta.length)
       throw InternalException("Expected array length " + std::to_string(meta.length) + " for column " + f.name + " but found " + std::to_string(n));
+    if (keep && f.type == MI_AT_RUN_END && !(f.has_dictionary && !value_only)) {
+      // structural checks that need only the metadata (the run ends themselves are checked on the device / by the exporter)
+      if (nulls != 0) throw InternalException("Run-end encoded column " + f.name + " has null_count " + std::to_string(nulls) + ", expected 0");
+      if (f.children.size() != 2)
+        throw InternalException("Run-end encoded column " + f.name + " has " + std::to_string(f.children.size()) + " children, expected 2 (run_ends, values)");
+      if (cur.node + 1 >= meta.nodes.size()) throw InternalException("RecordBatch has too few field nodes");
+      // the children's nodes follow right away: run_ends is always a leaf (an integer), values comes after it
+      const int64_t re_len = meta.nodes[cur.node].first, re_nulls = meta.nodes[cur.node].second;
+      const int64_t v_len = meta.nodes[cur.node + 1].first;
+      if (re_nulls != 0) throw InternalException("Run ends of column " + f.name + " have null_count " + std::to_string(re_nulls) + ", expected 0");
+      if (re_len != v_len)
+        throw InternalException("Run-end encoded column " + f.name + " has " + std::to_string(re_len) + " run ends but " + std::to_string(v_len) + " values");
+      if ((re_len == 0) != (n == 0))
+        throw InternalException("Run-end encoded column " + f.name + " of length " + std::to_string(n) + " has " + std::to_string(re_len) + " runs");
+    }
     if (keep && parent >= 0) {
       const DecodedNode& pn = out->nodes[static_cast<size_t>(parent)];
       const int32_t pt = pn.field->type;
@@ -1144,7 +1173,7 @@ void IPCStreamReader::SliceBatch(const RecordBatchMeta& meta, DecodedBatch* out)
       own = 2;
     } else {
       switch (f.type) {
-        case MI_AT_NULL: own = 0; break;
+        case MI_AT_NULL: case MI_AT_RUN_END: own = 0; break;  // run-end encoded: its data lives in its two children
         case MI_AT_STRUCT: case MI_AT_FIXED_LIST: own = 1; break;
         case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: own = 3; break;
         case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {

@@ -39,6 +39,11 @@ hipError_t LaunchTranscode(int cls, const mi_col_task* d_tasks, const uint32_t* 
 // 1 nested, 2 rare flat
 int MiscGroupOfKind(int32_t kind);
 
+// Run-end encoded columns (kernels_run_end.hip): MI_K_RUN_END tasks only, one workgroup per 2048-row tile.  Launched after
+// every other slice of the plan: the values child must be decoded first.
+hipError_t LaunchRunEnd(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task, int32_t n_tasks,
+                        uint32_t total_tiles, uint32_t* d_status, hipStream_t stream);
+
 //! Fused consumer: sum(a * b) over the rows that pass up to 4 conjunctive range filters, straight
 //! from the decoded vectors in HBM.  acc = {sum low 64 bits, sum high 64 bits (two's complement), rows selected}.
 struct AggSumProductArgs {

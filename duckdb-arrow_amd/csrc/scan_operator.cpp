@@ -257,20 +257,24 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
         }
         int32_t kind, w, nb;
         int64_t param;
+        // a run-end encoded column is filtered on its flat vector: what matters is the kind of its values
+        const ArrowField& vf = sc.field.type == MI_AT_RUN_END && sc.field.children.size() == 2 ? sc.field.children[1] : sc.field;
+        if (&vf != &sc.field && !sc.field.Plan(&kind, &param, &w, &nb))
+          throw NotImplementedException("Column '" + sc.name + "': Arrow type +r with these children is not decoded by the MI355X scan path");
         // IN () -- an empty range -- keeps nothing (its negation every valid row) whatever the column holds
         if (!leaf.is_string && leaf.op == device::kLeafRange && !leaf.lo_open && !leaf.hi_open && leaf.lo > leaf.hi) continue;
         if (leaf.is_string) {
           // byte-string constants: the column must decode to string_t rows that point into ONE data buffer
-          const bool value_ok = sc.field.Plan(&kind, &param, &w, &nb, /*value_only*/ true) && (kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY);
+          const bool value_ok = vf.Plan(&kind, &param, &w, &nb, /*value_only*/ true) && (kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY);
           if (!value_ok)
             throw NotImplementedException("string filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
                                           ") needs a utf8 / large_utf8 / binary / fixed_size_binary column (dictionary-encoded or not)");
           continue;
         }
-        const bool ok = sc.field.Plan(&kind, &param, &w, &nb) && !sc.field.has_dictionary &&
+        const bool ok = vf.Plan(&kind, &param, &w, &nb) && !vf.has_dictionary &&
                         (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
                          kind == MI_K_DIV_I64 || kind == MI_K_NARROW || kind == MI_K_BOOL) &&
-                        (w == 1 || w == 2 || w == 4 || w == 8) && sc.field.type != MI_AT_FLOAT;
+                        (w == 1 || w == 2 || w == 4 || w == 8) && vf.type != MI_AT_FLOAT;
         if (!ok)
           throw NotImplementedException("filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
                                         ") needs an integer / boolean / date / time / timestamp / decimal(<=18) column");
@@ -794,13 +798,17 @@ void ArrowScan::EnqueueBatch(Slot& s) {
         if (leaf.is_string) {
           // the rows' long-string pointers are consumer addresses (pn.ptr_base = byte 0 of the Arrow data buffer as the
           // consumer sees it); the kernel reads the bytes from the HBM copy of that buffer
-          const DecodedNode& dn = b.nodes[static_cast<size_t>(pn.source_node)];
-          const size_t data_span = pn.kind == MI_K_FIXED_BINARY ? 1 : 2;
+          const DecodedNode& src = b.nodes[static_cast<size_t>(pn.source_node)];
+          // run-end encoded: the rows point into the values child's data buffer
+          const DecodedNode& dn = pn.kind == MI_K_RUN_END ? b.nodes[static_cast<size_t>(src.children[1])] : src;
+          const int32_t vkind = pn.kind == MI_K_RUN_END ? pn.value_kind : pn.kind;
+          const size_t data_span = vkind == MI_K_FIXED_BINARY ? 1 : 2;
           L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(s.d_in.get() + (dn.spans.size() > data_span ? dn.spans[data_span].offset : 0)));
           L.hi = static_cast<int64_t>(pn.ptr_base);
           continue;
         }
-        if (sc.field.type == MI_AT_INT && !sc.field.is_signed) {
+        const ArrowField& vf = sc.field.type == MI_AT_RUN_END && sc.field.children.size() == 2 ? sc.field.children[1] : sc.field;
+        if (vf.type == MI_AT_INT && !vf.is_signed) {
           L.flags |= device::kLeafUnsigned;
           if (pn.width == 8 && leaf.op != device::kLeafIsNull && leaf.op != device::kLeafIsNotNull) {
             // uint64: compared through the order-preserving map x ^ 2^63 on both sides.  Constants arrive as int64, a
@@ -1143,7 +1151,8 @@ void ArrowScan::BuildVector(const Slot& s, int32_t node, size_t window, int64_t 
   v->kind = o.kind;
   v->out_width = o.width;
   v->count = r1 - r0;
-  if (o.kind == MI_K_STR32 || o.kind == MI_K_STR64 || o.kind == MI_K_FIXED_BINARY) {
+  const int32_t vk = o.kind == MI_K_RUN_END ? o.value_kind : o.kind;  // run-end encoded: the values' string heap
+  if (vk == MI_K_STR32 || vk == MI_K_STR64 || vk == MI_K_FIXED_BINARY) {
     v->heap = reinterpret_cast<const void*>(o.ptr_base);
     v->heap_size = o.heap_size;
   }

@@ -100,6 +100,9 @@ enum mi_kind {
                              buf2 = i64 window starts in this list's row space (NULL: windows are the 2048-row tiles) */
   MI_K_LIST64 = 20,       /* large_list */
   MI_K_STRUCT = 21,       /* struct / fixed_size_list: validity only (children are their own tasks) */
+  MI_K_RUN_END = 22,      /* run_end_encoded -> flat vector of the values' type; buf1 = run ends, param = run-end width (2,4,8) |
+                             out width << 8, param2 = number of runs; buf2 / validity = the values child's decoded vector and
+                             validity words (NULL: all valid), null_count != 0 when those words exist.  Runs after its values */
   /* encode direction (K7), used by mi_encode_* plans */
   MI_K_ENC_COPY = 32,     /* K7b fixed-width copy; param = width */
   MI_K_ENC_DEC128 = 33,   /* K7b int16/32/64 -> decimal128 sign extension; param = in width */
@@ -317,6 +320,7 @@ typedef struct mi_col_task {
 #define MI_ST_INTERNAL 128u       /* a kernel gave up waiting for another workgroup (bounded spin): results are not valid */
 #define MI_ST_DECOMPRESS 256u     /* a compressed buffer is malformed or does not expand to its declared length (EIO,
                                    * base_stream_reader.cpp:24-29) */
+#define MI_ST_BAD_RUN_ENDS 512u   /* run ends not positive and strictly increasing, or short of the array (FULL validation) */
 
 /* Uploads the task table to HBM (descriptor table + tile index) and returns a reusable plan.  One plan =
  * any number of (batch, column) tasks = ONE fused kernel launch per mi_plan_launch. */

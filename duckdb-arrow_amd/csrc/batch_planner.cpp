@@ -66,9 +66,9 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
                               int64_t parent_valid_off, int32_t parent_div, int32_t parent, int64_t extra_rows) {
   const DecodedBatch& b = *where.batch;
   const DecodedNode& nd = b.nodes[static_cast<size_t>(ni)];
-  int32_t kind, w, nb;
+  int32_t kind, w;
   int64_t param;
-  if (!nd.field->Plan(&kind, &param, &w, &nb, nd.value_only))
+  if (!nd.field->Plan(&kind, &param, &w, nd.value_only))
     throw NotImplementedException("Arrow type " + nd.field->Format() + " of field '" + nd.field->name + "' is not decoded by the MI355X scan path");
   const int64_t n = nd.length;
   if (kind == MI_K_RUN_END) {

@@ -165,9 +165,9 @@ int mi_reader_next_batch(mi_reader* r, int32_t accept_dictionaries, mi_batch* ou
       std::memset(&c, 0, sizeof(c));
       std::snprintf(c.name, sizeof(c.name), "%s", nd.field->name.c_str());
       c.arrow_type = nd.field->type;
-      int32_t kind = 0, w = 0, nb = 0;
+      int32_t kind = 0, w = 0;
       int64_t param = 0;
-      if (nd.field->Plan(&kind, &param, &w, &nb, nd.value_only)) {
+      if (nd.field->Plan(&kind, &param, &w, nd.value_only)) {
         c.kind = kind;
         c.out_width = w;
         c.param = param;

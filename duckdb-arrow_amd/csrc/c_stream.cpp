@@ -144,9 +144,9 @@ void CheckOffsets(const DecodedBatch& b, const DecodedNode& nd, int64_t limit, c
 }
 
 void ValidateNodeFull(const DecodedBatch& b, const DecodedNode& nd, const std::map<int64_t, std::shared_ptr<DictValues>>& dicts) {
-  int32_t kind, w, nb;
+  int32_t kind, w;
   int64_t param;
-  if (!nd.field->Plan(&kind, &param, &w, &nb, nd.value_only))
+  if (!nd.field->Plan(&kind, &param, &w, nd.value_only))
     throw NotImplementedException("Arrow type " + nd.field->Format() + " of field '" + nd.field->name + "' is not exported by this reader");
   switch (kind) {
     case MI_K_STR32: CheckOffsets<int32_t>(b, nd, nd.spans[2].length, "string"); break;

@@ -104,11 +104,10 @@ std::string ArrowField::DuckType() const {
   }
 }
 
-bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, int32_t* n_buffers, bool value_only) const {
+bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, bool value_only) const {
   *kind = 0;
   *param = 0;
   *out_width = 0;
-  *n_buffers = 2;
   if (has_dictionary && !value_only) {
     *kind = MI_K_DICT;
     *param = (dict_index_bit_width / 8) | (static_cast<int64_t>(dict_index_signed ? 1 : 0) << 8);
@@ -118,7 +117,7 @@ bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, int32_t
   auto set = [&](int32_t k, int64_t p, int32_t w) { *kind = k; *param = p; *out_width = w; return true; };
   switch (type) {
     case MI_AT_INT: return set(MI_K_COPY, bit_width / 8, bit_width / 8);
-    case MI_AT_NULL: *n_buffers = 0; return set(MI_K_NULL, 0, 1);
+    case MI_AT_NULL: return set(MI_K_NULL, 0, 1);
     case MI_AT_FLOAT:
       if (precision == 0) return set(MI_K_HALF_FLOAT, 0, 4);
       return set(MI_K_COPY, precision == 1 ? 4 : 8, precision == 1 ? 4 : 8);
@@ -155,25 +154,24 @@ bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, int32_t
       if (unit == 0) return set(MI_K_INTERVAL_MONTHS, 0, 16);
       if (unit == 2) return set(MI_K_INTERVAL_MDN, 0, 16);
       return false;  // day_time: upstream's conversion is not restated
-    case MI_AT_UTF8: case MI_AT_BINARY: *n_buffers = 3; return set(MI_K_STR32, 0, 16);
-    case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: *n_buffers = 3; return set(MI_K_STR64, 0, 16);
+    case MI_AT_UTF8: case MI_AT_BINARY: return set(MI_K_STR32, 0, 16);
+    case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: return set(MI_K_STR64, 0, 16);
     case MI_AT_FIXED_BINARY: return set(MI_K_FIXED_BINARY, byte_width, 16);
     case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: return set(MI_K_STRVIEW, 0, 16);  // + variadic data buffers
     case MI_AT_LIST: case MI_AT_MAP: return set(MI_K_LIST32, 0, 16);
     case MI_AT_LARGE_LIST: return set(MI_K_LIST64, 0, 16);
-    case MI_AT_STRUCT: *n_buffers = 1; return set(MI_K_STRUCT, 0, 0);
-    case MI_AT_FIXED_LIST: *n_buffers = 1; return set(MI_K_STRUCT, byte_width, 0);  // DuckDB ARRAY: validity + one child
+    case MI_AT_STRUCT: return set(MI_K_STRUCT, 0, 0);
+    case MI_AT_FIXED_LIST: return set(MI_K_STRUCT, byte_width, 0);  // DuckDB ARRAY: validity + one child
     case MI_AT_RUN_END: {
       // no buffers of its own: run_ends (signed int16/32/64) and values (a flat kind, not dictionary-encoded) are its children
-      *n_buffers = 0;
       if (children.size() != 2) return false;
       const ArrowField& re = children[0];
       const ArrowField& v = children[1];
       if (re.type != MI_AT_INT || !re.is_signed || re.has_dictionary || (re.bit_width != 16 && re.bit_width != 32 && re.bit_width != 64))
         return false;
-      int32_t vk, vw, vnb;
+      int32_t vk, vw;
       int64_t vp;
-      if (v.has_dictionary || !v.Plan(&vk, &vp, &vw, &vnb)) return false;
+      if (v.has_dictionary || !v.Plan(&vk, &vp, &vw)) return false;
       if (vk == MI_K_NULL || vk == MI_K_LIST32 || vk == MI_K_LIST64 || vk == MI_K_STRUCT || vk == MI_K_RUN_END) return false;
       return set(MI_K_RUN_END, (re.bit_width / 8) | (static_cast<int64_t>(vw) << 8), vw);
     }
@@ -181,10 +179,50 @@ bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, int32_t
   }
 }
 
+static ByteSwap SwapOfWidth(int32_t bytes) {
+  return bytes == 2 || bytes == 4 || bytes == 8 || bytes == 16 || bytes == 32 ? static_cast<ByteSwap>(bytes) : ByteSwap::NONE;
+}
+
+FieldLayout ArrowField::Layout(bool value_only) const {
+  constexpr BufferLayout validity{BufferRole::VALIDITY, 0, ByteSwap::NONE};
+  auto values = [&](int32_t width, ByteSwap swap) { return FieldLayout{2, {validity, {BufferRole::FIXED, width, swap}}}; };
+  auto ints = [&](int32_t width) { return values(width, SwapOfWidth(width)); };
+  auto offsets = [&](int32_t width, int32_t n) {
+    return FieldLayout{n, {validity, {BufferRole::OFFSETS, width, SwapOfWidth(width)}, {BufferRole::PAYLOAD, 1, ByteSwap::NONE}}};
+  };
+  if (has_dictionary && !value_only) return ints(dict_index_bit_width / 8);
+  switch (type) {
+    case MI_AT_NULL: case MI_AT_RUN_END: return {};  // run-end encoded: run_ends and values are its children
+    case MI_AT_STRUCT: case MI_AT_FIXED_LIST: return {1, {validity}};
+    case MI_AT_BOOL: return {2, {validity, {BufferRole::BITS, 0, ByteSwap::NONE}}};
+    case MI_AT_INT: case MI_AT_DECIMAL: return ints(bit_width / 8);
+    case MI_AT_FLOAT: return ints(precision == 0 ? 2 : precision == 1 ? 4 : 8);
+    case MI_AT_DATE: return ints(unit == 0 ? 4 : 8);
+    // the width follows the unit, as the decode does; the swap follows the declared bitWidth (the two agree in valid files)
+    case MI_AT_TIME: return values(unit == 0 || unit == 1 ? 4 : 8, SwapOfWidth(bit_width / 8));
+    case MI_AT_TIMESTAMP: case MI_AT_DURATION: return ints(8);
+    case MI_AT_INTERVAL:  // year_month: int32; day_time: two int32; month_day_nano: {int32, int32, int64}
+      return unit == 2 ? values(16, ByteSwap::MONTH_DAY_NANO) : values(unit == 0 ? 4 : unit == 1 ? 8 : 16, ByteSwap::W4);
+    case MI_AT_FIXED_BINARY: return values(byte_width, ByteSwap::NONE);
+    case MI_AT_UTF8: case MI_AT_BINARY: return offsets(4, 3);
+    case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: return offsets(8, 3);
+    case MI_AT_LIST: case MI_AT_MAP: return offsets(4, 2);
+    case MI_AT_LARGE_LIST: return offsets(8, 2);
+    case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {
+      FieldLayout l = values(16, ByteSwap::VIEW);
+      l.variadic = true;
+      return l;
+    }
+    case MI_AT_UNION:  // no validity: type ids, and offsets when dense (UnionMode 1)
+      return {unit == 1 ? 2 : 1, {{BufferRole::FIXED, 1, ByteSwap::NONE}, {BufferRole::FIXED, 4, ByteSwap::W4}}};
+    default: return values(16, ByteSwap::NONE);  // unknown: as wide as the widest fixed-width value, bytes
+  }
+}
+
 bool ArrowField::Supported(std::string* why) const {
-  int32_t kind, w, nb;
+  int32_t kind, w;
   int64_t param;
-  if (!Plan(&kind, &param, &w, &nb)) {
+  if (!Plan(&kind, &param, &w)) {
     if (why) *why = "Arrow type " + Format() + " of field '" + name + "'";
     return false;
   }
@@ -216,15 +254,9 @@ int64_t ArrowField::CountFields() const {
 }
 
 int64_t ArrowField::CountBuffers() const {
-  int64_t own;
-  if (has_dictionary) return 2;
-  switch (type) {
-    case MI_AT_NULL: case MI_AT_RUN_END: own = 0; break;
-    case MI_AT_STRUCT: case MI_AT_FIXED_LIST: own = 1; break;
-    case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: own = 3; break;
-    case MI_AT_UNION: own = 2; break;  // dense (sparse has 1): unions are outside the path
-    default: own = 2; break;           // validity + data / offsets (list, map) / views (+ variadic, outside the path)
-  }
+  // mi_field::n_buffers has always counted 2 for a union, dense or sparse (unions are outside the path)
+  int64_t own = type == MI_AT_UNION && !has_dictionary ? 2 : Layout().n;
+  if (has_dictionary) return own;  // its values and their children live in the dictionary batch
   for (auto& c : children) own += c.CountBuffers();
   return own;
 }
@@ -251,9 +283,9 @@ void FillCField(const ArrowField& f, int32_t flat_index, mi_field* out) {
   out->dict_index_bit_width = f.dict_index_bit_width;
   out->dict_index_signed = f.dict_index_signed;
   out->dict_id = f.dict_id;
-  int32_t kind, w, nb;
+  int32_t kind, w;
   int64_t param;
-  if (f.Plan(&kind, &param, &w, &nb)) {
+  if (f.Plan(&kind, &param, &w)) {
     out->kind = kind;
     out->param = param;
     out->out_width = w;

@@ -52,6 +52,31 @@ struct ConversionException : Exception {
 enum class MessageType : int32_t { UNINITIALIZED = 0, SCHEMA = 1, DICTIONARY_BATCH = 2, RECORD_BATCH = 3, TENSOR = 4, SPARSE_TENSOR = 5 };
 const char* MessageTypeString(MessageType t);  // base_stream_reader.cpp:296-313
 
+//! What one RecordBatch.buffers entry of a field node holds (Arrow columnar format, "Buffer Listing for Each Layout").
+enum class BufferRole : uint8_t {
+  VALIDITY,  // bitmap, one bit a row
+  BITS,      // boolean values, one bit a row
+  FIXED,     // `width` bytes a row: values, dictionary indices, 16-byte views, union type ids / offsets
+  OFFSETS,   // `width` (4 or 8) bytes for each of length + 1 rows
+  PAYLOAD,   // string / binary bytes, addressed by the OFFSETS buffer before it
+};
+//! How a big-endian producer stored the buffer (Arrow columnar format, "Endianness"): Wn = n-byte integers.
+enum class ByteSwap : uint8_t { NONE = 0, W2 = 2, W4 = 4, W8 = 8, W16 = 16, W32 = 32, MONTH_DAY_NANO = 100, VIEW = 101 };
+
+struct BufferLayout {
+  BufferRole role;
+  int32_t width;
+  ByteSwap swap;
+};
+
+//! The buffers a field node owns, in RecordBatch order.  View types own one more data buffer (bytes, no swap) per
+//! variadicBufferCounts entry; a field's children own theirs after it.
+struct FieldLayout {
+  int32_t n = 0;
+  BufferLayout buffers[3];
+  bool variadic = false;
+};
+
 struct ArrowField {
   std::string name;
   std::string timezone;
@@ -75,10 +100,12 @@ struct ArrowField {
   std::string Format() const;    // Arrow C data interface format string
   std::string DuckType() const;  // DuckDB logical type name
   // Transcode plan for the value type (ignoring dictionary encoding when value_only)
-  bool Plan(int32_t* kind, int64_t* param, int32_t* out_width, int32_t* n_buffers, bool value_only = false) const;
+  bool Plan(int32_t* kind, int64_t* param, int32_t* out_width, bool value_only = false) const;
+  // Buffers of this node (the dictionary's values when value_only, else its indices): the one place that knows them
+  FieldLayout Layout(bool value_only = false) const;
   bool Supported(std::string* why) const;  // this field and all its descendants can be decoded by the path
   int64_t CountFields() const;   // IPCStreamReader::CountFields (base_stream_reader.cpp:271-277)
-  int64_t CountBuffers() const;  // buffers this field and its children own in a RecordBatch body
+  int64_t CountBuffers() const;  // buffers this field and its children own in a RecordBatch body (no variadic ones)
 };
 
 struct ArrowSchemaModel {

@@ -494,9 +494,6 @@ void Lz4DecompressFrame(const Lz4Api& z, uint8_t* dst, int64_t n, const uint8_t*
 }
 }  // namespace
 
-static void SubtreeBufferBounds(const ArrowField& f, const RecordBatchMeta& meta, size_t* node, size_t* variadic, bool value_only,
-                                std::vector<int64_t>* out);
-
 // list / map columns: the planner samples their offsets on the host (child windows of every chunk), so their record batches
 // need the decompressed body in host memory
 static bool HasListField(const ArrowField& f) {
@@ -683,6 +680,96 @@ bool WalkZstdFrame(const uint8_t* body, int64_t frame_off, int64_t frame_len, ui
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ record-batch walk
+namespace {
+//! One field node of a record batch, in the depth-first order of RecordBatch.nodes
+struct WalkNode {
+  const ArrowField* field;
+  bool value_only;                  // the values of a dictionary batch
+  int32_t column;                   // the top-level column it belongs to
+  int32_t depth;
+  int64_t parent;                   // node index of its parent, -1 at the top
+  size_t node;                      // index into RecordBatch.nodes: may lie past its end
+  size_t first_buffer, n_buffers;   // its RecordBatch.buffers entries, layout.n then the variadic ones: may run past the end
+  FieldLayout layout;
+  const char* defect;               // its variadicBufferCounts entry is missing (counted as 0) or out of range (clamped)
+};
+
+struct WalkEnd {
+  size_t nodes = 0, buffers = 0, variadic = 0;  // entries the walk consumed
+  bool defect = false;                          // some node has a WalkNode::defect
+  bool unknown_dictionary = false;              // a DictionaryBatch whose id no field carries: nothing was visited
+};
+
+const ArrowField* FindDictionary(const ArrowField& f, int64_t id) {
+  if (f.has_dictionary && f.dict_id == id) return &f;
+  for (auto& c : f.children)
+    if (const ArrowField* hit = FindDictionary(c, id)) return hit;
+  return nullptr;
+}
+
+template <class Visit>
+void WalkField(const ArrowField& f, const RecordBatchMeta& meta, int32_t column, int64_t parent, int32_t depth, bool value_only,
+               WalkEnd* end, Visit& visit) {
+  WalkNode v{&f, value_only, column, depth, parent, end->nodes++, end->buffers, 0, f.Layout(value_only), nullptr};
+  v.n_buffers = static_cast<size_t>(v.layout.n);
+  if (v.layout.variadic) {
+    if (end->variadic >= meta.variadic_counts.size()) {
+      v.defect = "RecordBatch has too few variadicBufferCounts";
+    } else {
+      const int64_t vc = meta.variadic_counts[end->variadic++];
+      if (vc < 0 || vc > (1 << 20)) v.defect = "Invalid variadic buffer count";
+      v.n_buffers += static_cast<size_t>(std::min<int64_t>(std::max<int64_t>(vc, 0), 1 << 20));
+    }
+    end->defect |= v.defect != nullptr;
+  }
+  end->buffers += v.n_buffers;
+  visit(v);
+  if (f.has_dictionary && !value_only) return;  // its values and their children live in the dictionary batch
+  for (auto& c : f.children) WalkField(c, meta, column, static_cast<int64_t>(v.node), depth + 1, false, end, visit);
+}
+
+//! Visits every field node a RecordBatch (all columns) or a DictionaryBatch (the values of the field that carries its id,
+//! at any depth) covers, and keeps the cursors of RecordBatch.{nodes, buffers, variadicBufferCounts} in step.  It never
+//! throws: what the metadata lacks shows as an index past the end or as WalkNode::defect, and each caller decides --
+//! SliceBatch refuses the batch, the bound / swap / projection helpers fall back to what is safe.
+template <class Visit>
+WalkEnd WalkBatch(const std::vector<ArrowField>& fields, const RecordBatchMeta& meta, Visit&& visit) {
+  WalkEnd end;
+  for (size_t i = 0; i < fields.size(); i++) {
+    if (!meta.is_dictionary) {
+      WalkField(fields[i], meta, static_cast<int32_t>(i), -1, 0, false, &end, visit);
+    } else if (const ArrowField* owner = FindDictionary(fields[i], meta.dict_id)) {
+      WalkField(*owner, meta, static_cast<int32_t>(i), -1, 0, true, &end, visit);
+      return end;
+    }
+  }
+  end.unknown_dictionary = meta.is_dictionary;
+  return end;
+}
+
+// Upper bound of the UNCOMPRESSED size of buffer k of a node of n <= 2^40 rows: a compressed buffer declares its own
+// uncompressed length, and that number sizes an allocation (pinned, for scans) before a byte is decoded -- a few damaged
+// bytes must not be able to ask for terabytes.  Bitmaps, values and offsets are bounded by the row count, string data by
+// the offset width (2 GiB for int32 offsets); what is not known keeps 2^40.
+constexpr int64_t kLooseBound = int64_t(1) << 40;
+int64_t BufferBound(const FieldLayout& l, int32_t k, int64_t n) {
+  auto rows = [&](int64_t extra_rows) {
+    int64_t b = 0;
+    const int64_t per_row = l.buffers[k].width;
+    if (per_row <= 0 || __builtin_mul_overflow(n + extra_rows, per_row, &b) || b > kLooseBound) return kLooseBound;
+    return b + 64;
+  };
+  switch (l.buffers[k].role) {
+    case BufferRole::VALIDITY: case BufferRole::BITS: return (n + 7) / 8 + 64;
+    case BufferRole::FIXED: return rows(0);
+    case BufferRole::OFFSETS: return rows(1);
+    case BufferRole::PAYLOAD: return l.buffers[k - 1].width == 4 ? (int64_t(1) << 31) + 64 : kLooseBound;
+  }
+  return kLooseBound;
+}
+}  // namespace
+
 void IPCStreamReader::DecompressBody(RecordBatchMeta* meta) {
   if (meta->compression != 0 && meta->compression != 1) throw IOException("Unknown BodyCompression codec " + std::to_string(meta->compression));
   const bool lz4 = meta->compression == 0;
@@ -695,23 +782,12 @@ void IPCStreamReader::DecompressBody(RecordBatchMeta* meta) {
   // the projection are neither read (DecodeBody) nor decompressed
   const std::vector<char> needed = NeededBuffers(*meta);
   const size_t nbuf = meta->buffers.size();
-  std::vector<int64_t> bound;
-  {
-    size_t node = 0, variadic = 0;
-    if (meta->is_dictionary) {
-      std::function<const ArrowField*(const ArrowField&)> find = [&](const ArrowField& f) -> const ArrowField* {
-        if (f.has_dictionary && f.dict_id == meta->dict_id) return &f;
-        for (auto& c : f.children)
-          if (const ArrowField* hit = find(c)) return hit;
-        return nullptr;
-      };
-      for (auto& f : base_schema.fields)
-        if (const ArrowField* hit = find(f)) { SubtreeBufferBounds(*hit, *meta, &node, &variadic, true, &bound); break; }
-    } else {
-      for (auto& f : base_schema.fields) SubtreeBufferBounds(f, *meta, &node, &variadic, false, &bound);
-    }
-    if (bound.size() != nbuf) bound.assign(nbuf, int64_t(1) << 40);  // metadata the walk cannot follow: validation reports it
-  }
+  std::vector<int64_t> bound(nbuf, kLooseBound);
+  const WalkEnd walked = WalkBatch(base_schema.fields, *meta, [&](const WalkNode& v) {
+    const int64_t n = v.node < meta->nodes.size() ? std::max<int64_t>(0, std::min(meta->nodes[v.node].first, kLooseBound)) : kLooseBound;
+    for (int32_t k = 0; k < v.layout.n && v.first_buffer + k < nbuf; k++) bound[v.first_buffer + k] = BufferBound(v.layout, k, n);
+  });
+  if (walked.buffers != nbuf) bound.assign(nbuf, kLooseBound);  // metadata the walk cannot follow: validation reports it
   std::vector<int64_t> ulen(nbuf, 0), opos(nbuf, 0);
   int64_t total = 0;
   for (size_t i = 0; i < nbuf; i++) {
@@ -825,91 +901,6 @@ void IPCStreamReader::DecompressBody(RecordBatchMeta* meta) {
   meta->compression = -1;
 }
 
-// Upper bound of the UNCOMPRESSED size of every RecordBatch.buffers entry, from the field nodes alone: a compressed buffer
-// declares its own uncompressed length, and that number sizes an allocation (pinned, for scans) before a byte is decoded --
-// a few damaged bytes must not be able to ask for terabytes.  Validity, fixed-width data and offsets are bounded by the
-// node's row count; string data by the offset width (2 GiB for int32 offsets); what the walk cannot follow keeps 2^40.
-static void SubtreeBufferBounds(const ArrowField& f, const RecordBatchMeta& meta, size_t* node, size_t* variadic, bool value_only,
-                                std::vector<int64_t>* out) {
-  constexpr int64_t kLoose = int64_t(1) << 40;
-  const int64_t n = *node < meta.nodes.size() ? std::max<int64_t>(0, std::min<int64_t>(meta.nodes[*node].first, kLoose)) : kLoose;
-  (*node)++;
-  auto rows = [&](int64_t per_row, int64_t extra_rows = 0) {
-    int64_t b = 0;
-    if (per_row <= 0 || __builtin_mul_overflow(n + extra_rows, per_row, &b) || b > kLoose) return kLoose;
-    return b + 64;
-  };
-  const int64_t bitmap = (n + 7) / 8 + 64;
-  if (f.has_dictionary && !value_only) {
-    out->push_back(bitmap);
-    out->push_back(rows(f.dict_index_bit_width / 8));
-    return;
-  }
-  switch (f.type) {
-    case MI_AT_NULL: case MI_AT_RUN_END: break;  // run-end encoded: run_ends and values are children
-    case MI_AT_STRUCT: case MI_AT_FIXED_LIST: out->push_back(bitmap); break;
-    case MI_AT_UTF8: case MI_AT_BINARY: out->push_back(bitmap); out->push_back(rows(4, 1)); out->push_back((int64_t(1) << 31) + 64); break;
-    case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: out->push_back(bitmap); out->push_back(rows(8, 1)); out->push_back(kLoose); break;
-    case MI_AT_LIST: case MI_AT_MAP: out->push_back(bitmap); out->push_back(rows(4, 1)); break;
-    case MI_AT_LARGE_LIST: out->push_back(bitmap); out->push_back(rows(8, 1)); break;
-    case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {
-      out->push_back(bitmap);
-      out->push_back(rows(16));
-      const int64_t vc = *variadic < meta.variadic_counts.size() ? meta.variadic_counts[(*variadic)++] : 0;
-      for (int64_t k = 0; k < vc && k < (1 << 20); k++) out->push_back(kLoose);
-      break;
-    }
-    case MI_AT_UNION: out->push_back(rows(1)); if (f.unit == 1) out->push_back(rows(4)); break;
-    case MI_AT_BOOL: out->push_back(bitmap); out->push_back(bitmap); break;
-    default: {
-      int32_t kind, w, nb;
-      int64_t param;
-      out->push_back(bitmap);
-      int64_t width = 16;  // the widest fixed-width value of the format (decimal256 aside, which is not decoded)
-      if (f.Plan(&kind, &param, &w, &nb, true)) {
-        switch (kind) {
-          case MI_K_COPY: case MI_K_FIXED_BINARY: width = param; break;
-          case MI_K_DEC128: case MI_K_INTERVAL_MDN: width = 16; break;
-          case MI_K_NARROW: width = param & 0xFF; break;
-          case MI_K_HALF_FLOAT: width = 2; break;
-          case MI_K_MUL_I32: case MI_K_INTERVAL_MONTHS: width = 4; break;
-          default: width = 8; break;
-        }
-      } else if (f.type == MI_AT_DECIMAL) {
-        width = 32;
-      }
-      out->push_back(rows(width));
-      break;
-    }
-  }
-  for (auto& c : f.children) SubtreeBufferBounds(c, meta, node, variadic, false, out);
-}
-
-// Number of RecordBatch.buffers entries a field subtree owns (same rules as the walk in SliceBatch)
-static bool CountSubtreeBuffers(const ArrowField& f, const RecordBatchMeta& meta, size_t* variadic, size_t* buffers) {
-  if (f.has_dictionary) {
-    *buffers += 2;
-    return true;
-  }
-  switch (f.type) {
-    case MI_AT_NULL: case MI_AT_RUN_END: break;
-    case MI_AT_STRUCT: case MI_AT_FIXED_LIST: *buffers += 1; break;
-    case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: *buffers += 3; break;
-    case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {
-      if (*variadic >= meta.variadic_counts.size()) return false;
-      const int64_t vc = meta.variadic_counts[(*variadic)++];
-      if (vc < 0 || vc > (1 << 20)) return false;
-      *buffers += 2 + static_cast<size_t>(vc);
-      break;
-    }
-    case MI_AT_UNION: *buffers += f.unit == 1 ? 2 : 1; break;
-    default: *buffers += 2; break;
-  }
-  for (auto& c : f.children)
-    if (!CountSubtreeBuffers(c, meta, variadic, buffers)) return false;
-  return true;
-}
-
 // Per RecordBatch.buffers entry: does a projected column own it?  Empty = all of them (no projection, dictionary batch,
 // or metadata the walk cannot follow -- the full validation reports that).
 std::vector<char> IPCStreamReader::NeededBuffers(const RecordBatchMeta& meta) const {
@@ -918,14 +909,11 @@ std::vector<char> IPCStreamReader::NeededBuffers(const RecordBatchMeta& meta) co
   std::vector<char> wanted(base_schema.fields.size(), 0);
   for (int32_t c : projected_columns) wanted[static_cast<size_t>(c)] = 1;
   need.assign(meta.buffers.size(), 0);
-  size_t buf = 0, variadic = 0;
-  for (size_t i = 0; i < base_schema.fields.size(); i++) {
-    size_t n = 0;
-    if (!CountSubtreeBuffers(base_schema.fields[i], meta, &variadic, &n) || buf + n > meta.buffers.size()) return {};
-    if (wanted[i])
-      for (size_t k = buf; k < buf + n; k++) need[k] = 1;
-    buf += n;
-  }
+  const WalkEnd walked = WalkBatch(base_schema.fields, meta, [&](const WalkNode& v) {
+    if (wanted[static_cast<size_t>(v.column)])
+      for (size_t k = v.first_buffer; k < v.first_buffer + v.n_buffers && k < need.size(); k++) need[k] = 1;
+  });
+  if (walked.defect || walked.buffers > meta.buffers.size()) return {};
   return need;
 }
 
@@ -954,20 +942,18 @@ std::vector<std::pair<int64_t, int64_t>> IPCStreamReader::ProjectedBodyRanges(co
 
 // ------------------------------------------------------------------------------------------------ big-endian bodies
 namespace {
-enum class Swap : int { NONE = 0, W2 = 2, W4 = 4, W8 = 8, W16 = 16, W32 = 32, MONTH_DAY_NANO = 100, VIEW = 101 };
-
-void SwapElements(uint8_t* p, int64_t bytes, Swap how) {
+void SwapElements(uint8_t* p, int64_t bytes, ByteSwap how) {
   switch (how) {
-    case Swap::NONE: return;
-    case Swap::W2: { uint16_t* v = reinterpret_cast<uint16_t*>(p); for (int64_t i = 0; i < bytes / 2; i++) v[i] = __builtin_bswap16(v[i]); return; }
-    case Swap::W4: { uint32_t* v = reinterpret_cast<uint32_t*>(p); for (int64_t i = 0; i < bytes / 4; i++) v[i] = __builtin_bswap32(v[i]); return; }
-    case Swap::W8: { uint64_t* v = reinterpret_cast<uint64_t*>(p); for (int64_t i = 0; i < bytes / 8; i++) v[i] = __builtin_bswap64(v[i]); return; }
-    case Swap::W16: case Swap::W32: {  // one wide integer: the whole value is reversed
+    case ByteSwap::NONE: return;
+    case ByteSwap::W2: { uint16_t* v = reinterpret_cast<uint16_t*>(p); for (int64_t i = 0; i < bytes / 2; i++) v[i] = __builtin_bswap16(v[i]); return; }
+    case ByteSwap::W4: { uint32_t* v = reinterpret_cast<uint32_t*>(p); for (int64_t i = 0; i < bytes / 4; i++) v[i] = __builtin_bswap32(v[i]); return; }
+    case ByteSwap::W8: { uint64_t* v = reinterpret_cast<uint64_t*>(p); for (int64_t i = 0; i < bytes / 8; i++) v[i] = __builtin_bswap64(v[i]); return; }
+    case ByteSwap::W16: case ByteSwap::W32: {  // one wide integer: the whole value is reversed
       const int w = static_cast<int>(how);
       for (int64_t i = 0; i + w <= bytes; i += w) std::reverse(p + i, p + i + w);
       return;
     }
-    case Swap::MONTH_DAY_NANO:  // {int32 months, int32 days, int64 nanoseconds}
+    case ByteSwap::MONTH_DAY_NANO:  // {int32 months, int32 days, int64 nanoseconds}
       for (int64_t i = 0; i + 16 <= bytes; i += 16) {
         uint32_t a, b;
         uint64_t c;
@@ -982,7 +968,7 @@ void SwapElements(uint8_t* p, int64_t bytes, Swap how) {
         std::memcpy(p + i + 8, &c, 8);
       }
       return;
-    case Swap::VIEW:  // {int32 length, 12 inline bytes} or {int32 length, 4 prefix bytes, int32 buffer, int32 offset}
+    case ByteSwap::VIEW:  // {int32 length, 12 inline bytes} or {int32 length, 4 prefix bytes, int32 buffer, int32 offset}
       for (int64_t i = 0; i + 16 <= bytes; i += 16) {
         uint32_t len;
         std::memcpy(&len, p + i, 4);
@@ -1002,78 +988,16 @@ void SwapElements(uint8_t* p, int64_t bytes, Swap how) {
   }
 }
 
-// How every RecordBatch.buffers entry of a field subtree is stored (Arrow columnar format, "Endianness"): only multi-byte
-// numbers are affected -- bitmaps, boolean data, string / binary payloads and fixed_size_binary values are byte sequences.
-void SubtreeSwaps(const ArrowField& f, const RecordBatchMeta& meta, size_t* variadic, bool value_only, std::vector<Swap>* out) {
-  auto of_width = [](int bytes) {
-    switch (bytes) {
-      case 2: return Swap::W2;
-      case 4: return Swap::W4;
-      case 8: return Swap::W8;
-      case 16: return Swap::W16;
-      case 32: return Swap::W32;
-      default: return Swap::NONE;
-    }
-  };
-  if (f.has_dictionary && !value_only) {
-    out->push_back(Swap::NONE);
-    out->push_back(of_width(f.dict_index_bit_width / 8));
-    return;
-  }
-  switch (f.type) {
-    case MI_AT_NULL: case MI_AT_RUN_END: break;  // its run_ends child swaps as the int it is
-    case MI_AT_STRUCT: case MI_AT_FIXED_LIST: out->push_back(Swap::NONE); break;
-    case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LIST: case MI_AT_MAP:
-      out->push_back(Swap::NONE);
-      out->push_back(Swap::W4);
-      if (f.type == MI_AT_UTF8 || f.type == MI_AT_BINARY) out->push_back(Swap::NONE);
-      break;
-    case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: case MI_AT_LARGE_LIST:
-      out->push_back(Swap::NONE);
-      out->push_back(Swap::W8);
-      if (f.type != MI_AT_LARGE_LIST) out->push_back(Swap::NONE);
-      break;
-    case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {
-      out->push_back(Swap::NONE);
-      out->push_back(Swap::VIEW);
-      const int64_t vc = *variadic < meta.variadic_counts.size() ? meta.variadic_counts[(*variadic)++] : 0;
-      for (int64_t k = 0; k < vc && k < (1 << 20); k++) out->push_back(Swap::NONE);
-      break;
-    }
-    case MI_AT_UNION: out->push_back(Swap::NONE); if (f.unit == 1) out->push_back(Swap::W4); break;
-    case MI_AT_BOOL: case MI_AT_FIXED_BINARY: out->push_back(Swap::NONE); out->push_back(Swap::NONE); break;
-    case MI_AT_INT: out->push_back(Swap::NONE); out->push_back(of_width(f.bit_width / 8)); break;
-    case MI_AT_FLOAT: out->push_back(Swap::NONE); out->push_back(of_width(f.precision == 0 ? 2 : f.precision == 1 ? 4 : 8)); break;
-    case MI_AT_DECIMAL: out->push_back(Swap::NONE); out->push_back(of_width(f.bit_width / 8)); break;
-    case MI_AT_DATE: out->push_back(Swap::NONE); out->push_back(f.unit == 0 ? Swap::W4 : Swap::W8); break;
-    case MI_AT_TIME: out->push_back(Swap::NONE); out->push_back(of_width(f.bit_width / 8)); break;
-    case MI_AT_TIMESTAMP: case MI_AT_DURATION: out->push_back(Swap::NONE); out->push_back(Swap::W8); break;
-    case MI_AT_INTERVAL:
-      out->push_back(Swap::NONE);
-      out->push_back(f.unit == 2 ? Swap::MONTH_DAY_NANO : Swap::W4);  // year_month: int32; day_time: two int32
-      break;
-    default: out->push_back(Swap::NONE); out->push_back(Swap::NONE); break;
-  }
-  for (auto& c : f.children) SubtreeSwaps(c, meta, variadic, false, out);
-}
 }  // namespace
 
+// Only multi-byte numbers are affected (FieldLayout's swap rules): bitmaps, boolean data, string / binary payloads and
+// fixed_size_binary values are byte sequences.
 void IPCStreamReader::SwapBodyEndianness(const RecordBatchMeta& meta) {
-  std::vector<Swap> how;
-  size_t variadic = 0;
-  if (meta.is_dictionary) {
-    std::function<const ArrowField*(const ArrowField&)> find = [&](const ArrowField& f) -> const ArrowField* {
-      if (f.has_dictionary && f.dict_id == meta.dict_id) return &f;
-      for (auto& c : f.children)
-        if (const ArrowField* hit = find(c)) return hit;
-      return nullptr;
-    };
-    for (auto& f : base_schema.fields)
-      if (const ArrowField* hit = find(f)) { SubtreeSwaps(*hit, meta, &variadic, true, &how); break; }
-  } else {
-    for (auto& f : base_schema.fields) SubtreeSwaps(f, meta, &variadic, false, &how);
-  }
-  if (how.size() != meta.buffers.size()) return;  // metadata the walk cannot follow: the full validation reports it
+  std::vector<ByteSwap> how(meta.buffers.size(), ByteSwap::NONE);
+  const WalkEnd walked = WalkBatch(base_schema.fields, meta, [&](const WalkNode& v) {
+    for (int32_t k = 0; k < v.layout.n && v.first_buffer + k < how.size(); k++) how[v.first_buffer + k] = v.layout.buffers[k].swap;
+  });
+  if (walked.buffers != how.size()) return;  // metadata the walk cannot follow: the full validation reports it
   // the body must be ours to rewrite: caller-owned buffers (scan_arrow_ipc) are copied first
   if (!cur_owner) {
     uint8_t* copy = nullptr;
@@ -1086,7 +1010,7 @@ void IPCStreamReader::SwapBodyEndianness(const RecordBatchMeta& meta) {
   const std::vector<char> needed = NeededBuffers(meta);
   IoPool::Get().Run(static_cast<int>(how.size()), [&](int i) {
     const mi_buffer_span& b = meta.buffers[static_cast<size_t>(i)];
-    if (how[static_cast<size_t>(i)] == Swap::NONE || b.length <= 0) return;
+    if (how[static_cast<size_t>(i)] == ByteSwap::NONE || b.length <= 0) return;
     if (!needed.empty() && !needed[static_cast<size_t>(i)]) return;    // never read from the file: nothing there to swap
     if (!SpanInside(b.offset, b.length, cur_size)) return;             // reported by SliceBatch
     SwapElements(body + b.offset, b.length, how[static_cast<size_t>(i)]);
@@ -1122,33 +1046,52 @@ void IPCStreamReader::SliceBatch(const RecordBatchMeta& meta, DecodedBatch* out)
     if (s.offset % 8 != 0) throw InternalException("Buffer offset " + std::to_string(s.offset) + " is not 8-byte aligned");
   };
 
-  // Depth-first walk over ALL fields keeps the node / buffer / variadic cursors of RecordBatch.{nodes,buffers,
-  // variadicBufferCounts} in step; nodes are materialised only for the projected columns and their descendants.
-  struct Cursor {
-    size_t node = 0, buf = 0, variadic = 0;
+  auto add_column = [&](int32_t top_index, int32_t node_idx) {
+    const DecodedNode& nd = out->nodes[static_cast<size_t>(node_idx)];
+    out->column_field.push_back(top_index);
+    out->column_node.push_back(node_idx);
+    out->null_count.push_back(nd.null_count);
+    out->column_length.push_back(nd.length);
+    for (size_t k = 0; k < 3; k++) out->buffers.push_back(k < nd.spans.size() ? nd.spans[k] : mi_buffer_span{0, 0});
   };
-  std::function<int32_t(const ArrowField&, Cursor&, bool, int32_t, int32_t, bool)> walk =
-      [&](const ArrowField& f, Cursor& cur, bool keep, int32_t parent, int32_t depth, bool value_only) -> int32_t {
-    if (cur.node >= meta.nodes.size()) throw InternalException("RecordBatch has too few field nodes");
-    const int64_t n = meta.nodes[cur.node].first;
-    const int64_t nulls = meta.nodes[cur.node].second;
-    cur.node++;
+  out->nodes.clear();
+  out->column_node.clear();
+
+  // Nodes are materialised only for the projected columns and their descendants (all of a dictionary batch), in walk
+  // order: a kept node's index is its column root's plus its distance from that root in RecordBatch.nodes.
+  std::vector<int32_t> node_of_field(base_schema.fields.size(), -1);
+  std::vector<char> wanted(base_schema.fields.size(), HasProjection() && !meta.is_dictionary ? 0 : 1);
+  if (!meta.is_dictionary)
+    for (int32_t c : projected_columns) wanted[static_cast<size_t>(c)] = 1;
+  int32_t root = 0;
+  size_t root_node = 0;
+  const WalkEnd walked = WalkBatch(base_schema.fields, meta, [&](const WalkNode& v) {
+    const ArrowField& f = *v.field;
+    if (v.node >= meta.nodes.size()) throw InternalException("RecordBatch has too few field nodes");
+    const int64_t n = meta.nodes[v.node].first;
+    const int64_t nulls = meta.nodes[v.node].second;
     if (n < 0) throw InternalException("Field node length is negative");
     // lengths come from the file: bound them before anything is multiplied by them (ArrowArrayViewValidate checks the
     // same relations), so a damaged RecordBatch cannot overflow a size computation and slip past the buffer checks
     if (n > (int64_t(1) << 40)) throw InternalException("Field node length " + std::to_string(n) + " is implausible");
     if (nulls < -1 || nulls > n) throw InternalException("Field node null_count " + std::to_string(nulls) + " is outside [0, length]");
-    if (depth == 0 && !value_only && n != meta.length)
+    if (v.depth == 0 && !v.value_only && n != meta.length)
       throw InternalException("Expected array length " + std::to_string(meta.length) + " for column " + f.name + " but found " + std::to_string(n));
-    if (keep && f.type == MI_AT_RUN_END && !(f.has_dictionary && !value_only)) {
+    const bool keep = wanted[static_cast<size_t>(v.column)] != 0;
+    if (keep && v.depth == 0) {
+      root = static_cast<int32_t>(out->nodes.size());
+      root_node = v.node;
+    }
+    const int32_t parent = v.parent < 0 ? -1 : root + static_cast<int32_t>(static_cast<size_t>(v.parent) - root_node);
+    if (keep && f.type == MI_AT_RUN_END && !(f.has_dictionary && !v.value_only)) {
       // structural checks that need only the metadata (the run ends themselves are checked on the device / by the exporter)
       if (nulls != 0) throw InternalException("Run-end encoded column " + f.name + " has null_count " + std::to_string(nulls) + ", expected 0");
       if (f.children.size() != 2)
         throw InternalException("Run-end encoded column " + f.name + " has " + std::to_string(f.children.size()) + " children, expected 2 (run_ends, values)");
-      if (cur.node + 1 >= meta.nodes.size()) throw InternalException("RecordBatch has too few field nodes");
+      if (v.node + 2 >= meta.nodes.size()) throw InternalException("RecordBatch has too few field nodes");
       // the children's nodes follow right away: run_ends is always a leaf (an integer), values comes after it
-      const int64_t re_len = meta.nodes[cur.node].first, re_nulls = meta.nodes[cur.node].second;
-      const int64_t v_len = meta.nodes[cur.node + 1].first;
+      const int64_t re_len = meta.nodes[v.node + 1].first, re_nulls = meta.nodes[v.node + 1].second;
+      const int64_t v_len = meta.nodes[v.node + 2].first;
       if (re_nulls != 0) throw InternalException("Run ends of column " + f.name + " have null_count " + std::to_string(re_nulls) + ", expected 0");
       if (re_len != v_len)
         throw InternalException("Run-end encoded column " + f.name + " has " + std::to_string(re_len) + " run ends but " + std::to_string(v_len) + " values");
@@ -1167,128 +1110,59 @@ void IPCStreamReader::SliceBatch(const RecordBatchMeta& meta, DecodedBatch* out)
                                   std::to_string(pn.length) + " x " + std::to_string(pn.field->byte_width));
       }
     }
-    const bool dict = f.has_dictionary && !value_only;
-    size_t own;
-    if (dict) {
-      own = 2;
-    } else {
-      switch (f.type) {
-        case MI_AT_NULL: case MI_AT_RUN_END: own = 0; break;  // run-end encoded: its data lives in its two children
-        case MI_AT_STRUCT: case MI_AT_FIXED_LIST: own = 1; break;
-        case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: own = 3; break;
-        case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: {
-          if (cur.variadic >= meta.variadic_counts.size()) throw InternalException("RecordBatch has too few variadicBufferCounts");
-          const int64_t vc = meta.variadic_counts[cur.variadic++];
-          if (vc < 0 || vc > (1 << 20)) throw InternalException("Invalid variadic buffer count");
-          own = 2 + static_cast<size_t>(vc);
-          break;
-        }
-        case MI_AT_UNION: own = f.unit == 1 ? 2 : 1; break;  // dense: types + offsets, sparse: types
-        default: own = 2; break;
-      }
+    if (v.defect) throw InternalException(v.defect);
+    if (v.first_buffer + v.n_buffers > meta.buffers.size()) throw InternalException("RecordBatch has too few buffers");
+    if (!keep) return;
+    DecodedNode nd;
+    nd.field = &f;
+    nd.parent = parent;
+    nd.depth = v.depth;
+    nd.length = n;
+    nd.null_count = nulls;
+    nd.value_only = v.value_only;
+    for (size_t k = 0; k < v.n_buffers; k++) {
+      nd.spans.push_back(meta.buffers[v.first_buffer + k]);
+      check_span(nd.spans.back());
     }
-    if (cur.buf + own > meta.buffers.size()) throw InternalException("RecordBatch has too few buffers");
-    int32_t idx = -1;
-    if (keep) {
-      idx = static_cast<int32_t>(out->nodes.size());
-      out->nodes.emplace_back();
-      DecodedNode nd;
-      nd.field = &f;
-      nd.parent = parent;
-      nd.depth = depth;
-      nd.length = n;
-      nd.null_count = nulls;
-      nd.value_only = value_only;
-      for (size_t k = 0; k < own; k++) {
-        nd.spans.push_back(meta.buffers[cur.buf + k]);
-        check_span(nd.spans.back());
+    // size checks of ArrowArrayViewValidate (FULL), minus the data-dependent offsets walk (done on the device)
+    int32_t kind, w;
+    int64_t param;
+    if (f.Plan(&kind, &param, &w, v.value_only)) {
+      const size_t own = v.n_buffers;
+      const mi_buffer_span none{0, 0};
+      const mi_buffer_span& s0 = own > 0 ? nd.spans[0] : none;
+      const mi_buffer_span& s1 = own > 1 ? nd.spans[1] : none;
+      if (s0.length != 0 && s0.length < (n + 7) / 8) throw InternalException(BufferSizeError(f.name, 0, (n + 7) / 8, s0.length));
+      if (kind != MI_K_NULL && s0.length == 0 && n > 0 && nulls > 0)
+        throw InternalException("Column " + f.name + " has null_count " + std::to_string(nulls) + " but no validity buffer");
+      int64_t need1 = 0, per_row = 0, rows = n;
+      if (v.layout.n > 1) {
+        const BufferLayout& b1 = v.layout.buffers[1];
+        if (b1.role == BufferRole::BITS) need1 = (n + 7) / 8;
+        else per_row = b1.width;
+        if (b1.role == BufferRole::OFFSETS) rows = n > 0 ? n + 1 : 0;
       }
-      // size checks of ArrowArrayViewValidate (FULL), minus the data-dependent offsets walk (done on the device)
-      int32_t kind, w, nb;
-      int64_t param;
-      if (f.Plan(&kind, &param, &w, &nb, value_only)) {
-        const mi_buffer_span none{0, 0};
-        const mi_buffer_span& s0 = own > 0 ? nd.spans[0] : none;
-        const mi_buffer_span& s1 = own > 1 ? nd.spans[1] : none;
-        if (s0.length != 0 && s0.length < (n + 7) / 8) throw InternalException(BufferSizeError(f.name, 0, (n + 7) / 8, s0.length));
-        if (kind != MI_K_NULL && s0.length == 0 && n > 0 && nulls > 0)
-          throw InternalException("Column " + f.name + " has null_count " + std::to_string(nulls) + " but no validity buffer");
-        int64_t need1 = 0, per_row = 0, rows = n;
-        switch (kind) {
-          case MI_K_COPY: case MI_K_FIXED_BINARY: per_row = param; break;
-          case MI_K_BOOL: need1 = (n + 7) / 8; break;
-          case MI_K_DEC128: case MI_K_INTERVAL_MDN: case MI_K_STRVIEW: per_row = 16; break;
-          case MI_K_DATE64: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DURATION: per_row = 8; break;
-          case MI_K_MUL_I32: case MI_K_INTERVAL_MONTHS: per_row = 4; break;
-          case MI_K_STR32: case MI_K_LIST32: per_row = 4; rows = n > 0 ? n + 1 : 0; break;
-          case MI_K_STR64: case MI_K_LIST64: per_row = 8; rows = n > 0 ? n + 1 : 0; break;
-          case MI_K_DICT: case MI_K_NARROW: per_row = param & 0xFF; break;
-          case MI_K_HALF_FLOAT: per_row = 2; break;
-          default: break;
-        }
-        // rows <= 2^40 + 1 and widths come from the schema (validated, but up to 2^31 for fixed_size_binary): the
-        // product is formed with an overflow check so that a wrapped size can never pass for a small one
-        if (per_row < 0 || (per_row > 0 && __builtin_mul_overflow(rows, per_row, &need1)))
-          throw InternalException("Column " + f.name + " needs more bytes than a buffer can hold (" + std::to_string(rows) + " x " + std::to_string(per_row) + ")");
-        if (s1.length < need1) throw InternalException(BufferSizeError(f.name, 1, need1, s1.length));
-      }
-      out->nodes[static_cast<size_t>(idx)] = std::move(nd);
+      // rows <= 2^40 + 1 and widths come from the schema (validated, but up to 2^31 for fixed_size_binary): the
+      // product is formed with an overflow check so that a wrapped size can never pass for a small one
+      if (per_row < 0 || (per_row > 0 && __builtin_mul_overflow(rows, per_row, &need1)))
+        throw InternalException("Column " + f.name + " needs more bytes than a buffer can hold (" + std::to_string(rows) + " x " + std::to_string(per_row) + ")");
+      if (s1.length < need1) throw InternalException(BufferSizeError(f.name, 1, need1, s1.length));
     }
-    cur.buf += own;
-    if (!dict) {
-      for (auto& c : f.children) {
-        const int32_t ci = walk(c, cur, keep, idx, depth + 1, false);
-        if (keep) out->nodes[static_cast<size_t>(idx)].children.push_back(ci);
-      }
-    }
-    return idx;
-  };
-  auto add_column = [&](int32_t top_index, int32_t node_idx) {
-    const DecodedNode& nd = out->nodes[static_cast<size_t>(node_idx)];
-    out->column_field.push_back(top_index);
-    out->column_node.push_back(node_idx);
-    out->null_count.push_back(nd.null_count);
-    out->column_length.push_back(nd.length);
-    for (size_t k = 0; k < 3; k++) out->buffers.push_back(k < nd.spans.size() ? nd.spans[k] : mi_buffer_span{0, 0});
-  };
-  out->nodes.clear();
-  out->column_node.clear();
-
-  if (meta.is_dictionary) {
-    // one node: the dictionary values of the field that carries this id -- anywhere in the field tree (a list or struct
-    // child may be dictionary-encoded too); `top` = the top-level column it belongs to
-    const ArrowField* owner_field = nullptr;
-    int32_t top = -1;
-    std::function<const ArrowField*(const ArrowField&)> find = [&](const ArrowField& f) -> const ArrowField* {
-      if (f.has_dictionary && f.dict_id == meta.dict_id) return &f;
-      for (auto& c : f.children)
-        if (const ArrowField* hit = find(c)) return hit;
-      return nullptr;
-    };
-    for (size_t i = 0; i < base_schema.fields.size() && !owner_field; i++) {
-      owner_field = find(base_schema.fields[i]);
-      if (owner_field) top = static_cast<int32_t>(i);
-    }
-    if (!owner_field) throw IOException("DictionaryBatch refers to unknown dictionary id " + std::to_string(meta.dict_id));
-    Cursor cur;
-    add_column(top, walk(*owner_field, cur, true, -1, 0, /*value_only*/ true));
-    return;
-  }
-
-  std::vector<int32_t> node_of_field(base_schema.fields.size(), -1);
-  std::vector<char> wanted(base_schema.fields.size(), HasProjection() ? 0 : 1);
-  for (int32_t c : projected_columns) wanted[static_cast<size_t>(c)] = 1;
-  Cursor cur;
-  for (size_t i = 0; i < base_schema.fields.size(); i++)
-    node_of_field[i] = walk(base_schema.fields[i], cur, wanted[i] != 0, -1, 0, false);
-  if (cur.node != meta.nodes.size()) {
-    throw InternalException("Expected " + std::to_string(cur.node) + " field nodes in message but found " +
+    const int32_t idx = static_cast<int32_t>(out->nodes.size());
+    if (parent >= 0) out->nodes[static_cast<size_t>(parent)].children.push_back(idx);
+    else node_of_field[static_cast<size_t>(v.column)] = idx;
+    out->nodes.push_back(std::move(nd));
+  });
+  if (walked.unknown_dictionary) throw IOException("DictionaryBatch refers to unknown dictionary id " + std::to_string(meta.dict_id));
+  if (!meta.is_dictionary && walked.nodes != meta.nodes.size()) {
+    throw InternalException("Expected " + std::to_string(walked.nodes) + " field nodes in message but found " +
                             std::to_string(meta.nodes.size()));
   }
-  if (HasProjection()) {
+  if (HasProjection() && !meta.is_dictionary) {
     for (int32_t c : projected_columns) add_column(c, node_of_field[static_cast<size_t>(c)]);
   } else {
-    for (size_t i = 0; i < base_schema.fields.size(); i++) add_column(static_cast<int32_t>(i), node_of_field[i]);
+    for (size_t i = 0; i < base_schema.fields.size(); i++)
+      if (node_of_field[i] >= 0) add_column(static_cast<int32_t>(i), node_of_field[i]);
   }
 }
 

@@ -255,23 +255,23 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
           if (!sc.field.Supported(&why)) throw NotImplementedException("Column '" + sc.name + "': " + why + " is not decoded by the MI355X scan path yet");
           continue;
         }
-        int32_t kind, w, nb;
+        int32_t kind, w;
         int64_t param;
         // a run-end encoded column is filtered on its flat vector: what matters is the kind of its values
         const ArrowField& vf = sc.field.type == MI_AT_RUN_END && sc.field.children.size() == 2 ? sc.field.children[1] : sc.field;
-        if (&vf != &sc.field && !sc.field.Plan(&kind, &param, &w, &nb))
+        if (&vf != &sc.field && !sc.field.Plan(&kind, &param, &w))
           throw NotImplementedException("Column '" + sc.name + "': Arrow type +r with these children is not decoded by the MI355X scan path");
         // IN () -- an empty range -- keeps nothing (its negation every valid row) whatever the column holds
         if (!leaf.is_string && leaf.op == device::kLeafRange && !leaf.lo_open && !leaf.hi_open && leaf.lo > leaf.hi) continue;
         if (leaf.is_string) {
           // byte-string constants: the column must decode to string_t rows that point into ONE data buffer
-          const bool value_ok = vf.Plan(&kind, &param, &w, &nb, /*value_only*/ true) && (kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY);
+          const bool value_ok = vf.Plan(&kind, &param, &w, /*value_only*/ true) && (kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY);
           if (!value_ok)
             throw NotImplementedException("string filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
                                           ") needs a utf8 / large_utf8 / binary / fixed_size_binary column (dictionary-encoded or not)");
           continue;
         }
-        const bool ok = vf.Plan(&kind, &param, &w, &nb) && !vf.has_dictionary &&
+        const bool ok = vf.Plan(&kind, &param, &w) && !vf.has_dictionary &&
                         (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
                          kind == MI_K_DIV_I64 || kind == MI_K_NARROW || kind == MI_K_BOOL) &&
                         (w == 1 || w == 2 || w == 4 || w == 8) && vf.type != MI_AT_FLOAT;
@@ -317,9 +317,9 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
     if (opts.filter_compact) {
       for (auto& c : out_columns) {
         if (c.is_filename || c.is_hive) continue;
-        int32_t kind, w, nb;
+        int32_t kind, w;
         int64_t param;
-        c.field.Plan(&kind, &param, &w, &nb);
+        c.field.Plan(&kind, &param, &w);
         if (!device::KindCanGather(kind) || !c.field.children.empty())
           throw NotImplementedException("filter_compact needs flat projected columns: '" + c.name + "' (" + c.field.DuckType() +
                                         ") is decoded window by window, use the selection vector instead");
@@ -378,9 +378,9 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
   (void)src;
   if (b.column_node.empty() || b.nodes.empty()) throw InternalException("DictionaryBatch without a value node");
   const ArrowField& f = *b.nodes[static_cast<size_t>(b.column_node[0])].field;  // the field that carries the id (any depth)
-  int32_t kind, w, nb;
+  int32_t kind, w;
   int64_t param;
-  if (!f.Plan(&kind, &param, &w, &nb, /*value_only*/ true))
+  if (!f.Plan(&kind, &param, &w, /*value_only*/ true))
     throw NotImplementedException("Dictionary value type " + f.Format() + " is not decoded by the MI355X scan path");
   // the values are decoded as ONE flat task below: value types that need more than {validity, buffer 1, buffer 2}
   // (string views: a table of variadic buffers; lists / structs: child nodes) are refused instead of mis-wired
@@ -457,11 +457,12 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
     const mi_buffer_span* sp = &b.buffers[0];
     t.validity = sp[0].length ? heap + sp[0].offset : nullptr;
     t.buf1 = heap + sp[1].offset;
-    t.buf2 = nb > 2 ? heap + sp[2].offset : nullptr;
-    t.buf2_len = nb > 2 ? sp[2].length : 0;
+    const bool payload = f.Layout(/*value_only*/ true).n > 2;   // strings: offsets in buffer 1, their bytes in buffer 2
+    t.buf2 = payload ? heap + sp[2].offset : nullptr;
+    t.buf2_len = payload ? sp[2].length : 0;
     t.out_data = scratch_data;
     t.out_validity = nullptr;   // built on the host, above
-    const int64_t data_off = nb > 2 ? sp[2].offset : sp[1].offset;
+    const int64_t data_off = payload ? sp[2].offset : sp[1].offset;
     t.ptr_base = opts.device_resident ? reinterpret_cast<uint64_t>(heap + data_off) : reinterpret_cast<uint64_t>(b.body + data_off);
     t.nrows = n_new;
     t.null_count = b.null_count[0];
@@ -583,9 +584,9 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   }
   std::vector<int32_t> widths(out_columns.size(), 0);
   auto width_of = [](const ScanColumn& c) {
-    int32_t kind, w, nb;
+    int32_t kind, w;
     int64_t param;
-    c.field.Plan(&kind, &param, &w, &nb);
+    c.field.Plan(&kind, &param, &w);
     return w;
   };
   // ---- layout.  Full decode: [projected columns | sel | counts] travel back, then the filter-only columns.
@@ -1078,9 +1079,9 @@ void ArrowScan::EnqueueStageB(Slot& s) {
   std::vector<int32_t> widths(out_columns.size(), 0);
   for (size_t c = 0; c < out_columns.size(); c++) {
     if (out_columns[c].is_filename || out_columns[c].is_hive) continue;
-    int32_t kind, nb;
+    int32_t kind;
     int64_t param;
-    out_columns[c].field.Plan(&kind, &param, &widths[c], &nb);
+    out_columns[c].field.Plan(&kind, &param, &widths[c]);
     const int32_t fc = src.out_to_file_column[c];
     if (fc < 0) {
       s.absent[c] = cp.AddAbsentColumn(total, widths[c]);
@@ -1609,9 +1610,9 @@ void ArrowScan::BuildChunk(const BatchRef& ref, int32_t window, ChunkStorage* st
     if (s.col_root[c] >= 0) {
       BuildVector(s, s.col_root[c], static_cast<size_t>(window), s.compact ? n : -1, base, st, &v);
     } else {  // absent in this file: all NULL
-      int32_t kind, w, nb;
+      int32_t kind, w;
       int64_t param;
-      out_columns[c].field.Plan(&kind, &param, &w, &nb);
+      out_columns[c].field.Plan(&kind, &param, &w);
       v.data = base + s.absent[c].first + static_cast<size_t>(row0) * static_cast<size_t>(std::max(w, 1));
       v.validity = reinterpret_cast<mi_validity_t*>(base + s.absent[c].second) + row0 / 64;
       v.kind = kind;
@@ -1703,9 +1704,9 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
   Init(proj);
   for (auto& name : proj) {
     const ScanColumn& c = out_columns[static_cast<size_t>(slot_of(name))];
-    int32_t kind, w, nb;
+    int32_t kind, w;
     int64_t param;
-    const bool ok = !c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &w, &nb) &&
+    const bool ok = !c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &w) &&
                     (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
                      kind == MI_K_DIV_I64 || kind == MI_K_NARROW) &&
                     (w == 1 || w == 2 || w == 4 || w == 8) && c.field.type != MI_AT_FLOAT;

@@ -878,9 +878,9 @@ void PumpScanParallel(mi_writer* w, ArrowScan* scan, int threads, int64_t* rows_
     const int64_t row_bytes = std::max<int64_t>(1, [&] {   // staged bytes per row, for row_group_size_bytes
       int64_t b = 0;
       for (auto& c : scan->OutputColumns()) {
-        int32_t kind, wd, nb;
+        int32_t kind, wd;
         int64_t param;
-        if (!c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &wd, &nb)) b += wd; else b += 16;
+        if (!c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &wd)) b += wd; else b += 16;
       }
       return b;
     }());
@@ -1408,9 +1408,9 @@ int mi_writer_sink_scan(mi_writer* w, mi_scan* scan, int64_t* rows) {
       // rows after which the one-thread sink flushes (row_group_size, or row_group_size_bytes at the staged row width)
       int64_t row_bytes = 0;
       for (auto& c : single->OutputColumns()) {
-        int32_t kind, wd, nb;
+        int32_t kind, wd;
         int64_t param;
-        row_bytes += (!c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &wd, &nb)) ? wd : 16;
+        row_bytes += (!c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &wd)) ? wd : 16;
       }
       row_bytes = std::max<int64_t>(1, row_bytes);
       const int64_t group = std::max<int64_t>(1, std::min(w->opts.row_group_size, (w->opts.row_group_size_bytes + row_bytes - 1) / row_bytes));

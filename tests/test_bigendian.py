@@ -68,3 +68,22 @@ def test_scan_of_a_big_endian_stream_equals_the_little_endian_scan(tool, golden_
     first = con.read_arrow(be, accept_dictionaries=True).columns[0]
     want_first = repr(con.read_arrow(os.path.join(golden_dir, rel), accept_dictionaries=True).project([first]).fetch_columns())
     assert repr(con.read_arrow(be, accept_dictionaries=True).project([first]).fetch_columns()) == want_first
+
+
+def test_big_endian_interval_and_view_columns_under_projection(tool, tmp_path):
+    """CPU: a month_day_nano interval (swapped as {int32, int32, int64}) and string / binary views (length, buffer index
+    and offset swapped, prefix and inline bytes not), read whole and one column at a time."""
+    long = ["a view longer than twelve bytes %d" % i for i in range(50)]
+    t = pa.table({"m": pa.array([pa.MonthDayNano([i, -i, 1000 * i]) for i in range(50)], pa.month_day_nano_interval()),
+                  "v": pa.array([s if i % 3 else "short %d" % i for i, s in enumerate(long)], pa.string_view()),
+                  "k": pa.array(range(50), pa.int32()),
+                  "w": pa.array([s.encode() for s in long], pa.binary_view())})
+    le, be = str(tmp_path / "le.arrows"), str(tmp_path / "be.arrows")
+    with ipc.new_stream(le, t.schema) as w:
+        w.write_table(t, max_chunksize=20)
+    subprocess.run([tool, le, be], check=True)
+    assert _same(da.Reader(path=be).export_stream().read_all(), t)
+    for col in t.column_names:
+        rd = da.Reader(path=be)
+        rd.set_projection([col])
+        assert _same(rd.export_stream().read_all(), t.select([col]))

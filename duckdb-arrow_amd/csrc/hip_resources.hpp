@@ -57,12 +57,6 @@ class HipBuffer {
 using DeviceBuffer = HipBuffer<false>;
 using PinnedBuffer = HipBuffer<true>;
 
-//! Capacity for `need` bytes in a buffer of `cap` bytes: a quarter of headroom, at least half again the old capacity
-//! (record batches of a file, row groups of a table differ by a few percent), in whole granules.
-inline size_t GrownCapacity(size_t need, size_t cap, size_t granule) {
-  return (std::max(need + need / 4, cap + cap / 2) + granule - 1) / granule * granule;
-}
-
 //! When `buf` is empty or holds fewer than `need` bytes, it becomes a new allocation of `new_cap` bytes that starts with
 //! the first `keep_bytes` of the old one (pinned buffers only), and the old allocation is returned: the caller frees it at
 //! once (lets it go) or keeps it.  The returned buffer is empty when nothing grew or there was nothing before.

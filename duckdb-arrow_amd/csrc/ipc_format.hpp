@@ -6,6 +6,7 @@
 // ArrowTableFunction::PopulateArrowTableType performs for src/file_scanner/arrow_file_scan.cpp:17-18.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -22,6 +23,12 @@ using idx_t = uint64_t;
 //! and `offset + length > size` wraps for values near INT64_MAX and then passes.
 inline bool SpanInside(int64_t offset, int64_t length, int64_t size) {
   return offset >= 0 && length >= 0 && offset <= size && length <= size - offset;
+}
+
+//! Capacity for `need` bytes in a buffer of `cap` bytes: a quarter of headroom, at least half again the old capacity
+//! (record batches of a file, row groups of a table differ by a few percent), in whole granules.
+inline size_t GrownCapacity(size_t need, size_t cap, size_t granule) {
+  return (std::max(need + need / 4, cap + cap / 2) + granule - 1) / granule * granule;
 }
 
 // Exception types mirror the DuckDB exception classes the reference throws; the C ABI maps them to errno codes

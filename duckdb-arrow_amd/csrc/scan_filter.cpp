@@ -1,10 +1,15 @@
-// scan_filter.cpp -- pushed-down predicate trees -> conjunctive normal form over normalised leaves.
+// scan_filter.cpp -- the host side of pushed-down predicates: trees -> conjunctive normal form over normalised leaves
+// (NormaliseFilter), the leaves bound to the scan's columns and their constants in HBM (BoundFilter::Resolve /
+// UploadConstants), the leaves as the kernel takes them for one record batch (BoundFilter::Program).
 //
 // The reference pushes no filters (filter_pushdown = false, src/scanner/read_arrow.cpp:47-48); what is accepted here is
 // what DuckDB's TableFilterSet can hand a scan: constant comparisons, IS [NOT] NULL, IN-lists,
 // AND / OR trees.  On integers every comparison is an inclusive range (v < c is [MIN, c-1], v <> c is NOT [c, c]), so
 // the kernel knows four leaf forms only and adjacent range conjuncts on one column intersect into one leaf.
+#include <hip/hip_runtime.h>
+
 #include <algorithm>
+#include <cstring>
 #include <limits>
 
 #include "scan_operator.hpp"
@@ -14,6 +19,7 @@ namespace miarrow {
 namespace {
 constexpr int64_t kMin = std::numeric_limits<int64_t>::min(), kMax = std::numeric_limits<int64_t>::max();
 constexpr size_t kMaxLeaves = static_cast<size_t>(device::kMaxFilterLeaves);
+size_t RoundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 FilterLeaf LeafOf(const mi_filter_node& n) {
   if (!n.column || !*n.column) throw InvalidInputException("filter leaf without a column name");
@@ -162,6 +168,217 @@ FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t 
     throw NotImplementedException("filter needs " + std::to_string(LeafCount(merged)) + " leaves in conjunctive normal form, at most " +
                                   std::to_string(kMaxLeaves) + " are pushed into the scan");
   return merged;
+}
+
+void BoundFilter::Resolve(const std::vector<ScanColumn>& all_columns, const std::vector<ScanColumn>& out_columns) {
+  // a filter column is either projected (its decoded vector is reused) or decoded for the filter alone
+  columns.clear();
+  only.clear();
+  std::vector<std::string> filter_names;
+  for (auto& clause : cnf) {
+    for (auto& leaf : clause) {
+      auto known = std::find(filter_names.begin(), filter_names.end(), leaf.column);
+      if (known == filter_names.end()) {
+        int32_t where = -1;
+        for (size_t i = 0; i < out_columns.size(); i++)
+          if (out_columns[i].name == leaf.column) where = static_cast<int32_t>(i);
+        if (where < 0) {
+          auto it = std::find_if(all_columns.begin(), all_columns.end(), [&](const ScanColumn& sc) { return sc.name == leaf.column; });
+          if (it == all_columns.end()) throw InvalidInputException("filter column '" + leaf.column + "' does not exist in IPC file schema");
+          only.push_back(*it);
+          where = ~static_cast<int32_t>(only.size() - 1);
+        }
+        filter_names.push_back(leaf.column);
+        columns.push_back(where);
+        known = filter_names.end() - 1;
+      }
+      leaf.out_col = static_cast<int32_t>(known - filter_names.begin());
+      const ScanColumn& sc = Column(static_cast<size_t>(leaf.out_col), out_columns);
+      if (sc.is_constant()) throw NotImplementedException("filter on the constant column '" + sc.name + "' is not pushed into the scan");
+      if (leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull) {
+        std::string why;
+        if (!sc.field.Supported(&why)) throw NotImplementedException("Column '" + sc.name + "': " + why + " is not decoded by the MI355X scan path yet");
+        continue;
+      }
+      int32_t kind, w;
+      int64_t param;
+      const ArrowField& vf = ValueField(sc.field);
+      if (&vf != &sc.field && !sc.field.Plan(&kind, &param, &w))
+        throw NotImplementedException("Column '" + sc.name + "': Arrow type +r with these children is not decoded by the MI355X scan path");
+      // IN () -- an empty range -- keeps nothing (its negation every valid row) whatever the column holds
+      if (!leaf.is_string && leaf.op == device::kLeafRange && !leaf.lo_open && !leaf.hi_open && leaf.lo > leaf.hi) continue;
+      if (leaf.is_string) {
+        // byte-string constants: the column must decode to string_t rows that point into ONE data buffer
+        if (!(vf.Plan(&kind, &param, &w, /*value_only*/ true) && IsStringKind(kind)))
+          throw NotImplementedException("string filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
+                                        ") needs a utf8 / large_utf8 / binary / fixed_size_binary column (dictionary-encoded or not)");
+        continue;
+      }
+      if (!(vf.Plan(&kind, &param, &w) && !vf.has_dictionary && IsIntegerLike(kind, w, vf, /*allow_bool*/ true)))
+        throw NotImplementedException("filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
+                                      ") needs an integer / boolean / date / time / timestamp / decimal(<=18) column");
+    }
+  }
+}
+
+void BoundFilter::UploadConstants() {
+  d_in_lists.clear();
+  for (auto& clause : cnf)
+    for (auto& leaf : clause) {
+      DeviceBuffer list;
+      if (leaf.op == device::kLeafIn) {
+        list = DeviceBuffer(leaf.in_values.size() * 8);
+        MI_HIP_CHECK(hipMemcpy(list.get(), leaf.in_values.data(), leaf.in_values.size() * 8, hipMemcpyHostToDevice));
+      } else if ((leaf.op == device::kLeafStrIn || leaf.op == device::kLeafStrRange) && !leaf.str_values.empty()) {
+        // 3 words per constant (its string_t image + the device address of its bytes), the bytes behind the table
+        const size_t nc = leaf.str_values.size();
+        size_t bytes = 0;
+        for (auto& v : leaf.str_values) bytes += RoundUp(v.size() + 1, 8);
+        std::vector<uint8_t> img(nc * 24 + bytes, 0);
+        list = DeviceBuffer(img.size());
+        size_t at = nc * 24;
+        for (size_t k = 0; k < nc; k++) {
+          const std::string& v = leaf.str_values[k];
+          if (v.size() > 0xFFFFFFFFull) throw InvalidInputException("string filter constant too long");
+          uint32_t dw[3] = {0, 0, 0};
+          std::memcpy(dw, v.data(), std::min<size_t>(v.size(), v.size() <= 12 ? 12 : 4));
+          const uint64_t w0 = static_cast<uint64_t>(v.size()) | (static_cast<uint64_t>(dw[0]) << 32);
+          const uint64_t w1 = v.size() <= 12 ? (static_cast<uint64_t>(dw[1]) | (static_cast<uint64_t>(dw[2]) << 32)) : 0;
+          const uint64_t w2 = reinterpret_cast<uint64_t>(list.get() + at);
+          std::memcpy(&img[k * 24], &w0, 8);
+          std::memcpy(&img[k * 24 + 8], &w1, 8);
+          std::memcpy(&img[k * 24 + 16], &w2, 8);
+          std::memcpy(&img[at], v.data(), v.size());
+          at += RoundUp(v.size() + 1, 8);
+        }
+        MI_HIP_CHECK(hipMemcpy(list.get(), img.data(), img.size(), hipMemcpyHostToDevice));
+      }
+      d_in_lists.push_back(std::move(list));
+    }
+}
+
+namespace {
+// Which entries of a string-valued dictionary version pass `leaf` (one byte per entry: 0 no, 1 yes, 2 NULL), in HBM.
+// Made once per (version, leaf); the upload rides `stream` in front of the filter kernel that reads it.
+const void* DictMatchMap(DictState* dict, size_t li, const FilterLeaf& leaf, hipStream_t stream) {
+  auto it = dict->match_maps.find(li);
+  if (it != dict->match_maps.end()) return it->second.get();
+  std::vector<uint8_t> codes(static_cast<size_t>(dict->dict_len) + 1, 0);
+  auto passes = [&](const std::string& v) {   // std::string compares byte-wise (unsigned), a proper prefix first
+    if (leaf.op != device::kLeafStrRange) return std::binary_search(leaf.str_values.begin(), leaf.str_values.end(), v);
+    auto cmp = [](const std::string& a, const std::string& b) {
+      const int c = std::memcmp(a.data(), b.data(), std::min(a.size(), b.size()));
+      return c != 0 ? c : (a.size() < b.size() ? -1 : a.size() > b.size() ? 1 : 0);
+    };
+    if (!leaf.lo_open) {
+      const int c = cmp(v, leaf.str_values[0]);
+      if (c < 0 || (c == 0 && !leaf.lo_incl)) return false;
+    }
+    if (!leaf.hi_open) {
+      const int c = cmp(v, leaf.str_values[1]);
+      if (c > 0 || (c == 0 && !leaf.hi_incl)) return false;
+    }
+    return true;
+  };
+  for (int64_t e = 0; e < dict->dict_len; e++)
+    codes[static_cast<size_t>(e)] = !dict->host_valid[static_cast<size_t>(e)] ? 2
+                                    : (leaf.is_string && passes(dict->host_strings[static_cast<size_t>(e)])) ? 1 : 0;
+  codes[static_cast<size_t>(dict->dict_len)] = 2;   // the NULL entry rows without a value point at
+  // device copy + its pinned source
+  const size_t map_bytes = RoundUp(codes.size() + 16, 256);
+  auto map = std::make_shared<std::pair<DeviceBuffer, PinnedBuffer>>(DeviceBuffer(map_bytes), PinnedBuffer(map_bytes));
+  std::memcpy(map->second.get(), codes.data(), codes.size());
+  MI_HIP_CHECK(hipMemcpyAsync(map->first.get(), map->second.get(), codes.size(), hipMemcpyHostToDevice, stream));
+  return dict->match_maps.emplace(li, std::shared_ptr<void>(map, map->first.get())).first->second.get();
+}
+}  // namespace
+
+device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_columns, const Batch& b, hipStream_t stream) const {
+  device::FilterProgram prog;
+  std::memset(&prog, 0, sizeof(prog));
+  size_t li = 0;
+  for (auto& clause : cnf) {
+    for (size_t j = 0; j < clause.size(); j++, li++) {
+      const FilterLeaf& leaf = clause[j];
+      device::FilterLeafDev& L = prog.leaves[prog.n_leaves++];
+      const int32_t root = b.roots[static_cast<size_t>(leaf.out_col)];
+      L.op = leaf.op;
+      L.flags = (j + 1 == clause.size() ? device::kLeafEndsClause : 0) | (leaf.negate ? device::kLeafNegate : 0);
+      L.lo = leaf.lo;
+      L.hi = leaf.hi;
+      L.in_values = d_in_lists[li].get<int64_t>();
+      L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.in_values.size());
+      if (leaf.op == device::kLeafStrRange)
+        L.n_in = (leaf.lo_open ? 0 : 1) | (leaf.lo_incl ? 2 : 0) | (leaf.hi_open ? 0 : 4) | (leaf.hi_incl ? 8 : 0);
+      L.width = 1;
+      if (root < 0) {
+        // the column is absent from this file (union_by_name): every row is NULL -- IS NULL keeps every row, everything
+        // else keeps none (an empty, non-negated range over any readable bytes: the selection buffer itself)
+        L.validity = nullptr;
+        L.flags &= ~device::kLeafNegate;
+        if (leaf.op == device::kLeafIsNull) {
+          L.op = device::kLeafIsNotNull;
+        } else {
+          L.op = device::kLeafRange;
+          L.lo = 1;
+          L.hi = 0;
+          L.data = b.d_empty;
+        }
+        continue;
+      }
+      const PlannedNode& pn = b.nodes[static_cast<size_t>(root)];
+      L.data = pn.alias_body_off >= 0 ? static_cast<const void*>(b.d_in + pn.alias_body_off) : static_cast<const void*>(b.d_out + pn.data_off);
+      L.validity = pn.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(b.d_out + pn.valid_off) : nullptr;
+      L.width = std::max(pn.width, 1);
+      const bool null_test = leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull;
+      if (pn.kind == MI_K_DICT && (leaf.is_string || null_test)) {
+        // dictionary-encoded: match the dictionary version this batch uses once (host), the rows by index.  IS [NOT] NULL
+        // goes the same way: a row is NULL when its index or its dictionary entry is
+        const std::shared_ptr<DictState>& dict = b.node_dict[static_cast<size_t>(root)];
+        if (!dict || (leaf.is_string && static_cast<int64_t>(dict->host_strings.size()) != dict->dict_len))
+          throw NotImplementedException("string filter on the dictionary-encoded column '" + leaf.column + "': its dictionary values are not strings");
+        L.op = device::kLeafDictMap;
+        L.in_values = static_cast<const int64_t*>(DictMatchMap(dict.get(), li, leaf, stream));
+        L.n_in = static_cast<int32_t>(std::min<int64_t>(dict->dict_len + 1, 0x7FFFFFFF));
+        L.lo = leaf.op == device::kLeafIsNull ? 2 : leaf.op == device::kLeafIsNotNull ? 3 : leaf.negate ? 1 : 0;
+        L.flags &= ~device::kLeafNegate;   // applied inside the kernel: a NULL entry fails = and <> alike
+        L.width = 4;
+        continue;
+      }
+      if (leaf.is_string) {
+        // the rows' long-string pointers are consumer addresses (pn.ptr_base = byte 0 of the Arrow data buffer as the
+        // consumer sees it); the kernel reads the bytes from the HBM copy of that buffer
+        const DecodedNode& src = b.batch.nodes[static_cast<size_t>(pn.source_node)];
+        // run-end encoded: the rows point into the values child's data buffer
+        const DecodedNode& dn = pn.kind == MI_K_RUN_END ? b.batch.nodes[static_cast<size_t>(src.children[1])] : src;
+        const int32_t vkind = pn.kind == MI_K_RUN_END ? pn.value_kind : pn.kind;
+        const size_t data_span = vkind == MI_K_FIXED_BINARY ? 1 : 2;
+        L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(b.d_in + (dn.spans.size() > data_span ? dn.spans[data_span].offset : 0)));
+        L.hi = static_cast<int64_t>(pn.ptr_base);
+        continue;
+      }
+      const ArrowField& vf = ValueField(Column(static_cast<size_t>(leaf.out_col), out_columns).field);
+      if (vf.type == MI_AT_INT && !vf.is_signed) {
+        L.flags |= device::kLeafUnsigned;
+        if (pn.width == 8 && !null_test) {
+          // uint64: compared through the order-preserving map x ^ 2^63 on both sides.  Constants arrive as int64, a
+          // negative one is below every value of the column.
+          L.flags |= device::kLeafBias;
+          const int64_t bias = static_cast<int64_t>(0x8000000000000000ull);
+          if (leaf.op == device::kLeafRange) {
+            if (!leaf.hi_open && leaf.hi < 0) { L.lo = 1; L.hi = 0; }   // empty (its negation keeps every valid row, as it must)
+            else {
+              L.lo = (leaf.lo_open || leaf.lo < 0) ? bias : (leaf.lo ^ bias);            // bias = the image of 0
+              L.hi = leaf.hi_open ? static_cast<int64_t>(0x7FFFFFFFFFFFFFFFull) : (leaf.hi ^ bias);   // image of UINT64_MAX
+            }
+          }
+          // IN-lists of uint64 columns are uploaded unbiased: compare them unbiased too
+          if (leaf.op == device::kLeafIn) L.flags &= ~device::kLeafBias;
+        }
+      }
+    }
+  }
+  return prog;
 }
 
 }  // namespace miarrow

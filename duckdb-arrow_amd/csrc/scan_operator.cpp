@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <thread>
+#include <tuple>
 
 namespace miarrow {
 
@@ -53,90 +55,63 @@ mi_string_t MakeHostString(const std::string& s) {
   return r;
 }
 
-// ZSTD bodies in HBM pay only with many record batches side by side, and those need hardware queues of their own: the HIP
-// runtime reads GPU_MAX_HW_QUEUES once, at its first call (default 4; the library asks for 24 when it is loaded, c_api.cpp).
-bool ManyHardwareQueues() {
-  const char* v = std::getenv("GPU_MAX_HW_QUEUES");
-  return v != nullptr && std::atoi(v) >= 12;
+std::vector<std::string> AtLeastOne(std::vector<std::string> paths) {
+  if (paths.empty()) throw InvalidInputException("read_arrow needs at least one file");
+  return paths;
 }
-bool DeferZstd(const mi_scan_options& o) { return o.host_decompress < 0 || (o.host_decompress == 0 && o.device_resident != 0 && ManyHardwareQueues()); }
 int PipelineDepth(const mi_scan_options& o) { return std::max(2, std::min(kMaxDepth, o.pipeline_depth > 0 ? o.pipeline_depth : 3)); }
 }  // namespace
 
-ArrowScan::ArrowScan(Context* ctx_p, std::vector<std::string> paths, const mi_scan_options& o) : ctx(ctx_p), opts(o) {
-  if (paths.empty()) throw InvalidInputException("read_arrow needs at least one file");
-  for (auto& p : paths) {
-    Source s;
-    s.path = p;
-    sources.push_back(std::move(s));
-  }
-  slots.resize(static_cast<size_t>(PipelineDepth(opts)));
-  staging.resize(kMaxDepth + 2 * kMaxProducers + 2);   // the deepest pipeline's slots + queues + the bodies being read + a decompressed copy (buffers are allocated on first use)
-}
+ArrowScan::ArrowScan(Context* ctx_p, std::vector<std::string> paths, const mi_scan_options& o) : ArrowScan(ctx_p, AtLeastOne(std::move(paths)), {}, o) {}
+ArrowScan::ArrowScan(Context* ctx_p, std::vector<ArrowIPCBuffer> buffers, const mi_scan_options& o) : ArrowScan(ctx_p, {}, std::move(buffers), o) {}
 
-ArrowScan::ArrowScan(Context* ctx_p, std::vector<ArrowIPCBuffer> buffers_p, const mi_scan_options& o)
-    : ctx(ctx_p), opts(o), buffers(std::move(buffers_p)), is_buffers(true) {
-  Source s;
-  sources.push_back(std::move(s));
+ArrowScan::ArrowScan(Context* ctx_p, std::vector<std::string> paths, std::vector<ArrowIPCBuffer> buffers, const mi_scan_options& o)
+    : ctx(ctx_p), opts(o), sources(std::max<size_t>(paths.size(), 1)), is_buffers(paths.empty()),
+      readahead(paths, std::move(buffers), o, kMaxDepth,
+                ReadAhead::Hooks{[this](size_t bytes, uint8_t** ptr) {
+                                   ctx->Bind();
+                                   std::shared_ptr<void> mem = Shared<PinnedBuffer>(bytes);
+                                   *ptr = static_cast<uint8_t*>(mem.get());
+                                   return mem;
+                                 },
+                                 [this] {
+                                   ctx->Bind();
+                                   ctx->BindThisThread();
+                                 },
+                                 [this](size_t si, const ArrowSchemaModel& schema) { return MapColumns(si, schema); }}) {
+  if (opts.hive_partitioning)
+    for (size_t i = 0; i < paths.size(); i++) sources[i].hive = ParseHive(paths[i]);
   slots.resize(static_cast<size_t>(PipelineDepth(opts)));
-  staging.resize(kMaxDepth + 2 * kMaxProducers + 2);   // the deepest pipeline's slots + queues + the bodies being read + a decompressed copy (buffers are allocated on first use)
 }
-
-namespace {
-inline int64_t TraceNow() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-}  // namespace
 
 ArrowScan::~ArrowScan() {
-  StopProducer();
+  readahead.Stop();
   if (trace)
     std::fprintf(stderr, "mi scan trace: %lld batches, %.2f in flight after a submit, %.2f ms from a submit to its batch being handed out; pipeline thread: enqueue %.3f s (K8: tables and copies %.3f s, launches %.3f s), waiting for input %.3f s, waiting for the GPU %.3f s, polling %.3f s; "
                          "producers (%d, summed): reading %.3f s, queue full %.3f s, no staging buffer %.3f s\n",
                  static_cast<long long>(stats.record_batches), stats.record_batches ? double(tr_inflight_sum) / stats.record_batches : 0.0,
-                 stats.record_batches ? tr_latency_ns * 1e-6 / stats.record_batches : 0.0, tr_enqueue_ns * 1e-9, tr_k8_prep_ns * 1e-9, tr_k8_launch_ns * 1e-9, tr_fetch_wait_ns * 1e-9, tr_event_wait_ns * 1e-9, tr_poll_ns * 1e-9, n_producers,
-                 tr_read_ns.load() * 1e-9, tr_push_wait_ns.load() * 1e-9, tr_lease_wait_ns.load() * 1e-9);
+                 stats.record_batches ? tr_latency_ns * 1e-6 / stats.record_batches : 0.0, tr_enqueue_ns * 1e-9, tr_k8_prep_ns * 1e-9, tr_k8_launch_ns * 1e-9, tr_fetch_wait_ns * 1e-9, tr_event_wait_ns * 1e-9, tr_poll_ns * 1e-9, readahead.Producers(),
+                 readahead.ReadSeconds(), readahead.PushWaitSeconds(), readahead.LeaseWaitSeconds());
   try {
     ctx->Bind();
   } catch (...) {
   }
   // The device is done with every buffer before any of them goes (the members, after this body).  The batches in the
-  // slots and in the read-ahead queues hold staging leases, whose release marks the staging buffer free: they go first.
+  // slots and in the read-ahead queues hold staging leases, whose release marks the staging buffer free: they go first
+  // (the slots' here, the queues' when the read-ahead, the last member, is the first to go).
   (void)hipStreamSynchronize(ctx->h2d_stream);
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipStreamSynchronize(ctx->d2h_stream);
   for (auto& s : slots)
     if (s.lz4_stream) (void)hipStreamSynchronize(s.lz4_stream);   // a borrowed stream: its owner is still alive
   for (auto& s : slots) s.batch = DecodedBatch();
-  fetched.clear();
-  extra_readers.clear();
-}
-
-void ArrowScan::OpenSource(size_t i) {
-  Source& s = sources[i];
-  if (s.opened) return;
-  if (is_buffers) {
-    s.reader = std::make_unique<IPCBufferStreamReader>(buffers);
-  } else {
-    s.reader = std::make_unique<IPCFileStreamReader>(s.path);
-    if (opts.hive_partitioning) s.hive = ParseHive(s.path);
-  }
-  // LZ4_FRAME bodies stay compressed until they are in HBM (K8) when the consumer is on the device too.  A host consumer can
-  // ask for it (host_decompress = -1: the string payloads come back beside the vectors, Slot::h_mirror), but by default its
-  // bodies are decompressed by the reader's host threads: on this platform D2H copies run as copy kernels, which then
-  // queue up with the K8 kernels instead of overlapping them (SF10: 0.85 s against 0.68 s, tools/lz4_bench.py)
-  s.reader->SetDeferLz4(opts.host_decompress < 0 || (opts.host_decompress == 0 && opts.device_resident != 0));
-  // ZSTD likewise, when the process has hardware queues for many record batches side by side (its entropy stage is one serial
-  // chain per 128 KiB block: with the HIP runtime's default of 4 queues the reader's host threads are faster)
-  s.reader->SetDeferZstd(DeferZstd(opts));
-  s.reader->GetBaseSchema();
-  s.opened = true;
 }
 
 const std::vector<ScanColumn>& ArrowScan::Bind() {
   if (bound) return all_columns;
   // schema of the first file (ArrowFileScan ctor, arrow_file_scan.cpp:9-23); union_by_name visits every file
-  OpenSource(0);
   auto add_file_columns = [&](size_t si, bool first) {
-    const ArrowSchemaModel& schema = sources[si].reader->GetBaseSchema();
+    const ArrowSchemaModel& schema = readahead.Schema(si);   // opens the file
     std::vector<std::string> names;
     for (auto& f : schema.fields) names.push_back(f.name);
     DeduplicateColumns(names);
@@ -153,10 +128,7 @@ const std::vector<ScanColumn>& ArrowScan::Bind() {
   };
   add_file_columns(0, true);
   if (opts.union_by_name) {
-    for (size_t i = 1; i < sources.size(); i++) {
-      OpenSource(i);
-      add_file_columns(i, false);
-    }
+    for (size_t i = 1; i < sources.size(); i++) add_file_columns(i, false);
   }
   if (all_columns.empty()) {
     throw InvalidInputException("Provided table/dataframe must have at least one column");
@@ -186,13 +158,9 @@ const std::vector<ScanColumn>& ArrowScan::Bind() {
 
 void ArrowScan::SetFilter(FilterCnf cnf) {
   if (initialized) throw InvalidInputException("set the filter before mi_scan_init");
-  if (has_filter) {  // a second filter is ANDed with the first
-    filter.insert(filter.end(), cnf.begin(), cnf.end());
-  } else {
-    filter = std::move(cnf);
-  }
+  filter.cnf.insert(filter.cnf.end(), cnf.begin(), cnf.end());   // a second filter is ANDed with the first
   size_t leaves = 0;
-  for (auto& c : filter) leaves += c.size();
+  for (auto& c : filter.cnf) leaves += c.size();
   if (leaves > static_cast<size_t>(device::kMaxFilterLeaves))
     throw NotImplementedException("filter needs more than " + std::to_string(device::kMaxFilterLeaves) + " leaves");
   has_filter = true;
@@ -201,7 +169,6 @@ void ArrowScan::SetFilter(FilterCnf cnf) {
 void ArrowScan::Init(const std::vector<std::string>& projected) {
   Bind();
   out_columns.clear();
-  filter_only_columns.clear();
   if (projected.empty()) {
     out_columns = all_columns;
   } else {
@@ -212,7 +179,7 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
     }
   }
   for (auto& c : out_columns) {
-    if (c.is_filename || c.is_hive) continue;
+    if (c.is_constant()) continue;
     std::string why;
     if (!c.field.Supported(&why)) {
       throw NotImplementedException("Column '" + c.name + "': " + why + " is not decoded by the MI355X scan path yet");
@@ -226,97 +193,11 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
   ctx->Bind();
   compact = false;
   if (has_filter) {
-    // resolve the leaves: a filter column is either projected (its decoded vector is reused) or decoded for the filter alone
-    filter_columns.clear();
-    std::vector<std::string> filter_names;
-    for (auto& clause : filter) {
-      for (auto& leaf : clause) {
-        auto known = std::find(filter_names.begin(), filter_names.end(), leaf.column);
-        if (known == filter_names.end()) {
-          int32_t where = -1;
-          for (size_t i = 0; i < out_columns.size(); i++)
-            if (out_columns[i].name == leaf.column) where = static_cast<int32_t>(i);
-          if (where < 0) {
-            auto it = std::find_if(all_columns.begin(), all_columns.end(), [&](const ScanColumn& sc) { return sc.name == leaf.column; });
-            if (it == all_columns.end()) throw InvalidInputException("filter column '" + leaf.column + "' does not exist in IPC file schema");
-            filter_only_columns.push_back(*it);
-            where = ~static_cast<int32_t>(filter_only_columns.size() - 1);
-          }
-          filter_names.push_back(leaf.column);
-          filter_columns.push_back(where);
-          known = filter_names.end() - 1;
-        }
-        leaf.out_col = static_cast<int32_t>(known - filter_names.begin());
-        const int32_t where = filter_columns[static_cast<size_t>(leaf.out_col)];
-        const ScanColumn& sc = where >= 0 ? out_columns[static_cast<size_t>(where)] : filter_only_columns[static_cast<size_t>(~where)];
-        if (sc.is_filename || sc.is_hive) throw NotImplementedException("filter on the constant column '" + sc.name + "' is not pushed into the scan");
-        if (leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull) {
-          std::string why;
-          if (!sc.field.Supported(&why)) throw NotImplementedException("Column '" + sc.name + "': " + why + " is not decoded by the MI355X scan path yet");
-          continue;
-        }
-        int32_t kind, w;
-        int64_t param;
-        // a run-end encoded column is filtered on its flat vector: what matters is the kind of its values
-        const ArrowField& vf = sc.field.type == MI_AT_RUN_END && sc.field.children.size() == 2 ? sc.field.children[1] : sc.field;
-        if (&vf != &sc.field && !sc.field.Plan(&kind, &param, &w))
-          throw NotImplementedException("Column '" + sc.name + "': Arrow type +r with these children is not decoded by the MI355X scan path");
-        // IN () -- an empty range -- keeps nothing (its negation every valid row) whatever the column holds
-        if (!leaf.is_string && leaf.op == device::kLeafRange && !leaf.lo_open && !leaf.hi_open && leaf.lo > leaf.hi) continue;
-        if (leaf.is_string) {
-          // byte-string constants: the column must decode to string_t rows that point into ONE data buffer
-          const bool value_ok = vf.Plan(&kind, &param, &w, /*value_only*/ true) && (kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY);
-          if (!value_ok)
-            throw NotImplementedException("string filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
-                                          ") needs a utf8 / large_utf8 / binary / fixed_size_binary column (dictionary-encoded or not)");
-          continue;
-        }
-        const bool ok = vf.Plan(&kind, &param, &w) && !vf.has_dictionary &&
-                        (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
-                         kind == MI_K_DIV_I64 || kind == MI_K_NARROW || kind == MI_K_BOOL) &&
-                        (w == 1 || w == 2 || w == 4 || w == 8) && vf.type != MI_AT_FLOAT;
-        if (!ok)
-          throw NotImplementedException("filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
-                                        ") needs an integer / boolean / date / time / timestamp / decimal(<=18) column");
-      }
-    }
-    // IN-lists live in HBM for the lifetime of the scan
-    d_in_lists.clear();
-    for (auto& clause : filter)
-      for (auto& leaf : clause) {
-        DeviceBuffer list;
-        if (leaf.op == device::kLeafIn) {
-          list = DeviceBuffer(leaf.in_values.size() * 8);
-          MI_HIP_CHECK(hipMemcpy(list.get(), leaf.in_values.data(), leaf.in_values.size() * 8, hipMemcpyHostToDevice));
-        } else if ((leaf.op == device::kLeafStrIn || leaf.op == device::kLeafStrRange) && !leaf.str_values.empty()) {
-          // 3 words per constant (its string_t image + the device address of its bytes), the bytes behind the table
-          const size_t nc = leaf.str_values.size();
-          size_t bytes = 0;
-          for (auto& v : leaf.str_values) bytes += RoundUp(v.size() + 1, 8);
-          std::vector<uint8_t> img(nc * 24 + bytes, 0);
-          list = DeviceBuffer(img.size());
-          size_t at = nc * 24;
-          for (size_t k = 0; k < nc; k++) {
-            const std::string& v = leaf.str_values[k];
-            if (v.size() > 0xFFFFFFFFull) throw InvalidInputException("string filter constant too long");
-            uint32_t dw[3] = {0, 0, 0};
-            std::memcpy(dw, v.data(), std::min<size_t>(v.size(), v.size() <= 12 ? 12 : 4));
-            const uint64_t w0 = static_cast<uint64_t>(v.size()) | (static_cast<uint64_t>(dw[0]) << 32);
-            const uint64_t w1 = v.size() <= 12 ? (static_cast<uint64_t>(dw[1]) | (static_cast<uint64_t>(dw[2]) << 32)) : 0;
-            const uint64_t w2 = reinterpret_cast<uint64_t>(list.get() + at);
-            std::memcpy(&img[k * 24], &w0, 8);
-            std::memcpy(&img[k * 24 + 8], &w1, 8);
-            std::memcpy(&img[k * 24 + 16], &w2, 8);
-            std::memcpy(&img[at], v.data(), v.size());
-            at += RoundUp(v.size() + 1, 8);
-          }
-          MI_HIP_CHECK(hipMemcpy(list.get(), img.data(), img.size(), hipMemcpyHostToDevice));
-        }
-        d_in_lists.push_back(std::move(list));
-      }
+    filter.Resolve(all_columns, out_columns);
+    filter.UploadConstants();
     if (opts.filter_compact) {
       for (auto& c : out_columns) {
-        if (c.is_filename || c.is_hive) continue;
+        if (c.is_constant()) continue;
         int32_t kind, w;
         int64_t param;
         c.field.Plan(&kind, &param, &w);
@@ -351,13 +232,17 @@ void ArrowScan::InitSlot(Slot& s) {
 void ArrowScan::EnsurePipelineDepth(int depth) {
   depth = std::min(depth, kMaxDepth);
   if (static_cast<int>(slots.size()) >= depth) return;
-  if (producer_started || !inflight.empty()) return;   // a scan that has started keeps the depth it has
-  std::vector<Slot> bigger(static_cast<size_t>(depth));
+  if (readahead.Started() || !inflight.empty()) return;   // a scan that has started keeps the depth it has
+  GrowSlots(static_cast<size_t>(depth));
+}
+
+// (only the pipeline thread touches the slots; the rest of the scan names them by index)
+void ArrowScan::GrowSlots(size_t n) {
+  std::vector<Slot> bigger(n);
   for (size_t i = 0; i < slots.size(); i++) bigger[i] = std::move(slots[i]);
   slots = std::move(bigger);
-  staging.resize(kMaxDepth + 2 * kMaxProducers + 2);   // the deepest pipeline's slots + queues + the bodies being read + a decompressed copy (buffers are allocated on first use)
   if (initialized)
-    for (auto& s : slots) InitSlot(s);
+    for (auto& s : slots) InitSlot(s);   // (those that came along keep what they have)
 }
 
 void ArrowScan::EnsureHostOut(Slot& s, size_t bytes) {
@@ -373,9 +258,8 @@ ArrowScan::Slot* ArrowScan::FreeSlot() {
   return nullptr;
 }
 
-void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
+void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
   ctx->Bind();
-  (void)src;
   if (b.column_node.empty() || b.nodes.empty()) throw InternalException("DictionaryBatch without a value node");
   const ArrowField& f = *b.nodes[static_cast<size_t>(b.column_node[0])].field;  // the field that carries the id (any depth)
   int32_t kind, w;
@@ -478,7 +362,7 @@ void ArrowScan::DecodeDictionary(Source& src, const DecodedBatch& b) {
   // dictionary once and against the rows by index (the offsets are validated here; the device validates them again)
   d->host_valid.resize(static_cast<size_t>(n));
   for (int64_t i = 0; i < n; i++) d->host_valid[static_cast<size_t>(i)] = (words[static_cast<size_t>(i >> 6)] >> (i & 63)) & 1;
-  if (kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY) {
+  if (IsStringKind(kind)) {
     if (delta) d->host_strings = old->host_strings;
     const mi_buffer_span* sp = &b.buffers[0];
     for (int64_t i = 0; i < n_new; i++) {
@@ -527,6 +411,58 @@ void ArrowScan::UploadAux(Slot& s, const std::vector<uint64_t>& aux) {
   MI_HIP_CHECK(hipMemcpyAsync(s.d_aux.get(), s.h_aux.get(), aux_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
 }
 
+// Where the planner finds the batch of a slot and where the consumer of its vectors will see the body.
+BatchPlacement ArrowScan::MakePlacement(const Slot& s) {
+  BatchPlacement where;
+  where.batch = &s.batch;
+  where.in_base = s.d_in.get();
+  // a host consumer of a body that only exists decompressed in HBM: string_t rows point into a pinned mirror of the body
+  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in.get())
+                                             : reinterpret_cast<uint64_t>(s.batch.deferred ? s.h_mirror.get() : s.batch.body);
+  where.dict_len = [this](int64_t id) -> int64_t {
+    auto it = dicts.find(id);
+    if (it == dicts.end()) throw IOException("RecordBatch uses dictionary id " + std::to_string(id) + " before its DictionaryBatch");
+    return it->second->dict_len;
+  };
+  return where;
+}
+
+void ArrowScan::CopyRanges(std::vector<std::pair<int64_t, int64_t>> ranges, const uint8_t* from, uint8_t* to, int64_t align_within) {
+  std::sort(ranges.begin(), ranges.end());
+  int64_t lo = -1, hi = -1;
+  auto flush = [&]() {
+    if (lo < 0) return;
+    if (align_within >= 0) hi = std::min<int64_t>((hi + 63) & ~int64_t(63), align_within);
+    MI_HIP_CHECK(hipMemcpyAsync(to + lo, from + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
+    stats.h2d_bytes += hi - lo;
+  };
+  for (const auto& r : ranges) {
+    if (lo >= 0 && r.first <= hi + (64 << 10)) {   // a gap this small is cheaper to copy than to split
+      hi = std::max(hi, r.first + r.second);
+      continue;
+    }
+    flush();
+    lo = align_within >= 0 ? r.first & ~int64_t(63) : r.first;
+    hi = r.first + r.second;
+  }
+  flush();
+}
+
+// A column absent from a file (union_by_name) is an all-NULL vector: reserved by the planner of the stage that lays the
+// projected columns out, zeroed (data 0, validity 0) on the compute stream, handed out by BuildChunk.
+void ArrowScan::PlanAbsentColumn(Slot& s, BatchPlanner& planner, size_t c, int64_t rows) {
+  Slot::Absent& a = s.absent[c];
+  int64_t param;
+  out_columns[c].field.Plan(&a.kind, &param, &a.width);
+  std::tie(a.data_off, a.valid_off) = planner.AddAbsentColumn(rows, a.width);
+}
+
+void ArrowScan::ZeroAbsentColumn(const Slot& s, size_t c, uint8_t* base, int64_t rows) {
+  const Slot::Absent& a = s.absent[c];
+  MI_HIP_CHECK(hipMemsetAsync(base + a.data_off, 0, static_cast<size_t>(rows) * static_cast<size_t>(std::max(a.width, 1)), ctx->stream));
+  MI_HIP_CHECK(hipMemsetAsync(base + a.valid_off, 0, static_cast<size_t>((rows + 63) / 64) * 8, ctx->stream));
+}
+
 // Stage A of a record batch: H2D of the body, the full-width decode tasks (every projected column; with compaction only
 // the filter columns), the filter, the fused aggregate and -- unless the batch is compacted, which needs the selected row
 // count on the host first (stage B) -- the copy back.
@@ -558,31 +494,20 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   s.planner.opts = po;
   s.planner.Clear();
   s.col_root.assign(out_columns.size(), -1);
-  s.absent.assign(out_columns.size(), {0, 0});
-  s.filter_root.assign(filter_columns.size(), -1);
+  s.absent.assign(out_columns.size(), {});
+  s.filter_root.assign(filter.columns.size(), -1);
   s.node_dict.clear();
 
-  BatchPlacement where;
-  where.batch = &b;
-  where.in_base = s.d_in.get();
-  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in.get())
-                                             : reinterpret_cast<uint64_t>(mirror ? s.h_mirror.get() : b.body);
-  where.dict_len = [&](int64_t id) -> int64_t {
-    auto it = dicts.find(id);
-    if (it == dicts.end()) throw IOException("RecordBatch uses dictionary id " + std::to_string(id) + " before its DictionaryBatch");
-    return it->second->dict_len;
-  };
+  BatchPlacement where = MakePlacement(s);
   // filter columns read their decoded vectors from HBM: never aliased into a body that may not even be uploaded
   std::vector<char> no_alias(b.nodes.size(), 0);
   if (has_filter) {
-    for (size_t k = 0; k < filter_columns.size(); k++) {
-      const int32_t wc = filter_columns[k];
-      const int32_t fc = wc >= 0 ? src.out_to_file_column[static_cast<size_t>(wc)] : src.filter_to_file_column[static_cast<size_t>(~wc)];
+    for (const int32_t wc : filter.columns) {
+      const int32_t fc = src.FileColumn(wc);
       if (fc >= 0) no_alias[static_cast<size_t>(b.column_node[static_cast<size_t>(fc)])] = 1;
     }
     where.no_alias = &no_alias;
   }
-  std::vector<int32_t> widths(out_columns.size(), 0);
   auto width_of = [](const ScanColumn& c) {
     int32_t kind, w;
     int64_t param;
@@ -593,14 +518,10 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   //      Compaction (stage A): only the filter columns + sel + counts; the projected columns are planned in stage B.
   if (!s.compact) {
     for (size_t c = 0; c < out_columns.size(); c++) {
-      if (out_columns[c].is_filename || out_columns[c].is_hive) continue;
-      widths[c] = width_of(out_columns[c]);
+      if (out_columns[c].is_constant()) continue;
       const int32_t fc = src.out_to_file_column[c];
-      if (fc < 0) {  // column absent in this file (union_by_name): an all-NULL vector
-        s.absent[c] = s.planner.AddAbsentColumn(n, widths[c]);
-        continue;
-      }
-      s.col_root[c] = s.planner.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
+      if (fc < 0) PlanAbsentColumn(s, s.planner, c, n);
+      else s.col_root[c] = s.planner.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
     }
   }
   if (has_filter) {
@@ -609,13 +530,13 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   }
   s.d2h_bytes = s.compact ? 0 : s.planner.arena_bytes;
   if (has_filter) {
-    for (size_t k = 0; k < filter_columns.size(); k++) {
-      const int32_t wc = filter_columns[k];
+    for (size_t k = 0; k < filter.columns.size(); k++) {
+      const int32_t wc = filter.columns[k];
       if (wc >= 0 && !s.compact) {
         s.filter_root[k] = s.col_root[static_cast<size_t>(wc)];
         continue;
       }
-      const int32_t fc = wc >= 0 ? src.out_to_file_column[static_cast<size_t>(wc)] : src.filter_to_file_column[static_cast<size_t>(~wc)];
+      const int32_t fc = src.FileColumn(wc);
       if (fc >= 0) s.filter_root[k] = s.planner.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
     }
   }
@@ -628,7 +549,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   if (s.compact) {
     stage_b_worst = 4096;
     for (auto& c : out_columns)
-      if (!c.is_filename && !c.is_hive)
+      if (!c.is_constant())
         stage_b_worst += RoundUp(static_cast<size_t>(n) * static_cast<size_t>(std::max(width_of(c), 1)) + 16) + RoundUp(static_cast<size_t>((n + 63) / 64) * 8 + 8);
   }
   const size_t out_bytes = s.stage_a_bytes + stage_b_worst + 64;
@@ -670,165 +591,25 @@ void ArrowScan::EnqueueBatch(Slot& s) {
       if (nd.alias_body_off >= 0) upload.emplace_back(nd.alias_body_off, nd.nrows * nd.width);
   if (s.compact) {  // stage B reads every projected column
     for (size_t c = 0; c < out_columns.size(); c++) {
-      const int32_t fc = (out_columns[c].is_filename || out_columns[c].is_hive) ? -1 : src.out_to_file_column[c];
+      const int32_t fc = out_columns[c].is_constant() ? -1 : src.out_to_file_column[c];
       if (fc < 0) continue;
       for (const auto& sp : b.nodes[static_cast<size_t>(b.column_node[static_cast<size_t>(fc)])].spans)
         if (sp.length > 0) upload.emplace_back(sp.offset, sp.length);
     }
   }
-  if (b.body_size > 0) {
-    std::sort(upload.begin(), upload.end());
-    int64_t lo = -1, hi = -1;
-    auto flush = [&]() {
-      if (lo < 0) return;
-      hi = std::min<int64_t>((hi + 63) & ~int64_t(63), b.body_size);
-      MI_HIP_CHECK(hipMemcpyAsync(s.d_in.get() + lo, b.body + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
-      stats.h2d_bytes += hi - lo;
-    };
-    for (const auto& r : upload) {
-      if (lo >= 0 && r.first <= hi + (64 << 10)) {
-        hi = std::max(hi, r.first + r.second);
-        continue;
-      }
-      flush();
-      lo = r.first & ~int64_t(63);
-      hi = r.first + r.second;
-    }
-    flush();
-  }
+  if (b.body_size > 0) CopyRanges(std::move(upload), b.body, s.d_in.get(), /*align_within*/ b.body_size);
   }
   MI_HIP_CHECK(hipEventRecord(s.h2d_done, ctx->h2d_stream));
   MI_HIP_CHECK(hipStreamWaitEvent(ctx->stream, s.h2d_done, 0));
-  // absent columns: all-NULL vectors (data 0, validity 0)
-  if (!s.compact) {
-    for (size_t c = 0; c < out_columns.size(); c++) {
-      if (out_columns[c].is_filename || out_columns[c].is_hive) continue;
-      if (src.out_to_file_column[c] < 0 && n > 0) {
-        MI_HIP_CHECK(hipMemsetAsync(s.d_out.get() + s.absent[c].first, 0, static_cast<size_t>(n) * static_cast<size_t>(std::max(widths[c], 1)), ctx->stream));
-        MI_HIP_CHECK(hipMemsetAsync(s.d_out.get() + s.absent[c].second, 0, static_cast<size_t>((n + 63) / 64) * 8, ctx->stream));
-      }
-    }
-  }
+  if (!s.compact && n > 0)
+    for (size_t c = 0; c < out_columns.size(); c++)
+      if (!out_columns[c].is_constant() && src.out_to_file_column[c] < 0) ZeroAbsentColumn(s, c, s.d_out.get(), n);
   s.plan->Set(s.planner.tasks.data(), static_cast<int32_t>(s.planner.tasks.size()), ctx->stream);
   MI_HIP_CHECK(hipMemsetAsync(s.plan->d_status.get(), 0, sizeof(uint32_t), ctx->stream));
   s.plan->Launch(ctx->stream);
   if (has_filter && n > 0) {
-    device::FilterProgram prog;
-    std::memset(&prog, 0, sizeof(prog));
-    size_t li = 0;
-    for (auto& clause : filter) {
-      for (size_t j = 0; j < clause.size(); j++, li++) {
-        const FilterLeaf& leaf = clause[j];
-        device::FilterLeafDev& L = prog.leaves[prog.n_leaves++];
-        const int32_t wc = filter_columns[static_cast<size_t>(leaf.out_col)];
-        const ScanColumn& sc = wc >= 0 ? out_columns[static_cast<size_t>(wc)] : filter_only_columns[static_cast<size_t>(~wc)];
-        const int32_t root = s.filter_root[static_cast<size_t>(leaf.out_col)];
-        L.op = leaf.op;
-        L.flags = (j + 1 == clause.size() ? device::kLeafEndsClause : 0) | (leaf.negate ? device::kLeafNegate : 0);
-        L.lo = leaf.lo;
-        L.hi = leaf.hi;
-        L.in_values = d_in_lists[li].get<int64_t>();
-        L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.in_values.size());
-        if (leaf.op == device::kLeafStrRange)
-          L.n_in = (leaf.lo_open ? 0 : 1) | (leaf.lo_incl ? 2 : 0) | (leaf.hi_open ? 0 : 4) | (leaf.hi_incl ? 8 : 0);
-        L.width = 1;
-        if (root < 0) {
-          // the column is absent from this file (union_by_name): every row is NULL -- IS NULL keeps every row, everything
-          // else keeps none (an empty, non-negated range over any readable bytes: the selection buffer itself)
-          L.validity = nullptr;
-          L.flags &= ~device::kLeafNegate;
-          if (leaf.op == device::kLeafIsNull) {
-            L.op = device::kLeafIsNotNull;
-          } else {
-            L.op = device::kLeafRange;
-            L.lo = 1;
-            L.hi = 0;
-            L.data = s.d_out.get() + s.sel_off;
-          }
-          continue;
-        }
-        const PlannedNode& pn = s.planner.nodes[static_cast<size_t>(root)];
-        L.data = pn.alias_body_off >= 0 ? static_cast<const void*>(s.d_in.get() + pn.alias_body_off) : static_cast<const void*>(s.d_out.get() + pn.data_off);
-        L.validity = pn.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out.get() + pn.valid_off) : nullptr;
-        L.width = std::max(pn.width, 1);
-        const bool null_test = leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull;
-        if (pn.kind == MI_K_DICT && (leaf.is_string || null_test)) {
-          // dictionary-encoded: match the dictionary version this batch uses once (host), the rows by index.  IS [NOT] NULL
-          // goes the same way: a row is NULL when its index or its dictionary entry is
-          const std::shared_ptr<DictState>& dict = s.node_dict[static_cast<size_t>(root)];
-          if (!dict || (leaf.is_string && static_cast<int64_t>(dict->host_strings.size()) != dict->dict_len))
-            throw NotImplementedException("string filter on the dictionary-encoded column '" + leaf.column + "': its dictionary values are not strings");
-          auto it = dict->match_maps.find(li);
-          if (it == dict->match_maps.end()) {
-            std::vector<uint8_t> codes(static_cast<size_t>(dict->dict_len) + 1, 0);
-            auto passes = [&](const std::string& v) {   // std::string compares byte-wise (unsigned), a proper prefix first
-              if (leaf.op != device::kLeafStrRange) return std::binary_search(leaf.str_values.begin(), leaf.str_values.end(), v);
-              auto cmp = [](const std::string& a, const std::string& b) {
-                const int c = std::memcmp(a.data(), b.data(), std::min(a.size(), b.size()));
-                return c != 0 ? c : (a.size() < b.size() ? -1 : a.size() > b.size() ? 1 : 0);
-              };
-              if (!leaf.lo_open) {
-                const int c = cmp(v, leaf.str_values[0]);
-                if (c < 0 || (c == 0 && !leaf.lo_incl)) return false;
-              }
-              if (!leaf.hi_open) {
-                const int c = cmp(v, leaf.str_values[1]);
-                if (c > 0 || (c == 0 && !leaf.hi_incl)) return false;
-              }
-              return true;
-            };
-            for (int64_t e = 0; e < dict->dict_len; e++)
-              codes[static_cast<size_t>(e)] = !dict->host_valid[static_cast<size_t>(e)] ? 2
-                                              : (leaf.is_string && passes(dict->host_strings[static_cast<size_t>(e)])) ? 1 : 0;
-            codes[static_cast<size_t>(dict->dict_len)] = 2;   // the NULL entry rows without a value point at
-            // device copy + its pinned source, uploaded on the compute stream in front of the filter kernel that reads it
-            DeviceBuffer d_map(RoundUp(codes.size() + 16));
-            auto map = std::make_shared<std::pair<DeviceBuffer, PinnedBuffer>>(std::move(d_map), PinnedBuffer(RoundUp(codes.size() + 16)));
-            std::memcpy(map->second.get(), codes.data(), codes.size());
-            MI_HIP_CHECK(hipMemcpyAsync(map->first.get(), map->second.get(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
-            it = dict->match_maps.emplace(li, std::shared_ptr<void>(map, map->first.get())).first;
-          }
-          L.op = device::kLeafDictMap;
-          L.in_values = static_cast<const int64_t*>(it->second.get());
-          L.n_in = static_cast<int32_t>(std::min<int64_t>(dict->dict_len + 1, 0x7FFFFFFF));
-          L.lo = leaf.op == device::kLeafIsNull ? 2 : leaf.op == device::kLeafIsNotNull ? 3 : leaf.negate ? 1 : 0;
-          L.flags &= ~device::kLeafNegate;   // applied inside the kernel: a NULL entry fails = and <> alike
-          L.width = 4;
-          continue;
-        }
-        if (leaf.is_string) {
-          // the rows' long-string pointers are consumer addresses (pn.ptr_base = byte 0 of the Arrow data buffer as the
-          // consumer sees it); the kernel reads the bytes from the HBM copy of that buffer
-          const DecodedNode& src = b.nodes[static_cast<size_t>(pn.source_node)];
-          // run-end encoded: the rows point into the values child's data buffer
-          const DecodedNode& dn = pn.kind == MI_K_RUN_END ? b.nodes[static_cast<size_t>(src.children[1])] : src;
-          const int32_t vkind = pn.kind == MI_K_RUN_END ? pn.value_kind : pn.kind;
-          const size_t data_span = vkind == MI_K_FIXED_BINARY ? 1 : 2;
-          L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(s.d_in.get() + (dn.spans.size() > data_span ? dn.spans[data_span].offset : 0)));
-          L.hi = static_cast<int64_t>(pn.ptr_base);
-          continue;
-        }
-        const ArrowField& vf = sc.field.type == MI_AT_RUN_END && sc.field.children.size() == 2 ? sc.field.children[1] : sc.field;
-        if (vf.type == MI_AT_INT && !vf.is_signed) {
-          L.flags |= device::kLeafUnsigned;
-          if (pn.width == 8 && leaf.op != device::kLeafIsNull && leaf.op != device::kLeafIsNotNull) {
-            // uint64: compared through the order-preserving map x ^ 2^63 on both sides.  Constants arrive as int64, a
-            // negative one is below every value of the column.
-            L.flags |= device::kLeafBias;
-            const int64_t bias = static_cast<int64_t>(0x8000000000000000ull);
-            if (leaf.op == device::kLeafRange) {
-              if (!leaf.hi_open && leaf.hi < 0) { L.lo = 1; L.hi = 0; }   // empty (its negation keeps every valid row, as it must)
-              else {
-                L.lo = (leaf.lo_open || leaf.lo < 0) ? bias : (leaf.lo ^ bias);            // bias = the image of 0
-                L.hi = leaf.hi_open ? static_cast<int64_t>(0x7FFFFFFFFFFFFFFFull) : (leaf.hi ^ bias);   // image of UINT64_MAX
-              }
-            }
-            // IN-lists of uint64 columns are uploaded unbiased: compare them unbiased too
-            if (leaf.op == device::kLeafIn) L.flags &= ~device::kLeafBias;
-          }
-        }
-      }
-    }
+    const device::FilterProgram prog =
+        filter.Program(out_columns, {b, s.planner.nodes, s.filter_root, s.node_dict, s.d_in.get(), s.d_out.get(), s.d_out.get() + s.sel_off}, ctx->stream);
     MI_HIP_CHECK(device::LaunchFilterProgram(prog, n, reinterpret_cast<mi_sel_t*>(s.d_out.get() + s.sel_off),
                                              reinterpret_cast<uint32_t*>(s.d_out.get() + s.sel_count_off), ctx->stream));
   }
@@ -893,11 +674,8 @@ void ArrowScan::EnqueueLz4(Slot& s) {
     // the deployment to at least slots + 3 -- every slot gets a stream of its own: 0.24 s instead of 0.29 s at 8 slots
     // and 20 queues (profiles/r02/lz4/streams_ab.txt); on the default 4 queues the same choice was the 0.46 s above.
     int kLz4Streams = d.codec == 1 ? 16 : 3;
-    {
-      const char* hwq = std::getenv("GPU_MAX_HW_QUEUES");
-      const int n_slots = static_cast<int>(slots.size());
-      if (hwq != nullptr && std::atoi(hwq) >= n_slots + 3) kLz4Streams = n_slots;
-    }
+    const int n_slots = static_cast<int>(slots.size());
+    if (HardwareQueues() >= n_slots + 3) kLz4Streams = n_slots;
     const int idx = static_cast<int>(&s - slots.data());
     if (idx >= kLz4Streams) {
       Slot& owner = slots[static_cast<size_t>(idx % kLz4Streams)];
@@ -971,26 +749,10 @@ void ArrowScan::EnqueueLz4(Slot& s) {
   // H2D on the copy stream: the compressed bytes of the needed buffers (neighbours closer than 64 KiB travel as one copy)
   std::vector<std::pair<int64_t, int64_t>> ranges;
   for (auto& f : d.buffers) ranges.emplace_back(f.comp_off, f.comp_len);
-  std::sort(ranges.begin(), ranges.end());
-  int64_t lo = -1, hi = -1;
-  auto flush = [&]() {
-    if (lo < 0) return;
-    MI_HIP_CHECK(hipMemcpyAsync(s.d_comp.get() + lo, d.comp + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
-    stats.h2d_bytes += hi - lo;
-  };
   if (is_zstd) stats.zstd_batches_on_device++;
   else stats.lz4_batches_on_device++;
   stats.decompressed_bytes += b.body_size;
-  for (const auto& r : ranges) {
-    if (lo >= 0 && r.first <= hi + (64 << 10)) {
-      hi = std::max(hi, r.first + r.second);
-      continue;
-    }
-    flush();
-    lo = r.first;
-    hi = r.first + r.second;
-  }
-  flush();
+  CopyRanges(std::move(ranges), d.comp, s.d_comp.get(), /*align_within*/ -1);
   MI_HIP_CHECK(hipMemcpyAsync(s.d_lz4.get(), s.h_lz4.get(), tables_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
   MI_HIP_CHECK(hipEventRecord(s.h2d_done, ctx->h2d_stream));
   hipStream_t q = s.lz4_stream;
@@ -1064,30 +826,14 @@ void ArrowScan::EnqueueStageB(Slot& s) {
   // a fresh planner pass for the projected columns: arena offsets relative to the compact region behind stage A's arrays
   BatchPlanner cp(s.planner.opts);
   cp.opts.zero_copy_direct = false;
-  BatchPlacement where;
-  where.batch = &b;
-  where.in_base = s.d_in.get();
-  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in.get())
-                                             : reinterpret_cast<uint64_t>(b.deferred ? s.h_mirror.get() : b.body);
+  BatchPlacement where = MakePlacement(s);
   where.alloc_rows = total;
-  where.dict_len = [&](int64_t id) -> int64_t {
-    auto it = dicts.find(id);
-    if (it == dicts.end()) throw IOException("RecordBatch uses dictionary id " + std::to_string(id) + " before its DictionaryBatch");
-    return it->second->dict_len;
-  };
   s.col_root.assign(out_columns.size(), -1);
-  std::vector<int32_t> widths(out_columns.size(), 0);
   for (size_t c = 0; c < out_columns.size(); c++) {
-    if (out_columns[c].is_filename || out_columns[c].is_hive) continue;
-    int32_t kind;
-    int64_t param;
-    out_columns[c].field.Plan(&kind, &param, &widths[c]);
+    if (out_columns[c].is_constant()) continue;
     const int32_t fc = src.out_to_file_column[c];
-    if (fc < 0) {
-      s.absent[c] = cp.AddAbsentColumn(total, widths[c]);
-      continue;
-    }
-    s.col_root[c] = cp.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
+    if (fc < 0) PlanAbsentColumn(s, cp, c, total);
+    else s.col_root[c] = cp.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
   }
   s.d2h_bytes = cp.arena_bytes;
   const size_t region_off = RoundUp(s.stage_a_bytes, 4096);
@@ -1102,10 +848,9 @@ void ArrowScan::EnqueueStageB(Slot& s) {
   hipStream_t st = ctx->stream;
   // validity words start as all ones (the gather kernel clears the NULLs); absent columns are all NULL
   for (size_t c = 0; c < out_columns.size(); c++) {
-    if (out_columns[c].is_filename || out_columns[c].is_hive || total == 0) continue;
+    if (out_columns[c].is_constant() || total == 0) continue;
     if (s.col_root[c] < 0) {
-      MI_HIP_CHECK(hipMemsetAsync(region + s.absent[c].first, 0, static_cast<size_t>(total) * static_cast<size_t>(std::max(widths[c], 1)), st));
-      MI_HIP_CHECK(hipMemsetAsync(region + s.absent[c].second, 0, static_cast<size_t>((total + 63) / 64) * 8, st));
+      ZeroAbsentColumn(s, c, region, total);
       continue;
     }
     const PlannedNode& pn = cp.nodes[static_cast<size_t>(s.col_root[c])];
@@ -1153,7 +898,7 @@ void ArrowScan::BuildVector(const Slot& s, int32_t node, size_t window, int64_t 
   v->out_width = o.width;
   v->count = r1 - r0;
   const int32_t vk = o.kind == MI_K_RUN_END ? o.value_kind : o.kind;  // run-end encoded: the values' string heap
-  if (vk == MI_K_STR32 || vk == MI_K_STR64 || vk == MI_K_FIXED_BINARY) {
+  if (IsStringKind(vk)) {
     v->heap = reinterpret_cast<const void*>(o.ptr_base);
     v->heap_size = o.heap_size;
   }
@@ -1173,12 +918,11 @@ void ArrowScan::BuildVector(const Slot& s, int32_t node, size_t window, int64_t 
   }
 }
 
-// per-file column mapping by name (DuckDB's multi-file column mapping) + reader projection
-void ArrowScan::PrepareSource(size_t si) {
-  OpenSource(si);
+// Per-file column mapping by name (DuckDB's multi-file column mapping): where every output and filter-only column lies in
+// the batches of file `si`, and with that the columns its readers project.
+std::vector<std::string> ArrowScan::MapColumns(size_t si, const ArrowSchemaModel& schema) {
   Source& src = sources[si];
-  if (src.prepared) return;
-  const ArrowSchemaModel& schema = src.reader->GetBaseSchema();
+  const std::string& path = readahead.Path(si);
   std::vector<std::string> names;
   for (auto& f : schema.fields) names.push_back(f.name);
   DeduplicateColumns(names);
@@ -1187,14 +931,14 @@ void ArrowScan::PrepareSource(size_t si) {
     auto it = std::find(names.begin(), names.end(), col.name);
     if (it == names.end()) {
       if (!opts.union_by_name) {
-        throw InvalidInputException("Failed to read file \"" + src.path + "\": schema mismatch: column \"" + col.name +
+        throw InvalidInputException("Failed to read file \"" + path + "\": schema mismatch: column \"" + col.name +
                                     "\" is missing. If you are trying to read files with different schemas, try setting union_by_name=True");
       }
       return -1;
     }
     const ArrowField& ff = schema.fields[static_cast<size_t>(it - names.begin())];
     if (ff.Format() != col.field.Format()) {
-      throw NotImplementedException("Column \"" + col.name + "\" has type " + ff.DuckType() + " in file \"" + src.path +
+      throw NotImplementedException("Column \"" + col.name + "\" has type " + ff.DuckType() + " in file \"" + path +
                                     "\" but " + col.field.DuckType() +
                                     " in the first file; cross-file casts are done by DuckDB's MultiFileReader above this path");
     }
@@ -1204,214 +948,25 @@ void ArrowScan::PrepareSource(size_t si) {
     return static_cast<int32_t>(wanted.size() - 1);
   };
   src.out_to_file_column.assign(out_columns.size(), -1);
-  for (size_t c = 0; c < out_columns.size(); c++) {
-    if (out_columns[c].is_filename || out_columns[c].is_hive) continue;
-    src.out_to_file_column[c] = map_column(out_columns[c]);
-  }
-  src.filter_to_file_column.assign(filter_only_columns.size(), -1);
-  for (size_t c = 0; c < filter_only_columns.size(); c++) src.filter_to_file_column[c] = map_column(filter_only_columns[c]);
-  if (!wanted.empty()) src.reader->SetColumnProjection(wanted);
-  {
-    std::lock_guard<std::mutex> lk(q_mu);   // the other producers wait for this before they open their own reader of the file
-    src.wanted = wanted;
-    src.prepared = true;
-  }
-  q_cv.notify_all();
-}
-
-// A pinned staging buffer for one record-batch body; the returned handle gives it back when the batch is released.
-std::shared_ptr<void> ArrowScan::LeaseStaging(size_t bytes, uint8_t** ptr) {
-  Staging* st = nullptr;
-  {
-    std::unique_lock<std::mutex> lk(q_mu);
-    const int64_t t0 = trace ? TraceNow() : 0;
-    q_cv.wait(lk, [&] {
-      if (producer_stop) return true;
-      for (auto& x : staging)
-        if (!x.leased) return true;
-      return false;
-    });
-    if (trace) tr_lease_wait_ns += TraceNow() - t0;
-    if (producer_stop) throw IOException("scan closed while reading");
-    // prefer a free buffer that is already large enough
-    for (auto& x : staging)
-      if (!x.leased && x.buf.size() >= bytes + 64) { st = &x; break; }
-    if (!st)
-      for (auto& x : staging)
-        if (!x.leased) { st = &x; break; }
-    st->leased = true;
-  }
-  if (bytes + 64 > st->buf.size()) {
-    ctx->Bind();
-    Retire(Grow(st->buf, bytes + 64, GrownCapacity(bytes + 64, st->buf.size(), 1 << 16)));
-  }
-  *ptr = st->buf.get();
-  return std::shared_ptr<void>(st->buf.get(), [this, st](void*) {
-    {
-      std::lock_guard<std::mutex> lk(q_mu);
-      st->leased = false;
-    }
-    q_cv.notify_all();
-  });
-}
-
-void ArrowScan::ProducerLoop(int p) {
-  size_t cap = n_producers > 1 ? 2 : static_cast<size_t>(kReadAhead);
-  if (const char* v = std::getenv("MI_SCAN_READAHEAD")) cap = static_cast<size_t>(std::max(1, std::min(4, std::atoi(v))));   // fetched batches a producer holds (A/B)
-  auto push = [&](Fetched&& f) {
-    std::unique_lock<std::mutex> lk(q_mu);
-    const int64_t t0 = trace ? TraceNow() : 0;
-    q_cv.wait(lk, [&] { return producer_stop || fetched[static_cast<size_t>(p)].size() < cap; });
-    if (trace) tr_push_wait_ns += TraceNow() - t0;
-    if (producer_stop) return false;
-    fetched[static_cast<size_t>(p)].push_back(std::move(f));
-    lk.unlock();
-    q_cv.notify_all();
-    return true;
-  };
-  try {
-    ctx->Bind();
-    ctx->BindThisThread();   // the GPU's NUMA node: this thread's preads (and the I/O pool's, for it) and its pinned staging buffers
-    size_t si = 0;
-    int64_t ordinal = 0, share = 0;   // record batches of the file list; of those, this scan's (rank / world)
-    while (si < sources.size()) {
-      {
-        std::lock_guard<std::mutex> lk(q_mu);
-        if (producer_stop) return;
-      }
-      IPCStreamReader* reader = nullptr;
-      if (p == 0) {
-        PrepareSource(si);
-        reader = sources[si].reader.get();
-      } else {
-        // a reader of its own over the same file, with the projection producer 0 settled on
-        auto& mine = extra_readers[static_cast<size_t>(p - 1)];
-        if (mine.size() <= si) mine.resize(sources.size());
-        if (!mine[si]) {
-          std::vector<std::string> wanted;
-          {
-            std::unique_lock<std::mutex> lk(q_mu);
-            q_cv.wait(lk, [&] { return producer_stop || producer_error || sources[si].prepared; });
-            if (producer_stop) return;
-            if (producer_error) std::rethrow_exception(producer_error);   // producer 0 could not prepare the file: same error here
-            wanted = sources[si].wanted;
-          }
-          mine[si] = std::make_unique<IPCFileStreamReader>(sources[si].path);
-          mine[si]->SetDeferLz4(opts.host_decompress < 0 || (opts.host_decompress == 0 && opts.device_resident != 0));
-          mine[si]->SetDeferZstd(DeferZstd(opts));
-          mine[si]->GetBaseSchema();
-          if (!wanted.empty()) mine[si]->SetColumnProjection(wanted);
-        }
-        reader = mine[si].get();
-      }
-      reader->SetBodyAllocator([this](size_t bytes, MessageType type, uint8_t** ptr) -> std::shared_ptr<void> {
-        if (type == MessageType::DICTIONARY_BATCH) {  // lives as long as the dictionary version that points into it
-          ctx->Bind();
-          std::shared_ptr<void> body = Shared<PinnedBuffer>(bytes + 64);
-          *ptr = static_cast<uint8_t*>(body.get());
-          return body;
-        }
-        return LeaseStaging(bytes, ptr);
-      });
-      Fetched f;
-      const bool in_share = opts.world <= 1 || (ordinal % opts.world) == opts.rank;
-      const bool mine = in_share && (share % n_producers) == p;
-      const int64_t t_read = trace ? TraceNow() : 0;
-      const bool got = reader->GetNextBatch(&f.batch, opts.accept_dictionaries != 0, /*skip_body*/ !mine);
-      if (trace) tr_read_ns += TraceNow() - t_read;
-      reader->ReleaseCurrentBody();  // the lease belongs to the batch alone
-      if (!got) {
-        si++;
-        continue;
-      }
-      f.source = static_cast<int32_t>(si);
-      if (!f.batch.is_dictionary) {
-        f.ordinal = ordinal++;
-        if (in_share) share++;
-        if (!mine) continue;
-      }
-      if (!push(std::move(f))) return;
-    }
-    Fetched end;
-    end.end = true;
-    push(std::move(end));
-  } catch (...) {
-    Fetched err;
-    err.error = std::current_exception();
-    {
-      std::lock_guard<std::mutex> lk(q_mu);   // producers waiting for this one (a file it was to prepare) fail with it
-      if (!producer_error) producer_error = err.error;
-    }
-    q_cv.notify_all();
-    push(std::move(err));
-  }
-}
-
-void ArrowScan::StartProducer() {
-  if (producer_started) return;
-  producer_started = true;
-  trace = std::getenv("MI_SCAN_TRACE") != nullptr;
-  // several producers only where record batches are independent of what came before them in the stream (no dictionary
-  // batches, which every later batch of the file depends on) and where there is a pread to overlap (files, not caller buffers)
-  // How many: ONE when the bodies only have to be read (plain bodies, and compressed ones that are expanded in HBM) -- its preads
-  // already run on the whole I/O pool, and with a CPU quota of 16 more threads only throttle one another (SF10 host consumer:
-  // 0.18 s with one producer, 0.20 with three) -- THREE when the reader's host threads decompress them (a producer then spends
-  // most of its time waiting for its own body's decompression: LZ4 0.29 against 0.60 s, ZSTD 0.61 against 1.27 s).  Which it
-  // is shows in the first record batch's header.
-  n_producers = 1;
-  if (!is_buffers && !opts.accept_dictionaries) {
-    int wanted = 1;
-    try {
-      IPCFileStreamReader peek(sources[0].path);
-      peek.GetBaseSchema();
-      DecodedBatch first;
-      if (peek.GetNextBatch(&first, /*accept_dictionaries*/ false, /*skip_body*/ true) && first.compression >= 0) {
-        const bool in_hbm = first.compression == 1 ? DeferZstd(opts) : (opts.host_decompress < 0 || (opts.host_decompress == 0 && opts.device_resident != 0));
-        if (!in_hbm) wanted = 3;
-      }
-    } catch (...) {   // whatever is wrong with the file, the scan itself will say
-    }
-    const char* v = std::getenv("MI_SCAN_PRODUCERS");
-    n_producers = std::max(1, std::min(kMaxProducers, v ? std::atoi(v) : wanted));
-  }
-  fetched.assign(static_cast<size_t>(n_producers), {});
-  extra_readers.resize(static_cast<size_t>(n_producers - 1));
-  next_fetch = 0;
-  for (int p = 0; p < n_producers; p++) producers.emplace_back([this, p] { ProducerLoop(p); });
-}
-
-void ArrowScan::StopProducer() {
-  if (!producer_started) return;
-  {
-    std::lock_guard<std::mutex> lk(q_mu);
-    producer_stop = true;
-  }
-  q_cv.notify_all();
-  for (auto& t : producers)
-    if (t.joinable()) t.join();
+  for (size_t c = 0; c < out_columns.size(); c++)
+    if (!out_columns[c].is_constant()) src.out_to_file_column[c] = map_column(out_columns[c]);
+  src.filter_to_file_column.assign(filter.only.size(), -1);
+  for (size_t c = 0; c < filter.only.size(); c++) src.filter_to_file_column[c] = map_column(filter.only[c]);
+  return wanted;
 }
 
 bool ArrowScan::SubmitNextBatch(bool may_block) {
-  StartProducer();
+  if (!readahead.Started()) {
+    trace = std::getenv("MI_SCAN_TRACE") != nullptr;
+    readahead.Start(trace);
+  }
   while (!exhausted) {
     Slot* slot = FreeSlot();
     if (!slot) return false;
     Fetched f;
-    {
-      // in order: batch j of this scan's share comes from producer j mod P (a dictionary batch -- single producer only --
-      // does not count)
-      std::unique_lock<std::mutex> lk(q_mu);
-      auto& q = fetched[static_cast<size_t>(next_fetch % n_producers)];
-      if (q.empty()) {
-        if (!may_block) return false;
-        const int64_t t0 = trace ? TraceNow() : 0;
-        q_cv.wait(lk, [&] { return !q.empty(); });
-        if (trace) tr_fetch_wait_ns += TraceNow() - t0;
-      }
-      f = std::move(q.front());
-      q.pop_front();
-    }
-    q_cv.notify_all();
+    const int64_t t0 = trace && may_block ? TraceNow() : 0;
+    if (!readahead.Take(&f, may_block)) return false;
+    if (trace && may_block) tr_fetch_wait_ns += TraceNow() - t0;
     if (f.error) {
       exhausted = true;
       std::rethrow_exception(f.error);
@@ -1420,24 +975,16 @@ bool ArrowScan::SubmitNextBatch(bool may_block) {
       exhausted = true;
       return false;
     }
-    cur_source = static_cast<size_t>(f.source);
-    Source& src = sources[cur_source];
     if (f.batch.is_dictionary) {
-      DecodeDictionary(src, f.batch);
+      DecodeDictionary(f.batch);
       continue;
     }
-    next_fetch++;
     if (f.batch.deferred && opts.pipeline_depth == 0) {
       // compressed bodies that are expanded in HBM spend 0.5 (LZ4) to 5 ms (ZSTD) in latency-bound kernels that leave the chip
       // nearly idle: a caller who left the depth to the scan gets as many record batches side by side as that takes
       const size_t wanted = f.batch.deferred->codec == 1 ? 16 : 8;
       if (slots.size() < wanted) {
-        const size_t had = slots.size();
-        std::vector<Slot> bigger(wanted);
-        for (size_t i = 0; i < had; i++) bigger[i] = std::move(slots[i]);   // (only this thread touches the slots; the rest of the scan names them by index)
-        slots = std::move(bigger);
-        if (initialized)
-          for (size_t i = had; i < wanted; i++) InitSlot(slots[i]);
+        GrowSlots(wanted);
         slot = FreeSlot();
       }
     }
@@ -1495,9 +1042,7 @@ bool ArrowScan::AcquireBatch(BatchRef* out) {
     if (q == hipSuccess) break;
     if (q != hipErrorNotReady) MI_HIP_CHECK(q);
     const int64_t t0 = trace ? TraceNow() : 0;
-    std::unique_lock<std::mutex> lk(q_mu);
-    auto& ready = fetched[static_cast<size_t>(next_fetch % n_producers)];
-    q_cv.wait_for(lk, std::chrono::microseconds(100), [&] { return !ready.empty(); });
+    readahead.WaitReady(std::chrono::microseconds(100));
     if (trace) tr_poll_ns += TraceNow() - t0;
   }
   const int si = inflight.front();
@@ -1554,7 +1099,7 @@ void ArrowScan::EnsureHostVectors(const BatchRef& ref) {
 void ArrowScan::DeviceColumn(const BatchRef& ref, size_t c, DeviceColumnView* out) const {
   *out = DeviceColumnView();
   const Slot& s = slots[static_cast<size_t>(ref.slot)];
-  if (s.compact || s.batch.deferred || c >= out_columns.size() || out_columns[c].is_filename || out_columns[c].is_hive || s.col_root[c] < 0) return;
+  if (s.compact || s.batch.deferred || c >= out_columns.size() || out_columns[c].is_constant() || s.col_root[c] < 0) return;
   const PlannedNode& pn = s.planner.nodes[static_cast<size_t>(s.col_root[c])];
   if (!pn.children.empty() || pn.dict_id >= 0 || pn.source_node < 0) return;
   if (pn.alias_body_off >= 0 && !opts.device_resident) return;   // aliased into the HOST body: not in HBM at all
@@ -1590,9 +1135,9 @@ void ArrowScan::BuildChunk(const BatchRef& ref, int32_t window, ChunkStorage* st
   const Source& src = sources[static_cast<size_t>(s.source)];
   for (size_t c = 0; c < out_columns.size(); c++) {
     mi_vector& v = st->vectors[c];
-    if (out_columns[c].is_filename || out_columns[c].is_hive) {
+    if (out_columns[c].is_constant()) {
       // strings are kept alive in the source (path / hive map), one vector of 2048 copies per (file, column)
-      const std::string& stable = out_columns[c].is_filename ? src.path : src.hive.at(out_columns[c].hive_key);
+      const std::string& stable = out_columns[c].is_filename ? readahead.Path(static_cast<size_t>(s.source)) : src.hive.at(out_columns[c].hive_key);
       const mi_string_t* cv;
       {
         std::lock_guard<std::mutex> lk(const_mu);
@@ -1610,13 +1155,11 @@ void ArrowScan::BuildChunk(const BatchRef& ref, int32_t window, ChunkStorage* st
     if (s.col_root[c] >= 0) {
       BuildVector(s, s.col_root[c], static_cast<size_t>(window), s.compact ? n : -1, base, st, &v);
     } else {  // absent in this file: all NULL
-      int32_t kind, w;
-      int64_t param;
-      out_columns[c].field.Plan(&kind, &param, &w);
-      v.data = base + s.absent[c].first + static_cast<size_t>(row0) * static_cast<size_t>(std::max(w, 1));
-      v.validity = reinterpret_cast<mi_validity_t*>(base + s.absent[c].second) + row0 / 64;
-      v.kind = kind;
-      v.out_width = w;
+      const Slot::Absent& a = s.absent[c];
+      v.data = base + a.data_off + static_cast<size_t>(row0) * static_cast<size_t>(std::max(a.width, 1));
+      v.validity = reinterpret_cast<mi_validity_t*>(base + a.valid_off) + row0 / 64;
+      v.kind = a.kind;
+      v.out_width = a.width;
       v.count = n;
     }
   }
@@ -1706,11 +1249,7 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
     const ScanColumn& c = out_columns[static_cast<size_t>(slot_of(name))];
     int32_t kind, w;
     int64_t param;
-    const bool ok = !c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &w) &&
-                    (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
-                     kind == MI_K_DIV_I64 || kind == MI_K_NARROW) &&
-                    (w == 1 || w == 2 || w == 4 || w == 8) && c.field.type != MI_AT_FLOAT;
-    if (!ok) throw InvalidInputException("Column '" + name + "' (" + c.field.DuckType() + ") is not a fixed-width integer-like column: the fused aggregate takes integers, DATE, TIME/TIMESTAMP and DECIMAL(<=18)");
+    if (!(!c.is_constant() && c.field.Plan(&kind, &param, &w) && IsIntegerLike(kind, w, c.field, /*allow_bool*/ false))) throw InvalidInputException("Column '" + name + "' (" + c.field.DuckType() + ") is not a fixed-width integer-like column: the fused aggregate takes integers, DATE, TIME/TIMESTAMP and DECIMAL(<=18)");
   }
   agg.d_acc = DeviceBuffer(4 * sizeof(unsigned long long));
   MI_HIP_CHECK(hipMemsetAsync(agg.d_acc.get(), 0, agg.d_acc.size(), ctx->stream));
@@ -1733,12 +1272,7 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
   agg.on = false;
 }
 
-double ArrowScan::Progress() {
-  if (sources.empty()) return 100;
-  double done = static_cast<double>(std::min(cur_source, sources.size()));
-  if (cur_source < sources.size() && sources[cur_source].reader) done += sources[cur_source].reader->GetProgress() / 100.0;
-  return std::min(100.0, 100.0 * done / static_cast<double>(sources.size()));
-}
+double ArrowScan::Progress() { return readahead.Progress(); }
 
 // ------------------------------------------------------------------------------------------------ multi-device
 MultiDeviceScan::MultiDeviceScan(const std::vector<Context*>& ctxs, std::vector<std::string> paths, const mi_scan_options& o) {
@@ -1887,21 +1421,29 @@ namespace miarrow {
 ArrowScan* SingleScanOf(mi_scan* s) { return s ? s->single : nullptr; }
 }  // namespace miarrow
 
+namespace {
+// the mi_scan_open_* calls: the options (all zero when the caller gives none), the scan `make` builds from them, the handle
+template <typename Make>
+void OpenScan(const mi_scan_options* opts, mi_scan** out, Make make) {
+  mi_scan_options o;
+  std::memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  auto s = std::make_unique<mi_scan>();
+  auto scan = make(o);
+  s->single = dynamic_cast<ArrowScan*>(scan.get());
+  s->scan = std::move(scan);
+  *out = s.release();
+}
+}  // namespace
+
 extern "C" {
 
 int mi_scan_open_files(mi_ctx* ctx, const char* const* paths, int32_t n_paths, const mi_scan_options* opts, mi_scan** out) {
   return WrapC([&] {
     if (!ctx || !paths || n_paths <= 0 || !out) throw InvalidInputException("mi_scan_open_files: bad argument");
-    mi_scan_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (opts) o = *opts;
-    std::vector<std::string> v;
-    for (int32_t i = 0; i < n_paths; i++) v.emplace_back(paths[i]);
-    auto s = std::make_unique<mi_scan>();
-    auto scan = std::make_unique<ArrowScan>(ContextOf(ctx), std::move(v), o);
-    s->single = scan.get();
-    s->scan = std::move(scan);
-    *out = s.release();
+    OpenScan(opts, out, [&](const mi_scan_options& o) {
+      return std::make_unique<ArrowScan>(ContextOf(ctx), std::vector<std::string>(paths, paths + n_paths), o);
+    });
   });
 }
 
@@ -1909,32 +1451,22 @@ int mi_scan_open_files_multi(mi_ctx* const* ctxs, int32_t n_ctxs, const char* co
                              const mi_scan_options* opts, mi_scan** out) {
   return WrapC([&] {
     if (!ctxs || n_ctxs <= 0 || !paths || n_paths <= 0 || !out) throw InvalidInputException("mi_scan_open_files_multi: bad argument");
-    mi_scan_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (opts) o = *opts;
-    std::vector<std::string> v;
-    for (int32_t i = 0; i < n_paths; i++) v.emplace_back(paths[i]);
-    std::vector<Context*> cs;
-    for (int32_t i = 0; i < n_ctxs; i++) cs.push_back(ContextOf(ctxs[i]));
-    auto s = std::make_unique<mi_scan>();
-    s->scan = std::make_unique<MultiDeviceScan>(cs, std::move(v), o);
-    *out = s.release();
+    OpenScan(opts, out, [&](const mi_scan_options& o) {
+      std::vector<Context*> cs;
+      for (int32_t i = 0; i < n_ctxs; i++) cs.push_back(ContextOf(ctxs[i]));
+      return std::make_unique<MultiDeviceScan>(cs, std::vector<std::string>(paths, paths + n_paths), o);
+    });
   });
 }
 
 int mi_scan_open_buffers(mi_ctx* ctx, const mi_ipc_buffer* buffers, int32_t n_buffers, const mi_scan_options* opts, mi_scan** out) {
   return WrapC([&] {
     if (!ctx || (!buffers && n_buffers) || n_buffers < 0 || !out) throw InvalidInputException("mi_scan_open_buffers: bad argument");
-    mi_scan_options o;
-    std::memset(&o, 0, sizeof(o));
-    if (opts) o = *opts;
-    std::vector<ArrowIPCBuffer> v;
-    for (int32_t i = 0; i < n_buffers; i++) v.emplace_back(buffers[i].ptr, buffers[i].size);
-    auto s = std::make_unique<mi_scan>();
-    auto scan = std::make_unique<ArrowScan>(ContextOf(ctx), std::move(v), o);
-    s->single = scan.get();
-    s->scan = std::move(scan);
-    *out = s.release();
+    OpenScan(opts, out, [&](const mi_scan_options& o) {
+      std::vector<ArrowIPCBuffer> v;
+      for (int32_t i = 0; i < n_buffers; i++) v.emplace_back(buffers[i].ptr, buffers[i].size);
+      return std::make_unique<ArrowScan>(ContextOf(ctx), std::move(v), o);
+    });
   });
 }
 

@@ -11,16 +11,17 @@
 // The per-value work of ArrowToDuckDB runs in the HIP kernels; this class is the pipeline around them:
 // record-batch body -> pinned slot -> hipMemcpyAsync H2D (copy stream) -> class kernels (compute stream) ->
 // hipMemcpyAsync D2H (copy-back stream) -> DataChunks that alias the pinned output slot.
+// What feeds the pipeline and what it is told to keep live beside it:
+//   scan_readahead.{hpp,cpp}   ReadAhead: producer threads, their queues and pinned staging buffers (host code only)
+//   scan_filter.cpp            pushed-down predicates: normalisation, binding to the scan's columns, constants in HBM,
+//                              the per-batch FilterProgram
 #pragma once
 
-#include <atomic>
 #include <hip/hip_runtime_api.h>
 
-#include <condition_variable>
 #include <deque>
 #include <map>
 #include <mutex>
-#include <thread>
 #include <memory>
 #include <string>
 #include <vector>
@@ -28,6 +29,7 @@
 #include "batch_planner.hpp"
 #include "engine.hpp"
 #include "ipc_stream_reader.hpp"
+#include "scan_readahead.hpp"
 
 namespace miarrow {
 
@@ -39,7 +41,20 @@ struct ScanColumn {
   bool is_filename = false;   // `filename` option (README.md:104-107)
   bool is_hive = false;       // hive partition key
   std::string hive_key;
+  //! one value per file, made on the host: never read from a file, decoded or filtered on the GPU
+  bool is_constant() const { return is_filename || is_hive; }
 };
+
+inline bool IsStringKind(int32_t kind) { return kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY; }
+//! a run-end encoded column is filtered on its flat vector: what matters is the field of its values
+inline const ArrowField& ValueField(const ArrowField& f) { return f.type == MI_AT_RUN_END && f.children.size() == 2 ? f.children[1] : f; }
+//! Columns a range comparison / the fused aggregate reads as integers: integers, DATE, TIME / TIMESTAMP, DECIMAL(<= 18)
+//! -- and booleans where `allow_bool` -- by their transcode plan
+inline bool IsIntegerLike(int32_t kind, int32_t width, const ArrowField& f, bool allow_bool) {
+  return (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
+          kind == MI_K_DIV_I64 || kind == MI_K_NARROW || (allow_bool && kind == MI_K_BOOL)) &&
+         (width == 1 || width == 2 || width == 4 || width == 8) && f.type != MI_AT_FLOAT;
+}
 
 //! One leaf of a pushed-down predicate after normalisation (scan_filter.cpp): every comparison on an integer-like column
 //! is an inclusive range (optionally negated), plus IS [NOT] NULL and IN-lists.
@@ -59,6 +74,59 @@ struct FilterLeaf {
 //! Conjunctive normal form: every clause is an OR of leaves, the filter is the AND of its clauses.
 using FilterCnf = std::vector<std::vector<FilterLeaf>>;
 FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root);  // scan_filter.cpp
+
+//! One immutable version of a decoded dictionary (dict_len + 1 entries, the last one NULL).  Record batches keep the
+//! version they were enqueued with, so a later replacement / delta never changes what an in-flight batch sees.
+struct DictState {
+  DeviceBuffer d_data;           // decoded values on the device
+  DeviceBuffer d_validity;
+  PinnedBuffer h_data;           // pinned host copy (host consumers)
+  void* h_validity = nullptr;    // == h_words for host consumers
+  PinnedBuffer h_words;          // the validity words (uint64_t) as built on the host (uploaded from here)
+  PinnedBuffer h_status;         // status word (uint32_t) of the decode of the values, checked with the first batch that uses them
+  HipEvent uploaded;             // the dictionary body is in HBM
+  std::unique_ptr<Plan> decode_plan;   // kept until the version dies: its status word is read asynchronously
+  std::vector<std::shared_ptr<void>> d_heaps;      // device copies of the dictionary bodies (long string payload)
+  std::vector<std::shared_ptr<void>> host_bodies;  // host bodies: long dictionary strings point into them
+  int64_t dict_len = 0;
+  int32_t kind = 0, out_width = 0;
+  //! string-valued dictionaries: the values themselves (empty + not valid for NULL entries), for pushed-down string
+  //! predicates -- the dictionary is matched once, on the host, the rows by index (K6, kLeafDictMap)
+  std::vector<std::string> host_strings;
+  std::vector<char> host_valid;
+  std::map<size_t, std::shared_ptr<void>> match_maps;   // filter leaf -> device byte per entry: 0 no, 1 yes, 2 NULL
+};
+
+//! A pushed-down filter bound to the columns of a scan (ArrowScan::Init)
+struct BoundFilter {
+  FilterCnf cnf;
+  //! filter column k (FilterLeaf::out_col) -> output column (>= 0) or ~index into `only` (< 0)
+  std::vector<int32_t> columns;
+  std::vector<ScanColumn> only;          // filter columns outside the projection: decoded, never emitted
+  std::vector<DeviceBuffer> d_in_lists;  // per leaf (clause order): its IN-list / string constants in HBM, or empty
+  const ScanColumn& Column(size_t k, const std::vector<ScanColumn>& out_columns) const {
+    const int32_t wc = columns[k];
+    return wc >= 0 ? out_columns[static_cast<size_t>(wc)] : only[static_cast<size_t>(~wc)];
+  }
+  //! resolves every leaf to a filter column (projected, or decoded for the filter alone) and checks that its type can be
+  //! compared on the GPU
+  void Resolve(const std::vector<ScanColumn>& all_columns, const std::vector<ScanColumn>& out_columns);
+  //! IN-lists and string constants -> HBM, for the lifetime of the scan
+  void UploadConstants();
+  //! What Program() reads of one record batch in its pipeline slot
+  struct Batch {
+    const DecodedBatch& batch;
+    const std::vector<PlannedNode>& nodes;
+    const std::vector<int32_t>& roots;                          // per filter column: planner node of its decoded vector, -1 absent
+    const std::vector<std::shared_ptr<DictState>>& node_dict;   // per planner node
+    const uint8_t* d_in;                                        // the body in HBM
+    const uint8_t* d_out;                                       // the arena of decoded vectors
+    const uint8_t* d_empty;                                     // any readable bytes (leaves over absent columns)
+  };
+  //! The leaves as the filter kernel takes them for this record batch.  Dictionary match maps that the batch's dictionary
+  //! versions do not have yet are made here and uploaded on `stream`, in front of the kernel that reads them.
+  device::FilterProgram Program(const std::vector<ScanColumn>& out_columns, const Batch& b, hipStream_t stream) const;
+};
 
 //! Vectors of one DataChunk (the storage behind mi_data_chunk.columns)
 struct ChunkStorage {
@@ -153,35 +221,16 @@ class ArrowScan : public ScanBase {
   void DeviceColumn(const BatchRef& ref, size_t column, DeviceColumnView* out) const;
 
  private:
+  //! files, or (without any) caller buffers
+  ArrowScan(Context* ctx, std::vector<std::string> paths, std::vector<ArrowIPCBuffer> buffers, const mi_scan_options& opts);
+  //! What the scan knows of one file beside the read-ahead's reader of it.  The column mapping is written by MapColumns
+  //! on the first producer thread before that file's first batch is queued, and read by the pipeline after it took one.
   struct Source {
-    std::string path;                          // empty for buffers
-    std::unique_ptr<IPCStreamReader> reader;
     std::vector<int32_t> out_to_file_column;   // per output column: index in this file's projected batch, -1 = absent
     std::vector<int32_t> filter_to_file_column;  // per filter-only column (not in the projection)
     std::map<std::string, std::string> hive;   // key -> value parsed from the path
-    bool opened = false, prepared = false;
-    std::vector<std::string> wanted;           // the reader projection PrepareSource settled on (the extra producers' readers take it too)
-  };
-  //! One immutable version of a decoded dictionary (dict_len + 1 entries, the last one NULL).  Record batches keep the
-  //! version they were enqueued with, so a later replacement / delta never changes what an in-flight batch sees.
-  struct DictState {
-    DeviceBuffer d_data;           // decoded values on the device
-    DeviceBuffer d_validity;
-    PinnedBuffer h_data;           // pinned host copy (host consumers)
-    void* h_validity = nullptr;    // == h_words for host consumers
-    PinnedBuffer h_words;          // the validity words (uint64_t) as built on the host (uploaded from here)
-    PinnedBuffer h_status;         // status word (uint32_t) of the decode of the values, checked with the first batch that uses them
-    HipEvent uploaded;             // the dictionary body is in HBM
-    std::unique_ptr<Plan> decode_plan;   // kept until the version dies: its status word is read asynchronously
-    std::vector<std::shared_ptr<void>> d_heaps;      // device copies of the dictionary bodies (long string payload)
-    std::vector<std::shared_ptr<void>> host_bodies;  // host bodies: long dictionary strings point into them
-    int64_t dict_len = 0;
-    int32_t kind = 0, out_width = 0;
-    //! string-valued dictionaries: the values themselves (empty + not valid for NULL entries), for pushed-down string
-    //! predicates -- the dictionary is matched once, on the host, the rows by index (K6, kLeafDictMap)
-    std::vector<std::string> host_strings;
-    std::vector<char> host_valid;
-    std::map<size_t, std::shared_ptr<void>> match_maps;   // filter leaf -> device byte per entry: 0 no, 1 yes, 2 NULL
+    //! where output column `wc` (>= 0) or filter-only column ~wc (< 0) lies in this file's projected batch, -1 = absent
+    int32_t FileColumn(int32_t wc) const { return wc >= 0 ? out_to_file_column[static_cast<size_t>(wc)] : filter_to_file_column[static_cast<size_t>(~wc)]; }
   };
   struct Slot {
     int64_t tr_enqueued_ns = 0;       // MI_SCAN_TRACE: when the batch was submitted
@@ -200,7 +249,11 @@ class ArrowScan : public ScanBase {
     int64_t nrows = 0;
     BatchPlanner planner{PlannerOptions{}};            // layout + tasks of the projected columns
     std::vector<int32_t> col_root;                     // per output column: planner node (-1: absent in this file)
-    std::vector<std::pair<size_t, size_t>> absent;     // per output column absent in this file: {data_off, valid_off}
+    struct Absent {                                    // the all-NULL vector of an output column absent in this file
+      size_t data_off = 0, valid_off = 0;              // in the arena the projected columns are laid out in
+      int32_t kind = 0, width = 0;
+    };
+    std::vector<Absent> absent;                        // per output column
     std::vector<std::shared_ptr<DictState>> node_dict; // per planner node: the dictionary version this batch uses
     PinnedBuffer h_aux;                                // list window tables, string-view buffer tables, filter program
     DeviceBuffer d_aux;
@@ -225,70 +278,41 @@ class ArrowScan : public ScanBase {
     uint8_t* compact_region = nullptr;                 // device address of the dense arrays
   };
 
-  void OpenSource(size_t i);
   //! takes the next fetched record batch and enqueues its GPU work; false when nothing could be submitted (no free
   //! slot, nothing fetched yet while `may_block` is false, or every source is exhausted)
   bool SubmitNextBatch(bool may_block);
-  // ---- read-ahead: a producer thread walks the sources (open, column mapping, projection, sharding, pread into pinned
-  // staging buffers) a few record batches ahead of the consumer, so file I/O overlaps whatever the consumer does between
-  // two Next() calls; the reference reads synchronously inside the scan call (ipc_file_stream_reader.cpp:71-94)
-  struct Fetched {
-    DecodedBatch batch;
-    int32_t source = 0;
-    int64_t ordinal = 0;
-    bool end = false;                 // every source is exhausted
-    std::exception_ptr error;         // raised where the consumer reaches it, after the batches read before it
-  };
-  struct Staging {                    // pinned body buffers, leased to one record batch at a time
-    PinnedBuffer buf;
-    bool leased = false;
-  };
-  void StartProducer();
-  void StopProducer();
-  void ProducerLoop(int p);
-  void PrepareSource(size_t si);      // per-file column mapping + reader projection
-  std::shared_ptr<void> LeaseStaging(size_t bytes, uint8_t** ptr);
-  static constexpr int kReadAhead = 3;              // fetched batches waiting for a slot (per producer: 2 when there are several)
-  static constexpr int kMaxProducers = 4;
-  //! Several read-ahead threads for file scans without dictionaries: producer p reads the record batches j of this scan's
-  //! share with j mod P == p (every producer walks every header, bodies that are not its own are stepped over unread -- the
-  //! rank / world rule once more, inside the process), so the pread of one body overlaps the header walk, staging lease and
-  //! pread of the next ones.  The consumer takes them back in order: batch j from queue j mod P.
-  int n_producers = 1;
-  std::vector<std::thread> producers;
-  std::mutex q_mu;
-  std::condition_variable q_cv;
-  std::vector<std::deque<Fetched>> fetched;         // one queue per producer
-  int64_t next_fetch = 0;                           // j of the batch the consumer takes next
-  std::exception_ptr producer_error;                // the first failure of any producer
-  std::vector<std::vector<std::unique_ptr<IPCStreamReader>>> extra_readers;   // [producer - 1][source]
-  std::vector<Staging> staging;                     // in flight on the GPU + waiting + the one being read
-  bool producer_started = false, producer_stop = false;
+  //! per-file column mapping by name (ReadAhead::Hooks::project): fills sources[si], returns the reader projection
+  std::vector<std::string> MapColumns(size_t si, const ArrowSchemaModel& schema);
+  void GrowSlots(size_t n);
   void InitSlot(Slot& s);
   void EnqueueBatch(Slot& s);
   void EnqueueStageB(Slot& s);
   void EnqueueLz4(Slot& s);
   void UploadAux(Slot& s, const std::vector<uint64_t>& aux);
   void BuildVector(const Slot& s, int32_t node, size_t window, int64_t compact_rows, uint8_t* base, ChunkStorage* st, mi_vector* out);
-  void DecodeDictionary(Source& src, const DecodedBatch& b);
+  void DecodeDictionary(const DecodedBatch& b);
+  BatchPlacement MakePlacement(const Slot& s);
+  //! H2D on the copy stream: `ranges` ({offset, length}, the same in `from` and `to`) closer than 64 KiB travel as one copy.
+  //! align_within >= 0: every copy starts and ends on a multiple of 64 bytes, or at that size.
+  void CopyRanges(std::vector<std::pair<int64_t, int64_t>> ranges, const uint8_t* from, uint8_t* to, int64_t align_within);
+  //! a column absent from a file (union_by_name): its all-NULL vector of `rows` rows reserved in `planner`'s arena, ...
+  void PlanAbsentColumn(Slot& s, BatchPlanner& planner, size_t column, int64_t rows);
+  //! ... and zeroed on the compute stream
+  void ZeroAbsentColumn(const Slot& s, size_t column, uint8_t* base, int64_t rows);
   void EnsureHostOut(Slot& s, size_t bytes);
   Slot* FreeSlot();
 
   Context* ctx;
   mi_scan_options opts;
   std::vector<Source> sources;
-  std::vector<ArrowIPCBuffer> buffers;
-  bool is_buffers = false;
+  const bool is_buffers;
   bool bound = false, initialized = false;
   std::vector<ScanColumn> all_columns;   // bind result
   std::vector<ScanColumn> out_columns;   // after projection
-  std::vector<ScanColumn> filter_only_columns;  // filter columns outside the projection: decoded, never emitted
-  std::vector<std::string> projected_names;
 
   // pipeline
   std::vector<Slot> slots;
   std::deque<int> inflight;              // slot indices in submission order (not yet acquired)
-  size_t cur_source = 0;
   bool exhausted = false;
   // consumer cursor of Next()
   BatchRef cur_ref;
@@ -310,27 +334,24 @@ class ArrowScan : public ScanBase {
   std::vector<mi_validity_t> all_valid;
   // dictionaries by id
   std::map<int64_t, std::shared_ptr<DictState>> dicts;
-  // filter
   bool has_filter = false;
-  FilterCnf filter;
-  //! filter column k -> output column (>= 0) or ~index into filter_only_columns (< 0)
-  std::vector<int32_t> filter_columns;
+  BoundFilter filter;
   // Buffers a slot has outgrown.  Freeing a buffer waits for the device to go idle -- with the other slots' record batches
   // in flight that is a pipeline stall of milliseconds -- so they are kept until the scan closes (growth is geometric: at
   // most twice the final sizes in all).
   std::vector<DeviceBuffer> retired_device;
   std::vector<PinnedBuffer> retired_host;
-  std::mutex retire_mu;   // the pipeline thread and the producers (staging buffers) both retire
-  void Retire(DeviceBuffer b) { if (b) { std::lock_guard<std::mutex> lk(retire_mu); retired_device.push_back(std::move(b)); } }
-  void Retire(PinnedBuffer b) { if (b) { std::lock_guard<std::mutex> lk(retire_mu); retired_host.push_back(std::move(b)); } }
-  std::vector<DeviceBuffer> d_in_lists;  // per leaf (clause order): its IN-list in HBM, or empty
+  void Retire(DeviceBuffer b) { if (b) retired_device.push_back(std::move(b)); }   // (the pipeline thread alone)
+  void Retire(PinnedBuffer b) { if (b) retired_host.push_back(std::move(b)); }
   bool compact = false;
   bool keep_on_device = false;
   mi_scan_stats stats{};
   // MI_SCAN_TRACE: where the host threads' time went (seconds), printed when the scan closes (diagnostics only)
   bool trace = false;
-  std::atomic<int64_t> tr_read_ns{0}, tr_push_wait_ns{0}, tr_lease_wait_ns{0};
   int64_t tr_latency_ns = 0, tr_inflight_sum = 0, tr_k8_prep_ns = 0, tr_k8_launch_ns = 0, tr_enqueue_ns = 0, tr_fetch_wait_ns = 0, tr_event_wait_ns = 0, tr_poll_ns = 0;
+  // Last member, so the first to go: its queues and readers release their staging leases while everything above is
+  // still there, and its pinned buffers are freed after ~ArrowScan's body has synchronised the streams.
+  ReadAhead readahead;
 };
 
 //! read_arrow over several GPUs of one process: one ArrowScan per context, record batch k of the file list

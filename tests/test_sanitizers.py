@@ -109,3 +109,53 @@ def test_zstd_stages_on_the_cpu(tmp_path):
     import re
     seen = [int(x) for x in re.findall(r"\d+", run.stdout.split("\n")[0])]
     assert all(v > 0 for v in seen[:3]), run.stdout
+
+
+def test_readahead_orders_and_shards_under_tsan(tmp_path):
+    """The scan's read-ahead (duckdb-arrow_amd/csrc/scan_readahead.cpp: producer threads, per-producer queues, staging
+    leases) is host code with the GPU behind two hooks, so tests/sanitize/readahead_check.cpp runs it under ThreadSanitizer
+    with malloc for pinned memory: for 1 to 4 producers and for world 1 and ranks 0..2 of world 3 every batch of the share
+    comes out once, in stream order, byte-equal to a single-threaded read; a missing file in the middle of the list fails
+    after the batches before it; stopping while the producers are blocked returns."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.ipc as ipc
+    csrc = os.path.join(ROOT, "duckdb-arrow_amd", "csrc")
+    exe = str(tmp_path / "readahead_check")
+    build = subprocess.run(
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I", os.path.join(ROOT, "include"),
+         os.path.join(ROOT, "tests", "sanitize", "readahead_check.cpp"), os.path.join(csrc, "scan_readahead.cpp"),
+         os.path.join(csrc, "ipc_stream_reader.cpp"), os.path.join(csrc, "ipc_format.cpp"), "-ldl", "-lpthread", "-o", exe],
+        capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert build.returncode == 0, build.stderr[-2000:]
+    rng = np.random.default_rng(11)
+
+    def write(name, n_batches, compression=None, dictionary=False):
+        rows = 400
+        cols = {"k": np.arange(n_batches * rows, dtype=np.int64), "v": rng.integers(0, 1 << 40, n_batches * rows),
+                "s": ["row %d of %s" % (i % 53, name) for i in range(n_batches * rows)]}
+        t = pa.table(cols)
+        if dictionary:
+            t = t.append_column("d", pa.array(["tag %d" % (i % 7) for i in range(n_batches * rows)]).dictionary_encode())
+        path = str(tmp_path / name)
+        with ipc.new_stream(path, t.schema, options=ipc.IpcWriteOptions(compression=compression)) as w:
+            w.write_table(t, max_chunksize=rows)
+        return path
+
+    cases = {
+        "plain": ([write("p%d.arrows" % i, 30 + 3 * i) for i in range(4)], [], 1),
+        # LZ4 bodies that the reader's host threads decompress: three producers unless told otherwise
+        "lz4": ([write("z%d.arrows" % i, 28 + 5 * i, compression="lz4") for i in range(3)], [], 3),
+        # dictionary batches order every later batch of their file: one producer, whatever is asked for
+        "dict": ([write("d%d.arrows" % i, 32 + i, dictionary=True) for i in range(3)], ["--dict"], 1),
+    }
+    for name, (files, flags, producers) in cases.items():
+        run = subprocess.run([exe] + flags + files, capture_output=True, text=True, timeout=600,
+                             env=dict(os.environ, MI_IO_THREADS="2", TSAN_OPTIONS="halt_on_error=0"))
+        assert run.returncode == 0, (name, run.stdout[-1000:], run.stderr[-3000:])
+        assert "ThreadSanitizer" not in run.stderr and "FAILED" not in run.stderr, (name, run.stderr[-3000:])
+        assert "%d producers by default" % producers in run.stdout and "32 runs, 0 failed" in run.stdout, (name, run.stdout)

@@ -504,6 +504,11 @@ std::vector<int64_t> Plan::NullCounts(bool reset) {
   return MapNullCounts(per_slot.data());
 }
 
+void Plan::ResetCounters(hipStream_t stream) {
+  MI_HIP_CHECK(hipMemsetAsync(d_status.get(), 0, sizeof(uint32_t), stream));
+  if (n_null_counts) MI_HIP_CHECK(hipMemsetAsync(d_null_counts.get(), 0, static_cast<size_t>(n_null_counts) * 8, stream));
+}
+
 std::vector<int64_t> Plan::MapNullCounts(const int64_t* per_slot) const {
   // back to the caller's task order (non-encode tasks report 0)
   std::vector<int64_t> out(order.size(), 0);

@@ -98,6 +98,8 @@ struct Plan {
           class_rows[device::kNumClasses] = {0};
   uint32_t Status();
   std::vector<int64_t> NullCounts(bool reset);
+  //! Clears the status word and the NULL counters on `stream`, for callers that copy both back asynchronously themselves
+  void ResetCounters(hipStream_t stream);
   //! per_slot = a host copy of d_null_counts (n_null_counts entries) -> NULL counts in the caller's task order
   std::vector<int64_t> MapNullCounts(const int64_t* per_slot) const;
 };

@@ -1,7 +1,8 @@
 // writer.cpp -- see writer.hpp.
 #include "writer.hpp"
 #include "ipc_stream_reader.hpp"
-#include "scan_operator.hpp"
+#include "writer_internal.hpp"
+#include "writer_plan.hpp"
 
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -20,17 +21,12 @@ namespace miarrow {
 
 int WrapC(const std::function<void()>& f);  // c_api.cpp
 
-namespace {
-// MI_WRITER_TIMING=1: cumulative seconds per stage of the COPY sink, printed when a writer is finalized
-struct SinkTimers {
-  double append = 0, serialize = 0, write = 0;
-  bool on = std::getenv("MI_WRITER_TIMING") != nullptr;
-  std::mutex mu;  // several sink threads add their stage times
-};
 SinkTimers& Timers() {
   static SinkTimers t;
   return t;
 }
+
+namespace {
 struct ScopedTimer {
   double* acc;
   std::chrono::steady_clock::time_point t0;
@@ -42,16 +38,6 @@ struct ScopedTimer {
     *acc += dt;
   }
 };
-constexpr size_t kBufferAlign = 64;  // Arrow's recommended buffer alignment; any multiple of 8 is valid IPC
-size_t RoundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// The sink's buffers grow by GrownCapacity -- a quarter of headroom: row groups of one table differ by a few percent, and
-// the outgrown buffer is freed at once, which waits for the device to go idle (with the other sink threads' row groups in
-// flight a stall of milliseconds).  `keep_bytes`: what the new buffer starts with (pinned buffers).
-template <typename Buffer>
-void Fit(Buffer& buf, size_t need, size_t keep_bytes = 0) {
-  Grow(buf, need, GrownCapacity(need, buf.size(), 1 << 16), keep_bytes);
-}
 
 // DuckDB logical type -> how the vector is laid out and which K7 kernel encodes it
 void EncodePlanFor(const ArrowField& f, int32_t* enc_kind, int64_t* param, int32_t* width) {
@@ -260,7 +246,6 @@ void ChunkCollection::Reset() {
   for (auto& c : columns) {
     c.count = 0;
     c.heap_used = 0;
-    c.ptr_base = 0;
     c.payload_bytes = 0;
     c.has_nulls = false;
     if (c.validity) std::memset(c.validity.get(), 0xFF, c.validity.size());
@@ -295,116 +280,62 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   if (!plan) plan = std::make_unique<Plan>(ctx);
   if (n_top > 0x7FFFFFFFll) throw InvalidInputException("record batch too large");
 
-  // body layout: field nodes depth first, per node validity, then (offsets) / data -- the order
-  // ArrowIpcEncoderEncodeSimpleRecordBatch walks the ArrowArray tree; device staging layout beside it
+  // the body layout, and the device staging layout beside it
   const size_t n_nodes = buffer.columns.size();
-  std::vector<mi_buffer_span> spans;
-  struct InOff { size_t data, validity, heap; size_t first_span; };
+  std::vector<EncodeNode> nodes(n_nodes);
+  struct InOff { size_t data, validity, heap; };
   std::vector<InOff> in_off(n_nodes);
-  size_t body_off = 0, in_bytes = 0;
-  auto add_span = [&](int64_t len) {
-    spans.push_back(mi_buffer_span{static_cast<int64_t>(body_off), len});
-    body_off += RoundUp(static_cast<size_t>(len), kBufferAlign);
-  };
+  size_t in_bytes = 0;
   for (size_t ci = 0; ci < n_nodes; ci++) {
     auto& c = buffer.columns[ci];
-    const int64_t n = c.count;
-    if (n > 0x7FFFFFFFll) throw InvalidInputException("record batch too large");
-    in_off[ci].first_span = spans.size();
-    add_span((n + 7) / 8);  // validity: always emitted (ArrowAppender::FinalizeChild)
-    const int64_t off_width = c.large_offsets ? 8 : 4;
-    if (c.IsList()) {
-      add_span((n + 1) * off_width);
-    } else if (!c.IsGroup()) {
-      switch (c.enc_kind) {
-        case MI_K_ENC_COPY: add_span(n * c.param); break;
-        case MI_K_ENC_DEC128: add_span(n * 16); break;
-        case MI_K_ENC_BOOL: add_span((n + 7) / 8); break;
-        case MI_K_ENC_STR32:
-          if (c.payload_bytes > 0x7FFFFFFFll && !c.large_offsets) {
-            throw InvalidInputException(
-                "Arrow Appender: The maximum total string size for regular string buffers is 2147483647 but the offset of " +
-                std::to_string(c.payload_bytes) + " exceeds this.\n* SET arrow_large_buffer_size=true to use large string buffers");
-          }
-          add_span((n + 1) * off_width);
-          add_span(c.payload_bytes);
-          break;
-        default: break;
-      }
-    }
-    const int64_t staged_rows = n;
+    nodes[ci] = EncodeNode{c.IsGroup() ? MI_K_ENC_VALIDITY : c.enc_kind, c.param, c.large_offsets, c.count, c.payload_bytes};
     in_off[ci].data = in_bytes;
-    in_bytes += RoundUp(static_cast<size_t>(staged_rows) * static_cast<size_t>(c.width) + 16, 256);
+    in_bytes += RoundUp(static_cast<size_t>(c.count) * static_cast<size_t>(c.width) + 16, 256);
     in_off[ci].validity = in_bytes;
-    in_bytes += RoundUp(static_cast<size_t>((n + 63) / 64) * 8 + 8, 256);
+    in_bytes += RoundUp(static_cast<size_t>((c.count + 63) / 64) * 8 + 8, 256);
     in_off[ci].heap = in_bytes;
     in_bytes += RoundUp(static_cast<size_t>(c.heap_used) + 16, 256);
   }
-  body_size = static_cast<int64_t>(body_off);
+  BodyLayout layout;
+  LayOutBody(nodes, &layout);
+  body_size = layout.body_size;
+  const size_t body_bytes = static_cast<size_t>(body_size);
   Fit(d_in, in_bytes + 256);
-  Fit(d_body, body_off + 256);
+  Fit(d_body, body_bytes + 256);
   PinnedBuffer& h_body = bodies[cur_body];
-  Fit(h_body, body_off + 256);
+  Fit(h_body, body_bytes + 256);
 
   hipStream_t s = stream;
-  MI_HIP_CHECK(hipMemsetAsync(d_body.get(), 0, body_off, s));  // the padding bytes of every buffer are zero
+  MI_HIP_CHECK(hipMemsetAsync(d_body.get(), 0, body_bytes, s));  // the padding bytes of every buffer are zero
   std::vector<mi_col_task> tasks;
   std::vector<int32_t> validity_task(n_nodes, -1);  // task whose NULL counter belongs to node ci
   for (size_t ci = 0; ci < n_nodes; ci++) {
     auto& c = buffer.columns[ci];
     const int64_t n = c.count;
     if (n == 0) continue;  // zero-length buffers, no work
-    const size_t sp = in_off[ci].first_span;
-    const int64_t staged_rows = n;
+    const uint8_t* d_data = d_in.get() + in_off[ci].data;
+    const uint8_t* d_validity = d_in.get() + in_off[ci].validity;
+    const uint8_t* d_heap = d_in.get() + in_off[ci].heap;
     if (c.width > 0)
-      MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].data, c.data.get(), static_cast<size_t>(staged_rows) * static_cast<size_t>(c.width), hipMemcpyHostToDevice, s));
+      MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].data, c.data.get(), static_cast<size_t>(n) * static_cast<size_t>(c.width), hipMemcpyHostToDevice, s));
     if (c.has_nulls)
       MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].validity, c.validity.get(), static_cast<size_t>((n + 63) / 64) * 8, hipMemcpyHostToDevice, s));
     if (c.heap_used)
       MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].heap, c.heap.get(), static_cast<size_t>(c.heap_used), hipMemcpyHostToDevice, s));
-    mi_col_task t;
-    std::memset(&t, 0, sizeof(t));
-    t.nrows = n;
-    t.validity = c.has_nulls ? d_in.get() + in_off[ci].validity : nullptr;
-    t.out_validity = d_body.get() + spans[sp].offset;
+    // a struct / fixed-size list reads its own validity words; the staged string_t rows point at heap offsets (ptr_base 0)
+    const EncodeInput in{c.IsGroup() ? d_validity : d_data, c.has_nulls ? d_validity : nullptr, d_heap, 0};
     validity_task[ci] = static_cast<int32_t>(tasks.size());
-    if (c.IsGroup()) {
-      // struct / fixed_size_list: the node's own bitmap + NULL count
-      t.kind = MI_K_ENC_VALIDITY;
-      t.buf1 = d_in.get() + in_off[ci].validity;
-      t.out_data = d_body.get() + spans[sp].offset;
-      tasks.push_back(t);
-      continue;
-    }
-    t.flags = c.large_offsets ? 1 : 0;
-    if (c.IsList()) {  // list / map: bitmap + int32 (or int64) offsets from the staged list_entry_t rows
-      t.kind = MI_K_ENC_LIST32;
-      t.buf1 = d_in.get() + in_off[ci].data;
-      t.out_data = d_body.get() + spans[sp + 1].offset;
-      tasks.push_back(t);
-      continue;
-    }
-    t.kind = c.enc_kind;
-    t.param = c.param;
-    t.buf1 = d_in.get() + in_off[ci].data;
-    t.out_data = d_body.get() + spans[sp + 1].offset;
-    if (c.enc_kind == MI_K_ENC_STR32) {
-      t.buf2 = d_in.get() + in_off[ci].heap;
-      t.buf2_len = c.payload_bytes;
-      t.ptr_base = c.ptr_base;
-      t.out_aux = d_body.get() + spans[sp + 2].offset;
-    }
-    tasks.push_back(t);
+    tasks.push_back(EncodeTask(nodes[ci], &layout.spans[static_cast<size_t>(layout.first_span[ci])], in, d_body.get()));
   }
   plan->Set(tasks.data(), static_cast<int32_t>(tasks.size()), s);
   plan->Launch(s);
-  MI_HIP_CHECK(hipMemcpyAsync(h_body.get(), d_body.get(), body_off, hipMemcpyDeviceToHost, s));
+  MI_HIP_CHECK(hipMemcpyAsync(h_body.get(), d_body.get(), body_bytes, hipMemcpyDeviceToHost, s));
   ThrowForStatus(plan->Status());  // synchronises the stream
   std::vector<int64_t> null_counts = plan->NullCounts(/*reset*/ true);
-  std::vector<std::pair<int64_t, int64_t>> nodes;
+  std::vector<std::pair<int64_t, int64_t>> node_counts;
   for (size_t ci = 0; ci < n_nodes; ci++)
-    nodes.emplace_back(buffer.columns[ci].count, validity_task[ci] >= 0 ? null_counts[static_cast<size_t>(validity_task[ci])] : 0);
-  header = EncodeRecordBatchMessage(n_top, nodes, spans, body_size);
+    node_counts.emplace_back(buffer.columns[ci].count, validity_task[ci] >= 0 ? null_counts[static_cast<size_t>(validity_task[ci])] : 0);
+  header = EncodeRecordBatchMessage(n_top, node_counts, layout.spans, body_size);
   return 1;
 }
 
@@ -464,6 +395,17 @@ int64_t ArrowStreamWriter::ReserveRowGroup(size_t bytes) {
   return at;
 }
 
+void ArrowStreamWriter::WriteMessageAt(int64_t offset, const uint8_t* header, size_t header_size, const uint8_t* body, size_t body_size) {
+  WriteAt(offset, header, header_size);
+  WriteAt(offset + static_cast<int64_t>(header_size), body, body_size);
+}
+
+int64_t ArrowStreamWriter::WriteMessage(const uint8_t* header, size_t header_size, const uint8_t* body, size_t body_size) {
+  const int64_t at = ReserveRowGroup(header_size + body_size);
+  WriteMessageAt(at, header, header_size, body, body_size);
+  return at;
+}
+
 void ArrowStreamWriter::WriteData(const uint8_t* p, size_t n) {
   int64_t at;
   {
@@ -490,10 +432,7 @@ void ArrowStreamWriter::IoLoop() {
       io_jobs.pop_front();
     }
     try {
-      if (!io_error) {
-        WriteAt(job.offset, job.header.data(), job.header.size());
-        WriteAt(job.offset + static_cast<int64_t>(job.header.size()), job.body, job.body_size);
-      }
+      if (!io_error) WriteMessageAt(job.offset, job.header.data(), job.header.size(), job.body, job.body_size);
     } catch (...) {
       std::lock_guard<std::mutex> lk(io_mu);
       if (!io_error) io_error = std::current_exception();
@@ -555,7 +494,35 @@ void ArrowStreamWriter::Finalize() {
                  Timers().serialize, Timers().write);
 }
 
+std::unique_ptr<mi_writer_local> MakeLocal(mi_writer* w) {
+  auto l = std::make_unique<mi_writer_local>();
+  l->w = w;
+  l->buffer = std::make_unique<ChunkCollection>(w->ctx, w->fields);
+  l->serializer = std::make_unique<ColumnDataCollectionSerializer>(w->ctx, /*own_stream*/ true);
+  l->serializer->Init(&w->writer->Schema());
+  return l;
+}
+
 }  // namespace miarrow
+
+void mi_writer_local::FlushRowGroup(const std::function<void()>& before_claim, const std::function<void()>& after_claim) {
+  miarrow::ArrowStreamWriter& out = *w->writer;
+  if (serializer->Serialize(*buffer) == 0) {
+    buffer->Reset();
+    if (before_claim) before_claim();
+    out.CountEmptyFlush();
+    if (after_claim) after_claim();
+    return;
+  }
+  buffer->Reset();
+  const auto& header = serializer->GetHeader();
+  const size_t body = static_cast<size_t>(serializer->GetBodySize());
+  if (before_claim) before_claim();
+  const int64_t at = out.ReserveRowGroup(header.size() + body);
+  if (after_claim) after_claim();
+  out.WriteMessageAt(at, header.data(), header.size(), serializer->GetBody(), body);
+}
+
 
 // ------------------------------------------------------------------------------------------------ C ABI
 using namespace miarrow;
@@ -563,22 +530,6 @@ using namespace miarrow;
 namespace miarrow {
 Context* ContextOf(mi_ctx* c);
 }
-
-namespace miarrow {
-ArrowScan* SingleScanOf(mi_scan* s);  // scan_operator.cpp
-}
-
-struct mi_writer {
-  Context* ctx = nullptr;
-  mi_write_options opts;
-  std::vector<ArrowField> fields;
-  std::unique_ptr<ArrowStreamWriter> writer;        // COPY TO file
-  std::unique_ptr<ChunkCollection> buffer;
-  // to_arrow_ipc mode
-  ArrowSchemaModel schema;
-  std::unique_ptr<ColumnDataCollectionSerializer> serializer;
-  std::vector<uint8_t> blob;
-};
 
 namespace {
 std::string LowerStr(std::string s) {
@@ -747,633 +698,6 @@ int mi_writer_sink(mi_writer* w, const mi_data_chunk* chunk) {
   });
 }
 
-// ---- per-thread sink state (ArrowWriteInitializeLocal / Sink / Combine, write_arrow_stream.cpp:141-174): every sink
-// thread buffers its own chunks AND serializes its own row groups (H2D + K7 + D2H on a stream of its own), so staging,
-// encoding and writing of different row groups overlap; only the claim of the file range is serialised.
-}  // extern "C"
-
-struct mi_writer_local {
-  mi_writer* w = nullptr;
-  std::unique_ptr<ChunkCollection> buffer;
-  std::unique_ptr<ColumnDataCollectionSerializer> serializer;
-  //! serializes the buffered rows as one record batch and writes it at the next free position of the file
-  void FlushRowGroup(const std::function<void()>& before_claim = nullptr, const std::function<void()>& after_claim = nullptr) {
-    ArrowStreamWriter& out = *w->writer;
-    if (serializer->Serialize(*buffer) == 0) {
-      buffer->Reset();
-      if (before_claim) before_claim();
-      out.CountEmptyFlush();
-      if (after_claim) after_claim();
-      return;
-    }
-    buffer->Reset();
-    const auto& header = serializer->GetHeader();
-    const size_t body = static_cast<size_t>(serializer->GetBodySize());
-    if (before_claim) before_claim();   // ordered sinks wait for their turn here
-    const int64_t at = out.ReserveRowGroup(header.size() + body);
-    if (after_claim) after_claim();
-    out.WriteAt(at, header.data(), header.size());
-    out.WriteAt(at + static_cast<int64_t>(header.size()), serializer->GetBody(), body);
-  }
-};
-
-namespace {
-std::unique_ptr<mi_writer_local> MakeLocal(mi_writer* w) {
-  auto l = std::make_unique<mi_writer_local>();
-  l->w = w;
-  l->buffer = std::make_unique<ChunkCollection>(w->ctx, w->fields);
-  l->serializer = std::make_unique<ColumnDataCollectionSerializer>(w->ctx, /*own_stream*/ true);
-  l->serializer->Init(&w->writer->Schema());
-  return l;
-}
-
-int SinkThreads() {
-  const char* v = std::getenv("MI_WRITER_THREADS");
-  if (v) return std::max(1, std::min(16, std::atoi(v)));
-  const int hw = static_cast<int>(std::thread::hardware_concurrency());
-  return std::max(1, std::min(6, hw / 3));
-}
-
-// COPY (FROM read_arrow(...)) TO 'file': the pump DuckDB's executor is between a scan and a copy sink, with the batch
-// copy's re-partitioning (PhysicalBatchCopyToFile hands prepare_batch collections of desired_batch_size = row_group_size
-// rows, write_arrow_stream.cpp:225-245).  The pump thread pulls whole record batches from the scan and cuts the stream of
-// their 2048-row chunks into row groups exactly where the one-thread sink would flush (after the chunk that reaches
-// row_group_size rows / row_group_size_bytes); each row group goes to one of T sink threads which appends its chunks,
-// encodes it and writes it -- claims of the file range happen in row-group order, so the file equals the one-thread file.
-void PumpScanParallel(mi_writer* w, ArrowScan* scan, int threads, int64_t* rows_out, const BatchRef* first = nullptr) {
-  struct Piece { int batch; int32_t w0, w1; };        // windows [w0, w1) of held batch `batch`
-  // `spilled`: rows of this row group the pump has already staged itself (see spill_cur below); the worker that takes the
-  // job appends the remaining pieces to it and flushes it instead of its own state
-  struct Job { std::vector<Piece> pieces; int64_t seq = 0; std::unique_ptr<mi_writer_local> spilled; };
-  struct Held { BatchRef ref; int pieces_open = 0; bool fully_cut = false; };
-  if (!first) scan->EnsurePipelineDepth(threads + 4);   // with a batch already acquired the caller has done it
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<Job> jobs;
-  std::vector<Held> held;             // index = batch token
-  std::deque<int> to_release;         // tokens whose last piece was appended (released by the pump thread: it owns the scan)
-  int64_t next_claim = 0;             // sequence number of the row group that may claim its file range next
-  bool done = false;
-  std::exception_ptr error;
-  std::vector<std::thread> workers;
-  auto fail = [&](std::exception_ptr e) {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!error) error = e;
-    cv.notify_all();
-  };
-  for (int t = 0; t < threads; t++) {
-    workers.emplace_back([&] {
-      try {
-        auto local = MakeLocal(w);
-        ChunkStorage storage;
-        mi_data_chunk chunk;
-        while (true) {
-          Job job;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return error || done || !jobs.empty(); });
-            if (error) return;
-            if (jobs.empty()) return;  // done
-            job = std::move(jobs.front());
-            jobs.pop_front();
-          }
-          mi_writer_local* sink = job.spilled ? job.spilled.get() : local.get();
-          for (const Piece& pc : job.pieces) {
-            BatchRef ref;
-            {
-              std::lock_guard<std::mutex> lk(mu);
-              ref = held[static_cast<size_t>(pc.batch)].ref;
-            }
-            for (int32_t wi = pc.w0; wi < pc.w1; wi++) {
-              scan->BuildChunk(ref, wi, &storage, &chunk);
-              sink->buffer->Append(chunk);
-            }
-            std::lock_guard<std::mutex> lk(mu);
-            Held& h = held[static_cast<size_t>(pc.batch)];
-            if (--h.pieces_open == 0 && h.fully_cut) {
-              to_release.push_back(pc.batch);
-              cv.notify_all();
-            }
-          }
-          sink->FlushRowGroup(
-              [&] {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return error || next_claim == job.seq; });
-              },
-              [&] {
-                std::lock_guard<std::mutex> lk(mu);
-                next_claim = job.seq + 1;
-                cv.notify_all();
-              });
-        }
-      } catch (...) {
-        fail(std::current_exception());
-      }
-    });
-  }
-  int64_t rows = 0, seq = 0;
-  try {
-    Job cur;
-    int64_t cur_rows = 0, cur_bytes = 0;
-    const int64_t row_bytes = std::max<int64_t>(1, [&] {   // staged bytes per row, for row_group_size_bytes
-      int64_t b = 0;
-      for (auto& c : scan->OutputColumns()) {
-        int32_t kind, wd;
-        int64_t param;
-        if (!c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &wd)) b += wd; else b += 16;
-      }
-      return b;
-    }());
-    int64_t n_released = 0;           // batches given back to the scan so far
-    auto dispatch = [&] {
-      if (cur.pieces.empty() && !cur.spilled) return;
-      cur.seq = seq++;
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        jobs.push_back(std::move(cur));
-      }
-      cv.notify_all();
-      cur = Job();
-      cur_rows = cur_bytes = 0;
-    };
-    auto release_ready = [&](bool wait) {
-      std::unique_lock<std::mutex> lk(mu);
-      if (wait) cv.wait(lk, [&] { return error || !to_release.empty(); });
-      if (error) std::rethrow_exception(error);
-      while (!to_release.empty()) {
-        const int tok = to_release.front();
-        to_release.pop_front();
-        const BatchRef ref = held[static_cast<size_t>(tok)].ref;
-        lk.unlock();
-        scan->ReleaseBatch(ref);
-        n_released++;
-        lk.lock();
-      }
-    };
-    // A row group that spans more record batches than the scan has slots: every slot is held by a piece of the row group
-    // still being cut, which no sink thread will see before it is full.  The pump then stages those rows itself (a sink
-    // state of its own that travels with the job) and gives the slots back; the worker that gets the job appends the rest.
-    ChunkStorage spill_storage;
-    mi_data_chunk spill_chunk;
-    auto spill_cur = [&] {
-      if (!cur.spilled) cur.spilled = MakeLocal(w);
-      for (const Piece& pc : cur.pieces) {
-        const BatchRef ref = held[static_cast<size_t>(pc.batch)].ref;   // only the pump thread grows `held`
-        for (int32_t wi = pc.w0; wi < pc.w1; wi++) {
-          scan->BuildChunk(ref, wi, &spill_storage, &spill_chunk);
-          cur.spilled->buffer->Append(spill_chunk);
-        }
-        bool give_back;
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          Held& h = held[static_cast<size_t>(pc.batch)];
-          give_back = --h.pieces_open == 0 && h.fully_cut;
-        }
-        if (give_back) {
-          scan->ReleaseBatch(ref);
-          n_released++;
-        }
-      }
-      cur.pieces.clear();
-    };
-    while (true) {
-      release_ready(false);
-      BatchRef ref;
-      if (first) {
-        ref = *first;
-        first = nullptr;
-      } else if (!scan->AcquireBatch(&ref)) {
-        if (scan->Exhausted()) break;
-        // every slot is held.  Batches whose pieces all went to sink threads come back by themselves; the ones that only
-        // the undispatched row group refers to never would
-        std::vector<int> cur_toks;
-        for (const Piece& pc : cur.pieces)
-          if (std::find(cur_toks.begin(), cur_toks.end(), pc.batch) == cur_toks.end()) cur_toks.push_back(pc.batch);
-        bool with_workers;
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          with_workers = static_cast<int64_t>(held.size()) - n_released - static_cast<int64_t>(cur_toks.size()) > 0;
-        }
-        if (with_workers) release_ready(true);
-        else if (!cur.pieces.empty()) spill_cur();
-        else throw InternalException("COPY pump: no record batch can be acquired and none is held");
-        continue;
-      }
-      scan->EnsureHostVectors(ref);
-      rows += ref.chunk_rows;
-      int tok;
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        held.push_back(Held{ref, 0, false});
-        tok = static_cast<int>(held.size() - 1);
-      }
-      if (ref.n_windows == 0) {
-        std::lock_guard<std::mutex> lk(mu);
-        held[static_cast<size_t>(tok)].fully_cut = true;
-        to_release.push_back(tok);
-        continue;
-      }
-      int32_t w0 = 0;
-      for (int32_t wi = 0; wi < ref.n_windows; wi++) {
-        const int64_t n = std::min<int64_t>(MI_VECTOR_SIZE, ref.chunk_rows - static_cast<int64_t>(wi) * MI_VECTOR_SIZE);
-        cur_rows += n;
-        cur_bytes += n * row_bytes;
-        const bool full = cur_rows >= w->opts.row_group_size || cur_bytes >= w->opts.row_group_size_bytes;
-        if (full || wi + 1 == ref.n_windows) {
-          {
-            std::lock_guard<std::mutex> lk(mu);
-            held[static_cast<size_t>(tok)].pieces_open++;
-            if (wi + 1 == ref.n_windows) held[static_cast<size_t>(tok)].fully_cut = true;
-          }
-          cur.pieces.push_back(Piece{tok, w0, wi + 1});
-          w0 = wi + 1;
-          if (full) dispatch();
-        }
-      }
-    }
-    dispatch();   // the tail row group (ArrowWriteCombine)
-  } catch (...) {
-    fail(std::current_exception());
-  }
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    done = true;
-  }
-  cv.notify_all();
-  for (auto& t : workers) t.join();
-  if (Timers().on)
-    std::fprintf(stderr, "[mi_writer] pump with %d sink threads (thread-seconds): append %.3f, serialize (H2D + K7 + D2H) %.3f, write %.3f\n", threads,
-                 Timers().append, Timers().serialize, Timers().write);
-  // give every batch back before reporting
-  for (int tok : to_release) scan->ReleaseBatch(held[static_cast<size_t>(tok)].ref);
-  if (error) std::rethrow_exception(error);
-  if (rows_out) *rows_out = rows;
-}
-
-// ---- the fused COPY (FROM read_arrow(...)) TO 'file': decode and encode both run on the GPU, so the decoded vectors never
-// have to leave HBM.  For every row group that lies inside one record batch of the scan the K7 kernels read the scan slot's
-// vectors where the K1-K4 kernels wrote them (string payloads: the HBM copy of the Arrow data buffer the string_t rows
-// point into) and write the IPC body; only that body travels back (one D2H) and is written by an I/O thread.  Per row this
-// takes the host out of the loop except for pread -> H2D and D2H -> pwrite: no D2H of the vectors, no staging copy, no H2D
-// of the staged rows (DESIGN.md section 10 has the byte counts).  Row groups are cut exactly where the one-thread sink cuts
-// them (after the 2048-row chunk that reaches row_group_size); rows of a row group that straddles two record batches take
-// the host path (EnsureHostVectors + ChunkCollection) on the pump thread, so the file is byte-identical to the
-// one-thread file in every case.
-struct FusedEncoder {
-  DeviceBuffer d_body;
-  PinnedBuffer h_body;
-  PinnedBuffer h_nulls;     // int64_t: copy of the plan's NULL counters
-  PinnedBuffer h_status;    // uint32_t
-  std::unique_ptr<Plan> plan;
-  HipEvent encoded, done;
-  bool busy = false;
-  // the row group in flight
-  int64_t nrows = 0, body_size = 0;
-  std::vector<mi_buffer_span> spans;
-  std::vector<int32_t> first_span;
-};
-
-bool FusedSinkPossible(mi_writer* w, ArrowScan* scan) {
-  if (std::getenv("MI_WRITER_NO_FUSED")) return false;
-  if (scan->HasFilter() || w->buffer->Count() != 0) return false;
-  const auto& cols = scan->OutputColumns();
-  if (cols.size() != w->buffer->roots.size() || w->buffer->columns.size() != cols.size()) return false;   // flat schema only
-  for (size_t c = 0; c < cols.size(); c++) {
-    if (cols[c].is_filename || cols[c].is_hive) return false;
-    const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
-    if (!wc.children.empty()) return false;
-    if (wc.enc_kind != MI_K_ENC_COPY && wc.enc_kind != MI_K_ENC_DEC128 && wc.enc_kind != MI_K_ENC_BOOL && wc.enc_kind != MI_K_ENC_STR32) return false;
-  }
-  return true;
-}
-
-void PumpScanFused(mi_writer* w, ArrowScan* scan, const BatchRef& first, int64_t rows_per_group, int64_t* rows_out) {
-  Context* ctx = w->ctx;
-  ArrowStreamWriter& out = *w->writer;
-  ctx->Bind();
-  auto local = MakeLocal(w);             // host path of row groups that straddle record batches
-  constexpr int kEncoders = 4;
-  HipStream enc_stream = HipStream::Create();
-  HipStream back_stream = HipStream::Create();
-  std::vector<FusedEncoder> enc(kEncoders);
-  // whatever ends this function, the GPU is done with the encoders' buffers before they go
-  struct SyncStreams { hipStream_t a, b; ~SyncStreams() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } };
-  SyncStreams sync_streams{enc_stream, back_stream};
-  for (auto& e : enc) {
-    e.plan = std::make_unique<Plan>(ctx);
-    e.encoded = HipEvent::Create();
-    e.done = HipEvent::Create();
-    e.h_status = PinnedBuffer(64);
-  }
-  ChunkStorage storage;
-  mi_data_chunk chunk;
-
-  struct WriteJob {
-    int enc = -1;                        // fused encoder; -1: `header` / `body` are ready (host-serialized row group)
-    int tok = -1;                        // batch token whose open count drops once the GPU has read it
-    std::vector<uint8_t> header;
-    const uint8_t* body = nullptr;
-    size_t body_size = 0;
-  };
-  struct Held { BatchRef ref; int open = 0; bool fully_cut = false; bool released = false; };
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<WriteJob> jobs;
-  std::vector<Held> held;
-  std::deque<int> to_release;
-  bool stop = false;
-  int64_t jobs_written = 0, jobs_queued = 0;
-  std::exception_ptr error;
-  const size_t n_cols = scan->NumOutputColumns();
-
-  std::thread io([&] {
-    try {
-      ctx->Bind();
-      while (true) {
-        WriteJob job;
-        {
-          std::unique_lock<std::mutex> lk(mu);
-          cv.wait(lk, [&] { return stop || error || !jobs.empty(); });
-          if (error || jobs.empty()) return;
-          job = std::move(jobs.front());
-          jobs.pop_front();
-        }
-        if (job.enc >= 0) {
-          FusedEncoder& e = enc[static_cast<size_t>(job.enc)];
-          MI_HIP_CHECK(hipEventSynchronize(e.done));
-          {
-            std::lock_guard<std::mutex> lk(mu);   // the GPU is done with the scan slot
-            Held& h = held[static_cast<size_t>(job.tok)];
-            if (--h.open == 0 && h.fully_cut && !h.released) {
-              h.released = true;
-              to_release.push_back(job.tok);
-            }
-          }
-          cv.notify_all();
-          ThrowForStatus(e.h_status.get<uint32_t>()[0]);
-          const std::vector<int64_t> nulls = e.plan->MapNullCounts(e.h_nulls.get<int64_t>());
-          std::vector<std::pair<int64_t, int64_t>> nodes;
-          for (size_t c = 0; c < n_cols; c++) nodes.emplace_back(e.nrows, nulls[c]);
-          job.header = EncodeRecordBatchMessage(e.nrows, nodes, e.spans, e.body_size);
-          job.body = e.h_body.get();
-          job.body_size = static_cast<size_t>(e.body_size);
-        }
-        const int64_t at = out.ReserveRowGroup(job.header.size() + job.body_size);
-        out.WriteAt(at, job.header.data(), job.header.size());
-        out.WriteAt(at + static_cast<int64_t>(job.header.size()), job.body, job.body_size);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          if (job.enc >= 0) enc[static_cast<size_t>(job.enc)].busy = false;
-          ++jobs_written;
-        }
-        cv.notify_all();
-      }
-    } catch (...) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (!error) error = std::current_exception();
-      cv.notify_all();
-    }
-  });
-
-  auto release_ready = [&](bool wait) {
-    std::unique_lock<std::mutex> lk(mu);
-    if (wait) cv.wait(lk, [&] { return error || !to_release.empty(); });
-    if (error) std::rethrow_exception(error);
-    while (!to_release.empty()) {
-      const int tok = to_release.front();
-      to_release.pop_front();
-      const BatchRef ref = held[static_cast<size_t>(tok)].ref;
-      lk.unlock();
-      scan->ReleaseBatch(ref);
-      lk.lock();
-    }
-  };
-  auto queue_job = [&](WriteJob&& job) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      jobs.push_back(std::move(job));
-      ++jobs_queued;
-    }
-    cv.notify_all();
-  };
-  // valid string bytes of rows [r0, r0 + m): the size of the Arrow data buffer the encoder will fill
-  auto payload_of = [](const DeviceColumnView& v, int64_t r0, int64_t m) -> int64_t {
-    auto off = [&](int64_t i) -> int64_t {
-      if (v.offset_width == 8) { int64_t x; std::memcpy(&x, v.h_offsets + i * 8, 8); return x; }
-      int32_t x; std::memcpy(&x, v.h_offsets + i * 4, 4); return x;
-    };
-    if (v.null_count == 0 || !v.h_validity) return off(r0 + m) - off(r0);
-    int64_t total = 0;
-    for (int64_t i = r0; i < r0 + m; i++)
-      if ((v.h_validity[i >> 3] >> (i & 7)) & 1) total += off(i + 1) - off(i);
-    return total;
-  };
-  // can rows of this batch be encoded where they lie?
-  auto views_of = [&](const BatchRef& ref, std::vector<DeviceColumnView>* views) -> bool {
-    views->resize(n_cols);
-    for (size_t c = 0; c < n_cols; c++) {
-      DeviceColumnView& v = (*views)[c];
-      scan->DeviceColumn(ref, c, &v);
-      if (!v.flat) return false;
-      const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
-      const bool is_string = v.kind == MI_K_STR32 || v.kind == MI_K_STR64;
-      if (wc.enc_kind == MI_K_ENC_STR32) {
-        if (!is_string) return false;
-      } else if (is_string || v.width != wc.width || v.kind == MI_K_STRVIEW || v.kind == MI_K_FIXED_BINARY) {
-        return false;
-      }
-    }
-    return true;
-  };
-  auto encode_on_gpu = [&](int tok, const std::vector<DeviceColumnView>& views, int64_t r0, int64_t m) {
-    // a free encoder (at most kEncoders row groups between the kernels and the file)
-    int ei = -1;
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] {
-        if (error) return true;
-        for (int i = 0; i < kEncoders; i++)
-          if (!enc[static_cast<size_t>(i)].busy) { ei = i; return true; }
-        return false;
-      });
-      if (error) std::rethrow_exception(error);
-      enc[static_cast<size_t>(ei)].busy = true;
-      held[static_cast<size_t>(tok)].open++;
-    }
-    FusedEncoder& e = enc[static_cast<size_t>(ei)];
-    e.nrows = m;
-    e.spans.clear();
-    e.first_span.assign(n_cols, 0);
-    size_t body_off = 0;
-    auto add_span = [&](int64_t len) {
-      e.spans.push_back(mi_buffer_span{static_cast<int64_t>(body_off), len});
-      body_off += RoundUp(static_cast<size_t>(len), kBufferAlign);
-    };
-    std::vector<int64_t> payload(n_cols, 0);
-    for (size_t c = 0; c < n_cols; c++) {
-      const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
-      e.first_span[c] = static_cast<int32_t>(e.spans.size());
-      add_span((m + 7) / 8);
-      switch (wc.enc_kind) {
-        case MI_K_ENC_COPY: add_span(m * wc.param); break;
-        case MI_K_ENC_DEC128: add_span(m * 16); break;
-        case MI_K_ENC_BOOL: add_span((m + 7) / 8); break;
-        default: {
-          payload[c] = payload_of(views[c], r0, m);
-          if (payload[c] > 0x7FFFFFFFll && !wc.large_offsets)
-            throw InvalidInputException(
-                "Arrow Appender: The maximum total string size for regular string buffers is 2147483647 but the offset of " +
-                std::to_string(payload[c]) + " exceeds this.\n* SET arrow_large_buffer_size=true to use large string buffers");
-          add_span((m + 1) * (wc.large_offsets ? 8 : 4));
-          add_span(payload[c]);
-        }
-      }
-    }
-    e.body_size = static_cast<int64_t>(body_off);
-    Fit(e.d_body, body_off + 256);
-    Fit(e.h_body, body_off + 256);
-    MI_HIP_CHECK(hipMemsetAsync(e.d_body.get(), 0, body_off, enc_stream));
-    std::vector<mi_col_task> tasks(n_cols);
-    for (size_t c = 0; c < n_cols; c++) {
-      const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
-      const DeviceColumnView& v = views[c];
-      const size_t sp = static_cast<size_t>(e.first_span[c]);
-      mi_col_task& t = tasks[c];
-      std::memset(&t, 0, sizeof(t));
-      t.nrows = m;
-      t.kind = wc.enc_kind;
-      t.param = wc.param;
-      t.flags = wc.large_offsets ? 1 : 0;
-      t.buf1 = v.d_data + static_cast<size_t>(r0) * static_cast<size_t>(v.width);
-      t.validity = v.d_validity ? v.d_validity + static_cast<size_t>(r0 / 64) * 8 : nullptr;   // r0 is a multiple of 2048
-      t.out_validity = e.d_body.get() + e.spans[sp].offset;
-      t.out_data = e.d_body.get() + e.spans[sp + 1].offset;
-      if (wc.enc_kind == MI_K_ENC_STR32) {
-        t.buf2 = v.d_heap;
-        t.buf2_len = payload[c];
-        t.ptr_base = v.ptr_base;
-        t.out_aux = e.d_body.get() + e.spans[sp + 2].offset;
-      }
-    }
-    e.plan->Set(tasks.data(), static_cast<int32_t>(tasks.size()), enc_stream);
-    MI_HIP_CHECK(hipMemsetAsync(e.plan->d_status.get(), 0, sizeof(uint32_t), enc_stream));
-    if (e.plan->n_null_counts) MI_HIP_CHECK(hipMemsetAsync(e.plan->d_null_counts.get(), 0, static_cast<size_t>(e.plan->n_null_counts) * 8, enc_stream));
-    e.plan->Launch(enc_stream);
-    MI_HIP_CHECK(hipEventRecord(e.encoded, enc_stream));
-    MI_HIP_CHECK(hipStreamWaitEvent(back_stream, e.encoded, 0));
-    MI_HIP_CHECK(hipMemcpyAsync(e.h_body.get(), e.d_body.get(), body_off, hipMemcpyDeviceToHost, back_stream));
-    Fit(e.h_nulls, static_cast<size_t>(e.plan->n_null_counts + 1) * 8);
-    if (e.plan->n_null_counts)
-      MI_HIP_CHECK(hipMemcpyAsync(e.h_nulls.get(), e.plan->d_null_counts.get(), static_cast<size_t>(e.plan->n_null_counts) * 8, hipMemcpyDeviceToHost, back_stream));
-    MI_HIP_CHECK(hipMemcpyAsync(e.h_status.get(), e.plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, back_stream));
-    MI_HIP_CHECK(hipEventRecord(e.done, back_stream));
-    WriteJob job;
-    job.enc = ei;
-    job.tok = tok;
-    queue_job(std::move(job));
-  };
-  // the host path: serialise the rows buffered in `local` and hand them to the I/O thread; its body buffer is reused by
-  // the next host-path row group, so wait until it is written (row groups that straddle batches are the exception)
-  auto flush_host = [&] {
-    if (local->serializer->Serialize(*local->buffer) == 0) {
-      local->buffer->Reset();
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return error || jobs_written == jobs_queued; });
-      out.CountEmptyFlush();
-      return;
-    }
-    local->buffer->Reset();
-    WriteJob job;
-    job.header = local->serializer->GetHeader();
-    job.body = local->serializer->GetBody();
-    job.body_size = static_cast<size_t>(local->serializer->GetBodySize());
-    queue_job(std::move(job));
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return error || jobs_written == jobs_queued; });
-    if (error) std::rethrow_exception(error);
-  };
-
-  int64_t rows = 0;
-  std::exception_ptr pump_error;
-  try {
-    const int64_t group_rows = (rows_per_group + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE * MI_VECTOR_SIZE;
-    int64_t carry = 0;                      // rows buffered on the host path
-    bool have_first = true;
-    std::vector<DeviceColumnView> views;
-    while (true) {
-      release_ready(false);
-      BatchRef ref;
-      if (have_first) {
-        ref = first;
-        have_first = false;
-      } else if (!scan->AcquireBatch(&ref)) {
-        if (scan->Exhausted()) break;
-        release_ready(true);
-        continue;
-      }
-      rows += ref.chunk_rows;
-      int tok;
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        held.push_back(Held{ref, 0, false, false});
-        tok = static_cast<int>(held.size() - 1);
-      }
-      const int64_t n = ref.chunk_rows;
-      const bool on_gpu = n > 0 && views_of(ref, &views);
-      int64_t r = 0;
-      while (r < n) {
-        if (carry == 0 && on_gpu && n - r >= rows_per_group) {
-          const int64_t m = std::min(group_rows, n - r);
-          encode_on_gpu(tok, views, r, m);
-          r += m;
-          continue;
-        }
-        // host path, chunk by chunk until the row group is full or the batch ends
-        scan->EnsureHostVectors(ref);
-        const int32_t wi = static_cast<int32_t>(r / MI_VECTOR_SIZE);
-        scan->BuildChunk(ref, wi, &storage, &chunk);
-        local->buffer->Append(chunk);
-        carry += chunk.size;
-        r += chunk.size;
-        if (carry >= rows_per_group) {
-          flush_host();
-          carry = 0;
-        }
-      }
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        Held& h = held[static_cast<size_t>(tok)];
-        h.fully_cut = true;
-        if (h.open == 0 && !h.released) {
-          h.released = true;
-          to_release.push_back(tok);
-        }
-      }
-    }
-    if (carry > 0) flush_host();   // the tail row group (ArrowWriteCombine)
-  } catch (...) {
-    pump_error = std::current_exception();
-    std::lock_guard<std::mutex> lk(mu);
-    if (!error) error = pump_error;
-  }
-  {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return error || jobs_written == jobs_queued; });
-    stop = true;
-  }
-  cv.notify_all();
-  io.join();
-  (void)hipStreamSynchronize(enc_stream);   // the GPU is done with every scan slot before the batches go back
-  (void)hipStreamSynchronize(back_stream);
-  for (size_t tok = 0; tok < held.size(); tok++)
-    if (!held[tok].released || std::find(to_release.begin(), to_release.end(), static_cast<int>(tok)) != to_release.end()) scan->ReleaseBatch(held[tok].ref);
-  if (error) std::rethrow_exception(error);
-  if (rows_out) *rows_out = rows;
-}
-}  // namespace
-
-extern "C" {
-
 int mi_writer_local_create(mi_writer* w, mi_writer_local** out) {
   return WrapC([&] {
     if (!w || !w->writer || !out) throw InvalidInputException("mi_writer_local_create: bad argument");
@@ -1397,56 +721,6 @@ int mi_writer_local_combine(mi_writer_local* l) {
 }
 
 void mi_writer_local_destroy(mi_writer_local* l) { delete l; }
-
-int mi_writer_sink_scan(mi_writer* w, mi_scan* scan, int64_t* rows) {
-  if (!w || !w->writer || !scan) return WrapC([] { throw InvalidInputException("mi_writer_sink_scan: bad argument"); });
-  ArrowScan* single = SingleScanOf(scan);
-  const int threads = SinkThreads();
-  if (single && single->HostConsumer() && w->buffer->Count() == 0 && !single->Initialized()) single->Init({});
-  if (single && single->HostConsumer() && w->buffer->Count() == 0 && (threads > 1 || FusedSinkPossible(w, single))) {
-    return WrapC([&] {
-      // rows after which the one-thread sink flushes (row_group_size, or row_group_size_bytes at the staged row width)
-      int64_t row_bytes = 0;
-      for (auto& c : single->OutputColumns()) {
-        int32_t kind, wd;
-        int64_t param;
-        row_bytes += (!c.is_filename && !c.is_hive && c.field.Plan(&kind, &param, &wd)) ? wd : 16;
-      }
-      row_bytes = std::max<int64_t>(1, row_bytes);
-      const int64_t group = std::max<int64_t>(1, std::min(w->opts.row_group_size, (w->opts.row_group_size_bytes + row_bytes - 1) / row_bytes));
-      // record batches at least one row group long are encoded where they lie in HBM; smaller ones go through the sink
-      // threads.  Decided on the first batch (the scan keeps its vectors on the device until then).
-      const bool fused = FusedSinkPossible(w, single);
-      single->EnsurePipelineDepth(std::max(1, threads) + 4);
-      // whatever happens below, the scan hands out host vectors again afterwards
-      struct Restore { ArrowScan* s; ~Restore() { s->KeepVectorsOnDevice(false); } } restore{single};
-      single->KeepVectorsOnDevice(fused);
-      BatchRef first;
-      if (!single->AcquireBatch(&first)) {
-        if (rows) *rows = 0;
-        return;
-      }
-      if (fused && first.chunk_rows >= group) {
-        PumpScanFused(w, single, first, group, rows);
-        return;
-      }
-      single->KeepVectorsOnDevice(false);
-      PumpScanParallel(w, single, std::max(1, threads), rows, &first);
-    });
-  }
-  int64_t n = 0;
-  mi_data_chunk ch;
-  while (true) {
-    int rc = mi_scan_next(scan, &ch);
-    if (rc != MI_OK) return rc;
-    if (ch.size == 0) break;
-    rc = mi_writer_sink(w, &ch);
-    if (rc != MI_OK) return rc;
-    n += ch.size;
-  }
-  if (rows) *rows = n;
-  return MI_OK;
-}
 
 int mi_writer_finalize(mi_writer* w) {
   return WrapC([&] {
@@ -1500,8 +774,7 @@ int mi_writer_append_message(mi_writer* w, const uint8_t* blob, int64_t size) {
       w->writer->CountEmptyFlush();
       return;
     }
-    const int64_t at = w->writer->ReserveRowGroup(static_cast<size_t>(size));
-    w->writer->WriteAt(at, blob, static_cast<size_t>(size));
+    w->writer->WriteMessage(blob, static_cast<size_t>(size), nullptr, 0);
   });
 }
 

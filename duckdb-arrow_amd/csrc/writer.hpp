@@ -10,6 +10,11 @@
 // part that runs on the GPU: the buffered chunks are staged in pinned memory, DMA'd to HBM, encoded by the K7 kernels
 // straight into the IPC body layout (every buffer padded to 8 bytes, column_data_collection_serializer.cpp:86-92 ->
 // ArrowIpcEncoderEncodeSimpleRecordBatch) and DMA'd back as one body.
+// The units of this direction:
+//   writer.{hpp,cpp}        chunk staging, the serializer, the stream writer, the C API with its option parser
+//   writer_plan.{hpp,cpp}   body layout, encode tasks, the pumps' cut rule and batch ledger (host code only)
+//   copy_pump.cpp           mi_writer_sink_scan: the sink-thread pump and the fused pump of COPY (FROM read_arrow(..))
+//   writer_internal.hpp     struct mi_writer / mi_writer_local, shared by writer.cpp and copy_pump.cpp
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -56,11 +61,10 @@ class ChunkCollection {
     int64_t payload_bytes = 0;    // sum of valid string lengths = size of the Arrow data buffer (list: child rows gathered)
     bool has_nulls = false;
     bool large_offsets = false;   // int64 Arrow offsets (arrow_large_buffer_size)
-    // long-string payloads are staged in `heap` and the staged string_t rows point at heap offsets (ptr_base 0).  When the
+    // long-string payloads are staged in `heap` and the staged string_t rows point at heap offsets.  When the
     // source vector declares the allocation its long strings live in (mi_vector.heap: the Arrow data buffer of a scanned
     // record batch) and they ascend inside it, the bytes from the first to the last long string of an appended slice are
     // staged with ONE copy; otherwise string by string.  Nothing outside a declared allocation or a string is ever read.
-    uint64_t ptr_base = 0;        // pointer value of heap[0] as the staged string_t rows see it (always 0)
     std::vector<int32_t> children;
     bool IsList() const { return arrow_type == MI_AT_LIST || arrow_type == MI_AT_LARGE_LIST || arrow_type == MI_AT_MAP; }
     bool IsGroup() const { return arrow_type == MI_AT_STRUCT || arrow_type == MI_AT_FIXED_LIST; }
@@ -124,6 +128,11 @@ class ArrowStreamWriter {
   int64_t ReserveRowGroup(size_t bytes);
   //! pwrite of a claimed range (any thread, no lock)
   void WriteAt(int64_t offset, const uint8_t* p, size_t n);
+  //! One record-batch message: claims its range (ReserveRowGroup), writes header and body there, returns the offset
+  int64_t WriteMessage(const uint8_t* header, size_t header_size, const uint8_t* body, size_t body_size);
+  //! The writing half, for callers whose claim happens elsewhere: Flush claims on the sink's thread and the I/O thread
+  //! writes; an ordered sink claims when its turn has come (mi_writer_local::FlushRowGroup)
+  void WriteMessageAt(int64_t offset, const uint8_t* header, size_t header_size, const uint8_t* body, size_t body_size);
   void CountEmptyFlush() { std::lock_guard<std::mutex> lk(io_mu); ++row_group_count; }
   Context* GetContext() const { return ctx; }
   idx_t NumberOfRowGroups() const { return row_group_count; }

@@ -1,0 +1,87 @@
+// writer_plan.cpp -- see writer_plan.hpp.
+#include "writer_plan.hpp"
+
+#include <cstring>
+
+namespace miarrow {
+
+void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out) {
+  out->spans.clear();
+  out->first_span.assign(nodes.size(), 0);
+  size_t body_off = 0;
+  auto add_span = [&](int64_t len) {
+    out->spans.push_back(mi_buffer_span{static_cast<int64_t>(body_off), len});
+    body_off += RoundUp(static_cast<size_t>(len), kBufferAlign);
+  };
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const EncodeNode& c = nodes[i];
+    const int64_t n = c.rows;
+    if (n > 0x7FFFFFFFll) throw InvalidInputException("record batch too large");
+    out->first_span[i] = static_cast<int32_t>(out->spans.size());
+    add_span((n + 7) / 8);
+    const int64_t off_width = c.large_offsets ? 8 : 4;
+    switch (c.kind) {
+      case MI_K_ENC_LIST32: add_span((n + 1) * off_width); break;
+      case MI_K_ENC_COPY: add_span(n * c.param); break;
+      case MI_K_ENC_DEC128: add_span(n * 16); break;
+      case MI_K_ENC_BOOL: add_span((n + 7) / 8); break;
+      case MI_K_ENC_STR32:
+        if (c.payload_bytes > 0x7FFFFFFFll && !c.large_offsets) {
+          throw InvalidInputException(
+              "Arrow Appender: The maximum total string size for regular string buffers is 2147483647 but the offset of " +
+              std::to_string(c.payload_bytes) + " exceeds this.\n* SET arrow_large_buffer_size=true to use large string buffers");
+        }
+        add_span((n + 1) * off_width);
+        add_span(c.payload_bytes);
+        break;
+      default: break;   // struct / fixed-size list: the bitmap alone
+    }
+  }
+  out->body_size = static_cast<int64_t>(body_off);
+}
+
+mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, const EncodeInput& in, uint8_t* body) {
+  mi_col_task t;
+  std::memset(&t, 0, sizeof(t));
+  t.nrows = node.rows;
+  t.kind = node.kind;
+  t.validity = in.validity;
+  t.buf1 = in.data;
+  t.out_validity = body + spans[0].offset;
+  if (node.kind == MI_K_ENC_VALIDITY) {   // the node's own bitmap + NULL count
+    t.out_data = body + spans[0].offset;
+    return t;
+  }
+  t.flags = node.large_offsets ? 1 : 0;
+  t.out_data = body + spans[1].offset;
+  if (node.kind == MI_K_ENC_LIST32) return t;   // bitmap + int32 (or int64) offsets from the staged list_entry_t rows
+  t.param = node.param;
+  if (node.kind == MI_K_ENC_STR32) {
+    t.buf2 = in.heap;
+    t.buf2_len = node.payload_bytes;
+    t.ptr_base = in.ptr_base;
+    t.out_aux = body + spans[2].offset;
+  }
+  return t;
+}
+
+std::vector<CutPiece> RowGroupCutter::Cut(int64_t rows) {
+  std::vector<CutPiece> pieces;
+  const int32_t n_windows = static_cast<int32_t>((rows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE);
+  int32_t w0 = 0;
+  bool fresh = open_rows == 0;
+  for (int32_t wi = 0; wi < n_windows; wi++) {
+    open_rows += std::min<int64_t>(MI_VECTOR_SIZE, rows - static_cast<int64_t>(wi) * MI_VECTOR_SIZE);
+    const bool full = open_rows >= rows_per_group;
+    if (!full && wi + 1 < n_windows) continue;
+    pieces.push_back(CutPiece{w0, wi + 1, fresh, full});
+    w0 = wi + 1;
+    if (full) {
+      open_rows = 0;
+      fresh = true;
+    }
+  }
+  return pieces;
+}
+
+}  // namespace miarrow

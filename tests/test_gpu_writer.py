@@ -681,3 +681,33 @@ def test_local_sink_states_from_several_threads(con, tmp_path):
     assert got.num_rows == 48000
     rows = sorted(zip(got.column("t").to_pylist(), got.column("i").to_pylist(), got.column("s").to_pylist()))
     assert rows == [(t_, i, "thread %d row %d long enough to leave the struct" % (t_, i)) for t_ in range(4) for i in range(12000)]
+
+
+def test_copy_pumps_cut_on_row_group_size_bytes(con, tmp_path, monkeypatch):
+    """Both COPY pumps under a binding row_group_size_bytes: they cut on rows x the staged row width (BIGINT 8 + DATE 4 +
+    VARCHAR 16 = 28 bytes, so 100000 bytes are reached at 3572 rows and a group closes after the 2048-row chunk that gets
+    there: 4096 rows, or the 3808 left of a 12000-row record batch).  The sink-thread pump and the fused pump write the same
+    file, and it reads back as the source."""
+    rng = np.random.default_rng(33)
+    n = 30000
+    t = pa.table({"k": pa.array(rng.integers(-2**60, 2**60, n), mask=rng.random(n) < 0.1),
+                  "d": pa.array(rng.integers(8000, 11000, n).astype(np.int32), pa.date32(), mask=rng.random(n) < 0.1),
+                  "s": pa.array(["v" * int(k) for k in rng.integers(0, 41, n)], mask=rng.random(n) < 0.1)})
+    src = str(tmp_path / "src.arrows")
+    with ipc.new_stream(src, t.schema) as w:
+        w.write_table(t, max_chunksize=12000)
+    outs = []
+    for fused in (False, True):
+        monkeypatch.setenv("MI_WRITER_THREADS", "4")
+        if fused:
+            monkeypatch.delenv("MI_WRITER_NO_FUSED", raising=False)
+        else:
+            monkeypatch.setenv("MI_WRITER_NO_FUSED", "1")
+        out = str(tmp_path / ("out_%d.arrows" % fused))
+        con.copy_to(con.read_arrow(src), out, preserve_insertion_order=False, row_group_size_bytes=100000)
+        outs.append(open(out, "rb").read())
+    assert outs[0] == outs[1]
+    assert ipc.open_stream(pa.BufferReader(outs[0])).read_all().equals(t)
+    sizes = [b.num_rows for b in ipc.open_stream(pa.BufferReader(outs[0]))]
+    print("row groups:", sizes)
+    assert sum(sizes) == n and sizes == [4096, 4096, 3808, 4096, 4096, 3808, 4096, 1904]

@@ -159,3 +159,27 @@ def test_readahead_orders_and_shards_under_tsan(tmp_path):
         assert run.returncode == 0, (name, run.stdout[-1000:], run.stderr[-3000:])
         assert "ThreadSanitizer" not in run.stderr and "FAILED" not in run.stderr, (name, run.stderr[-3000:])
         assert "%d producers by default" % producers in run.stdout and "32 runs, 0 failed" in run.stdout, (name, run.stdout)
+
+
+def test_writer_plan_under_asan_ubsan_and_tsan(tmp_path):
+    """The writer's planning unit (duckdb-arrow_amd/csrc/writer_plan.cpp: IPC body layout, encode tasks, the COPY pumps' cut
+    rule and batch ledger) is host code, so tests/sanitize/writer_plan_check.cpp runs it from that one source: buffer
+    lengths and alignment against the Arrow columnar format for every node kind, the int32 offset limit, the cutter against
+    a naive chunk-by-chunk cut, and the ledger with four closing threads -- once under ASan + UBSan, once under TSan."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    for name, flags in (("asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]), ("tsan", ["-fsanitize=thread"])):
+        exe = str(tmp_path / ("writer_plan_check_" + name))
+        build = subprocess.run(
+            ["g++", "-std=c++17", "-O1", "-g"] + flags + ["-I", os.path.join(ROOT, "include"),
+             os.path.join(ROOT, "tests", "sanitize", "writer_plan_check.cpp"),
+             os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "writer_plan.cpp"), "-lpthread", "-o", exe],
+            capture_output=True, text=True)
+        if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
+            pytest.skip("sanitizer runtime not installed")
+        assert build.returncode == 0, build.stderr[-2000:]
+        run = subprocess.run([exe], capture_output=True, text=True, timeout=300,
+                             env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", TSAN_OPTIONS="halt_on_error=0"))
+        assert run.returncode == 0, (name, run.stdout[-1000:], run.stderr[-3000:])
+        assert " 0 failed" in run.stdout and "FAILED" not in run.stderr, (name, run.stdout, run.stderr[-3000:])
+        assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, (name, run.stderr[-3000:])

@@ -37,23 +37,22 @@ def main():
         for target, tag in ((opath, "file"), ("/dev/null", "null_sink")):
             legs += [(target, tag, t) for t in [int(x) for x in args.threads.split(",")]]
         for target, tag, threads in legs:
-            for _once in (0,):
-                # threads 0: the fused pump (record batches encoded where the scan decoded them); else the sink-thread pump
-                if threads:
-                    os.environ["MI_WRITER_THREADS"] = str(threads)
-                    os.environ["MI_WRITER_NO_FUSED"] = "1"
-                else:
-                    os.environ.pop("MI_WRITER_NO_FUSED", None)
-                best = None
-                for _ in range(2):
-                    if target == opath and os.path.exists(opath):
-                        os.unlink(opath)
-                    t0 = time.perf_counter()
-                    con.copy_to(con.read_arrow(path), target, row_group_size=122880)
-                    dt = time.perf_counter() - t0
-                    best = dt if best is None else min(best, dt)
-                out[("%s_threads_%d" % (tag, threads)) if threads else tag] = {"seconds": best, "rows_per_s": info["n_rows"] / best, "GBps_out": buf.size / best / 1e9}
-                print("%s threads %d: %.3f s" % (tag, threads, best), file=sys.stderr, flush=True)
+            # threads 0: the fused pump (record batches encoded where the scan decoded them); else the sink-thread pump
+            if threads:
+                os.environ["MI_WRITER_THREADS"] = str(threads)
+                os.environ["MI_WRITER_NO_FUSED"] = "1"
+            else:
+                os.environ.pop("MI_WRITER_NO_FUSED", None)
+            best = None
+            for _ in range(2):
+                if target == opath and os.path.exists(opath):
+                    os.unlink(opath)
+                t0 = time.perf_counter()
+                con.copy_to(con.read_arrow(path), target, row_group_size=122880)
+                dt = time.perf_counter() - t0
+                best = dt if best is None else min(best, dt)
+            out[("%s_threads_%d" % (tag, threads)) if threads else tag] = {"seconds": best, "rows_per_s": info["n_rows"] / best, "GBps_out": buf.size / best / 1e9}
+            print("%s threads %d: %.3f s" % (tag, threads, best), file=sys.stderr, flush=True)
     finally:
         for p in (path, opath):
             if os.path.exists(p):

@@ -831,8 +831,12 @@ class Connection:
 
     def copy_to(self, table, path, preserve_insertion_order=True, file_size_bytes=None, arrow_large_buffer_size=False, **options):
         """COPY table TO 'path' (FORMAT ARROWS, row_group_size ..., chunk_size ..., row_group_size_bytes ...,
-        row_groups_per_file ..., kv_metadata {...}).  With row_groups_per_file / file_size_bytes `path` becomes a
-        directory of data_<i>.arrows files, like DuckDB's file rotation.  Returns the list of files written."""
+        row_groups_per_file ..., kv_metadata {...}, compression ...).  With row_groups_per_file / file_size_bytes `path`
+        becomes a directory of data_<i>.arrows files, like DuckDB's file rotation.  compression (or codec) = "lz4" /
+        "lz4_frame" writes record batches with BodyCompression LZ4_FRAME, compressed on the GPU -- any Arrow reader takes
+        them, and a device-resident read_arrow expands them in HBM; "none" / "uncompressed" is the default; "zstd" is
+        refused (ZSTD bodies are read, not written).  File sizes that rotation counts are compressed sizes.  Returns the
+        list of files written."""
         L = _ffi.lib()
         o = _ffi.WriteOptions()
         _ffi.check(L.mi_write_options_init(C.byref(o)))

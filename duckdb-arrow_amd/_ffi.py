@@ -158,7 +158,7 @@ class WriteOptions(C.Structure):
                 ("row_group_size_bytes_set", C.c_int32), ("preserve_insertion_order", C.c_int32),
                 ("n_kv_metadata", C.c_int32), ("kv_keys", (C.c_char * 64) * MAX_KV),
                 ("kv_values", (C.c_char * 256) * MAX_KV), ("kv_value_lens", C.c_int32 * MAX_KV),
-                ("arrow_large_buffer_size", C.c_int32), ("_reserved", C.c_int32)]
+                ("arrow_large_buffer_size", C.c_int32), ("compression", C.c_int32)]
 
 
 class ScanStats(C.Structure):
@@ -248,6 +248,7 @@ SIGNATURES = {
     "mi_writer_close": (None, [P]),
     "mi_writer_row_groups": (C.c_int64, [P]),
     "mi_writer_file_size": (C.c_int64, [P]),
+    "mi_lz4_frame_compress_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "mi_writer_rotate_next_file": (C.c_int, [P, C.c_int64]),
     "mi_writer_append_message": (C.c_int, [P, P, C.c_int64]),
     "mi_ipc_serializer_create": (C.c_int, [P, C.POINTER(Field), C.c_int32, PP]),

@@ -219,6 +219,9 @@ struct FusedEncoder {
   // the row group in flight
   int64_t nrows = 0;
   BodyLayout layout;
+  BodyCompressor compressor;                 // COMPRESSION lz4: d_body -> the body that goes to the file
+  std::vector<mi_buffer_span> file_spans;    // of the body that goes to the file
+  int64_t file_body_size = 0;
 };
 
 bool FusedSinkPossible(mi_writer* w, ArrowScan* scan) {
@@ -265,6 +268,7 @@ class FusedPump : PumpBase {
   void Pump(const BatchRef& first);
 
   const size_t n_cols;
+  const bool compressed;                    // COMPRESSION lz4
   std::unique_ptr<mi_writer_local> local;   // host path of row groups that straddle record batches
   HipStream enc_stream, back_stream;
   std::vector<FusedEncoder> enc;
@@ -277,7 +281,8 @@ class FusedPump : PumpBase {
 };
 
 FusedPump::FusedPump(mi_writer* w_p, ArrowScan* scan_p, int64_t rows_per_group)
-    : PumpBase(w_p, scan_p, rows_per_group), n_cols(scan_p->NumOutputColumns()) {
+    : PumpBase(w_p, scan_p, rows_per_group), n_cols(scan_p->NumOutputColumns()),
+      compressed(w_p->opts.compression == MI_WRITE_COMPRESSION_LZ4_FRAME) {
   w->ctx->Bind();
   local = MakeLocal(w);
   enc_stream = HipStream::Create();
@@ -300,9 +305,9 @@ void FusedPump::FinishEncoded(WriteJob* job) {
   const std::vector<int64_t> nulls = e.plan->MapNullCounts(e.h_nulls.get<int64_t>());
   std::vector<std::pair<int64_t, int64_t>> nodes;
   for (size_t c = 0; c < n_cols; c++) nodes.emplace_back(e.nrows, nulls[c]);
-  job->header = EncodeRecordBatchMessage(e.nrows, nodes, e.layout.spans, e.layout.body_size);
+  job->header = EncodeRecordBatchMessage(e.nrows, nodes, e.file_spans, e.file_body_size, compressed ? 0 : -1);
   job->body = e.h_body.get();
-  job->body_size = static_cast<size_t>(e.layout.body_size);
+  job->body_size = static_cast<size_t>(e.file_body_size);
 }
 
 void FusedPump::IoLoop() {
@@ -399,7 +404,6 @@ void FusedPump::EncodeOnGpu(int tok, const std::vector<DeviceColumnView>& views,
   LayOutBody(nodes, &e.layout);
   const size_t body_bytes = static_cast<size_t>(e.layout.body_size);
   Fit(e.d_body, body_bytes + 256);
-  Fit(e.h_body, body_bytes + 256);
   MI_HIP_CHECK(hipMemsetAsync(e.d_body.get(), 0, body_bytes, enc_stream));
   std::vector<mi_col_task> tasks(n_cols);
   for (size_t c = 0; c < n_cols; c++) {
@@ -411,9 +415,19 @@ void FusedPump::EncodeOnGpu(int tok, const std::vector<DeviceColumnView>& views,
   e.plan->Set(tasks.data(), static_cast<int32_t>(tasks.size()), enc_stream);
   e.plan->ResetCounters(enc_stream);
   e.plan->Launch(enc_stream);
+  const uint8_t* d_final = e.d_body.get();
+  e.file_spans = e.layout.spans;
+  e.file_body_size = e.layout.body_size;
+  if (compressed) {   // waits for the size words of this row group's blocks (and so for the kernels queued before them)
+    e.compressor.Run(e.layout, e.d_body.get(), enc_stream);
+    d_final = e.compressor.Body();
+    e.file_spans = e.compressor.Layout().spans;
+    e.file_body_size = e.compressor.Layout().body_size;
+  }
+  Fit(e.h_body, static_cast<size_t>(e.file_body_size) + 256);
   MI_HIP_CHECK(hipEventRecord(e.encoded, enc_stream));
   MI_HIP_CHECK(hipStreamWaitEvent(back_stream, e.encoded, 0));
-  MI_HIP_CHECK(hipMemcpyAsync(e.h_body.get(), e.d_body.get(), body_bytes, hipMemcpyDeviceToHost, back_stream));
+  MI_HIP_CHECK(hipMemcpyAsync(e.h_body.get(), d_final, static_cast<size_t>(e.file_body_size), hipMemcpyDeviceToHost, back_stream));
   Fit(e.h_nulls, static_cast<size_t>(e.plan->n_null_counts + 1) * 8);
   if (e.plan->n_null_counts)
     MI_HIP_CHECK(hipMemcpyAsync(e.h_nulls.get(), e.plan->d_null_counts.get(), static_cast<size_t>(e.plan->n_null_counts) * 8, hipMemcpyDeviceToHost, back_stream));

@@ -596,17 +596,25 @@ std::vector<uint8_t> EncodeSchemaMessage(const ArrowSchemaModel& schema) {
 }
 
 std::vector<uint8_t> EncodeRecordBatchMessage(int64_t length, const std::vector<std::pair<int64_t, int64_t>>& nodes,
-                                              const std::vector<mi_buffer_span>& buffers, int64_t body_length) {
+                                              const std::vector<mi_buffer_span>& buffers, int64_t body_length, int32_t compression) {
   fb::Builder fbb(1024 + 16 * (nodes.size() + buffers.size()));
   static_assert(sizeof(mi_buffer_span) == 16, "Buffer struct layout");
   static_assert(sizeof(mi_string_t) == 16, "string_t layout");
   static_assert(sizeof(std::pair<int64_t, int64_t>) == 16, "FieldNode struct layout");
   auto bufs = fbb.CreateStructVector(buffers.data(), buffers.size(), 16, 8);
   auto nds = fbb.CreateStructVector(nodes.data(), nodes.size(), 16, 8);
+  fb::Builder::Offset body_compression = 0;
+  if (compression >= 0) {   // BodyCompression { codec: CompressionType = LZ4_FRAME (0) [0]; method: BUFFER (0) [1] }
+    fbb.StartTable();
+    fbb.AddScalar<int8_t>(0, static_cast<int8_t>(compression), 0);
+    fbb.AddScalar<int8_t>(1, 0, 0);
+    body_compression = fbb.EndTable();
+  }
   fbb.StartTable();
   fbb.AddScalar<int64_t>(0, length, 0);
   fbb.AddOffset(1, nds);
   fbb.AddOffset(2, bufs);
+  fbb.AddOffset(3, body_compression);
   auto rb = fbb.EndTable();
   fbb.StartTable();
   fbb.AddScalar<int16_t>(0, 4, 0);   // V5

@@ -156,7 +156,8 @@ bool DecodeFooter(const uint8_t* file_tail, int64_t tail_len, int64_t file_size,
 // of 8, like ArrowIpcEncoderFinalizeBuffer(encoder, /*encapsulate*/ true, ...)) ----
 std::vector<uint8_t> EncodeSchemaMessage(const ArrowSchemaModel& schema);
 std::vector<uint8_t> EncodeRecordBatchMessage(int64_t length, const std::vector<std::pair<int64_t, int64_t>>& nodes,
-                                              const std::vector<mi_buffer_span>& buffers, int64_t body_length);
+                                              const std::vector<mi_buffer_span>& buffers, int64_t body_length,
+                                              int32_t compression = -1 /* RecordBatchMeta::compression: -1 none, 0 LZ4_FRAME */);
 
 // DuckDB logical type name ("BIGINT", "DECIMAL(15,2)", ...) -> Arrow field as ArrowConverter::ToArrowSchema
 // exports it (arrow_stream_writer.cpp:22-24). Throws NotImplementedException for types outside the path.

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/mi_arrow_ipc.h"
+#include "lz4_encode_format.hpp"
 
 namespace miarrow {
 namespace device {
@@ -157,6 +158,15 @@ hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_
 hipError_t LaunchEncodeString(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
                               int32_t n_tasks, uint32_t total_tiles, int64_t* d_tile_state, int64_t* d_null_counts,
                               uint32_t* d_status, bool has_lists, hipStream_t stream);
+
+// The writer's LZ4_FRAME compressor (kernels_lz4_encode.hip).  One wave per block of `d_blocks`: block b of the encoded body
+// `d_body` is compressed into d_slots + b * lz4enc::kSlotStride and d_words[b] becomes its size word (the compressed size,
+// or lz4enc::kStoredFlag | n: the slot holds nothing, the block's bytes are taken from the body).
+hipError_t LaunchLz4CompressBlocks(const uint8_t* d_body, const lz4enc::BlockIn* d_blocks, uint32_t n_blocks, uint8_t* d_slots,
+                                   uint32_t* d_words, hipStream_t stream);
+// Runs the copy table of LayOutCompressedBody (writer_plan.hpp): one workgroup per copy into `d_out`, which the caller zeroed.
+hipError_t LaunchCompactBody(const uint8_t* d_body, const uint8_t* d_slots, const lz4enc::BodyCopy* d_copies, uint32_t n_copies,
+                             uint8_t* d_out, hipStream_t stream);
 
 }  // namespace device
 }  // namespace miarrow

@@ -263,7 +263,10 @@ ColumnDataCollectionSerializer::ColumnDataCollectionSerializer(Context* ctx_p, b
   }
 }
 
-void ColumnDataCollectionSerializer::Init(const ArrowSchemaModel* schema_p) { schema = schema_p; }
+void ColumnDataCollectionSerializer::Init(const ArrowSchemaModel* schema_p, int32_t compression_p) {
+  schema = schema_p;
+  compression = compression_p;
+}
 
 void ColumnDataCollectionSerializer::SerializeSchema() {
   header = EncodeSchemaMessage(*schema);
@@ -298,12 +301,10 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   }
   BodyLayout layout;
   LayOutBody(nodes, &layout);
-  body_size = layout.body_size;
-  const size_t body_bytes = static_cast<size_t>(body_size);
+  const size_t body_bytes = static_cast<size_t>(layout.body_size);
   Fit(d_in, in_bytes + 256);
   Fit(d_body, body_bytes + 256);
   PinnedBuffer& h_body = bodies[cur_body];
-  Fit(h_body, body_bytes + 256);
 
   hipStream_t s = stream;
   MI_HIP_CHECK(hipMemsetAsync(d_body.get(), 0, body_bytes, s));  // the padding bytes of every buffer are zero
@@ -329,21 +330,32 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   }
   plan->Set(tasks.data(), static_cast<int32_t>(tasks.size()), s);
   plan->Launch(s);
-  MI_HIP_CHECK(hipMemcpyAsync(h_body.get(), d_body.get(), body_bytes, hipMemcpyDeviceToHost, s));
+  // what goes to the file: the encoded body, or (COMPRESSION lz4) the body the compressor makes of it in HBM
+  const uint8_t* d_final = d_body.get();
+  const std::vector<mi_buffer_span>* spans = &layout.spans;
+  body_size = layout.body_size;
+  if (compression == MI_WRITE_COMPRESSION_LZ4_FRAME) {
+    compressor.Run(layout, d_body.get(), s);
+    d_final = compressor.Body();
+    spans = &compressor.Layout().spans;
+    body_size = compressor.Layout().body_size;
+  }
+  Fit(h_body, static_cast<size_t>(body_size) + 256);
+  MI_HIP_CHECK(hipMemcpyAsync(h_body.get(), d_final, static_cast<size_t>(body_size), hipMemcpyDeviceToHost, s));
   ThrowForStatus(plan->Status());  // synchronises the stream
   std::vector<int64_t> null_counts = plan->NullCounts(/*reset*/ true);
   std::vector<std::pair<int64_t, int64_t>> node_counts;
   for (size_t ci = 0; ci < n_nodes; ci++)
     node_counts.emplace_back(buffer.columns[ci].count, validity_task[ci] >= 0 ? null_counts[static_cast<size_t>(validity_task[ci])] : 0);
-  header = EncodeRecordBatchMessage(n_top, node_counts, layout.spans, body_size);
+  header = EncodeRecordBatchMessage(n_top, node_counts, *spans, body_size, compression == MI_WRITE_COMPRESSION_LZ4_FRAME ? 0 : -1);
   return 1;
 }
 
 // ------------------------------------------------------------------------------------------------ stream writer
 ArrowStreamWriter::ArrowStreamWriter(Context* ctx_p, const std::string& file_path, const std::vector<ArrowField>& fields,
-                                     const std::vector<std::pair<std::string, std::string>>& metadata)
+                                     const std::vector<std::pair<std::string, std::string>>& metadata, int32_t compression)
     : ctx(ctx_p), serializer(ctx_p), file_name(file_path) {
-  InitSchema(fields, metadata);
+  InitSchema(fields, metadata, compression);
   if (!file_path.empty()) InitOutputFile(file_path);
 }
 
@@ -358,10 +370,10 @@ ArrowStreamWriter::~ArrowStreamWriter() {
 }
 
 void ArrowStreamWriter::InitSchema(const std::vector<ArrowField>& fields,
-                                   const std::vector<std::pair<std::string, std::string>>& metadata) {
+                                   const std::vector<std::pair<std::string, std::string>>& metadata, int32_t compression) {
   schema.fields = fields;
   schema.metadata = metadata;  // kv_metadata COPY option (arrow_stream_writer.cpp:26-44)
-  serializer.Init(&schema);
+  serializer.Init(&schema, compression);
 }
 
 void ArrowStreamWriter::InitOutputFile(const std::string& file_path) {
@@ -499,7 +511,7 @@ std::unique_ptr<mi_writer_local> MakeLocal(mi_writer* w) {
   l->w = w;
   l->buffer = std::make_unique<ChunkCollection>(w->ctx, w->fields);
   l->serializer = std::make_unique<ColumnDataCollectionSerializer>(w->ctx, /*own_stream*/ true);
-  l->serializer->Init(&w->writer->Schema());
+  l->serializer->Init(&w->writer->Schema(), w->opts.compression);
   return l;
 }
 
@@ -617,6 +629,12 @@ int mi_write_options_set(mi_write_options* o, const char* name, const char* valu
       o->row_group_size_bytes_set = 1;
     } else if (loption == "row_groups_per_file") {
       o->row_groups_per_file = static_cast<int64_t>(ParseU64(loption, value));
+    } else if (loption == "compression" || loption == "codec") {
+      const std::string codec = LowerStr(value);
+      if (codec == "uncompressed" || codec == "none") o->compression = MI_WRITE_COMPRESSION_NONE;
+      else if (codec == "lz4" || codec == "lz4_frame") o->compression = MI_WRITE_COMPRESSION_LZ4_FRAME;
+      else if (codec == "zstd") throw NotImplementedException("COMPRESSION zstd: ZSTD bodies are read but not written by this path (use lz4 or uncompressed)");
+      else throw BinderException("Unknown COMPRESSION '" + std::string(value) + "' for FORMAT ARROWS: expected uncompressed, none, lz4 or lz4_frame");
     }
     // other options are not ours: the bind loop ignores them (write_arrow_stream.cpp:62-105)
   });
@@ -681,7 +699,9 @@ int mi_writer_open(mi_ctx* ctx, const char* path, const mi_field* fields, int32_
     for (int32_t i = 0; i < w->opts.n_kv_metadata; i++)
       kv.emplace_back(w->opts.kv_keys[i], std::string(w->opts.kv_values[i], static_cast<size_t>(w->opts.kv_value_lens[i])));
     w->buffer = std::make_unique<ChunkCollection>(w->ctx, w->fields);
-    w->writer = std::make_unique<ArrowStreamWriter>(w->ctx, path, w->fields, kv);
+    if (w->opts.compression != MI_WRITE_COMPRESSION_NONE && w->opts.compression != MI_WRITE_COMPRESSION_LZ4_FRAME)
+      throw InvalidInputException("mi_write_options.compression " + std::to_string(w->opts.compression) + " is not a codec of this writer");
+    w->writer = std::make_unique<ArrowStreamWriter>(w->ctx, path, w->fields, kv, w->opts.compression);
     w->writer->WriteSchema();
     *out = w.release();
   });

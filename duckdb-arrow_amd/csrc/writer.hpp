@@ -12,7 +12,9 @@
 // ArrowIpcEncoderEncodeSimpleRecordBatch) and DMA'd back as one body.
 // The units of this direction:
 //   writer.{hpp,cpp}        chunk staging, the serializer, the stream writer, the C API with its option parser
-//   writer_plan.{hpp,cpp}   body layout, encode tasks, the pumps' cut rule and batch ledger (host code only)
+//   writer_plan.{hpp,cpp}   body layout, compressed body layout, encode tasks, the pumps' cut rule and batch ledger (host
+//                           code only)
+//   writer_compress.cpp     BodyCompressor: the encoded body in HBM -> the LZ4_FRAME body in HBM (COMPRESSION lz4)
 //   copy_pump.cpp           mi_writer_sink_scan: the sink-thread pump and the fused pump of COPY (FROM read_arrow(..))
 //   writer_internal.hpp     struct mi_writer / mi_writer_local, shared by writer.cpp and copy_pump.cpp
 #pragma once
@@ -30,8 +32,31 @@
 
 #include "engine.hpp"
 #include "ipc_format.hpp"
+#include "writer_plan.hpp"
 
 namespace miarrow {
+
+//! COPY ... (COMPRESSION lz4): turns the body the K7 kernels left in HBM into the body BodyCompression{LZ4_FRAME, BUFFER}
+//! describes, still in HBM.  One per serializer / fused encoder.  Its buffers grow with a quarter of headroom and an
+//! outgrown one is kept until the compressor goes: nothing is freed while row groups are in flight.
+class BodyCompressor {
+ public:
+  //! `d_body` holds plain.body_size encoded bytes once the work queued on `s` is done.  Compresses every 64 KiB block,
+  //! fetches the size words (synchronises `s` once), lays the compressed body out and queues its compaction on `s`.
+  //! Afterwards Layout() describes the body and Body() holds it as soon as `s` has run.
+  void Run(const BodyLayout& plain, const uint8_t* d_body, hipStream_t s);
+  const CompressedBodyLayout& Layout() const { return layout; }
+  const uint8_t* Body() const { return d_out.get(); }
+
+ private:
+  template <typename Buffer>
+  void Keep(Buffer& buf, std::vector<Buffer>& retired, size_t need);
+  DeviceBuffer d_tables, d_slots, d_out;   // d_tables: blocks | size words | copies
+  PinnedBuffer h_tables;
+  std::vector<DeviceBuffer> retired_device;
+  std::vector<PinnedBuffer> retired_pinned;
+  CompressedBodyLayout layout;
+};
 
 //! The buffered rows of one future record batch (the reference's local ColumnDataCollection,
 //! write_arrow_stream.cpp:43-52): per FIELD NODE (depth first; a flat column is one node) a pinned staging array in
@@ -85,7 +110,8 @@ class ColumnDataCollectionSerializer {
  public:
   //! own_stream: the encode runs on a stream of its own (one serializer per sink thread: their H2D / K7 / D2H overlap)
   explicit ColumnDataCollectionSerializer(Context* ctx, bool own_stream = false);
-  void Init(const ArrowSchemaModel* schema);
+  //! compression: mi_write_options::compression (0 none, 1 LZ4_FRAME bodies)
+  void Init(const ArrowSchemaModel* schema, int32_t compression = 0);
   void SerializeSchema();
   //! Serializes the collection as ONE record batch (header + body). Returns the number of messages (0 when empty).
   idx_t Serialize(ChunkCollection& buffer);
@@ -106,6 +132,8 @@ class ColumnDataCollectionSerializer {
   HipStream owned_stream;         // own_stream: the encode runs here, otherwise
   hipStream_t stream = nullptr;   // on the context's compute stream
   const ArrowSchemaModel* schema = nullptr;
+  int32_t compression = 0;
+  BodyCompressor compressor;
   std::vector<uint8_t> header;
   PinnedBuffer bodies[2];         // the current one is bodies[cur_body]
   int cur_body = 0;
@@ -117,7 +145,7 @@ class ColumnDataCollectionSerializer {
 class ArrowStreamWriter {
  public:
   ArrowStreamWriter(Context* ctx, const std::string& file_path, const std::vector<ArrowField>& fields,
-                    const std::vector<std::pair<std::string, std::string>>& metadata);
+                    const std::vector<std::pair<std::string, std::string>>& metadata, int32_t compression = 0);
   ~ArrowStreamWriter();
   void WriteSchema();
   void Flush(ChunkCollection& buffer);
@@ -140,7 +168,7 @@ class ArrowStreamWriter {
   const ArrowSchemaModel& Schema() const { return schema; }
 
  private:
-  void InitSchema(const std::vector<ArrowField>& fields, const std::vector<std::pair<std::string, std::string>>& metadata);
+  void InitSchema(const std::vector<ArrowField>& fields, const std::vector<std::pair<std::string, std::string>>& metadata, int32_t compression);
   void InitOutputFile(const std::string& file_path);
   void WriteData(const uint8_t* p, size_t n);   // appends at the end of what has been claimed so far
 

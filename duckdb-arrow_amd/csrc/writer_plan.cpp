@@ -1,6 +1,7 @@
 // writer_plan.cpp -- see writer_plan.hpp.
 #include "writer_plan.hpp"
 
+#include <algorithm>
 #include <cstring>
 
 namespace miarrow {
@@ -63,6 +64,54 @@ mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, cons
     t.out_aux = body + spans[2].offset;
   }
   return t;
+}
+
+std::vector<lz4enc::BlockIn> BlocksOfBody(const BodyLayout& plain) {
+  std::vector<lz4enc::BlockIn> blocks;
+  for (const mi_buffer_span& sp : plain.spans)
+    for (int64_t at = 0; at < sp.length; at += lz4enc::kBlockSize)
+      blocks.push_back(lz4enc::BlockIn{static_cast<uint64_t>(sp.offset + at),
+                                       static_cast<uint32_t>(std::min<int64_t>(lz4enc::kBlockSize, sp.length - at)), 0});
+  return blocks;
+}
+
+void LayOutCompressedBody(const BodyLayout& plain, const std::vector<uint32_t>& words, CompressedBodyLayout* out) {
+  using namespace lz4enc;
+  out->spans.clear();
+  out->copies.clear();
+  int64_t at = 0;
+  size_t block = 0;
+  auto immediate = [&](uint64_t bytes, uint32_t len) {
+    out->copies.push_back(BodyCopy{at, 0, len, kFromImmediate, bytes});
+    at += len;
+  };
+  for (const mi_buffer_span& sp : plain.spans) {
+    const int64_t n = sp.length, n_blocks = BlocksOf(n);
+    if (block + static_cast<size_t>(n_blocks) > words.size()) throw InternalException("compressed body: fewer size words than blocks");
+    if (n == 0) {
+      out->spans.push_back(mi_buffer_span{at, 0});
+      continue;
+    }
+    const int64_t start = at;
+    const bool framed = FrameWins(FrameSize(words.data() + block, n_blocks), n);
+    immediate(framed ? static_cast<uint64_t>(n) : ~0ull, 8);
+    if (framed) immediate(kFrameHeader, kFrameHeaderSize);
+    for (int64_t b = 0; b < n_blocks; b++, block++) {
+      const uint32_t word = words[block], size = word & ~kStoredFlag;
+      const int64_t in_block = std::min<int64_t>(kBlockSize, n - b * kBlockSize);
+      const bool stored = (word & kStoredFlag) != 0;
+      if (size == 0 || size > in_block || (stored && size != in_block)) throw InternalException("compressed body: impossible block size word");
+      if (framed) immediate(word, 4);
+      if (!framed || stored) out->copies.push_back(BodyCopy{at, sp.offset + b * kBlockSize, static_cast<uint32_t>(in_block), kFromBody, 0});
+      else out->copies.push_back(BodyCopy{at, static_cast<int64_t>(block) * kSlotStride, size, kFromSlots, 0});
+      at += framed ? size : in_block;
+    }
+    if (framed) immediate(0, kFrameEndSize);
+    out->spans.push_back(mi_buffer_span{start, at - start});
+    at = static_cast<int64_t>(RoundUp(static_cast<size_t>(at), 8));
+  }
+  if (block != words.size()) throw InternalException("compressed body: more size words than blocks");
+  out->body_size = at;
 }
 
 std::vector<CutPiece> RowGroupCutter::Cut(int64_t rows) {

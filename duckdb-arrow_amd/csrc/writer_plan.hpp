@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ipc_format.hpp"
+#include "lz4_encode_format.hpp"
 
 namespace miarrow {
 
@@ -48,6 +49,23 @@ struct EncodeInput {
 };
 //! The encode task of `node`: `spans` are the node's own (BodyLayout::first_span), `body` is where the body starts in HBM
 mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, const EncodeInput& in, uint8_t* body);
+
+// ------------------------------------------------------------------------------------------------ compressed body
+// BodyCompression{LZ4_FRAME, BUFFER}: every buffer of the encoded body is cut into 64 KiB blocks, the compress kernel leaves
+// block b in slot b of its scratch buffer and reports a size word for it (lz4_encode_format.hpp), and the body that goes to
+// the file is put together from those.  Blocks are numbered in span order; an empty buffer has none.
+
+//! The blocks of `plain`'s buffers, in the order of their size words
+std::vector<lz4enc::BlockIn> BlocksOfBody(const BodyLayout& plain);
+
+struct CompressedBodyLayout {
+  std::vector<mi_buffer_span> spans;     // RecordBatch.buffers: {offset, int64 prefix + frame (or + raw bytes), unpadded}
+  int64_t body_size = 0;                 // a multiple of 8
+  std::vector<lz4enc::BodyCopy> copies;  // what the compaction kernel copies into the (zeroed) body
+};
+//! Buffers start on multiples of 8.  A buffer whose frame is smaller than its bytes becomes {its length, the frame}, any
+//! other {-1, its bytes}, an empty one stays empty.  `words`: one size word per block of BlocksOfBody(plain).
+void LayOutCompressedBody(const BodyLayout& plain, const std::vector<uint32_t>& words, CompressedBodyLayout* out);
 
 // ------------------------------------------------------------------------------------------------ cut rule
 // The COPY pumps end a row group after the 2048-row chunk with which its rows reach row_group_size, or its rows x the

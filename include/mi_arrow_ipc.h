@@ -643,12 +643,19 @@ typedef struct mi_write_options {
   int32_t arrow_large_buffer_size; /* DuckDB's setting of the same name (ClientProperties.arrow_offset_size, passed to the
                                     * serializer at arrow_stream_writer.cpp:11-13): VARCHAR / BLOB / LIST export as
                                     * LargeUtf8 / LargeBinary / LargeList with int64 offsets; default 0 */
-  int32_t _reserved;
+  int32_t compression;           /* MI_WRITE_COMPRESSION_*: COMPRESSION / CODEC, default none */
 } mi_write_options;
+#define MI_WRITE_COMPRESSION_NONE 0
+#define MI_WRITE_COMPRESSION_LZ4_FRAME 1 /* BodyCompression{LZ4_FRAME, BUFFER}: every buffer an int64 length + one LZ4 frame of
+                                          * independent 64 KiB blocks, or -1 + its bytes when that is not smaller; compressed
+                                          * in HBM (csrc/kernels_lz4_encode.hip) */
 
 /* ArrowWriteBind (write_arrow_stream.cpp:54-125): _init fills the defaults; _set parses one COPY option (name is
- * matched case-insensitively: row_group_size | chunk_size | row_group_size_bytes | row_groups_per_file; a NULL value
- * is "<NAME> requires exactly one argument"); _add_kv appends one kv_metadata entry; _finalize applies the cross-option
+ * matched case-insensitively: row_group_size | chunk_size | row_group_size_bytes | row_groups_per_file | compression |
+ * codec; a NULL value is "<NAME> requires exactly one argument"; every other name is ignored).  compression / codec takes
+ * uncompressed | none | lz4 | lz4_frame; zstd is MI_ENOTSUP (ZSTD bodies are read but not written), anything else
+ * MI_EINVAL naming the value.  The option holds for mi_writer_sink, mi_writer_local_*, mi_writer_sink_scan and rotation
+ * (mi_writer_file_size counts compressed bytes); mi_ipc_serialize_chunks and mi_writer_append_message stay uncompressed; _add_kv appends one kv_metadata entry; _finalize applies the cross-option
  * rules.  Errors are MI_EINVAL with the reference's BinderException texts: "ROW_GROUP_SIZE and ROW_GROUP_SIZE_BYTES are
  * mutually exclusive", "ROW_GROUP_SIZE_BYTES does not work while preserving insertion order. Use \"SET
  * preserve_insertion_order=false;\" to disable preserving insertion order.". */
@@ -709,6 +716,12 @@ int mi_ipc_serializer_create(mi_ctx* ctx, const mi_field* fields, int32_t n_fiel
 int mi_ipc_serialize_schema(mi_writer* w, const uint8_t** blob, int64_t* size);
 int mi_ipc_serialize_chunks(mi_writer* w, const mi_data_chunk* chunks, int32_t n_chunks, const uint8_t** blob,
                             int64_t* size);
+
+/* Test and verification hook, host only: one body buffer of `n` bytes as the LZ4_FRAME writer stores it -- nothing when
+ * n == 0, else the int64 length and the frame, or -1 and the bytes -- computed by the serial restatement of the compress
+ * kernel (csrc/lz4_encode_format.hpp), whose bytes the kernel's equal.  *size = bytes written; when `out` is NULL or
+ * `cap` is too small nothing is written and *size = the room a call needs. */
+int mi_lz4_frame_compress_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t cap, int64_t* size);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """COPY (FROM read_arrow(file)) TO 'out.arrows' end to end (BASELINE config 4 through the operator path), per sink-thread
-count and output strategy, with the writer's stage timers.  usage: python tools/copy_bench.py [--sf 10] [--dir /dev/shm]"""
+count and output strategy, with the writer's stage timers.
+usage: python tools/copy_bench.py [--sf 10] [--dir /dev/shm] [--compression {none,lz4}]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -10,6 +11,7 @@ def main():
     ap.add_argument("--sf", type=float, default=10.0)
     ap.add_argument("--dir", default="/dev/shm")
     ap.add_argument("--threads", default="1,2,4,6")
+    ap.add_argument("--compression", choices=["none", "lz4"], default="none", help="body codec of the file written (COMPRESSION option)")
     args = ap.parse_args()
     os.environ["MI_WRITER_TIMING"] = "1"
     import duckdb_arrow_amd as da
@@ -18,7 +20,7 @@ def main():
     opath = os.path.join(args.dir, "mi_copy_out_sf%g.arrows" % args.sf)
     buf.tofile(path)
     con = da.Connection(0)
-    out = {"rows": info["n_rows"], "file_bytes": int(buf.size)}
+    out = {"rows": info["n_rows"], "file_bytes": int(buf.size), "compression": args.compression}
     try:
         t0 = time.perf_counter()
         n = con.read_arrow(path).count()
@@ -48,8 +50,10 @@ def main():
                 if target == opath and os.path.exists(opath):
                     os.unlink(opath)
                 t0 = time.perf_counter()
-                con.copy_to(con.read_arrow(path), target, row_group_size=122880)
+                con.copy_to(con.read_arrow(path), target, row_group_size=122880, compression=args.compression)
                 dt = time.perf_counter() - t0
+                if target == opath:
+                    out["bytes_written"] = os.path.getsize(opath)
                 best = dt if best is None else min(best, dt)
             out[("%s_threads_%d" % (tag, threads)) if threads else tag] = {"seconds": best, "rows_per_s": info["n_rows"] / best, "GBps_out": buf.size / best / 1e9}
             print("%s threads %d: %.3f s" % (tag, threads, best), file=sys.stderr, flush=True)

@@ -216,3 +216,121 @@ def rewrite_buffers_raw(stream_bytes, pick):
         bi += 1
     out += a[at:].tobytes()
     return bytes(out)
+
+
+# ------------------------------------------------------------------------------------------ late materialisation (gather)
+# The reference of the gather kernel (kernels_gather.hip): the oracle decodes the WHOLE column with its per-kind functions,
+# numpy then takes the selected rows.  There is no gather entry point in the oracle, on purpose: the compacted vectors must
+# be what slicing the flat vectors with the selection gives.
+ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL_RANGE, ST_DICT_INDEX = 1, 2, 4, 8, 16, 64  # mi_arrow_ipc.h
+
+_orc_ready = False
+
+
+def _orc():
+    """The oracle with the prototypes of the per-kind functions pyoracle.lib() leaves undeclared."""
+    global _orc_ready
+    import ctypes as C
+    L = po.lib()
+    if not _orc_ready:
+        P, I64, I32, U64, U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32
+        for name, args in (("orc_bool", [P, I64, I64, P]), ("orc_decimal128_narrow", [P, P, I64, I64, I32, P]),
+                           ("orc_date64_to_date32", [P, I64, I64, P]), ("orc_div_i64", [P, I64, I64, I64, P]),
+                           ("orc_fixed_binary", [P, I32, P, I64, I64, U64, P]), ("orc_dict_sel", [P, I32, I32, P, I64, I64, U32, P])):
+            getattr(L, name).argtypes = args
+        _orc_ready = True
+    return L
+
+
+def _words_of(ok):
+    """bool per row -> validity_t words, pad bits ones."""
+    n = len(ok)
+    return np.packbits(np.concatenate([ok.astype(bool), np.ones((-n) % 64, bool)]), bitorder="little").view(np.uint64).copy()
+
+
+def decode_column_reference(kind, nrows, buf1, *, param=0, param2=0, validity=None, null_count=-1, row_offset=0, buf2=None,
+                            buf2_len=None, ptr_base=0):
+    """Rows [row_offset, row_offset + nrows) of one Arrow column as the flat decode path hands them to DuckDB, from the
+    oracle's per-kind functions (each takes the array offset `o`): (data uint8[nrows, width], valid bool[nrows],
+    err uint32[nrows]).
+
+    err[r] = the MI_ST_* bits row r raises when it is decoded.  The oracle reports errors per call, not per row, so its
+    conditions are restated per row: FULL offset validation (first >= 0, non-decreasing, end <= data length) and "Strings
+    over 4GB" (an end offset past UINT32_MAX) for every row, NULL or not, as the whole-array validation is; multiply
+    overflow, an index that does not fit uint32 or points past the dictionary, and a decimal that is not the sign
+    extension of its narrowed value (Hugeint::TryCast; the oracle only truncates) for valid rows.  A row with damaged
+    offsets decodes to the canonical 16 zero bytes (the oracle is not asked to follow them)."""
+    L = _orc()
+    n, o = int(nrows), int(row_offset)
+    w = po.out_width(kind, param)
+    b1 = np.ascontiguousarray(buf1).view(np.uint8).reshape(-1)
+    bm = np.ascontiguousarray(validity).view(np.uint8).reshape(-1) if validity is not None else None
+    words = np.full(max((n + 63) // 64, 1), np.uint64(0xFFFFFFFFFFFFFFFF))
+    if n:
+        L.orc_validity(bm.ctypes.data if bm is not None else None, null_count, o, n, words.ctypes.data)
+    ok = po.valid_bits(words, n)
+    err = np.zeros(n, np.uint32)
+    out = np.zeros(max(n * w, 1), np.uint8)
+    rows = slice(o, o + n)
+    if n == 0:
+        return out[:0].reshape(0, max(w, 1)), ok, err
+    if kind == po.K_COPY:
+        out[: n * w] = b1[o * w: (o + n) * w]
+    elif kind == po.K_BOOL:
+        L.orc_bool(b1.ctypes.data, o, n, out.ctypes.data)
+    elif kind == po.K_DEC128:
+        L.orc_decimal128_narrow(b1.ctypes.data, words.ctypes.data, o, n, w, out.ctypes.data)
+        halves = b1[: (o + n) * 16].view(np.int64).reshape(-1, 2)[rows]
+        sext = halves[:, 0].astype({2: np.int16, 4: np.int32, 8: np.int64}[w]).astype(np.int64)
+        err[ok & ((sext != halves[:, 0]) | (halves[:, 1] != (sext >> 63)))] = ST_DECIMAL_RANGE
+    elif kind == po.K_DATE64:
+        L.orc_date64_to_date32(b1.ctypes.data, o, n, out.ctypes.data)
+    elif kind == po.K_MUL_I32:
+        assert 0 < param < 2**31      # an int32 times this cannot leave int64: no per-row condition
+        assert L.orc_mul_i32_to_i64(b1.ctypes.data, words.ctypes.data, o, n, param, out.ctypes.data) == 0
+    elif kind == po.K_MUL_I64:
+        L.orc_mul_i64(b1.ctypes.data, words.ctypes.data, o, n, param, out.ctypes.data)
+        src = b1[: (o + n) * 8].view(np.int64)[rows]
+        err[ok & ((src > (2**63 - 1) // param) | (src < -(2**63 // param)))] = ST_MUL_OVERFLOW
+    elif kind == po.K_DIV_I64:
+        L.orc_div_i64(b1.ctypes.data, o, n, param, out.ctypes.data)
+    elif kind in (po.K_STR32, po.K_STR64):
+        off = b1.view(np.int32 if kind == po.K_STR32 else np.int64)[o: o + n + 1].astype(np.int64)
+        b2 = np.ascontiguousarray(buf2).view(np.uint8).reshape(-1) if buf2 is not None and len(buf2) else np.zeros(16, np.uint8)
+        data_len = (len(np.ascontiguousarray(buf2).view(np.uint8).reshape(-1)) if buf2 is not None else 0) if buf2_len is None else buf2_len
+        a, b = off[:-1], off[1:]
+        bad = ~((a >= 0) & (b >= a) & (b <= data_len))
+        big = ~bad & (b > 0xFFFFFFFF) if kind == po.K_STR64 else np.zeros(n, bool)
+        err[bad] = ST_BAD_OFFSETS
+        err[big] = ST_STRING_TOO_LARGE
+        follow = _words_of(ok & ~bad & ~big)
+        fn = L.orc_string32 if kind == po.K_STR32 else L.orc_string64
+        fn(b1.ctypes.data, b2.ctypes.data, follow.ctypes.data, o, n, ptr_base, out.ctypes.data)
+    elif kind == po.K_FIXED_BINARY:
+        L.orc_fixed_binary(b1.ctypes.data, int(param), words.ctypes.data, o, n, ptr_base, out.ctypes.data)
+    elif kind == po.K_DICT:
+        iw, signed = int(param & 0xFF), int((param >> 8) & 1)
+        L.orc_dict_sel(b1.ctypes.data, iw, signed, words.ctypes.data, o, n, param2, out.ctypes.data)
+        idx = b1[: (o + n) * iw].view(np.dtype("%s%d" % ("i" if signed and iw < 8 else "u", iw)))[rows]
+        wide = (idx.astype(np.int64).view(np.uint64) if iw < 8 else idx) > np.uint64(0xFFFFFFFF)
+        past = ~wide & (idx.astype(np.uint64) >= np.uint64(param2))
+        err[ok & wide] = ST_INDEX_RANGE
+        err[ok & past] = ST_DICT_INDEX
+    else:
+        raise NotImplementedError("kind %d is not decoded through a selection vector" % kind)
+    return out[: n * w].reshape(n, w), ok, err
+
+
+def gather_take(data, ok, err, sel):
+    """The take-and-pack half of the gather reference.  `sel` = one ascending list of window-relative row indices per
+    2048-row window.  -> (rows 2048 * w + sel[w][i] of `data` in window order, densely packed, as uint8[total * width];
+    their validity bits as uint64 words with every bit past the total set; the OR of their err bits)."""
+    parts = [2048 * w + np.asarray(s, np.int64) for w, s in enumerate(sel)]
+    rows = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+    status = int(np.bitwise_or.reduce(err[rows])) if len(rows) else 0
+    return np.ascontiguousarray(data[rows]).reshape(-1), _words_of(ok[rows]), status
+
+
+def gather_reference(kind, nrows, buf1, sel, **column):
+    """Expected output bytes, validity words and status of one gather task (a column decoded through a selection vector)."""
+    return gather_take(*decode_column_reference(kind, nrows, buf1, **column), sel)

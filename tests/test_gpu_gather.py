@@ -1,0 +1,616 @@
+"""Late materialisation (kernels_gather.hip) against the flat decode: every gather task kind through the kernel-level ABI
+(mi_col_task.sel / sel_count) and every gatherable Arrow type through the scan operator's filter_compact.
+
+Reference (helpers.gather_reference, checked without a GPU in test_gather_reference_host.py): the oracle decodes the
+whole column, numpy takes rows 2048 * w + sel[w][i] and packs them.  NULL slots are compared too: no kind needed masking,
+the kernel's NULL slots are the oracle's for every kind (source bytes for COPY / BOOL / DATE64 / DIV_I64, canonical
+zero -- dict_len for DICT -- for the others).
+
+Buffers follow the host's contract (ArrowScan::EnqueueStageB): 2048 sel slots per window of which the first count[w] mean
+something, validity preset to ones for ceil(total / 64) words plus one guard word.  On top of that the output is filled
+with a sentinel and over-allocated, and the unused sel slots hold 2048: a row of the NEXT window.  Every source buffer
+is generated PAD_ROWS rows longer than the column, so a kernel that did follow such a slot would read defined bytes of
+the same allocation and show up as a wrong value, never as an access outside the buffers."""
+import decimal
+
+import numpy as np
+import pytest
+
+import duckdb_arrow_amd as da
+from duckdb_arrow_amd import _ffi
+from oracle import pyoracle as po
+
+from helpers import canon_python, decode_column_reference, gather_reference, gather_take
+
+pytestmark = pytest.mark.gpu
+
+WIN = 2048
+PAD_ROWS = WIN + 64
+SEL_FILL = 2048
+SENTINEL = 0xA5
+ONES = np.uint64(0xFFFFFFFFFFFFFFFF)
+PTR_BASE = 0x7000_0000_1003
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return da.Context(0)
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+@pytest.fixture(scope="module")
+def con():
+    return da.Connection(0)
+
+
+# ------------------------------------------------------------------------------------------------ columns
+def _dict_variant(iw, signed):
+    dict_len = {(1, 1): 100, (1, 0): 250, (2, 1): 30000, (2, 0): 60000, (4, 1): 2 * 10**9, (4, 0): 4 * 10**9}.get((iw, signed), 2**32 - 1)
+    return dict(kind=_ffi.K_DICT, param=iw | (signed << 8), param2=dict_len)
+
+
+VARIANTS = {
+    "copy1": dict(kind=_ffi.K_COPY, param=1), "copy2": dict(kind=_ffi.K_COPY, param=2), "copy4": dict(kind=_ffi.K_COPY, param=4),
+    "copy8": dict(kind=_ffi.K_COPY, param=8), "copy16": dict(kind=_ffi.K_COPY, param=16),
+    "dec128_i16": dict(kind=_ffi.K_DEC128, param=2), "dec128_i32": dict(kind=_ffi.K_DEC128, param=4),
+    "dec128_i64": dict(kind=_ffi.K_DEC128, param=8),
+    "str32": dict(kind=_ffi.K_STR32), "str64": dict(kind=_ffi.K_STR64),
+    "fixed1": dict(kind=_ffi.K_FIXED_BINARY, param=1), "fixed12": dict(kind=_ffi.K_FIXED_BINARY, param=12),
+    "fixed13": dict(kind=_ffi.K_FIXED_BINARY, param=13), "fixed16": dict(kind=_ffi.K_FIXED_BINARY, param=16),
+    "bool": dict(kind=_ffi.K_BOOL), "date64": dict(kind=_ffi.K_DATE64),
+    "mul_i32_1e6": dict(kind=_ffi.K_MUL_I32, param=1000000), "mul_i32_1e3": dict(kind=_ffi.K_MUL_I32, param=1000),
+    "mul_i64_1e6": dict(kind=_ffi.K_MUL_I64, param=1000000),
+    "div_i64_1000": dict(kind=_ffi.K_DIV_I64, param=1000), "div_i64_86400": dict(kind=_ffi.K_DIV_I64, param=86400),
+}
+for _iw in (1, 2, 4, 8):
+    for _signed in (1, 0):
+        VARIANTS["dict_%s%d" % ("i" if _signed else "u", 8 * _iw)] = _dict_variant(_iw, _signed)
+
+
+def make_column(variant, nrows, row_offset, nulls, rng):
+    """One source column of VARIANTS[variant]: `nrows` rows at Arrow array offset `row_offset`.  nulls: "bitmap" (random
+    bitmap, null_count -1; the NULL rows hold values that would raise a status flag if they were looked at), "count0" (a
+    random bitmap the kernel has to ignore: null_count 0) or "none"."""
+    col = dict(VARIANTS[variant], nrows=nrows, row_offset=row_offset, name="%s/%s/n%d/o%d" % (variant, nulls, nrows, row_offset))
+    kind, param = col["kind"], col.get("param", 0)
+    total = row_offset + nrows + PAD_ROWS
+    bitmap = rng.integers(0, 256, (total + 63) // 64 * 8 + 8, dtype=np.uint8)
+    null = ~np.unpackbits(bitmap, bitorder="little")[:total].astype(bool) if nulls == "bitmap" else np.zeros(total, bool)
+    if nulls != "none":
+        col.update(validity=bitmap, null_count=-1 if nulls == "bitmap" else 0)
+    if kind == _ffi.K_COPY:
+        buf1 = rng.integers(0, 256, total * param, dtype=np.uint8)
+    elif kind == _ffi.K_FIXED_BINARY:
+        buf1 = rng.integers(0, 256, total * param, dtype=np.uint8)
+        col["ptr_base"] = PTR_BASE
+    elif kind == _ffi.K_BOOL:
+        buf1 = rng.integers(0, 256, (total + 7) // 8, dtype=np.uint8)
+    elif kind == _ffi.K_DEC128:
+        lim = 1 << (8 * param - 1)
+        v = rng.integers(-lim, lim - 1, total, endpoint=True).astype(np.int64)
+        v[rng.integers(0, total, 8)] = [-lim, lim - 1, 0, -1, -lim, lim - 1, 1, -2]
+        halves = np.stack([v, v >> 63], axis=1)
+        halves[null] = rng.integers(-2**63, 2**63 - 1, (int(null.sum()), 2), endpoint=True)   # out of range, bad upper half
+        buf1 = halves.reshape(-1)
+    elif kind in (_ffi.K_STR32, _ffi.K_STR64):
+        lens = rng.choice([0, 1, 2, 3, 4, 5, 11, 12, 13, 14, 15, 16, 29, 40], total)
+        off = 5 + np.concatenate([[0], np.cumsum(lens)])      # every length at every payload misalignment
+        buf1 = off.astype(np.int32 if kind == _ffi.K_STR32 else np.int64)
+        col.update(buf2=rng.integers(1, 256, int(off[-1]), dtype=np.uint8), buf2_len=int(off[row_offset + nrows]), ptr_base=PTR_BASE)
+    elif kind == _ffi.K_DATE64:
+        buf1 = rng.integers(-3 * 10**14, 3 * 10**14, total).astype(np.int64)      # +- 9500 years of milliseconds
+        buf1[rng.integers(0, total, 6)] = [-1, 0, 86400000, -86400000, 86399999, -86400001]
+    elif kind == _ffi.K_MUL_I32:
+        buf1 = rng.integers(-2**31, 2**31 - 1, total, endpoint=True).astype(np.int32)
+    elif kind == _ffi.K_MUL_I64:
+        lim = (2**63 - 1) // param
+        buf1 = rng.integers(-lim, lim, total, endpoint=True).astype(np.int64)
+        buf1[rng.integers(0, total, 2)] = [-lim, lim]
+        buf1[null] = rng.integers(2**62, 2**63 - 1, int(null.sum()))              # would overflow
+    elif kind == _ffi.K_DIV_I64:
+        buf1 = rng.integers(-2**63, 2**63 - 1, total, endpoint=True).astype(np.int64)
+        buf1[rng.integers(0, total, 6)] = [-1, 0, param, -param, param - 1, 1 - param]
+    elif kind == _ffi.K_DICT:
+        iw, signed, dict_len = param & 0xFF, (param >> 8) & 1, col["param2"]
+        v = rng.integers(0, dict_len, total).astype(np.uint64)
+        v[rng.integers(0, total, 2)] = [0, dict_len - 1]
+        v[null] = ONES if (signed or iw == 8) else np.uint64(2**(8 * iw) - 1)        # -1, or past the dictionary
+        buf1 = v.astype(np.dtype("u%d" % iw))
+    else:
+        raise AssertionError(kind)
+    col["buf1"] = buf1
+    return col
+
+
+def _width(col):
+    return po.out_width(col["kind"], col.get("param", 0))
+
+
+def _reference_args(col):
+    return {k: col[k] for k in ("param", "param2", "validity", "null_count", "row_offset", "buf2", "buf2_len", "ptr_base") if k in col}
+
+
+# ------------------------------------------------------------------------------------------------ selections
+def make_sel(nrows, counts, rng):
+    """One ascending index list per 2048-row window with the wanted number of rows (clipped to the window's size; None =
+    every row).  A window with two rows or more selects its first and its last row, single rows alternate between them."""
+    sel = []
+    for w in range((nrows + WIN - 1) // WIN):
+        m = min(WIN, nrows - w * WIN)
+        c = m if counts[w % len(counts)] is None else min(counts[w % len(counts)], m)
+        if c == m:
+            s = np.arange(m)
+        elif c == 0:
+            s = np.zeros(0, np.int64)
+        elif c == 1:
+            s = np.array([0 if w % 2 else m - 1])
+        else:
+            s = np.sort(np.concatenate([[0, m - 1], 1 + rng.choice(m - 2, c - 2, replace=False)]))
+        sel.append(s.astype(np.int64))
+    return sel
+
+
+def _sel_arrays(sel):
+    flat = np.full(max(len(sel), 1) * WIN, SEL_FILL, np.uint32)
+    for w, s in enumerate(sel):
+        flat[w * WIN: w * WIN + len(s)] = s
+    return flat, np.array([len(s) for s in sel] + [0], np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ running a plan
+def _dev(torch, a):
+    """numpy array -> device bytes, padded as IPC buffers are (to 8 bytes, and never empty)"""
+    b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    return torch.from_numpy(np.concatenate([b, np.zeros(16 - len(b) % 8, np.uint8)])).cuda()
+
+
+def run_plan(ctx, torch, jobs, sels):
+    """jobs = [(column, key into sels or None for an ordinary flat task)], sels = {key: index lists per window}.  One Plan,
+    one launch.  -> ([(data bytes incl. the sentinel tail, validity words incl. the guard word) per job], status)."""
+    keep, dsel = [], {}
+    for key, sel in sels.items():
+        flat, counts = _sel_arrays(sel)
+        dsel[key] = (torch.from_numpy(flat.view(np.int32)).cuda(), torch.from_numpy(counts.view(np.int32)).cuda(), sum(len(s) for s in sel))
+    tasks, outs = [], []
+    for col, key in jobs:
+        total = dsel[key][2] if key is not None else col["nrows"]
+        d1, dv, d2 = _dev(torch, col["buf1"]), (_dev(torch, col["validity"]) if "validity" in col else None), \
+            (_dev(torch, col["buf2"]) if "buf2" in col else None)
+        out = torch.full((total * _width(col) + 64 + (-total * _width(col)) % 16,), SENTINEL, dtype=torch.uint8, device="cuda")
+        outv = torch.full(((total + 63) // 64 * 8 + 8,), 0xFF, dtype=torch.uint8, device="cuda")
+        keep += [d1, dv, d2]
+        outs.append((out, outv))
+        tasks.append(da.make_task(col["kind"], col["nrows"], d1.data_ptr(), out.data_ptr(), validity=dv.data_ptr() if dv is not None else 0,
+                                  buf2=d2.data_ptr() if d2 is not None else 0, out_validity=outv.data_ptr(), ptr_base=col.get("ptr_base", 0),
+                                  row_offset=col["row_offset"], buf2_len=col.get("buf2_len", 0), param=col.get("param", 0),
+                                  param2=col.get("param2", 0), null_count=col.get("null_count", -1),
+                                  sel=dsel[key][0].data_ptr() if key is not None else 0,
+                                  sel_count=dsel[key][1].data_ptr() if key is not None else 0))
+    plan = da.Plan(ctx, tasks)
+    plan.launch(torch.cuda.current_stream().cuda_stream)
+    status = plan.status()
+    got = [(out.cpu().numpy(), outv.cpu().numpy().view(np.uint64)) for out, outv in outs]
+    plan.close()
+    return got, status
+
+
+def check_job(col, sel, got, want=None):
+    """The four assertions on one task's output.  sel None = an ordinary flat task (every row, in place).  Returns the
+    expected status of the task."""
+    data, words = got
+    if sel is None:
+        sel = make_sel(col["nrows"], [None], None)
+    want_data, want_words, want_status = want if want is not None else gather_reference(col["kind"], col["nrows"], col["buf1"], sel, **_reference_args(col))
+    w, total, where = _width(col), sum(len(s) for s in sel), col.get("name", "")
+    if not np.array_equal(data[: total * w], want_data):
+        bad = np.nonzero(np.any(data[: total * w].reshape(-1, w) != want_data.reshape(-1, w), axis=1))[0]
+        raise AssertionError("%s: %d of %d output rows differ, first %d: got %s want %s" % (
+            where, len(bad), total, bad[0], data[bad[0] * w: bad[0] * w + w].tolist(), want_data[bad[0] * w: bad[0] * w + w].tolist()))
+    assert (data[total * w:] == SENTINEL).all(), (where, "bytes behind the last output row were written")
+    assert len(words) == (total + 63) // 64 + 1
+    if not np.array_equal(words[:-1], want_words):
+        bad = np.nonzero(words[:-1] != want_words)[0]
+        raise AssertionError("%s: %d validity words differ, first %d of %d: got %016x want %016x" % (
+            where, len(bad), bad[0], len(want_words), int(words[bad[0]]), int(want_words[bad[0]])))
+    assert words[-1] == ONES, (where, "the guard word behind the validity words lost bits")
+    return want_status
+
+
+# ------------------------------------------------------------------------------------------------ every kind
+ROW_OFFSETS = [0, 1, 7, 13, 64, 2051]
+# per-window counts by row count, one pattern per row offset: together 0, 1, 63, 64, 65, 255, 256, 257, 2047 and 2048 rows in a window
+# (the seams of gather_rows: one wave, one pass of 256 lanes, several passes); the short last window is fully selected
+COUNT_PATTERNS = {
+    1: [[None]] * 6,
+    2047: [[None]] * 6,
+    2048: [[2048], [1], [63], [64], [65], [255]],
+    2049: [[256, None], [257, None], [2047, None], [0, None], [2048, None], [1, None]],
+    5000: [[0, 2048, None], [1, 63, None], [64, 65, None], [255, 256, None], [257, 2047, None], [2048, 0, None]],
+}
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_every_kind_equals_the_flat_decode(ctx, torch, variant):
+    """One plan per kind variant: 5 row counts x 6 array offsets x 3 validity forms = 90 gather tasks over 30 selections.
+    Data rows, sentinel tail, validity words with pad bits and the guard word of every task, and status 0 (the NULL rows
+    of the bitmap form hold out-of-range values that must not be looked at)."""
+    rng = np.random.default_rng(sorted(VARIANTS).index(variant))
+    jobs, sels = [], {}
+    for nrows, patterns in COUNT_PATTERNS.items():
+        for row_offset, counts in zip(ROW_OFFSETS, patterns):
+            sels[(nrows, row_offset)] = make_sel(nrows, counts, rng)
+            for nulls in ("bitmap", "count0", "none"):
+                jobs.append((make_column(variant, nrows, row_offset, nulls, rng), (nrows, row_offset)))
+    got, status = run_plan(ctx, torch, jobs, sels)
+    for (col, key), g in zip(jobs, got):
+        assert check_job(col, sels[key], g) == 0, col["name"]
+    assert status == 0
+
+
+WINDOW_COUNTS = [0, 1, 63, 64, 65, 255, 256, 257, 2047, 2048, 0, 0, 2048, 2048, 1, None]
+
+
+@pytest.mark.parametrize("variant", ["copy4", "dec128_i64", "str32", "bool", "dict_i32"])
+def test_window_counts_at_the_loop_seams_in_one_column(ctx, torch, variant):
+    """All the seam counts in consecutive windows of ONE column, so every window's output range starts at an odd position
+    left by the windows before it (window_base) and shares validity words with its neighbours."""
+    rng = np.random.default_rng(77)
+    nrows = (len(WINDOW_COUNTS) - 1) * WIN + 77
+    sel = make_sel(nrows, WINDOW_COUNTS, rng)
+    col = make_column(variant, nrows, 13, "bitmap", rng)
+    got, status = run_plan(ctx, torch, [(col, "s")], {"s": sel})
+    assert check_job(col, sel, got[0]) == 0 and status == 0
+
+
+def test_single_rows_of_many_windows_share_validity_words(ctx, torch):
+    """150 windows with one selected row each, alternately NULL: 64 windows clear their bit of one output word, each with
+    its own atomicAnd.  Then the same with 65 rows per window, where every wave's word straddles two output words."""
+    rng = np.random.default_rng(5)
+    nw = 150
+    nrows = nw * WIN
+    jobs, sels = [], {}
+    for name, per in (("one", 1), ("sixty-five", 65)):
+        sel = [np.sort(rng.choice(WIN, per, replace=False)).astype(np.int64) for _ in range(nw)]
+        col = make_column("copy8", nrows, 3, "bitmap", rng)
+        bits = np.unpackbits(col["validity"], bitorder="little")
+        for w, s in enumerate(sel):
+            bits[3 + w * WIN + s] = (w + np.arange(per)) % 2      # alternately NULL along the output
+        col["validity"] = np.packbits(bits, bitorder="little")
+        jobs.append((col, name))
+        sels[name] = sel
+    got, status = run_plan(ctx, torch, jobs, sels)
+    for (col, key), g in zip(jobs, got):
+        check_job(col, sels[key], g)
+        if key == "one":
+            assert g[1][0] == np.uint64(0xAAAAAAAAAAAAAAAA) and g[1][1] == np.uint64(0xAAAAAAAAAAAAAAAA)
+    assert status == 0
+
+
+def test_long_column_runs_the_carry_loop_of_the_window_bases(ctx, torch):
+    """2 * 2048 + 3 windows (8.4 M rows): gather_window_bases scans 2048 windows per step, so this column takes two full
+    steps and a partial third, with the carry handed from step to step.  A COPY 1 and a COPY 8 task with NULLs share the
+    selection; the counts vary and include runs of empty and of full windows, also across the step boundaries."""
+    rng = np.random.default_rng(9)
+    nw = 2 * 2048 + 3
+    nrows = nw * WIN - 1000
+    p = rng.choice([0.0, 0.003, 0.05, 0.4, 1.0], nw, p=[0.2, 0.3, 0.2, 0.2, 0.1])
+    p[100:140], p[140:170] = 0.0, 1.0
+    p[2040:2047], p[2047:2050], p[4090:4096] = 1.0, 0.0, 1.0
+    p[-3:] = [0.0, 0.5, 1.0]
+    keep = rng.random(nw * WIN, dtype=np.float32) < np.repeat(p, WIN).astype(np.float32)
+    keep[nrows:] = False
+    rows = np.nonzero(keep)[0]
+    counts = np.bincount(rows >> 11, minlength=nw)
+    assert counts.max() == WIN and counts.min() == 0 and counts[-1] == WIN - 1000
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    flat = np.full(nw * WIN, SEL_FILL, np.uint32)
+    flat[(rows >> 11) * WIN + (np.arange(len(rows)) - starts[rows >> 11])] = rows & 2047
+    sel = np.split(rows & 2047, starts[1:-1])
+    assert np.array_equal(_sel_arrays(sel)[0], flat)
+    cols = [make_column("copy1", nrows, 5, "bitmap", rng), make_column("copy8", nrows, 2051, "bitmap", rng)]
+    got, status = run_plan(ctx, torch, [(c, "s") for c in cols], {"s": sel})
+    for col, g in zip(cols, got):
+        w, o = _width(col), col["row_offset"]
+        src = col["buf1"].reshape(-1, w)[o: o + nrows]
+        ok = np.unpackbits(col["validity"], bitorder="little")[o: o + nrows].astype(bool)
+        want = gather_take(src, ok, np.zeros(nrows, np.uint32), sel)     # COPY: the source bytes (helpers.decode_column_reference)
+        check_job(col, sel, g, want=want)
+    assert status == 0
+
+
+# ------------------------------------------------------------------------------------------------ plans
+def test_plan_with_gather_tasks_over_two_selections_and_flat_tasks(ctx, torch):
+    """window_base is indexed by the tile inside the gather slice: four gather tasks (two selections of different row
+    counts, a task of one selection between two of the other) and two ordinary tasks in one plan give what each gives in
+    a plan of its own."""
+    rng = np.random.default_rng(21)
+    na, nb = 3 * WIN + 500, 5 * WIN + 1
+    sels = {"a": make_sel(na, [700, 0, 2048, None], rng), "b": make_sel(nb, [1, 2047, 65, 0, 300, None], rng)}
+    jobs = [(make_column("str32", na, 7, "bitmap", rng), "a"), (make_column("copy2", nb, 0, "none", rng), None),
+            (make_column("dec128_i32", nb, 64, "bitmap", rng), "b"), (make_column("bool", na, 13, "bitmap", rng), "a"),
+            (make_column("dict_u16", nb, 1, "bitmap", rng), None), (make_column("fixed13", nb, 2051, "count0", rng), "b")]
+    got, status = run_plan(ctx, torch, jobs, sels)
+    assert status == 0
+    for (col, key), g in zip(jobs, got):
+        check_job(col, sels[key] if key else None, g)
+        alone, st = run_plan(ctx, torch, [(col, key)], {key: sels[key]} if key else {})
+        assert st == 0 and np.array_equal(alone[0][0], g[0]) and np.array_equal(alone[0][1], g[1]), col["name"]
+
+
+@pytest.mark.parametrize("variant", ["copy8", "str64", "dec128_i16", "dict_i8"])
+def test_nothing_selected_and_empty_columns_write_nothing(ctx, torch, variant):
+    rng = np.random.default_rng(2)
+    sels = {"none": make_sel(5000, [0], rng), "empty": []}
+    jobs = [(make_column(variant, 5000, 7, "bitmap", rng), "none"), (make_column(variant, 0, 0, "bitmap", rng), "empty")]
+    got, status = run_plan(ctx, torch, jobs, sels)
+    for (col, key), (data, words) in zip(jobs, got):
+        check_job(col, sels[key], (data, words))
+        assert (data == SENTINEL).all() and len(words) == 1 and words[0] == ONES
+    assert status == 0
+
+
+# ------------------------------------------------------------------------------------------------ status
+def _dec(values, width):
+    """python ints -> decimal128 halves; (lower, upper) tuples are taken as they are"""
+    out = []
+    for v in values:
+        out += list(v) if isinstance(v, tuple) else [v & (2**64 - 1), (v >> 64) & (2**64 - 1)]
+    return dict(kind=_ffi.K_DEC128, param=width, buf1=np.array(out, np.uint64))
+
+
+def _status_cases():
+    cases = {}
+    for w in (2, 4, 8):
+        lim = 1 << (8 * w - 1)
+        cases["dec128_i%d_above" % (8 * w)] = (lambda bad, w=w, lim=lim: _dec([lim if bad else lim - 1], w), _ffi.ST_DECIMAL_RANGE, True)
+        cases["dec128_i%d_below" % (8 * w)] = (lambda bad, w=w, lim=lim: _dec([-lim - 1 if bad else -lim], w), _ffi.ST_DECIMAL_RANGE, True)
+        cases["dec128_i%d_upper_half" % (8 * w)] = (lambda bad, w=w: _dec([(5, 1) if bad else 5], w), _ffi.ST_DECIMAL_RANGE, True)
+    cases["dec128_i64_upper_half_of_a_negative"] = (lambda bad: _dec([(2**64 - 5, 2**64 - 2) if bad else -5], 8), _ffi.ST_DECIMAL_RANGE, True)
+    big = (2**63 - 1) // 1000
+    cases["mul_i64_above"] = (lambda bad: dict(kind=_ffi.K_MUL_I64, param=1000, buf1=np.array([big + 1 if bad else big], np.int64)), _ffi.ST_MUL_OVERFLOW, True)
+    cases["mul_i64_below"] = (lambda bad: dict(kind=_ffi.K_MUL_I64, param=1000, buf1=np.array([-big - 2 if bad else -big], np.int64)), _ffi.ST_MUL_OVERFLOW, True)
+    for iw in (1, 2, 4):
+        cases["dict_i%d_negative" % (8 * iw)] = (lambda bad, iw=iw: dict(kind=_ffi.K_DICT, param=iw | 256, param2=90, buf1=np.array(
+            [-1 if bad else 3], np.dtype("i%d" % iw))), _ffi.ST_INDEX_RANGE, True)
+        cases["dict_u%d_past_the_dictionary" % (8 * iw)] = (lambda bad, iw=iw: dict(kind=_ffi.K_DICT, param=iw, param2=90, buf1=np.array(
+            [200 if bad else 89], np.dtype("u%d" % iw))), _ffi.ST_DICT_INDEX, True)
+    cases["dict_u64_wider_than_uint32"] = (lambda bad: dict(kind=_ffi.K_DICT, param=8, param2=90, buf1=np.array([2**32 if bad else 3], np.uint64)),
+                                           _ffi.ST_INDEX_RANGE, True)
+    cases["dict_i64_negative"] = (lambda bad: dict(kind=_ffi.K_DICT, param=8 | 256, param2=90, buf1=np.array([-1 if bad else 3], np.int64)),
+                                  _ffi.ST_INDEX_RANGE, True)
+    cases["dict_i32_equal_to_dict_len"] = (lambda bad: dict(kind=_ffi.K_DICT, param=4 | 256, param2=90, buf1=np.array([90 if bad else 89], np.int32)),
+                                           _ffi.ST_DICT_INDEX, True)
+    return cases
+
+
+STATUS_CASES = _status_cases()
+BAD_ROWS = [0, 70, WIN + 255, 2 * WIN + 99]       # lane 0 of a wave, inside a wave, second pass of a window, last window
+
+
+def _status_column(make, flag_row, nrows, rng):
+    """`nrows` good rows (the case's good value) with the case's bad value at `flag_row`; every row valid except where the
+    caller clears bits afterwards."""
+    good, bad = make(False), make(True)
+    per = len(good["buf1"])
+    buf1 = np.tile(good["buf1"], nrows + PAD_ROWS)
+    buf1[flag_row * per: (flag_row + 1) * per] = bad["buf1"]
+    return dict(good, buf1=buf1, nrows=nrows, row_offset=0, validity=np.full((nrows + PAD_ROWS + 63) // 64 * 8 + 8, 0xFF, np.uint8), null_count=-1)
+
+
+@pytest.mark.parametrize("case", list(STATUS_CASES))
+def test_value_checks_look_at_selected_valid_rows_only(ctx, torch, case):
+    """DECIMAL_RANGE / MUL_OVERFLOW / INDEX_RANGE / DICT_INDEX: raised when the offending row is selected and valid, not
+    raised when it is unselected, and not raised when it is selected but NULL.  Data (the DICT slot holds dict_len) and
+    validity equal the reference in all three."""
+    make, flag, _ = STATUS_CASES[case]
+    rng = np.random.default_rng(3)
+    nrows = 2 * WIN + 100
+    for bad_row in BAD_ROWS:
+        w, r = divmod(bad_row, WIN)
+        with_row = make_sel(nrows, [300, 300, None], rng)
+        if r not in with_row[w]:
+            with_row[w] = np.sort(np.concatenate([with_row[w][:-2], [r], with_row[w][-1:]]))
+        without = [s[s != r] if i == w else s for i, s in enumerate(with_row)]
+        col = _status_column(make, bad_row, nrows, rng)
+        col["name"] = "%s/row%d" % (case, bad_row)
+        null = dict(col, validity=col["validity"].copy())
+        null["validity"][bad_row >> 3] &= 0xFF ^ (1 << (bad_row & 7))
+        for c, sel, want in ((col, with_row, flag), (col, without, 0), (null, with_row, 0)):
+            got, status = run_plan(ctx, torch, [(c, "s")], {"s": sel})
+            assert check_job(c, sel, got[0]) == want, c["name"]
+            assert status == want, (c["name"], status)
+
+
+def _strings(kind, nrows, rng, long_row):
+    lens = rng.choice([0, 3, 12, 13, 30], nrows + PAD_ROWS)
+    lens[long_row] = 13                                  # the row to damage is not empty: no other row ends where it ends
+    off = 5 + np.concatenate([[0], np.cumsum(lens)]).astype(np.int32 if kind == _ffi.K_STR32 else np.int64)
+    return dict(kind=kind, buf1=off, buf2=rng.integers(1, 256, int(off[-1]), dtype=np.uint8), buf2_len=int(off[nrows]), nrows=nrows, row_offset=0,
+                validity=rng.integers(0, 256, (nrows + PAD_ROWS + 63) // 64 * 8 + 8, dtype=np.uint8), null_count=-1, ptr_base=PTR_BASE)
+
+
+@pytest.mark.parametrize("kind,damage", [(_ffi.K_STR32, "decreasing"), (_ffi.K_STR32, "past_the_data"), (_ffi.K_STR64, "decreasing"),
+                                         (_ffi.K_STR64, "past_the_data"), (_ffi.K_STR64, "too_large")],
+                         ids=["str32-decreasing", "str32-past_the_data", "str64-decreasing", "str64-past_the_data", "str64-too_large"])
+def test_offsets_are_validated_for_selected_rows_only(ctx, torch, kind, damage):
+    """Only the rows the selection names are read, so only they are validated (kernels_gather.hip, gather_string): a
+    damaged offset raises BAD_OFFSETS / STRING_TOO_LARGE when its row is selected -- NULL or not, like the flat kernel --
+    and nothing when it is not; the damaged row decodes to 16 zero bytes.  No selected row has an offset outside the
+    payload that the kernel would follow: end < start and end > buf2_len are refused by the kernel's own bound check
+    before any payload byte is read, and an end offset past 4 GB is refused before the payload is touched as well."""
+    rng = np.random.default_rng(4)
+    nrows = 2 * WIN + 100
+    for bad_row in BAD_ROWS:
+        col = _strings(kind, nrows, rng, bad_row)
+        col["name"] = "%s/row%d" % (damage, bad_row)
+        w, r = divmod(bad_row, WIN)
+        flag = _ffi.ST_BAD_OFFSETS
+        if damage == "decreasing":
+            col["buf1"][bad_row + 1] = col["buf1"][bad_row] - 1                  # ends before it starts; the next row starts early, which is legal
+        elif damage == "past_the_data":
+            col["buf2_len"] = int(col["buf1"][bad_row + 1]) - 1                  # this row and every later one end past the data
+        else:
+            col["buf1"][bad_row + 1:] += 2**32                                   # this row and every later one end past 4 GB ...
+            col["buf2_len"] = 2**33                                              # ... of a payload said to be that long: no payload byte of them is read
+            flag = _ffi.ST_STRING_TOO_LARGE
+        with_row = make_sel(nrows, [300, 300, None], rng)
+        if r not in with_row[w]:
+            with_row[w] = np.sort(np.concatenate([with_row[w][:-2], [r], with_row[w][-1:]]))
+        if damage != "decreasing":                                                # rows behind the damaged one are damaged too
+            with_row = [s[s <= r] if i == w else (s if i < w else s[:0]) for i, s in enumerate(with_row)]
+        without = [s[s != r] if i == w else s for i, s in enumerate(with_row)]
+        for sel, want in ((with_row, flag), (without, 0)):
+            got, status = run_plan(ctx, torch, [(col, "s")], {"s": sel})
+            assert check_job(col, sel, got[0]) == want, col["name"]
+            assert status == want, (col["name"], status)
+
+
+def test_gather_tasks_the_plan_refuses(ctx):
+    """ValidateTask; nothing is launched (the addresses are made up)."""
+    ok = dict(param=8, sel=4096, sel_count=8192)
+    da.Plan(ctx, [da.make_task(_ffi.K_COPY, 0, 16, 32, **ok)])
+    for match, kw, kind in (("need sel_count", dict(ok, sel_count=0), _ffi.K_COPY),
+                            ("cannot be decoded through a selection vector", dict(ok, param=1000), _ffi.K_DURATION),
+                            ("cannot be decoded through a selection vector", dict(ok, param=4 | (2 << 8)), _ffi.K_NARROW),
+                            ("cannot be decoded through a selection vector", dict(ok), _ffi.K_STRVIEW),
+                            ("top-level columns", dict(ok, out_aux=64), _ffi.K_COPY),
+                            ("top-level columns", dict(ok, depth=1), _ffi.K_COPY),
+                            ("selection vector misaligned", dict(ok, sel=4098), _ffi.K_COPY),
+                            ("selection vector misaligned", dict(ok, sel_count=8194), _ffi.K_COPY)):
+        with pytest.raises(da.MiError, match=match):
+            da.Plan(ctx, [da.make_task(kind, 10, 16, 32, **kw)])
+
+
+# ------------------------------------------------------------------------------------------------ the scan operator
+N_TABLE = 9000
+
+
+def _table():
+    """A column of every Arrow type the planner decodes with a gatherable kind, each with NULLs, and a row id."""
+    import pyarrow as pa
+    rng = np.random.default_rng(31)
+    n = N_TABLE
+    nul = lambda p=0.15: rng.random(n) < p
+    ints = lambda lo, hi, dt: rng.integers(lo, hi, n).astype(dt)
+    dec = lambda digits, p, s: pa.array([None if x else decimal.Decimal(int(v)).scaleb(-s) for x, v in zip(nul(), rng.integers(
+        -10**digits + 1, 10**digits, n))], pa.decimal128(p, s))
+    words = ["", "a", "twelve bytes", "thirteen byte", "a much longer string than fits inline"]
+    strs = ["%s%d" % (words[int(k)], i) if k else "" for i, k in enumerate(rng.integers(0, len(words), n))]
+    f32 = rng.standard_normal(n).astype(np.float32)
+    f32[:4] = [np.inf, -np.inf, -0.0, np.nan]
+    cols = {
+        "k": pa.array(np.arange(n, dtype=np.int64)),
+        "i8": pa.array(ints(-128, 128, np.int8), mask=nul()), "u8": pa.array(ints(0, 256, np.uint8), mask=nul()),
+        "i16": pa.array(ints(-2**15, 2**15, np.int16), mask=nul()), "i32": pa.array(ints(-1000, 1000, np.int32), mask=nul(0.2)),
+        "i64": pa.array(ints(-2**62, 2**62, np.int64), mask=nul()), "u64": pa.array(ints(0, 2**63, np.uint64), mask=nul()),
+        "f32": pa.array(f32, mask=nul()), "f64": pa.array(rng.standard_normal(n), mask=nul()),
+        "flag": pa.array(rng.random(n) < 0.5, mask=nul(0.3)),
+        "d32": pa.array(ints(-20000, 40000, np.int32), pa.date32(), mask=nul()),
+        "d64": pa.array(ints(-20000, 40000, np.int64) * 86400000, pa.date64(), mask=nul()),
+        "t32s": pa.array(ints(0, 86400, np.int32), pa.time32("s"), mask=nul()),
+        "t32ms": pa.array(ints(0, 86400000, np.int32), pa.time32("ms"), mask=nul()),
+        "t64us": pa.array(ints(0, 86400 * 10**6, np.int64), pa.time64("us"), mask=nul()),
+        "t64ns": pa.array(ints(0, 86400 * 10**9, np.int64), pa.time64("ns"), mask=nul()),
+        "ts_s": pa.array(ints(-2**31, 2**32, np.int64), pa.timestamp("s", tz="UTC"), mask=nul()),
+        "ts_ms": pa.array(ints(-2**41, 2**42, np.int64), pa.timestamp("ms", tz="UTC"), mask=nul()),
+        "ts_us": pa.array(ints(-2**51, 2**52, np.int64), pa.timestamp("us", tz="UTC"), mask=nul()),
+        "ts_ns": pa.array(ints(-2**61, 2**62, np.int64), pa.timestamp("ns", tz="UTC"), mask=nul()),
+        "ts_plain": pa.array(ints(-2**51, 2**52, np.int64), pa.timestamp("ms"), mask=nul()),
+        "dec4": dec(4, 4, 1), "dec9": dec(9, 9, 2), "dec18": dec(18, 18, 0), "dec30": dec(18, 30, 3),
+        "s": pa.array(strs, mask=nul(0.25)), "ls": pa.array(strs[::-1], pa.large_string(), mask=nul(0.25)),
+        "bin": pa.array([s.encode() for s in strs], pa.binary(), mask=nul()),
+        "fsb": pa.array([bytes(r) for r in rng.integers(0, 256, (n, 13), dtype=np.uint8)], pa.binary(13), mask=nul()),
+        "dict": pa.DictionaryArray.from_arrays(pa.array(ints(0, 5, np.int8), mask=nul()), pa.array(words[1:] + ["zz"])),
+    }
+    return pa.table(cols)
+
+
+def _stored(table):
+    """pyarrow's values of every column in the form the Python binding returns: stored integers in DuckDB's unit for
+    temporal and decimal types."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    trunc = lambda c, d: pc.multiply(pc.sign(c), pc.divide(pc.abs(c), d))       # C division, not floor
+    out = []
+    for f in table.schema:
+        c, t = table.column(f.name).combine_chunks(), f.type
+        if pa.types.is_dictionary(t):
+            c = c.cast(t.value_type)
+        elif pa.types.is_date32(t):
+            c = c.cast(pa.int32())
+        elif pa.types.is_date64(t):
+            c = trunc(c.cast(pa.int64()), 86400000)
+        elif pa.types.is_time(t) or pa.types.is_timestamp(t):
+            c = c.cast(pa.int32() if pa.types.is_time32(t) else pa.int64()).cast(pa.int64())
+            plain = pa.types.is_timestamp(t) and t.tz is None                    # stays in its own unit (TIMESTAMP_S / _MS / _NS)
+            c = c if plain else {"s": lambda: pc.multiply(c, 1000000), "ms": lambda: pc.multiply(c, 1000), "us": lambda: c,
+                                 "ns": lambda: trunc(c, 1000)}[t.unit]()
+        vals = c.to_pylist()
+        if pa.types.is_decimal(t):
+            vals = [None if v is None else int(v.scaleb(t.scale)) for v in vals]
+        out.append(canon_python(vals))
+    return out
+
+
+def _write_table(table, path, codec=None):
+    import pyarrow.ipc as ipc
+    opts = ipc.IpcWriteOptions(compression=codec) if codec else None
+    with ipc.new_stream(path, table.schema, options=opts) as w:
+        w.write_table(table, max_chunksize=N_TABLE // 3)
+    return path
+
+
+@pytest.fixture(scope="module")
+def table_file(tmp_path_factory):
+    t = _table()
+    return t, _write_table(t, str(tmp_path_factory.mktemp("gather") / "t.arrows"))
+
+
+def _i32_mask(t, f):
+    col = t.column("i32").combine_chunks()
+    return f(np.asarray(col.fill_null(0))) & ~np.asarray(col.is_null())
+
+
+PREDICATES = {
+    "none_pass": (("i32", "<", -5000), lambda t: _i32_mask(t, lambda v: v < -5000)),
+    "all_pass": (("k", ">=", 0), lambda t: np.ones(N_TABLE, bool)),
+    "one_percent": (("i32", "<", -975), lambda t: _i32_mask(t, lambda v: v < -975)),
+    "half": (("i32", ">=", 0), lambda t: _i32_mask(t, lambda v: v >= 0)),
+    # record batch 1 holds rows 3000 .. 5999: its first window passes whole, every other window of the file is empty
+    "one_full_window": (("and", ("k", ">=", 3000), ("k", "<", 3000 + WIN)), lambda t: (np.arange(N_TABLE) >= 3000) & (np.arange(N_TABLE) < 3000 + WIN)),
+}
+
+
+def _scan_equals_pyarrow(con, t, path, name):
+    import pyarrow as pa
+    expr, mask_of = PREDICATES[name]
+    mask = mask_of(t)
+    names = t.schema.names
+    flat, compact = (canon_python(con.read_arrow(path, filter_compact=c, accept_dictionaries=True).project(names).filter(expr).fetch_columns())
+                     for c in (False, True))
+    want = _stored(t.filter(pa.array(mask)))
+    assert compact[0] == np.nonzero(mask)[0].tolist()
+    for nm, c, f, w in zip(names, compact, flat, want):
+        assert c == f, nm
+        assert c == w, nm
+
+
+@pytest.mark.parametrize("name", list(PREDICATES))
+def test_compacted_scan_equals_the_selection_vector_scan_for_every_type(con, table_file, name):
+    """read_arrow(filter_compact=True) returns, column by column, what filter_compact=False returns for the same filter,
+    and both return pyarrow's filtered table; the row ids are numpy's."""
+    t, path = table_file
+    _scan_equals_pyarrow(con, t, path, name)
+
+
+@pytest.mark.parametrize("codec", ["lz4", "zstd"])
+def test_compacted_scan_of_a_compressed_body(con, table_file, tmp_path, codec):
+    """The gather kernel reads a body that was decompressed in HBM."""
+    t, _ = table_file
+    _scan_equals_pyarrow(con, t, _write_table(t, str(tmp_path / "z.arrows"), codec), "half")

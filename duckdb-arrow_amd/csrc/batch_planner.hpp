@@ -16,7 +16,7 @@
 #include <utility>
 #include <vector>
 
-#include "ipc_stream_reader.hpp"
+#include "batch_slice.hpp"
 
 namespace miarrow {
 

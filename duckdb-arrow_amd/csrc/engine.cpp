@@ -1,7 +1,7 @@
 // engine.cpp -- device context + transcode plans.  See engine.hpp.
 #include "engine.hpp"
 
-#include "ipc_stream_reader.hpp"
+#include "io_pool.hpp"
 
 #include <hip/hip_runtime.h>
 

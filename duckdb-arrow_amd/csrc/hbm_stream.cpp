@@ -13,6 +13,7 @@
 
 #include "batch_planner.hpp"
 #include "engine.hpp"
+#include "ipc_stream_reader.hpp"
 
 namespace miarrow {
 

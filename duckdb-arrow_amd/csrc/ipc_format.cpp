@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <unordered_map>
 
 #include "flatbuf.hpp"
 
@@ -762,6 +763,30 @@ ArrowField FieldFromDuckType(const std::string& name, const std::string& duck_ty
     return f;
   }
   throw NotImplementedException("Unsupported DuckDB type for Arrow export on this path: " + duck_type);
+}
+
+static std::string Lower(std::string s) {
+  for (auto& c : s) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+  return s;
+}
+
+void DeduplicateColumns(std::vector<std::string>& names) {
+  std::unordered_map<std::string, idx_t> seen;
+  for (auto& name : names) {
+    std::string low = Lower(name);
+    auto it = seen.find(low);
+    if (it == seen.end()) {
+      seen[low] = 1;
+      continue;
+    }
+    std::string candidate = name + "_" + std::to_string(seen[low]);
+    while (seen.find(Lower(candidate)) != seen.end()) {
+      seen[low]++;
+      candidate = name + "_" + std::to_string(seen[low]);
+    }
+    name = candidate;
+    seen[Lower(candidate)] = 1;
+  }
 }
 
 }  // namespace miarrow

@@ -163,6 +163,11 @@ std::vector<uint8_t> EncodeRecordBatchMessage(int64_t length, const std::vector<
 // exports it (arrow_stream_writer.cpp:22-24). Throws NotImplementedException for types outside the path.
 ArrowField FieldFromDuckType(const std::string& name, const std::string& duck_type);
 
+//! Same observable behaviour as DuckDB's QueryResult::DeduplicateColumns (used at base_stream_reader.cpp:177 and
+//! arrow_file_scan.cpp:19): case-insensitive; a repeated name gets "_<n>" appended, n counting repetitions and
+//! skipping suffixes that are already taken.
+void DeduplicateColumns(std::vector<std::string>& names);
+
 void FillCField(const ArrowField& f, int32_t flat_index, mi_field* out);
 
 }  // namespace miarrow

@@ -7,6 +7,8 @@
 // What differs by design: metadata is parsed by ipc_format.cpp instead of nanoarrow, GetNextBatch yields a flat
 // buffer table (DecodedBatch) instead of an ArrowArray, and the file reader can read message bodies straight into
 // caller-provided (pinned) memory so the body is copied exactly once on its way to HBM.
+// The units around it: io_pool (threads the bodies are read and decompressed on), host_codec (libzstd / liblz4),
+// frame_walk (tables for the GPU decompressors), batch_slice (everything the metadata says about a body: DecodedBatch).
 #pragma once
 
 #include <cstdint>
@@ -15,26 +17,9 @@
 #include <string>
 #include <vector>
 
-#include "ipc_format.hpp"
-#include "zstd_format.hpp"
+#include "batch_slice.hpp"
 
 namespace miarrow {
-
-//! Runs fn(i), i in [0, n), on the process-wide I/O pool (MI_IO_THREADS, default 8) + the calling thread; rethrows the
-//! first failure.  Callers on different threads share the pool.
-void ParallelFor(int n, const std::function<void(int)>& fn);
-int IoThreads();
-//! Grows the pool to at least n threads (bounded by the host's cores); multi-device scans ask for 8 per device
-void EnsureIoThreads(int n);
-// NUMA locality of the host side (engine.hpp, Context::BindThisThread).  BindThisThreadToNode pins the calling thread to
-// `cpus` (within what it may use) and makes its allocations prefer `node`; from then on the tasks it gives the I/O pool
-// (parallel preads of a body, host decompression) run under the same binding: a pool worker adopts the binding of the batch
-// of tasks it takes.  PreferNode(node) / PreferNode(-1): only the allocation policy of the calling thread.
-void BindThisThreadToNode(int node, const std::vector<int>& cpus);
-void PreferNode(int node);
-
-
-
 
 struct ArrowIpcMessagePrefix {  // base_stream_reader.hpp:39-42
   uint32_t continuation_token;
@@ -46,67 +31,6 @@ struct ArrowIPCBuffer {
   ArrowIPCBuffer(uint64_t ptr_p, uint64_t size_p) : ptr(ptr_p), size(size_p) {}
   uint64_t ptr;
   uint64_t size;
-};
-
-//! One field node of a record batch (depth-first), with every buffer it owns.
-struct DecodedNode {
-  const ArrowField* field = nullptr;
-  int32_t parent = -1;
-  int32_t depth = 0;
-  int64_t length = 0;
-  int64_t null_count = 0;
-  bool value_only = false;               // dictionary batch: decode with the value type, not as indices
-  std::vector<mi_buffer_span> spans;     // validity, buffer 1, buffer 2, ... (views: + variadic data buffers)
-  std::vector<int32_t> children;         // indices into DecodedBatch::nodes
-};
-
-//! A record-batch body whose LZ4_FRAME / ZSTD buffers are still compressed (IPCStreamReader::SetDeferLz4): the frames were
-//! walked on the host (frame header, block headers), the bytes are decompressed in HBM by the K8 kernels (kernels_lz4.hip).
-struct DeferredLz4Body {
-  struct Buffer {
-    int64_t comp_off = 0, comp_len = 0;   // raw: the bytes themselves; else the frame, inside the compressed body
-    int64_t out_off = 0, out_len = 0;     // place in the decompressed body
-    bool raw = false;                     // stored uncompressed (length prefix -1)
-    uint32_t first_block = 0, n_blocks = 0, block_max = 0;
-  };
-  struct Block {
-    uint32_t comp_off = 0, comp_size = 0, buffer = 0, stored = 0;
-    uint32_t seq_cap = 0;                 // ZSTD: sequence descriptors the block needs (LZ4: derived from comp_size)
-  };
-  const uint8_t* comp = nullptr;          // the compressed body as it was read (kept alive by DecodedBatch::owner)
-  int64_t comp_size = 0;
-  std::vector<Buffer> buffers;            // the needed, non-empty buffers of the message
-  std::vector<Block> blocks;              // every block of every non-raw buffer, buffer by buffer
-  int32_t codec = 0;                      // 0 LZ4_FRAME, 1 ZSTD
-  std::vector<zstd::BlockInfo> zblocks;   // ZSTD: one per entry of `blocks`
-  uint32_t literal_scratch = 0;           // ZSTD: bytes of decoded literals (BlockInfo::lit_pos of non-raw literals counts from 0)
-};
-//! Walks one ZSTD frame (one IPC buffer) from its headers.  false = a frame the device path does not take (dictionary,
-//! content checksum, several frames, anything malformed): the host decompressor handles it and reports what is wrong.
-bool WalkZstdFrame(const uint8_t* body, int64_t frame_off, int64_t frame_len, uint32_t buffer_index, int64_t declared_len,
-                   DeferredLz4Body::Buffer* buf, std::vector<DeferredLz4Body::Block>* blocks, std::vector<zstd::BlockInfo>* infos,
-                   uint32_t* literal_scratch);
-
-//! What GetNextBatch produces: the buffers of every (projected) top-level column of one message.
-struct DecodedBatch {
-  int64_t length = 0;
-  const uint8_t* body = nullptr;
-  int64_t body_size = 0;
-  int64_t body_file_offset = 0;
-  bool is_dictionary = false;
-  int64_t dict_id = -1;
-  bool is_delta = false;
-  int32_t compression = -1;
-  std::vector<int32_t> column_field;     // top-level field index per output column
-  std::vector<int64_t> null_count;       // per output column
-  std::vector<int64_t> column_length;    // per output column (== length for top-level fields)
-  std::vector<mi_buffer_span> buffers;   // 3 per output column: validity, buf1, buf2
-  std::vector<DecodedNode> nodes;        // the projected columns with their descendants, depth-first
-  std::vector<int32_t> column_node;      // per output column: its node
-  //! Keeps the body alive (file reader: shared ownership like shared_ptr<AllocatedData>, base_stream_reader.cpp:286-294)
-  std::shared_ptr<void> owner;
-  //! set: `body` is NULL, body_size and every span describe the DECOMPRESSED layout, the bytes are still compressed
-  std::shared_ptr<const DeferredLz4Body> deferred;
 };
 
 struct BatchIndexEntry {
@@ -132,7 +56,7 @@ class IPCStreamReader {
   bool GetNextBatch(DecodedBatch* out, bool accept_dictionaries = false, bool skip_record_batch_body = false);
   //! Sets the projection pushdown for this reader
   void SetColumnProjection(const std::vector<std::string>& column_names);
-  bool HasProjection() const { return !projected_fields.empty(); }
+  bool HasProjection() const { return !projected_columns.empty(); }
   //! Drops the reader's own reference to the body of the message it returned last (the DecodedBatch keeps its own);
   //! a caller that recycles body buffers needs this when it stops pulling from a reader
   void ReleaseCurrentBody() {
@@ -141,11 +65,6 @@ class IPCStreamReader {
     cur_ptr = nullptr;
     cur_size = 0;
   }
-  //! Byte ranges of a record-batch body that hold the buffers of the projected columns (merged when closer than
-  //! `gap`); empty = everything (no projection, compressed body, or malformed metadata: the full validation decides).
-  std::vector<char> NeededBuffers(const RecordBatchMeta& meta) const;
-  std::vector<std::pair<int64_t, int64_t>> ProjectedBodyRanges(const RecordBatchMeta& meta, int64_t body_length, int64_t gap) const;
-  const std::vector<int64_t>& ProjectedFlatFields() const { return projected_fields; }
 
   MessageType ReadNextMessage(std::vector<MessageType> expected_types, bool end_of_stream_ok = true);
   virtual MessageType ReadNextMessage() = 0;
@@ -163,7 +82,6 @@ class IPCStreamReader {
   //! the same for ZSTD record batches (frames with a dictionary id or a content checksum stay with the host library)
   void SetDeferZstd(bool on) { defer_zstd = on; }
 
-  static int64_t CountFields(const ArrowField& field) { return field.CountFields(); }
   static constexpr uint32_t kContinuationToken = 0xFFFFFFFF;
 
  protected:
@@ -177,24 +95,21 @@ class IPCStreamReader {
 
   //! Parses the current header into `message` (ENODATA == metadata_size 0 => returns false)
   bool ParseHeader(const uint8_t* header_with_prefix, idx_t size);
-  //! Slices cur_ptr/cur_size into per-column buffers, with the size checks of NANOARROW_VALIDATION_LEVEL_FULL that do
-  //! not need the data (offset monotonicity is checked on the device by the string kernel)
-  void SliceBatch(const RecordBatchMeta& meta, DecodedBatch* out);
-  //! Replaces cur_ptr/cur_size with the decompressed body and rewrites meta->buffers (ZSTD, per buffer; the CPU step the
-  //! reference performs in DuckDBDecompressZstd, base_stream_reader.cpp:11-32)
-  void DecompressBody(RecordBatchMeta* meta);
-  bool defer_lz4 = false, defer_zstd = false;
-  std::shared_ptr<const DeferredLz4Body> cur_deferred;   // set by DecompressBody when the current body stays compressed
-  //! Big-endian stream: every multi-byte number of the body is swapped in place (after decompression), so the rest of the
-  //! path sees little-endian buffers (what nanoarrow's decoder does for the reference, base_stream_reader.cpp:68-69)
+  //! Rewrites meta->buffers to the decompressed layout.  Either the body stays compressed and the frame / block tables
+  //! are returned (SetDeferLz4 / SetDeferZstd; cur_size becomes the decompressed size, cur_ptr stays), or cur_ptr/cur_size
+  //! become the body decompressed on the host (per buffer; the CPU step the reference performs in DuckDBDecompressZstd,
+  //! base_stream_reader.cpp:11-32) and nullptr is returned
+  std::shared_ptr<const DeferredBody> DecompressBody(RecordBatchMeta* meta);
+  //! Big-endian stream: refuses run-end encoded columns, then swaps the body in place (after decompression); a
+  //! caller-owned body is copied first
   void SwapBodyEndianness(const RecordBatchMeta& meta);
+  bool defer_lz4 = false, defer_zstd = false;
   std::shared_ptr<void> compressed_owner;
 
   MessageHeader message;               // the decoder's message_type / body_size_bytes
   const uint8_t* message_meta = nullptr;  // flatbuffer of the current message
   int64_t message_meta_len = 0;
 
-  std::vector<int64_t> projected_fields;   // flattened field index per projected column
   std::vector<int32_t> projected_columns;  // top-level field index per projected column
   ArrowSchemaModel projected_schema;
   ArrowSchemaModel base_schema;
@@ -222,13 +137,9 @@ class IPCFileStreamReader : public IPCStreamReader {
 
   MessageType ReadNextMessage() override;
   double GetProgress() override;
-  void PopulateNames(std::vector<std::string>& names);
   const std::vector<BatchIndexEntry>& BuildIndex() override;
   //! Positions the reader on a message found by BuildIndex (record-batch sharding)
   void Seek(int64_t prefix_offset);
-  int64_t FileSize() const { return file_size; }
-  //! true when BuildIndex() came from the IPC file footer instead of a header walk
-  bool IndexFromFooterUsed() const { return index_from_footer; }
 
  protected:
   const uint8_t* ReadData(uint8_t* ptr, idx_t size);
@@ -239,7 +150,6 @@ class IPCFileStreamReader : public IPCStreamReader {
   bool IndexFromFooter();
 
  private:
-  bool index_from_footer = false;
   int fd = -1;
   std::string path;
   int64_t file_size = 0;

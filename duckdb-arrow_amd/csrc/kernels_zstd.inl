@@ -2,7 +2,7 @@
 //
 // A ZSTD block is entropy-coded (zstd_format.hpp): its literals are Huffman streams, its sequences one FSE bitstream -- both
 // serial by construction, a symbol's length is known only once it is decoded.  What is parallel is the BLOCK: the host walk
-// (WalkZstdFrame) finds every block of every buffer from the headers and names, for tables a block inherits, the earlier block
+// (WalkZstdFrame, frame_walk.cpp) finds every block of every buffer from the headers and names, for tables a block inherits, the earlier block
 // whose bytes describe them, so no block waits for another:
 //   zstd_entropy   one workgroup of two waves per block.  Wave 0 builds the Huffman table and decodes the 4 literal streams on
 //                  4 lanes into the literal scratch (behind the compressed body, same allocation); wave 1 builds the three FSE

@@ -1,5 +1,6 @@
 // scan_operator.cpp -- see scan_operator.hpp.
 #include "scan_operator.hpp"
+#include "io_pool.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -15,7 +16,6 @@
 namespace miarrow {
 
 int WrapC(const std::function<void()>& f);  // c_api.cpp
-void EnsureIoThreads(int n);                // ipc_stream_reader.cpp
 
 namespace {
 constexpr size_t kAlign = 256;
@@ -664,7 +664,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
 void ArrowScan::EnqueueLz4(Slot& s) {
   const int64_t t_k8 = trace ? TraceNow() : 0;
   const DecodedBatch& b = s.batch;
-  const DeferredLz4Body& d = *b.deferred;
+  const DeferredBody& d = *b.deferred;
   if (!s.lz4_stream) {
     // the slots share kLz4Streams streams (slot i uses stream i mod 3): the K8 kernels of neighbouring record batches overlap
     // -- the token walk is latency-bound and leaves the chip idle -- without every slot holding a hardware queue of its own

@@ -33,8 +33,6 @@
 
 namespace miarrow {
 
-void DeduplicateColumns(std::vector<std::string>& names);  // ipc_stream_reader.cpp
-
 struct ScanColumn {
   std::string name;
   ArrowField field;           // arrow field of the first file that has it

@@ -1,6 +1,5 @@
 // writer.cpp -- see writer.hpp.
 #include "writer.hpp"
-#include "ipc_stream_reader.hpp"
 #include "writer_internal.hpp"
 #include "writer_plan.hpp"
 

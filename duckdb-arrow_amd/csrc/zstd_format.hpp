@@ -27,7 +27,7 @@ constexpr uint32_t kBlockMax = 128u << 10;          // Block_Maximum_Size
 constexpr uint32_t kHufMaxBits = 11;                // literals: Max_Number_of_Bits
 constexpr uint32_t kRepMarker = 0x80000000u;        // a sequence offset that names a repeat offset: kRepMarker | 0..3
 
-// One block of a frame as the host walk (WalkZstdFrame, ipc_stream_reader.cpp) finds it from the headers alone: the block
+// One block of a frame as the host walk (WalkZstdFrame, frame_walk.cpp) finds it from the headers alone: the block
 // header, the literals section header, the sequence count and the three table modes.  Tables a block inherits (Huffman
 // "treeless", FSE "repeat") are named by the index of the earlier block whose bytes describe them, so every block can be
 // decoded without waiting for another.

@@ -2,10 +2,17 @@
 tests/golden/make_golden.py computes with pyarrow), used for both the oracle and the HIP path."""
 import hashlib
 import json
+import os
 
 import numpy as np
 
 from oracle import pyoracle as po
+
+# The host sources of the IPC reader (duckdb-arrow_amd/csrc), for the g++ builds of tests/sanitize/*.cpp: metadata decode,
+# the I/O pool, libzstd / liblz4, the frame walks, the batch slicing and the reader classes.  Link with -ldl -lpthread.
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "duckdb-arrow_amd", "csrc")
+READER_HOST_SOURCES = [os.path.join(_CSRC, name + ".cpp")
+                       for name in ("ipc_format", "io_pool", "host_codec", "frame_walk", "batch_slice", "ipc_stream_reader")]
 
 # Arrow type ids (Schema.fbs Type union)
 T_INT, T_FLOAT, T_BINARY, T_UTF8, T_BOOL, T_DECIMAL, T_DATE, T_TIME, T_TIMESTAMP = 2, 3, 4, 5, 6, 7, 8, 9, 10

@@ -1,8 +1,10 @@
 // Host IPC reader under AddressSanitizer + UBSan (CPU build only: GPU sanitizers are not available on the pool).
-// Builds ipc_format.cpp + ipc_stream_reader.cpp with g++ (no HIP involved), then mutates the given fixture files the way
-// tests/test_reader_fuzz.py does and drains them through IPCBufferStreamReader with and without projections.
+// Builds the reader's host sources (tests/helpers.py: READER_HOST_SOURCES) with g++ (no HIP involved), then mutates the
+// given fixture files the way tests/test_reader_fuzz.py does and drains them through IPCBufferStreamReader with and without
+// projections.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -I include
-//       tests/sanitize/fuzz_reader.cpp duckdb-arrow_amd/csrc/ipc_format.cpp duckdb-arrow_amd/csrc/ipc_stream_reader.cpp
+//       tests/sanitize/fuzz_reader.cpp duckdb-arrow_amd/csrc/{ipc_format,io_pool,host_codec,frame_walk,batch_slice}.cpp
+//       duckdb-arrow_amd/csrc/{ipc_stream_reader,c_stream}.cpp
 //       -ldl -lpthread -o fuzz_reader && ./fuzz_reader ITERATIONS file...
 #include <cstdint>
 #include <cstdio>
@@ -74,7 +76,7 @@ static int DrainStream(const std::vector<uint8_t>& buf) {
 // What the K8 kernels compute from a deferred body (DecodedBatch::deferred: LZ4 frames still compressed, block tables built
 // by the reader), restated serially with every access checked: the tables are the host half of the GPU decompressor.
 static std::vector<uint8_t> DecodeDeferred(const DecodedBatch& b) {
-  const DeferredLz4Body& d = *b.deferred;
+  const DeferredBody& d = *b.deferred;
   std::vector<uint8_t> out(static_cast<size_t>(b.body_size), 0);
   auto need = [](bool ok) { if (!ok) throw std::runtime_error("deferred LZ4 body is malformed"); };
   for (auto& f : d.buffers) {
@@ -193,7 +195,7 @@ static int Drain(const std::vector<uint8_t>& buf, bool project, std::mt19937_64&
       const uint8_t* body = b.body;
       if (b.deferred && b.deferred->codec == 1) {
         // what the kernels rely on: every block, section and table source the walk names lies inside the body / the table
-        const DeferredLz4Body& d = *b.deferred;
+        const DeferredBody& d = *b.deferred;
         if (d.zblocks.size() != d.blocks.size()) std::abort();
         for (size_t i = 0; i < d.zblocks.size(); i++) {
           const zstd::BlockInfo& z = d.zblocks[i];

@@ -2,7 +2,7 @@
 // never shipped).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I include tests/sanitize/lz4_encode_check.cpp
-//       duckdb-arrow_amd/csrc/{writer_plan,ipc_format,ipc_stream_reader}.cpp -ldl -lpthread -o lz4_encode_check
+//       duckdb-arrow_amd/csrc/{writer_plan,ipc_format,io_pool,host_codec,frame_walk,batch_slice,ipc_stream_reader}.cpp -ldl -lpthread -o lz4_encode_check
 //
 // Runs the serial restatement of the compress kernel (lz4_encode_format.hpp: CompressBlockSerial, CompressBufferSerial)
 // and the body layout (writer_plan.cpp: BlocksOfBody, LayOutCompressedBody) over buffers of every length at which the

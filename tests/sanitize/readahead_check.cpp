@@ -2,7 +2,7 @@
 // ThreadSanitizer (test infrastructure, never shipped).  Pinned memory is plain malloc behind the allocation hook.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -I include tests/sanitize/readahead_check.cpp
-//       duckdb-arrow_amd/csrc/{scan_readahead,ipc_stream_reader,ipc_format}.cpp -ldl -lpthread -o readahead_check
+//       duckdb-arrow_amd/csrc/{scan_readahead,ipc_format,io_pool,host_codec,frame_walk,batch_slice,ipc_stream_reader}.cpp -ldl -lpthread -o readahead_check
 //   readahead_check [--dict] <stream file> ...
 //
 // Every file is read once on this thread with IPCFileStreamReader; then, for 1 to 4 producers (MI_SCAN_PRODUCERS) and for

@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "../../duckdb-arrow_amd/csrc/ipc_stream_reader.hpp"
+#include "../../duckdb-arrow_amd/csrc/frame_walk.hpp"
 #include "../../duckdb-arrow_amd/csrc/zstd_format.hpp"
 
 using namespace miarrow;
@@ -31,8 +31,8 @@ static bool DecodeFrame(const std::vector<uint8_t>& frame, size_t expect_size, s
   std::vector<uint64_t> arena((frame.size() + 64 + 7) / 8 + 1, 0);
   uint8_t* comp = reinterpret_cast<uint8_t*>(arena.data());
   std::memcpy(comp, frame.data(), frame.size());
-  DeferredLz4Body::Buffer buf;
-  std::vector<DeferredLz4Body::Block> blocks;
+  DeferredBody::Buffer buf;
+  std::vector<DeferredBody::Block> blocks;
   std::vector<zstd::BlockInfo> infos;
   uint32_t scratch_bytes = 0;
   if (!WalkZstdFrame(comp, 0, static_cast<int64_t>(frame.size()), 0, static_cast<int64_t>(expect_size), &buf, &blocks, &infos, &scratch_bytes)) {

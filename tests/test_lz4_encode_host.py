@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from duckdb_arrow_amd import _ffi
+from helpers import READER_HOST_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,8 +26,7 @@ def test_restatement_and_body_layout_under_asan_and_ubsan(tmp_path):
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
          "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "sanitize", "lz4_encode_check.cpp"),
-         os.path.join(csrc, "writer_plan.cpp"), os.path.join(csrc, "ipc_format.cpp"), os.path.join(csrc, "ipc_stream_reader.cpp"),
-         "-ldl", "-lpthread", "-o", exe], capture_output=True, text=True)
+         os.path.join(csrc, "writer_plan.cpp")] + READER_HOST_SOURCES + ["-ldl", "-lpthread", "-o", exe], capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
         pytest.skip("sanitizer runtime not installed")
     assert build.returncode == 0, build.stderr[-2000:]

@@ -1,11 +1,14 @@
 """AddressSanitizer + UBSan over the host IPC reader (CPU build only; GPU sanitizers are not available on the pool):
-tests/sanitize/fuzz_reader.cpp is built with g++ from the two host sources alone (no HIP) and drains mutated fixtures,
+tests/sanitize/fuzz_reader.cpp is built with g++ from the reader's host sources alone (no HIP) and drains mutated fixtures,
 touching every byte of every buffer span the reader hands out."""
 import os
+import re
 import shutil
 import subprocess
 
 import pytest
+
+from helpers import READER_HOST_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -16,10 +19,8 @@ def test_host_reader_is_clean_under_asan_and_ubsan(tmp_path, golden_dir):
     exe = str(tmp_path / "fuzz_reader")
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-         "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "sanitize", "fuzz_reader.cpp"),
-         os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "ipc_format.cpp"),
-         os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "ipc_stream_reader.cpp"),
-         os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "c_stream.cpp"), "-ldl", "-lpthread", "-o", exe],
+         "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "sanitize", "fuzz_reader.cpp")] + READER_HOST_SOURCES +
+        [os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "c_stream.cpp"), "-ldl", "-lpthread", "-o", exe],
         capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
         pytest.skip("sanitizer runtime not installed")
@@ -71,8 +72,7 @@ def test_zstd_stages_on_the_cpu(tmp_path):
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
          "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "sanitize", "zstd_check.cpp"),
-         os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "ipc_format.cpp"),
-         os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "ipc_stream_reader.cpp"), "-ldl", "-lpthread", "-o", exe],
+         os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "frame_walk.cpp"), "-o", exe],
         capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
         pytest.skip("sanitizer runtime not installed")
@@ -126,8 +126,8 @@ def test_readahead_orders_and_shards_under_tsan(tmp_path):
     exe = str(tmp_path / "readahead_check")
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I", os.path.join(ROOT, "include"),
-         os.path.join(ROOT, "tests", "sanitize", "readahead_check.cpp"), os.path.join(csrc, "scan_readahead.cpp"),
-         os.path.join(csrc, "ipc_stream_reader.cpp"), os.path.join(csrc, "ipc_format.cpp"), "-ldl", "-lpthread", "-o", exe],
+         os.path.join(ROOT, "tests", "sanitize", "readahead_check.cpp"), os.path.join(csrc, "scan_readahead.cpp")] + READER_HOST_SOURCES +
+        ["-ldl", "-lpthread", "-o", exe],
         capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
         pytest.skip("sanitizer runtime not installed")
@@ -183,3 +183,30 @@ def test_writer_plan_under_asan_ubsan_and_tsan(tmp_path):
         assert run.returncode == 0, (name, run.stdout[-1000:], run.stderr[-3000:])
         assert " 0 failed" in run.stdout and "FAILED" not in run.stderr, (name, run.stdout, run.stderr[-3000:])
         assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, (name, run.stderr[-3000:])
+
+
+def test_io_pool_under_tsan_and_asan_ubsan(tmp_path):
+    """The process-wide I/O pool and the NUMA binding (duckdb-arrow_amd/csrc/io_pool.cpp) serve every scan, every device and
+    the host decompressors; tests/sanitize/io_pool_check.cpp runs them from that one source, once under TSan and once under
+    ASan + UBSan: the serial path, six callers at once on four threads, a task that throws, a nested call, EnsureIoThreads
+    against the CPU budget of this process, and BindThisThreadToNode / PreferNode (that they return and the pool still works,
+    nothing about placement)."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    for name, flags in (("tsan", ["-fsanitize=thread"]), ("asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])):
+        exe = str(tmp_path / ("io_pool_check_" + name))
+        build = subprocess.run(
+            ["g++", "-std=c++17", "-O1", "-g"] + flags + [os.path.join(ROOT, "tests", "sanitize", "io_pool_check.cpp"),
+             os.path.join(ROOT, "duckdb-arrow_amd", "csrc", "io_pool.cpp"), "-lpthread", "-o", exe],
+            capture_output=True, text=True)
+        if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
+            pytest.skip("sanitizer runtime not installed")
+        assert build.returncode == 0, build.stderr[-2000:]
+        # the pool reads MI_IO_THREADS once, when it is first used: one process per setting
+        for threads, case in (("1", "serial"), ("4", "pool")):
+            run = subprocess.run([exe, case], capture_output=True, text=True, timeout=300,
+                                 env=dict(os.environ, MI_IO_THREADS=threads, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+                                          TSAN_OPTIONS="halt_on_error=0"))
+            assert run.returncode == 0, (name, case, run.stdout[-1000:], run.stderr[-3000:])
+            assert re.search(r"^\d+ checks, 0 failed$", run.stdout, re.M), (name, case, run.stdout, run.stderr[-3000:])
+            assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, (name, case, run.stderr[-3000:])

@@ -18,6 +18,7 @@ bool WalkLz4Frame(const uint8_t* body, int64_t frame_off, int64_t frame_len, uin
   const int bsid = (bd >> 4) & 7;
   if (bsid < 4 || (bd & 0x8F)) return false;
   buf->block_max = 1u << (8 + 2 * bsid);   // 4: 64 KiB, 5: 256 KiB, 6: 1 MiB, 7: 4 MiB
+  buf->independent = (flg & 0x20) != 0;    // block independence: liblz4 decodes every block without the ones before it
   at = 6 + (content_size ? 8 : 0) + 1;     // + header checksum
   if (at > frame_len) return false;
   buf->first_block = static_cast<uint32_t>(blocks->size());

@@ -18,6 +18,7 @@ struct DeferredBody {
     int64_t out_off = 0, out_len = 0;     // place in the decompressed body
     bool raw = false;                     // stored uncompressed (length prefix -1)
     uint32_t first_block = 0, n_blocks = 0, block_max = 0;
+    bool independent = false;             // LZ4: FLG bit 0x20, a match may not reach in front of its own block
   };
   struct Block {
     uint32_t comp_off = 0, comp_size = 0, buffer = 0, stored = 0;

@@ -73,7 +73,8 @@ struct Lz4BlockDev {
 struct Lz4BufferDev {
   uint64_t out_off, out_len;      // where the buffer lies in the decompressed body, and its declared length
   uint32_t first_block, n_blocks;
-  uint32_t block_max, _pad;       // the frame's maximum block size (BD byte)
+  uint32_t block_max;             // the frame's maximum block size (BD byte)
+  uint32_t independent;           // LZ4 FLG bit 0x20: matches stay inside their block (linked blocks: inside the buffer)
 };
 struct Lz4Args {
   const uint8_t* comp;            // compressed body (device)

@@ -632,7 +632,9 @@ __global__ __launch_bounds__(kBlockThreads) void k8_expand_local(Lz4Args a) {
   const uint32_t bi = chunk_block(a, w);
   const Lz4BlockDev b = a.blocks[bi];
   const uint64_t base = a.block_out_base[bi];       // offset of the block in the decompressed body
-  const uint64_t buffer_lo = a.buffers[b.buffer].out_off;
+  // the first byte a match may copy from: the buffer's, or with independent blocks (LZ4 FLG bit 0x20) the block's own --
+  // liblz4 decodes such a block without the ones before it and rejects a match that reaches in front of it
+  const uint64_t match_lo = a.buffers[b.buffer].independent ? base : a.buffers[b.buffer].out_off;
   const uint32_t n_out = a.block_out_size[bi];
   const uint32_t c0 = (w - a.chunk_base[bi]) * kChunkBytes;
   const uint32_t c1 = c0 + kChunkBytes < n_out ? c0 + kChunkBytes : n_out;
@@ -698,7 +700,7 @@ __global__ __launch_bounds__(kBlockThreads) void k8_expand_local(Lz4Args a) {
   // the words of output bytes [from, to) of sequence d (its first byte is output byte o0 of the block), step `stride`
   auto write_words = [&](const u32x4& d, uint32_t offset, uint32_t o0, uint32_t from, uint32_t to, uint32_t stride) {
     const uint64_t m_at = base + o0 + d.z;   // position of the match's first byte
-    const bool bad_offset = offset == 0 || offset > m_at - buffer_lo;   // reaches in front of the buffer: not a frame an encoder writes
+    const bool bad_offset = offset == 0 || offset > m_at - match_lo;   // reaches in front of the buffer (the block): not a frame an encoder writes
     for (uint32_t p = from; p < to; p += stride) {
       const uint32_t r = p - o0;
       uint32_t word;

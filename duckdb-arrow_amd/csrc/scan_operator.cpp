@@ -740,7 +740,7 @@ void ArrowScan::EnqueueLz4(Slot& s) {
     hf[i].first_block = f.first_block;
     hf[i].n_blocks = f.raw ? 0 : f.n_blocks;
     hf[i].block_max = f.block_max;
-    hf[i]._pad = 0;
+    hf[i].independent = f.independent ? 1u : 0u;
     if (!f.raw) {
       max_len = std::max<uint64_t>(max_len, static_cast<uint64_t>(f.out_len));
       max_blocks = std::max<uint32_t>(max_blocks, f.n_blocks);

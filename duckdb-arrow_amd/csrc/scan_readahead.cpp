@@ -144,7 +144,9 @@ void ReadAhead::ProducerLoop(int p) {
             std::unique_lock<std::mutex> lk(mu);
             cv.wait(lk, [&] { return stop || producer_error || sources[si].prepared; });
             if (stop) return;
-            if (producer_error) std::rethrow_exception(producer_error);   // producer 0 could not prepare the file: same error here
+            // producer 0 could not prepare the file: same error here.  A file it did prepare is still read: the error belongs
+            // to a later one, and this producer's batches in front of it are due first
+            if (!sources[si].prepared) std::rethrow_exception(producer_error);
             wanted = sources[si].wanted;
           }
           mine[si] = std::make_unique<IPCFileStreamReader>(sources[si].path);

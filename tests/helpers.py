@@ -178,12 +178,13 @@ def pyarrow_columns(table):
 
 
 # ------------------------------------------------------------------------------------------ raw (-1) compressed buffers
-def rewrite_buffers_raw(stream_bytes, pick):
-    """A compressed IPC stream with some of its buffers stored RAW: length prefix -1 followed by the uncompressed bytes, what
-    Arrow C++ (IpcWriteOptions::min_space_savings), arrow-rs and Arrow Java write for incompressible buffers.  pyarrow's
-    Python writer never emits them, so the stream is rewritten here: bodies re-laid out, RecordBatch.buffers and
-    Message.bodyLength patched in place in the flatbuffer (same metadata size).  pick(batch_index, buffer_index, length)
-    chooses the buffers.  Returns the new stream as bytes."""
+def rewrite_buffers(stream_bytes, encode, prefix=None, select=None):
+    """A compressed IPC stream with some of its buffers' frames replaced: bodies re-laid out, RecordBatch.buffers and
+    Message.bodyLength patched in place in the flatbuffer (same metadata size).  encode(batch_index, buffer_index,
+    uncompressed_bytes) is asked about every non-empty buffer: the frame bytes to write behind the buffer's unchanged 8-byte
+    length prefix, or None to keep the buffer as it is.  `prefix`: a length prefix to write in front of the replaced
+    buffers instead; select(batch_index, buffer_index, length in the stream): the buffers `encode` is asked about at all
+    (default: every one).  Returns the new stream as bytes."""
     import struct
     import pyarrow as pa
     a = np.frombuffer(stream_bytes, dtype=np.uint8)
@@ -204,10 +205,12 @@ def rewrite_buffers_raw(stream_bytes, pick):
         new_body, new_bufs = bytearray(), []
         for k, (off, ln) in enumerate(rb["buffers"]):
             piece = body[off: off + ln]
-            if ln > 8 and pick(bi, k, ln):
+            if ln > 8 and (select is None or select(bi, k, ln)):
                 (ulen,) = struct.unpack("<q", piece[:8])
-                if ulen != -1:
-                    piece = struct.pack("<q", -1) + codec.decompress(piece[8:], decompressed_size=ulen).to_pybytes()
+                plain = piece[8:] if ulen == -1 else codec.decompress(piece[8:], decompressed_size=ulen).to_pybytes()
+                new = encode(bi, k, plain)
+                if new is not None:
+                    piece = (piece[:8] if prefix is None else struct.pack("<q", prefix)) + bytes(new)
             new_bufs.append((len(new_body), len(piece)))
             new_body += piece + b"\0" * ((-len(piece)) % 8)
         old_vec = b"".join(struct.pack("<qq", o, l) for o, l in rb["buffers"])
@@ -223,6 +226,15 @@ def rewrite_buffers_raw(stream_bytes, pick):
         bi += 1
     out += a[at:].tobytes()
     return bytes(out)
+
+
+def rewrite_buffers_raw(stream_bytes, pick):
+    """A compressed IPC stream with some of its buffers stored RAW: length prefix -1 followed by the uncompressed bytes, what
+    Arrow C++ (IpcWriteOptions::min_space_savings), arrow-rs and Arrow Java write for incompressible buffers.  pyarrow's
+    Python writer never emits them, so the stream is rewritten here (rewrite_buffers).  pick(batch_index, buffer_index,
+    length) chooses the buffers, `length` being the buffer's length in the stream, prefix included.  Returns the new stream
+    as bytes."""
+    return rewrite_buffers(stream_bytes, lambda bi, k, plain: plain, prefix=-1, select=pick)
 
 
 # ------------------------------------------------------------------------------------------ late materialisation (gather)

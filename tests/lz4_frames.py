@@ -634,16 +634,16 @@ def bsid3_frame():
 
 
 # ------------------------------------------------------------------------------------------------- frames in a stream
-def ipc_stream(columns, frames):
-    """An Arrow IPC stream of ONE record batch whose column i holds columns[i]["want"] as values of columns[i]["dtype"] and
-    whose data buffer i is frames[i] (None: the LZ4 frame pyarrow wrote) behind the length prefix pyarrow wrote.
-    -> (stream bytes, the pyarrow table)."""
+def ipc_stream(columns, frames, codec="lz4"):
+    """An Arrow IPC stream of ONE record batch, written with compression=`codec` ("lz4" or "zstd"), whose column i holds
+    columns[i]["want"] as values of columns[i]["dtype"] and whose data buffer i is frames[i] (None: the frame pyarrow wrote)
+    behind the length prefix pyarrow wrote.  -> (stream bytes, the pyarrow table)."""
     import pyarrow as pa
     import pyarrow.ipc as ipc
     from helpers import rewrite_buffers
     table = pa.table({"c%d" % i: pa.array(np.frombuffer(c["want"], c["dtype"])) for i, c in enumerate(columns)})
     sink = pa.BufferOutputStream()
-    with ipc.new_stream(sink, table.schema, options=ipc.IpcWriteOptions(compression="lz4")) as w:
+    with ipc.new_stream(sink, table.schema, options=ipc.IpcWriteOptions(compression=codec)) as w:
         w.write_table(table, max_chunksize=max(table.num_rows, 1))
     seen = []
 

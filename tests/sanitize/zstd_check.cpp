@@ -3,7 +3,10 @@
 // duckdb-arrow_amd/csrc/zstd_format.hpp is compiled by hipcc into the kernels and by g++ into this program: the same
 // functions decode the same frames here, block by block in the kernels' order of stages (host walk -> per-block entropy
 // decode with tables taken from the blocks the walk names -> repeat offsets in frame order -> copy), and the result is compared
-// with the bytes the frame was made from.  usage: zstd_check <frame file> <expected bytes file> ...   (pairs)
+// with the bytes the frame was made from.
+// usage: zstd_check { <frame file> <expected bytes file> | --refuse <frame file> <declared length> } ...
+// --refuse: a frame that must NOT decode -- the walk or a stage turns it down (DecodeFrame returns false), without a report
+// from the sanitizers the program is built with.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -231,6 +234,8 @@ static bool DecodeFrame(const std::vector<uint8_t>& frame, size_t expect_size, s
       }
     }
   }
+  // zstd_layout's check, the reference's (base_stream_reader.cpp:24-29): the blocks add up to the declared length
+  if (out->size() != expect_size) { *why = "the blocks add up to " + std::to_string(out->size()) + " bytes, declared " + std::to_string(expect_size); return false; }
   return true;
 }
 
@@ -269,10 +274,25 @@ int main(int argc, char** argv) {
     std::printf("FAIL offset code 31 was decoded as a repeat offset\n");
     bad++;
   }
+  int refused = 0;
   for (int i = 1; i + 1 < argc; i += 2) {
-    const std::vector<uint8_t> frame = Slurp(argv[i]), expect = Slurp(argv[i + 1]);
     std::vector<uint8_t> got;
     std::string why;
+    if (std::strcmp(argv[i], "--refuse") == 0) {
+      if (i + 2 >= argc) break;
+      const std::vector<uint8_t> frame = Slurp(argv[i + 1]);
+      n++;
+      if (DecodeFrame(frame, static_cast<size_t>(std::atoll(argv[i + 2])), &got, &why)) {
+        std::printf("FAIL %s: decoded to %zu bytes, expected a refusal\n", argv[i + 1], got.size());
+        bad++;
+      } else {
+        std::printf("refused %s: %s\n", argv[i + 1], why.c_str());
+        refused++;
+      }
+      i++;
+      continue;
+    }
+    const std::vector<uint8_t> frame = Slurp(argv[i]), expect = Slurp(argv[i + 1]);
     n++;
     if (!DecodeFrame(frame, expect.size(), &got, &why)) {
       std::printf("FAIL %s: %s\n", argv[i], why.c_str());
@@ -288,6 +308,7 @@ int main(int argc, char** argv) {
               g_seen[0], g_seen[1], g_seen[2], g_seen[4], g_seen[5], g_seen[6], g_seen[7], g_seen[8], g_seen[9], g_seen[10], g_seen[11]);
   for (int t = 0; t < 3; t++)
     std::printf("table %d predefined/rle/fse/repeat %ld/%ld/%ld/%ld\n", t, g_seen[12 + 4 * t], g_seen[13 + 4 * t], g_seen[14 + 4 * t], g_seen[15 + 4 * t]);
+  if (refused) std::printf("%d frames refused as expected\n", refused);
   std::printf("%d frames, %d failed\n", n, bad);
   return bad ? 1 : 0;
 }

@@ -255,7 +255,11 @@ def _orc():
         P, I64, I32, U64, U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32
         for name, args in (("orc_bool", [P, I64, I64, P]), ("orc_decimal128_narrow", [P, P, I64, I64, I32, P]),
                            ("orc_date64_to_date32", [P, I64, I64, P]), ("orc_div_i64", [P, I64, I64, I64, P]),
-                           ("orc_fixed_binary", [P, I32, P, I64, I64, U64, P]), ("orc_dict_sel", [P, I32, I32, P, I64, I64, U32, P])):
+                           ("orc_fixed_binary", [P, I32, P, I64, I64, U64, P]), ("orc_dict_sel", [P, I32, I32, P, I64, I64, U32, P]),
+                           ("orc_duration_to_interval", [P, P, I64, I64, I64, P]), ("orc_interval_months", [P, I64, I64, P]),
+                           ("orc_interval_mdn", [P, I64, I64, P]), ("orc_narrow", [P, I32, P, I64, I64, I32, P]),
+                           ("orc_half_to_float", [P, I64, I64, P]), ("orc_string_view", [P, P, I64, I64, P, I64, P]),
+                           ("orc_list_entries", [P, I32, I64, I64, I64, I64, P])):
             getattr(L, name).argtypes = args
         _orc_ready = True
     return L
@@ -268,26 +272,42 @@ def _words_of(ok):
 
 
 def decode_column_reference(kind, nrows, buf1, *, param=0, param2=0, validity=None, null_count=-1, row_offset=0, buf2=None,
-                            buf2_len=None, ptr_base=0):
+                            buf2_len=None, ptr_base=0, window_starts=None, parent=None):
     """Rows [row_offset, row_offset + nrows) of one Arrow column as the flat decode path hands them to DuckDB, from the
     oracle's per-kind functions (each takes the array offset `o`): (data uint8[nrows, width], valid bool[nrows],
-    err uint32[nrows]).
+    err uint32[nrows]).  Every decode kind (the gather reference below refuses the ones a selection vector cannot take).
+
+    parent = (validity words of the struct / fixed_size_list vector that owns the column, rows per parent row): the
+    combined validity own & parent[r // max(div, 1)] is what the per-kind functions receive as `valid` and what comes back.
+    COPY, BOOL, DATE64, DIV_I64, the interval kinds and a dividing DURATION keep their source-derived values under NULL, as
+    the oracle does; NULL (the Arrow type) is zero bytes with every row NULL; STRUCT has no data (width 0).
+    STRVIEW: buf2 = the table of variadic buffers as uint64 {address, length} pairs, buf2_len = their number.
+    LIST32 / LIST64: param = child length, window_starts = the rows (of this column) where the top-level 2048-row windows
+    start (None: every 2048-row tile is one); orc_list_entries is called once per window with its win_row.
 
     err[r] = the MI_ST_* bits row r raises when it is decoded.  The oracle reports errors per call, not per row, so its
     conditions are restated per row: FULL offset validation (first >= 0, non-decreasing, end <= data length) and "Strings
-    over 4GB" (an end offset past UINT32_MAX) for every row, NULL or not, as the whole-array validation is; multiply
-    overflow, an index that does not fit uint32 or points past the dictionary, and a decimal that is not the sign
-    extension of its narrowed value (Hugeint::TryCast; the oracle only truncates) for valid rows.  A row with damaged
-    offsets decodes to the canonical 16 zero bytes (the oracle is not asked to follow them)."""
+    over 4GB" (an end offset past UINT32_MAX) for every row, NULL or not, as the whole-array validation is, and likewise
+    the list offsets (a < 0, b < a, b > child length, a < the window's base); multiply overflow (MUL_I64, a multiplying
+    DURATION), an index that does not fit uint32 or points past the dictionary, a decimal that is not the sign extension
+    of its narrowed value (Hugeint::TryCast / NARROW; the oracle only truncates), and a long string view whose buffer
+    index or offset + length leaves the table, for valid rows.  A row with damaged offsets decodes to the canonical 16
+    zero bytes (the oracle is not asked to follow them)."""
     L = _orc()
     n, o = int(nrows), int(row_offset)
     w = po.out_width(kind, param)
-    b1 = np.ascontiguousarray(buf1).view(np.uint8).reshape(-1)
+    b1 = np.ascontiguousarray(buf1).view(np.uint8).reshape(-1) if buf1 is not None else np.zeros(16, np.uint8)
     bm = np.ascontiguousarray(validity).view(np.uint8).reshape(-1) if validity is not None else None
     words = np.full(max((n + 63) // 64, 1), np.uint64(0xFFFFFFFFFFFFFFFF))
     if n:
         L.orc_validity(bm.ctypes.data if bm is not None else None, null_count, o, n, words.ctypes.data)
     ok = po.valid_bits(words, n)
+    if parent is not None and n:
+        pbits = np.unpackbits(np.ascontiguousarray(parent[0]).view(np.uint8), bitorder="little").astype(bool)
+        ok = ok & pbits[np.arange(n) // max(int(parent[1]), 1)]
+        words = _words_of(ok)
+    if kind == po.K_NULL:
+        ok = np.zeros(n, bool)
     err = np.zeros(n, np.uint32)
     out = np.zeros(max(n * w, 1), np.uint8)
     rows = slice(o, o + n)
@@ -335,9 +355,53 @@ def decode_column_reference(kind, nrows, buf1, *, param=0, param2=0, validity=No
         past = ~wide & (idx.astype(np.uint64) >= np.uint64(param2))
         err[ok & wide] = ST_INDEX_RANGE
         err[ok & past] = ST_DICT_INDEX
+    elif kind == po.K_DURATION:
+        L.orc_duration_to_interval(b1.ctypes.data, words.ctypes.data, o, n, param, out.ctypes.data)
+        if param > 0:
+            src = b1[: (o + n) * 8].view(np.int64)[rows]
+            err[ok & ((src > (2**63 - 1) // param) | (src < -(2**63 // param)))] = ST_MUL_OVERFLOW
+    elif kind == po.K_INTERVAL_MONTHS:
+        L.orc_interval_months(b1.ctypes.data, o, n, out.ctypes.data)
+    elif kind == po.K_INTERVAL_MDN:
+        L.orc_interval_mdn(b1.ctypes.data, o, n, out.ctypes.data)
+    elif kind == po.K_NARROW:
+        sw, dw = int(param & 0xFF), int((param >> 8) & 0xFF)
+        L.orc_narrow(b1.ctypes.data, sw, words.ctypes.data, o, n, dw, out.ctypes.data)
+        src = b1[: (o + n) * sw].view(np.int32 if sw == 4 else np.int64)[rows].astype(np.int64)
+        err[ok & (src.astype({2: np.int16, 4: np.int32}[dw]).astype(np.int64) != src)] = ST_DECIMAL_RANGE
+    elif kind == po.K_HALF_FLOAT:
+        L.orc_half_to_float(b1.ctypes.data, o, n, out.ctypes.data)
+    elif kind in (po.K_NULL, po.K_STRUCT):
+        pass
+    elif kind == po.K_STRVIEW:
+        nbuf = int(buf2_len or 0)
+        table = np.ascontiguousarray(buf2).view(np.uint64).reshape(-1) if nbuf else np.zeros(2, np.uint64)
+        L.orc_string_view(b1.ctypes.data, words.ctypes.data, o, n, table.ctypes.data, nbuf, out.ctypes.data)
+        v = b1[: (o + n) * 16].view(np.int32).reshape(-1, 4)[rows].astype(np.int64)
+        ln, bi, bo = v[:, 0] & 0xFFFFFFFF, v[:, 2], v[:, 3]
+        size = table[1::2].astype(np.int64)[np.clip(bi, 0, max(nbuf - 1, 0))]
+        err[ok & (ln > 12) & ((bi < 0) | (bi >= nbuf) | (bo < 0) | (bo + ln > size))] = ST_BAD_OFFSETS
+    elif kind in (po.K_LIST32, po.K_LIST64):
+        offw = 4 if kind == po.K_LIST32 else 8
+        off = b1.view(np.int32 if offw == 4 else np.int64)
+        wins = list(range(0, n, 2048)) if window_starts is None else [int(x) for x in window_starts]
+        base = np.zeros(n, np.int64)
+        for k, r0 in enumerate(wins):
+            r1 = min(wins[k + 1] if k + 1 < len(wins) else n, n)
+            if k == 0:
+                r0 = 0      # rows in front of the first start (there are none in a well-formed table) belong to it
+            if r1 > r0:
+                L.orc_list_entries(b1.ctypes.data, offw, o + r0, r1 - r0, o + wins[k], int(param), out[16 * r0:].ctypes.data)
+                base[r0: r1] = off[o + wins[k]]
+        a, b = off[o: o + n].astype(np.int64), off[o + 1: o + n + 1].astype(np.int64)
+        err[(a < 0) | (b < a) | (b > param) | (a < base)] = ST_BAD_OFFSETS
     else:
-        raise NotImplementedError("kind %d is not decoded through a selection vector" % kind)
+        raise NotImplementedError("kind %d" % kind)
     return out[: n * w].reshape(n, w), ok, err
+
+
+GATHER_KINDS = (po.K_COPY, po.K_DEC128, po.K_STR32, po.K_STR64, po.K_FIXED_BINARY, po.K_BOOL, po.K_DATE64, po.K_MUL_I32, po.K_MUL_I64,
+                po.K_DIV_I64, po.K_DICT)      # KindCanGather (kernels_gather.hip)
 
 
 def gather_take(data, ok, err, sel):
@@ -352,4 +416,6 @@ def gather_take(data, ok, err, sel):
 
 def gather_reference(kind, nrows, buf1, sel, **column):
     """Expected output bytes, validity words and status of one gather task (a column decoded through a selection vector)."""
+    if kind not in GATHER_KINDS:
+        raise NotImplementedError("kind %d is not decoded through a selection vector" % kind)
     return gather_take(*decode_column_reference(kind, nrows, buf1, **column), sel)

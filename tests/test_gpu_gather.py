@@ -18,18 +18,12 @@ import pytest
 
 import duckdb_arrow_amd as da
 from duckdb_arrow_amd import _ffi
-from oracle import pyoracle as po
 
-from helpers import canon_python, decode_column_reference, gather_reference, gather_take
+from decode_tasks import (ONES, PAD_ROWS, PTR_BASE, SEL_FILL, SENTINEL, STATUS_CASES, VARIANTS, WIN, _sel_arrays, _status_column, _width,
+                          check_job, make_column, make_sel, run_plan)
+from helpers import canon_python, gather_take
 
 pytestmark = pytest.mark.gpu
-
-WIN = 2048
-PAD_ROWS = WIN + 64
-SEL_FILL = 2048
-SENTINEL = 0xA5
-ONES = np.uint64(0xFFFFFFFFFFFFFFFF)
-PTR_BASE = 0x7000_0000_1003
 
 
 @pytest.fixture(scope="module")
@@ -47,179 +41,6 @@ def torch():
 @pytest.fixture(scope="module")
 def con():
     return da.Connection(0)
-
-
-# ------------------------------------------------------------------------------------------------ columns
-def _dict_variant(iw, signed):
-    dict_len = {(1, 1): 100, (1, 0): 250, (2, 1): 30000, (2, 0): 60000, (4, 1): 2 * 10**9, (4, 0): 4 * 10**9}.get((iw, signed), 2**32 - 1)
-    return dict(kind=_ffi.K_DICT, param=iw | (signed << 8), param2=dict_len)
-
-
-VARIANTS = {
-    "copy1": dict(kind=_ffi.K_COPY, param=1), "copy2": dict(kind=_ffi.K_COPY, param=2), "copy4": dict(kind=_ffi.K_COPY, param=4),
-    "copy8": dict(kind=_ffi.K_COPY, param=8), "copy16": dict(kind=_ffi.K_COPY, param=16),
-    "dec128_i16": dict(kind=_ffi.K_DEC128, param=2), "dec128_i32": dict(kind=_ffi.K_DEC128, param=4),
-    "dec128_i64": dict(kind=_ffi.K_DEC128, param=8),
-    "str32": dict(kind=_ffi.K_STR32), "str64": dict(kind=_ffi.K_STR64),
-    "fixed1": dict(kind=_ffi.K_FIXED_BINARY, param=1), "fixed12": dict(kind=_ffi.K_FIXED_BINARY, param=12),
-    "fixed13": dict(kind=_ffi.K_FIXED_BINARY, param=13), "fixed16": dict(kind=_ffi.K_FIXED_BINARY, param=16),
-    "bool": dict(kind=_ffi.K_BOOL), "date64": dict(kind=_ffi.K_DATE64),
-    "mul_i32_1e6": dict(kind=_ffi.K_MUL_I32, param=1000000), "mul_i32_1e3": dict(kind=_ffi.K_MUL_I32, param=1000),
-    "mul_i64_1e6": dict(kind=_ffi.K_MUL_I64, param=1000000),
-    "div_i64_1000": dict(kind=_ffi.K_DIV_I64, param=1000), "div_i64_86400": dict(kind=_ffi.K_DIV_I64, param=86400),
-}
-for _iw in (1, 2, 4, 8):
-    for _signed in (1, 0):
-        VARIANTS["dict_%s%d" % ("i" if _signed else "u", 8 * _iw)] = _dict_variant(_iw, _signed)
-
-
-def make_column(variant, nrows, row_offset, nulls, rng):
-    """One source column of VARIANTS[variant]: `nrows` rows at Arrow array offset `row_offset`.  nulls: "bitmap" (random
-    bitmap, null_count -1; the NULL rows hold values that would raise a status flag if they were looked at), "count0" (a
-    random bitmap the kernel has to ignore: null_count 0) or "none"."""
-    col = dict(VARIANTS[variant], nrows=nrows, row_offset=row_offset, name="%s/%s/n%d/o%d" % (variant, nulls, nrows, row_offset))
-    kind, param = col["kind"], col.get("param", 0)
-    total = row_offset + nrows + PAD_ROWS
-    bitmap = rng.integers(0, 256, (total + 63) // 64 * 8 + 8, dtype=np.uint8)
-    null = ~np.unpackbits(bitmap, bitorder="little")[:total].astype(bool) if nulls == "bitmap" else np.zeros(total, bool)
-    if nulls != "none":
-        col.update(validity=bitmap, null_count=-1 if nulls == "bitmap" else 0)
-    if kind == _ffi.K_COPY:
-        buf1 = rng.integers(0, 256, total * param, dtype=np.uint8)
-    elif kind == _ffi.K_FIXED_BINARY:
-        buf1 = rng.integers(0, 256, total * param, dtype=np.uint8)
-        col["ptr_base"] = PTR_BASE
-    elif kind == _ffi.K_BOOL:
-        buf1 = rng.integers(0, 256, (total + 7) // 8, dtype=np.uint8)
-    elif kind == _ffi.K_DEC128:
-        lim = 1 << (8 * param - 1)
-        v = rng.integers(-lim, lim - 1, total, endpoint=True).astype(np.int64)
-        v[rng.integers(0, total, 8)] = [-lim, lim - 1, 0, -1, -lim, lim - 1, 1, -2]
-        halves = np.stack([v, v >> 63], axis=1)
-        halves[null] = rng.integers(-2**63, 2**63 - 1, (int(null.sum()), 2), endpoint=True)   # out of range, bad upper half
-        buf1 = halves.reshape(-1)
-    elif kind in (_ffi.K_STR32, _ffi.K_STR64):
-        lens = rng.choice([0, 1, 2, 3, 4, 5, 11, 12, 13, 14, 15, 16, 29, 40], total)
-        off = 5 + np.concatenate([[0], np.cumsum(lens)])      # every length at every payload misalignment
-        buf1 = off.astype(np.int32 if kind == _ffi.K_STR32 else np.int64)
-        col.update(buf2=rng.integers(1, 256, int(off[-1]), dtype=np.uint8), buf2_len=int(off[row_offset + nrows]), ptr_base=PTR_BASE)
-    elif kind == _ffi.K_DATE64:
-        buf1 = rng.integers(-3 * 10**14, 3 * 10**14, total).astype(np.int64)      # +- 9500 years of milliseconds
-        buf1[rng.integers(0, total, 6)] = [-1, 0, 86400000, -86400000, 86399999, -86400001]
-    elif kind == _ffi.K_MUL_I32:
-        buf1 = rng.integers(-2**31, 2**31 - 1, total, endpoint=True).astype(np.int32)
-    elif kind == _ffi.K_MUL_I64:
-        lim = (2**63 - 1) // param
-        buf1 = rng.integers(-lim, lim, total, endpoint=True).astype(np.int64)
-        buf1[rng.integers(0, total, 2)] = [-lim, lim]
-        buf1[null] = rng.integers(2**62, 2**63 - 1, int(null.sum()))              # would overflow
-    elif kind == _ffi.K_DIV_I64:
-        buf1 = rng.integers(-2**63, 2**63 - 1, total, endpoint=True).astype(np.int64)
-        buf1[rng.integers(0, total, 6)] = [-1, 0, param, -param, param - 1, 1 - param]
-    elif kind == _ffi.K_DICT:
-        iw, signed, dict_len = param & 0xFF, (param >> 8) & 1, col["param2"]
-        v = rng.integers(0, dict_len, total).astype(np.uint64)
-        v[rng.integers(0, total, 2)] = [0, dict_len - 1]
-        v[null] = ONES if (signed or iw == 8) else np.uint64(2**(8 * iw) - 1)        # -1, or past the dictionary
-        buf1 = v.astype(np.dtype("u%d" % iw))
-    else:
-        raise AssertionError(kind)
-    col["buf1"] = buf1
-    return col
-
-
-def _width(col):
-    return po.out_width(col["kind"], col.get("param", 0))
-
-
-def _reference_args(col):
-    return {k: col[k] for k in ("param", "param2", "validity", "null_count", "row_offset", "buf2", "buf2_len", "ptr_base") if k in col}
-
-
-# ------------------------------------------------------------------------------------------------ selections
-def make_sel(nrows, counts, rng):
-    """One ascending index list per 2048-row window with the wanted number of rows (clipped to the window's size; None =
-    every row).  A window with two rows or more selects its first and its last row, single rows alternate between them."""
-    sel = []
-    for w in range((nrows + WIN - 1) // WIN):
-        m = min(WIN, nrows - w * WIN)
-        c = m if counts[w % len(counts)] is None else min(counts[w % len(counts)], m)
-        if c == m:
-            s = np.arange(m)
-        elif c == 0:
-            s = np.zeros(0, np.int64)
-        elif c == 1:
-            s = np.array([0 if w % 2 else m - 1])
-        else:
-            s = np.sort(np.concatenate([[0, m - 1], 1 + rng.choice(m - 2, c - 2, replace=False)]))
-        sel.append(s.astype(np.int64))
-    return sel
-
-
-def _sel_arrays(sel):
-    flat = np.full(max(len(sel), 1) * WIN, SEL_FILL, np.uint32)
-    for w, s in enumerate(sel):
-        flat[w * WIN: w * WIN + len(s)] = s
-    return flat, np.array([len(s) for s in sel] + [0], np.uint32)
-
-
-# ------------------------------------------------------------------------------------------------ running a plan
-def _dev(torch, a):
-    """numpy array -> device bytes, padded as IPC buffers are (to 8 bytes, and never empty)"""
-    b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    return torch.from_numpy(np.concatenate([b, np.zeros(16 - len(b) % 8, np.uint8)])).cuda()
-
-
-def run_plan(ctx, torch, jobs, sels):
-    """jobs = [(column, key into sels or None for an ordinary flat task)], sels = {key: index lists per window}.  One Plan,
-    one launch.  -> ([(data bytes incl. the sentinel tail, validity words incl. the guard word) per job], status)."""
-    keep, dsel = [], {}
-    for key, sel in sels.items():
-        flat, counts = _sel_arrays(sel)
-        dsel[key] = (torch.from_numpy(flat.view(np.int32)).cuda(), torch.from_numpy(counts.view(np.int32)).cuda(), sum(len(s) for s in sel))
-    tasks, outs = [], []
-    for col, key in jobs:
-        total = dsel[key][2] if key is not None else col["nrows"]
-        d1, dv, d2 = _dev(torch, col["buf1"]), (_dev(torch, col["validity"]) if "validity" in col else None), \
-            (_dev(torch, col["buf2"]) if "buf2" in col else None)
-        out = torch.full((total * _width(col) + 64 + (-total * _width(col)) % 16,), SENTINEL, dtype=torch.uint8, device="cuda")
-        outv = torch.full(((total + 63) // 64 * 8 + 8,), 0xFF, dtype=torch.uint8, device="cuda")
-        keep += [d1, dv, d2]
-        outs.append((out, outv))
-        tasks.append(da.make_task(col["kind"], col["nrows"], d1.data_ptr(), out.data_ptr(), validity=dv.data_ptr() if dv is not None else 0,
-                                  buf2=d2.data_ptr() if d2 is not None else 0, out_validity=outv.data_ptr(), ptr_base=col.get("ptr_base", 0),
-                                  row_offset=col["row_offset"], buf2_len=col.get("buf2_len", 0), param=col.get("param", 0),
-                                  param2=col.get("param2", 0), null_count=col.get("null_count", -1),
-                                  sel=dsel[key][0].data_ptr() if key is not None else 0,
-                                  sel_count=dsel[key][1].data_ptr() if key is not None else 0))
-    plan = da.Plan(ctx, tasks)
-    plan.launch(torch.cuda.current_stream().cuda_stream)
-    status = plan.status()
-    got = [(out.cpu().numpy(), outv.cpu().numpy().view(np.uint64)) for out, outv in outs]
-    plan.close()
-    return got, status
-
-
-def check_job(col, sel, got, want=None):
-    """The four assertions on one task's output.  sel None = an ordinary flat task (every row, in place).  Returns the
-    expected status of the task."""
-    data, words = got
-    if sel is None:
-        sel = make_sel(col["nrows"], [None], None)
-    want_data, want_words, want_status = want if want is not None else gather_reference(col["kind"], col["nrows"], col["buf1"], sel, **_reference_args(col))
-    w, total, where = _width(col), sum(len(s) for s in sel), col.get("name", "")
-    if not np.array_equal(data[: total * w], want_data):
-        bad = np.nonzero(np.any(data[: total * w].reshape(-1, w) != want_data.reshape(-1, w), axis=1))[0]
-        raise AssertionError("%s: %d of %d output rows differ, first %d: got %s want %s" % (
-            where, len(bad), total, bad[0], data[bad[0] * w: bad[0] * w + w].tolist(), want_data[bad[0] * w: bad[0] * w + w].tolist()))
-    assert (data[total * w:] == SENTINEL).all(), (where, "bytes behind the last output row were written")
-    assert len(words) == (total + 63) // 64 + 1
-    if not np.array_equal(words[:-1], want_words):
-        bad = np.nonzero(words[:-1] != want_words)[0]
-        raise AssertionError("%s: %d validity words differ, first %d of %d: got %016x want %016x" % (
-            where, len(bad), bad[0], len(want_words), int(words[bad[0]]), int(want_words[bad[0]])))
-    assert words[-1] == ONES, (where, "the guard word behind the validity words lost bits")
-    return want_status
 
 
 # ------------------------------------------------------------------------------------------------ every kind
@@ -356,51 +177,7 @@ def test_nothing_selected_and_empty_columns_write_nothing(ctx, torch, variant):
 
 
 # ------------------------------------------------------------------------------------------------ status
-def _dec(values, width):
-    """python ints -> decimal128 halves; (lower, upper) tuples are taken as they are"""
-    out = []
-    for v in values:
-        out += list(v) if isinstance(v, tuple) else [v & (2**64 - 1), (v >> 64) & (2**64 - 1)]
-    return dict(kind=_ffi.K_DEC128, param=width, buf1=np.array(out, np.uint64))
-
-
-def _status_cases():
-    cases = {}
-    for w in (2, 4, 8):
-        lim = 1 << (8 * w - 1)
-        cases["dec128_i%d_above" % (8 * w)] = (lambda bad, w=w, lim=lim: _dec([lim if bad else lim - 1], w), _ffi.ST_DECIMAL_RANGE, True)
-        cases["dec128_i%d_below" % (8 * w)] = (lambda bad, w=w, lim=lim: _dec([-lim - 1 if bad else -lim], w), _ffi.ST_DECIMAL_RANGE, True)
-        cases["dec128_i%d_upper_half" % (8 * w)] = (lambda bad, w=w: _dec([(5, 1) if bad else 5], w), _ffi.ST_DECIMAL_RANGE, True)
-    cases["dec128_i64_upper_half_of_a_negative"] = (lambda bad: _dec([(2**64 - 5, 2**64 - 2) if bad else -5], 8), _ffi.ST_DECIMAL_RANGE, True)
-    big = (2**63 - 1) // 1000
-    cases["mul_i64_above"] = (lambda bad: dict(kind=_ffi.K_MUL_I64, param=1000, buf1=np.array([big + 1 if bad else big], np.int64)), _ffi.ST_MUL_OVERFLOW, True)
-    cases["mul_i64_below"] = (lambda bad: dict(kind=_ffi.K_MUL_I64, param=1000, buf1=np.array([-big - 2 if bad else -big], np.int64)), _ffi.ST_MUL_OVERFLOW, True)
-    for iw in (1, 2, 4):
-        cases["dict_i%d_negative" % (8 * iw)] = (lambda bad, iw=iw: dict(kind=_ffi.K_DICT, param=iw | 256, param2=90, buf1=np.array(
-            [-1 if bad else 3], np.dtype("i%d" % iw))), _ffi.ST_INDEX_RANGE, True)
-        cases["dict_u%d_past_the_dictionary" % (8 * iw)] = (lambda bad, iw=iw: dict(kind=_ffi.K_DICT, param=iw, param2=90, buf1=np.array(
-            [200 if bad else 89], np.dtype("u%d" % iw))), _ffi.ST_DICT_INDEX, True)
-    cases["dict_u64_wider_than_uint32"] = (lambda bad: dict(kind=_ffi.K_DICT, param=8, param2=90, buf1=np.array([2**32 if bad else 3], np.uint64)),
-                                           _ffi.ST_INDEX_RANGE, True)
-    cases["dict_i64_negative"] = (lambda bad: dict(kind=_ffi.K_DICT, param=8 | 256, param2=90, buf1=np.array([-1 if bad else 3], np.int64)),
-                                  _ffi.ST_INDEX_RANGE, True)
-    cases["dict_i32_equal_to_dict_len"] = (lambda bad: dict(kind=_ffi.K_DICT, param=4 | 256, param2=90, buf1=np.array([90 if bad else 89], np.int32)),
-                                           _ffi.ST_DICT_INDEX, True)
-    return cases
-
-
-STATUS_CASES = _status_cases()
 BAD_ROWS = [0, 70, WIN + 255, 2 * WIN + 99]       # lane 0 of a wave, inside a wave, second pass of a window, last window
-
-
-def _status_column(make, flag_row, nrows, rng):
-    """`nrows` good rows (the case's good value) with the case's bad value at `flag_row`; every row valid except where the
-    caller clears bits afterwards."""
-    good, bad = make(False), make(True)
-    per = len(good["buf1"])
-    buf1 = np.tile(good["buf1"], nrows + PAD_ROWS)
-    buf1[flag_row * per: (flag_row + 1) * per] = bad["buf1"]
-    return dict(good, buf1=buf1, nrows=nrows, row_offset=0, validity=np.full((nrows + PAD_ROWS + 63) // 64 * 8 + 8, 0xFF, np.uint8), null_count=-1)
 
 
 @pytest.mark.parametrize("case", list(STATUS_CASES))

@@ -14,7 +14,10 @@ The package directory name carries a hyphen (it is the name the build contract a
 library or without a HIP device every scan / encode call raises.
 """
 import ctypes as C
+import decimal
 import os
+import re
+import struct
 
 import numpy as np
 
@@ -272,6 +275,35 @@ def filter_range(ctx, values_ptr, width, validity_ptr, nrows, lo, hi, sel_ptr, c
                                           C.c_void_p(stream or None)))
 
 
+def filter_between(ctx, values_ptr, width, validity_ptr, nrows, lo, hi, sel_ptr, count_ptr, stream=0):
+    """lo <= v <= hi on a resident vector (mi_filter_between): Python floats on FLOAT / DOUBLE vectors (width 4 / 8, DuckDB's
+    total order), ints on hugeint vectors (width 16)."""
+    if width == 16:
+        signed = lambda w: w - (1 << 64) if w >= (1 << 63) else w
+        words = [signed((v >> s) & ((1 << 64) - 1)) for v in (int(lo), int(hi)) for s in (0, 64)]
+        kind = _ffi.FV_INT128
+    else:
+        words = [struct.unpack("<q", struct.pack("<d", float(v)))[0] for v in (lo, hi)]
+        kind = _ffi.FV_DOUBLE
+    bounds = (C.c_int64 * len(words))(*words)
+    _ffi.check(_ffi.lib().mi_filter_between(ctx._h, values_ptr, width, validity_ptr or None, nrows, kind, bounds, sel_ptr, count_ptr,
+                                            C.c_void_p(stream or None)))
+
+
+def filter_float_key(value, width):
+    """The order-preserving integer key the filter kernel compares a FLOAT (width 4) / DOUBLE (width 8) value by."""
+    key = C.c_int64()
+    _ffi.check(_ffi.lib().mi_filter_float_key(float(value), width, C.byref(key)))
+    return key.value
+
+
+def filter_launch_counts():
+    """(launches of the filter kernel's base instance, launches of its FLOAT / DOUBLE / 128-bit instance) by this process."""
+    base, ext = C.c_int64(), C.c_int64()
+    _ffi.check(_ffi.lib().mi_filter_launch_counts(C.byref(base), C.byref(ext)))
+    return base.value, ext.value
+
+
 # ---------------------------------------------------------------------------------------------------- logical views
 def _valid_bits(validity_ptr, n, shift=0):
     """`shift`: bit of the first word that belongs to row 0 (mi_vector.validity_shift, nested children only)."""
@@ -461,12 +493,42 @@ class Relation:
         """Pushed-down predicate tree (mi_scan_set_filter).  `expr` is nested tuples:
             ("and", e1, e2, ...) | ("or", e1, e2, ...) | (column, op, value) with op in = <> != < <= > >= |
             (column, "in", [values]) | (column, "is null") | (column, "is not null") | (column, "starts_with", prefix)
-        Constants are the stored integers, or str / bytes for VARCHAR / BLOB columns (byte-wise order).  NULL semantics are
-        SQL's: a comparison with NULL is not true."""
+        Constants are the stored integers, or str / bytes for VARCHAR / BLOB columns (byte-wise order).  The column's DuckDB
+        type picks what a number is sent as: FLOAT / DOUBLE columns take Python floats (float('nan'), inf; ints are converted)
+        in DuckDB's total order -- NaN = NaN, NaN greatest, -0.0 = +0.0; HUGEINT / DECIMAL(19..38) columns take ints of up to
+        128 bits; a decimal.Decimal on any DECIMAL column is scaled to the stored integer.  A float against an integer column
+        is refused.  NULL semantics are SQL's: a comparison with NULL is not true."""
         ops = {"=": _ffi.F_EQ, "==": _ffi.F_EQ, "<>": _ffi.F_NE, "!=": _ffi.F_NE, "<": _ffi.F_LT, "<=": _ffi.F_LE,
                ">": _ffi.F_GT, ">=": _ffi.F_GE, "is null": _ffi.F_IS_NULL, "is not null": _ffi.F_IS_NOT_NULL, "in": _ffi.F_IN,
                "starts_with": _ffi.F_STARTS_WITH}
         nodes, keep = [None], []
+        duck = {f["name"]: f["duck_type"] for f in self.fields}
+
+        def numbers(col, vals):
+            """-> (value_kind, low words, high words or None) of the constants of one leaf"""
+            ty = duck.get(col, "")
+            if ty in ("FLOAT", "DOUBLE") and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in vals):
+                return _ffi.FV_DOUBLE, [struct.unpack("<q", struct.pack("<d", float(v)))[0] for v in vals], None
+            m = re.match(r"DECIMAL\((\d+),(\d+)\)$", ty)
+            stored = []
+            for v in vals:
+                if isinstance(v, decimal.Decimal):
+                    if not m:
+                        raise MiError(_ffi.MI_EINVAL, "filter on column '%s' (%s): a Decimal constant needs a DECIMAL column" % (col, ty))
+                    scaled = decimal.Context(prec=120).scaleb(v, int(m.group(2)))
+                    if scaled != scaled.to_integral_value():
+                        raise MiError(_ffi.MI_EINVAL, "filter on column '%s' (%s): %s has more digits behind the point than the column" % (col, ty, v))
+                    v = int(scaled)
+                stored.append(v)
+            if any(isinstance(v, float) for v in stored):   # the library names the column it does not fit
+                return _ffi.FV_DOUBLE, [struct.unpack("<q", struct.pack("<d", v))[0] for v in stored], None
+            stored = [int(v) for v in stored]
+            if all(-(1 << 63) <= v < (1 << 63) for v in stored):
+                return _ffi.FV_INT64, stored, None
+            if not all(-(1 << 127) <= v < (1 << 127) for v in stored):
+                raise MiError(_ffi.MI_EINVAL, "filter on column '%s': constant beyond 128 bits" % col)
+            signed = lambda w: w - (1 << 64) if w >= (1 << 63) else w
+            return _ffi.FV_INT128, [signed(v & ((1 << 64) - 1)) for v in stored], [signed((v >> 64) & ((1 << 64) - 1)) for v in stored]
 
         def emit(at, e):
             if e[0] in ("and", "or") and len(e) > 1 and isinstance(e[1], tuple):
@@ -487,15 +549,23 @@ class Relation:
                 keep.extend([vals, ptrs, lens])
                 n.str_values, n.str_lens, n.n_values = ptrs, lens, len(vals)
             elif op == "in":
-                arr = (C.c_int64 * max(len(e[2]), 1))(*[int(v) for v in e[2]])
+                n.value_kind, lows, highs = numbers(col, list(e[2]))
+                arr = (C.c_int64 * max(len(lows), 1))(*lows)
                 keep.append(arr)
-                n.values, n.n_values = arr, len(e[2])
+                n.values, n.n_values = arr, len(lows)
+                if highs is not None:
+                    arr_hi = (C.c_int64 * max(len(highs), 1))(*highs)
+                    keep.append(arr_hi)
+                    n.values_hi = arr_hi
             elif op not in ("is null", "is not null") and isinstance(e[2], (str, bytes)):
                 v = as_bytes(e[2])
                 keep.append(v)
                 n.str_value, n.str_len = v, len(v)
             elif op not in ("is null", "is not null"):
-                n.value = int(e[2])
+                n.value_kind, lows, highs = numbers(col, [e[2]])
+                n.value = lows[0]
+                if highs is not None:
+                    n.value_hi = highs[0]
             nodes[at] = n
 
         emit(0, expr)

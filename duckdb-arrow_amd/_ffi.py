@@ -86,10 +86,12 @@ class RangeFilter(C.Structure):
 class FilterNode(C.Structure):
     _fields_ = [("op", C.c_int32), ("first_child", C.c_int32), ("n_children", C.c_int32), ("n_values", C.c_int32),
                 ("column", C.c_char_p), ("value", C.c_int64), ("values", C.POINTER(C.c_int64)),
-                ("str_value", C.c_char_p), ("str_len", C.c_int32), ("_pad", C.c_int32),
-                ("str_values", C.POINTER(C.c_char_p)), ("str_lens", C.POINTER(C.c_int32))]
+                ("str_value", C.c_char_p), ("str_len", C.c_int32), ("value_kind", C.c_int32),
+                ("str_values", C.POINTER(C.c_char_p)), ("str_lens", C.POINTER(C.c_int32)),
+                ("value_hi", C.c_int64), ("values_hi", C.POINTER(C.c_int64))]
 
 
+FV_INT64, FV_DOUBLE, FV_INT128 = 0, 1, 2
 F_EQ, F_NE, F_LT, F_LE, F_GT, F_GE, F_IS_NULL, F_IS_NOT_NULL, F_IN, F_STARTS_WITH, F_AND, F_OR = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 16, 17
 
 
@@ -212,6 +214,9 @@ SIGNATURES = {
     "mi_scan_close": (None, [P]),
     "mi_scan_bind": (C.c_int, [P, C.POINTER(Field), C.c_int32, C.POINTER(C.c_int32)]),
     "mi_scan_init": (C.c_int, [P, C.POINTER(C.c_char_p), C.c_int32]),
+    "mi_filter_between": (C.c_int, [P, P, C.c_int32, P, C.c_int64, C.c_int32, C.POINTER(C.c_int64), P, P, P]),
+    "mi_filter_float_key": (C.c_int, [C.c_double, C.c_int32, C.POINTER(C.c_int64)]),
+    "mi_filter_launch_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mi_scan_set_filter_range": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64]),
     "mi_scan_set_filter": (C.c_int, [P, C.POINTER(FilterNode), C.c_int32, C.c_int32]),
     "mi_scan_open_files_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32,

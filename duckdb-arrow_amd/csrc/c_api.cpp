@@ -12,6 +12,7 @@
 
 #include "../../include/mi_arrow_ipc.h"
 #include "engine.hpp"
+#include "filter_key.hpp"
 #include "ipc_format.hpp"
 #include "ipc_stream_reader.hpp"
 #include "scan_operator.hpp"
@@ -322,6 +323,59 @@ int mi_filter_range(mi_ctx* ctx, const void* values, int32_t width, const void* 
     ctx->ctx->Bind();
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
     MI_HIP_CHECK(device::LaunchFilterRange(values, width, validity, nrows, lo, hi, sel_out, count_out, s));
+  });
+}
+
+int mi_filter_between(mi_ctx* ctx, const void* values, int32_t width, const void* validity, int64_t nrows, int32_t value_kind,
+                      const int64_t* bounds, mi_sel_t* sel_out, uint32_t* count_out, void* stream) {
+  return Wrap([&] {
+    if (!ctx || !values || !bounds || !sel_out || !count_out) throw InvalidInputException("mi_filter_between: NULL argument");
+    const bool is_float = value_kind == MI_FV_DOUBLE && (width == 4 || width == 8), is_wide = value_kind == MI_FV_INT128 && width == 16;
+    if (!is_float && !is_wide) throw InvalidInputException("mi_filter_between: MI_FV_DOUBLE takes width 4 or 8, MI_FV_INT128 width 16");
+    ctx->ctx->Bind();
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
+    device::FilterProgram prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_leaves = 1;
+    device::FilterLeafDev& L = prog.leaves[0];
+    L.data = values;
+    L.validity = static_cast<const uint64_t*>(validity);
+    L.width = width;
+    L.flags = device::kLeafEndsClause;
+    if (is_float) {
+      double lo, hi;
+      std::memcpy(&lo, &bounds[0], 8);
+      std::memcpy(&hi, &bounds[1], 8);
+      L.op = device::kLeafRange;
+      L.flags |= device::kLeafFloat;
+      L.lo = filterkey::FloatKeyOfDouble(lo, width);
+      L.hi = filterkey::FloatKeyOfDouble(hi, width);
+      MI_HIP_CHECK(device::LaunchFilterProgram(prog, nrows, sel_out, count_out, s));
+      return;
+    }
+    DeviceBuffer d_bounds(32);
+    MI_HIP_CHECK(hipMemcpy(d_bounds.get(), bounds, 32, hipMemcpyHostToDevice));
+    L.op = device::kLeafWideRange;
+    L.in_values = d_bounds.get<int64_t>();
+    MI_HIP_CHECK(device::LaunchFilterProgram(prog, nrows, sel_out, count_out, s));
+    MI_HIP_CHECK(hipStreamSynchronize(s));   // the bounds die with this call
+  });
+}
+
+int mi_filter_float_key(double v, int32_t width, int64_t* key) {
+  return Wrap([&] {
+    if (!key || (width != 4 && width != 8)) throw InvalidInputException("mi_filter_float_key: width must be 4 or 8");
+    *key = filterkey::FloatKeyOfDouble(v, width);
+  });
+}
+
+int mi_filter_launch_counts(int64_t* base, int64_t* extended) {
+  return Wrap([&] {
+    if (!base || !extended) throw InvalidInputException("mi_filter_launch_counts: NULL argument");
+    int64_t n[2];
+    device::FilterLaunchCounts(n);
+    *base = n[0];
+    *extended = n[1];
   });
 }
 

@@ -130,10 +130,15 @@ constexpr int kLeafDictMap = 6;     // dictionary-encoded string column: data = 
                                     // dictionary entry (n_in of them; 0 no, 1 yes, 2 NULL entry), lo = 0 match, 1 no match, 2 IS NULL, 3 IS NOT NULL
 constexpr int kLeafStrRange = 7;    // string_t column: lower bound <(=) row <(=) upper bound, byte-wise.  in_values: two constants in kLeafStrIn's
                                     // layout (lower, upper); n_in = bit 0 has lower, bit 1 lower inclusive, bit 2 has upper, bit 3 upper inclusive
+constexpr int kLeafWideRange = 8;   // 16-byte column (hugeint_t{uint64 lower; int64 upper}: HUGEINT, DECIMAL(19..38)): lo <= v <= hi, `upper`
+                                    // signed, then `lower` unsigned.  in_values = {lo.lower, lo.upper, hi.lower, hi.upper}
+constexpr int kLeafWideIn = 9;      // 16-byte column: v is one of n_in constants, in_values = {lower, upper} pairs
 constexpr int kLeafUnsigned = 1;    // flags: the column holds unsigned integers
 constexpr int kLeafNegate = 2;      //        NOT (range / in-list); NULL still fails
 constexpr int kLeafEndsClause = 4;
 constexpr int kLeafBias = 8;        //        uint64 column: values and constants are compared after x ^ 2^63
+constexpr int kLeafFloat = 16;      //        FLOAT / DOUBLE column (width 4 / 8): every value goes through filterkey::FloatKey
+                                    //        (filter_key.hpp) before the range / IN comparison, whose constants are keys
 constexpr int kMaxFilterLeaves = 24;
 struct FilterLeafDev {
   const void* data;                 // decoded fixed-width vector (device), NULL for IS [NOT] NULL
@@ -147,7 +152,12 @@ struct FilterProgram {
   int32_t _pad;
   FilterLeafDev leaves[kMaxFilterLeaves];
 };
+// Two instances of one kernel: programs of the leaves kLeafRange .. kLeafStrRange without kLeafFloat launch filter_program<false>,
+// which compiles none of the code of the others; a program that holds a kLeafFloat / kLeafWideRange / kLeafWideIn leaf
+// launches filter_program<true>.
 hipError_t LaunchFilterProgram(const FilterProgram& prog, int64_t nrows, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream);
+//! launches of each instance by this process so far: [0] filter_program<false>, [1] filter_program<true>
+void FilterLaunchCounts(int64_t out[2]);
 // lo <= v < hi on one column (mi_filter_range)
 hipError_t LaunchFilterRange(const void* values, int32_t width, const void* validity, int64_t nrows, int64_t lo,
                              int64_t hi, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream);

@@ -1,7 +1,9 @@
 // kernels_filter.hip -- K6: pushed-down predicates -> selection vectors, and the fused Q6-style consumer.
 #include "device_common.hpp"
+#include "filter_key.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <type_traits>
 
@@ -23,7 +25,9 @@ namespace {
 // sorted without a second pass.
 constexpr int kFilterWindows = 4;
 
-template <typename T>
+// FLOAT (filter_program<true> only, width 4 / 8): the column holds IEEE floats, each loaded value is replaced by its
+// order-preserving key (filter_key.hpp) and the constants are keys: DuckDB's total order, NaN greatest, -0.0 = +0.0.
+template <typename T, bool FLOAT = false>
 __device__ __forceinline__ void leaf_compare(const FilterLeafDev& L, int64_t first_window, int64_t nrows, int r,
                                              uint32_t (&m)[kFilterWindows]) {
   typedef T vec8 __attribute__((ext_vector_type(8)));
@@ -42,14 +46,16 @@ __device__ __forceinline__ void leaf_compare(const FilterLeafDev& L, int64_t fir
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         typedef typename std::make_unsigned<T>::type UT;
-        x[w][k] = (is_unsigned ? static_cast<int64_t>(static_cast<uint64_t>(static_cast<UT>(v[k]))) : static_cast<int64_t>(v[k])) ^ bias;
+        if constexpr (FLOAT) x[w][k] = filterkey::FloatKey(v[k]);
+        else x[w][k] = (is_unsigned ? static_cast<int64_t>(static_cast<uint64_t>(static_cast<UT>(v[k]))) : static_cast<int64_t>(v[k])) ^ bias;
       }
     } else {
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         typedef typename std::make_unsigned<T>::type UT;
         const T v = r + k < n ? values[row0 + r + k] : T(0);
-        x[w][k] = (is_unsigned ? static_cast<int64_t>(static_cast<uint64_t>(static_cast<UT>(v))) : static_cast<int64_t>(v)) ^ bias;
+        if constexpr (FLOAT) x[w][k] = filterkey::FloatKey(v);
+        else x[w][k] = (is_unsigned ? static_cast<int64_t>(static_cast<uint64_t>(static_cast<UT>(v))) : static_cast<int64_t>(v)) ^ bias;
       }
     }
   }
@@ -213,6 +219,45 @@ __device__ __forceinline__ void leaf_dictmap(const FilterLeafDev& L, int64_t fir
   }
 }
 
+// kLeafWideRange / kLeafWideIn: the column is a decoded hugeint_t vector (16 bytes per row: uint64 lower, int64 upper).  A lane's
+// 8 rows are 128 bytes, so one window at a time, as leaf_strin does (32 registers); rows past nrows are never loaded.  The
+// constants are uniform (scalar loads) and no loaded value is ever used as an address.
+__device__ __forceinline__ void leaf_wide(const FilterLeafDev& L, int64_t first_window, int64_t nrows, int r, uint32_t (&m)[kFilterWindows]) {
+  typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+  typedef u64x2 u64x2_a8 __attribute__((aligned(8)));   // a zero-copy alias of the Arrow body is 8-byte aligned only
+  gptr<const u64x2_a8> rows = GC<u64x2_a8>(L.data);
+#pragma clang loop unroll(disable)
+  for (int w = 0; w < kFilterWindows; w++) {
+    const int64_t row0 = (first_window + w) * kTileRows;
+    const int64_t left = nrows - row0;
+    const int n = left < kTileRows ? static_cast<int>(left < 0 ? 0 : left) : kTileRows;
+    u64x2 s[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const u64x2 zero = {0ull, 0ull};
+      s[k] = r + k < n ? __builtin_nontemporal_load(rows + row0 + r + k) : zero;
+    }
+    uint32_t mm = 0;
+    if (L.op == kLeafWideRange) {
+      const uint64_t lo_lower = static_cast<uint64_t>(L.in_values[0]), hi_lower = static_cast<uint64_t>(L.in_values[2]);
+      const int64_t lo_upper = L.in_values[1], hi_upper = L.in_values[3];
+#pragma unroll
+      for (int k = 0; k < 8; k++)
+        mm |= filterkey::WideInRange(static_cast<int64_t>(s[k].y), s[k].x, lo_upper, lo_lower, hi_upper, hi_lower) ? (1u << k) : 0u;
+    } else {
+      for (int j = 0; j < L.n_in; j++) {
+        const uint64_t c_lower = static_cast<uint64_t>(L.in_values[2 * j]), c_upper = static_cast<uint64_t>(L.in_values[2 * j + 1]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) mm |= (s[k].x == c_lower && s[k].y == c_upper) ? (1u << k) : 0u;
+      }
+    }
+    m[w] = mm;
+  }
+}
+
+// EXT = false: the leaves the kernel has always had, and none of the code of the others.  EXT = true adds kLeafFloat on
+// range / IN leaves and the 16-byte leaves; launched only for a program that holds one (LaunchFilterProgram).
+template <bool EXT>
 __global__ __launch_bounds__(kBlockThreads) void filter_program(const FilterProgram prog, int64_t nrows,
                                                                 mi_sel_t* __restrict__ sel_out_p,
                                                                 uint32_t* __restrict__ count_out_p) {
@@ -246,6 +291,11 @@ __global__ __launch_bounds__(kBlockThreads) void filter_program(const FilterProg
       if (L.op == kLeafStrIn) leaf_strin(L, first_window, nrows, r, m);
       else if (L.op == kLeafStrRange) leaf_strrange(L, first_window, nrows, r, m);
       else if (L.op == kLeafDictMap) leaf_dictmap(L, first_window, nrows, r, m);
+      else if (EXT && (L.op == kLeafWideRange || L.op == kLeafWideIn)) leaf_wide(L, first_window, nrows, r, m);
+      else if (EXT && (L.flags & kLeafFloat)) {
+        if (L.width == 4) leaf_compare<int32_t, true>(L, first_window, nrows, r, m);
+        else leaf_compare<int64_t, true>(L, first_window, nrows, r, m);
+      }
       else switch (L.width) {
         case 1: leaf_compare<int8_t>(L, first_window, nrows, r, m); break;
         case 2: leaf_compare<int16_t>(L, first_window, nrows, r, m); break;
@@ -357,13 +407,39 @@ hipError_t LaunchAggSumProduct(const AggSumProductArgs& args, unsigned long long
   return hipGetLastError();
 }
 
+namespace {
+std::atomic<int64_t> g_filter_launches[2];
+
+//! true when `prog` holds a leaf that only filter_program<true> knows
+bool FilterProgramIsExtended(const FilterProgram& prog) {
+  for (int l = 0; l < prog.n_leaves; l++) {
+    const FilterLeafDev& L = prog.leaves[l];
+    if (L.op == kLeafWideRange || L.op == kLeafWideIn || ((L.op == kLeafRange || L.op == kLeafIn) && (L.flags & kLeafFloat))) return true;
+  }
+  return false;
+}
+}  // namespace
+
+void FilterLaunchCounts(int64_t out[2]) {
+  out[0] = g_filter_launches[0].load();
+  out[1] = g_filter_launches[1].load();
+}
+
 hipError_t LaunchFilterProgram(const FilterProgram& prog, int64_t nrows, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream) {
   MI_DROP_STALE_ERROR();
   if (nrows <= 0) return hipSuccess;
   if (prog.n_leaves < 0 || prog.n_leaves > kMaxFilterLeaves) return hipErrorInvalidValue;
+  for (int l = 0; l < prog.n_leaves; l++) {   // what the 16-byte and float leaves may be bound to
+    const FilterLeafDev& L = prog.leaves[l];
+    if ((L.op == kLeafWideRange || L.op == kLeafWideIn) && (L.width != 16 || !L.in_values || !L.data)) return hipErrorInvalidValue;
+    if ((L.op == kLeafRange || L.op == kLeafIn) && (L.flags & kLeafFloat) && L.width != 4 && L.width != 8) return hipErrorInvalidValue;
+  }
   const int64_t windows = (nrows + kTileRows - 1) / kTileRows;
   const uint32_t grid = static_cast<uint32_t>((windows + kFilterWindows - 1) / kFilterWindows);
-  hipLaunchKernelGGL(filter_program, dim3(grid), dim3(kBlockThreads), 0, stream, prog, nrows, sel_out, count_out);
+  const bool ext = FilterProgramIsExtended(prog);
+  if (ext) hipLaunchKernelGGL(filter_program<true>, dim3(grid), dim3(kBlockThreads), 0, stream, prog, nrows, sel_out, count_out);
+  else hipLaunchKernelGGL(filter_program<false>, dim3(grid), dim3(kBlockThreads), 0, stream, prog, nrows, sel_out, count_out);
+  g_filter_launches[ext ? 1 : 0]++;
   return hipGetLastError();
 }
 

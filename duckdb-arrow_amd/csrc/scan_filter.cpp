@@ -5,30 +5,116 @@
 // The reference pushes no filters (filter_pushdown = false, src/scanner/read_arrow.cpp:47-48); what is accepted here is
 // what DuckDB's TableFilterSet can hand a scan: constant comparisons, IS [NOT] NULL, IN-lists,
 // AND / OR trees.  On integers every comparison is an inclusive range (v < c is [MIN, c-1], v <> c is NOT [c, c]), so
-// the kernel knows four leaf forms only and adjacent range conjuncts on one column intersect into one leaf.
+// the kernel knows four leaf forms only and adjacent range conjuncts on one column intersect into one leaf.  FLOAT /
+// DOUBLE columns go the same way on the order-preserving keys of filter_key.hpp (DuckDB's total order: NaN = NaN, NaN
+// greatest, -0.0 = +0.0; a strict bound is an inclusive one on key +- 1), so everything here works on keys unchanged;
+// HUGEINT / DECIMAL(19..38) columns are a leaf form of their own, as strings are, with 128-bit inclusive ranges.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <limits>
 
+#include "filter_key.hpp"
 #include "scan_operator.hpp"
 
 namespace miarrow {
 
+FilterValueClass FilterClassOf(const ArrowField& field) {
+  const ArrowField& vf = ValueField(field);
+  int32_t kind, w;
+  int64_t param;
+  if (!vf.Plan(&kind, &param, &w, /*value_only*/ true)) return FilterValueClass::kOther;
+  if (vf.type == MI_AT_FLOAT && (w == 4 || w == 8)) return w == 4 ? FilterValueClass::kFloat32 : FilterValueClass::kFloat64;
+  if (vf.type == MI_AT_DECIMAL && kind == MI_K_COPY && w == 16) return FilterValueClass::kWide;
+  return FilterValueClass::kOther;
+}
+
 namespace {
+using wide_t = __int128;
+constexpr wide_t kWideMax = static_cast<wide_t>(~static_cast<unsigned __int128>(0) >> 1), kWideMin = -kWideMax - 1;
+wide_t WideOf(int64_t lower, int64_t upper) {
+  return static_cast<wide_t>((static_cast<unsigned __int128>(static_cast<uint64_t>(upper)) << 64) | static_cast<uint64_t>(lower));
+}
+uint64_t LowerOf(wide_t v) { return static_cast<uint64_t>(static_cast<unsigned __int128>(v)); }
+int64_t UpperOf(wide_t v) { return static_cast<int64_t>(static_cast<uint64_t>(static_cast<unsigned __int128>(v) >> 64)); }
+
 constexpr int64_t kMin = std::numeric_limits<int64_t>::min(), kMax = std::numeric_limits<int64_t>::max();
 constexpr size_t kMaxLeaves = static_cast<size_t>(device::kMaxFilterLeaves);
 size_t RoundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-FilterLeaf LeafOf(const mi_filter_node& n) {
+// 128-bit columns: every comparison is an inclusive range on the stored integer, as on narrow integers
+FilterLeaf WideLeafOf(const mi_filter_node& n, FilterLeaf l) {
+  const bool is128 = n.value_kind == MI_FV_INT128;
+  auto constant = [&](int64_t lower, int64_t upper) { return is128 ? WideOf(lower, upper) : static_cast<wide_t>(lower); };   // an int64 is sign-extended
+  const wide_t c = constant(n.value, n.value_hi);
+  l.is_wide = true;
+  l.op = device::kLeafWideRange;
+  l.wide_lo = kWideMin;
+  l.wide_hi = kWideMax;
+  auto closed = [&](wide_t lo, wide_t hi) { l.wide_lo = lo; l.wide_hi = hi; };
+  switch (n.op) {
+    case MI_F_EQ: closed(c, c); break;
+    case MI_F_NE: closed(c, c); l.negate = true; break;
+    case MI_F_LT: if (c == kWideMin) closed(1, 0); else l.wide_hi = c - 1; break;
+    case MI_F_LE: l.wide_hi = c; break;
+    case MI_F_GT: if (c == kWideMax) closed(1, 0); else l.wide_lo = c + 1; break;
+    case MI_F_GE: l.wide_lo = c; break;
+    case MI_F_IN:
+      if (n.n_values < 0 || (n.n_values > 0 && (!n.values || (is128 && !n.values_hi)))) throw InvalidInputException("IN filter without values");
+      if (n.n_values > 256) throw NotImplementedException("IN-list with more than 256 values is not pushed down");
+      for (int32_t k = 0; k < n.n_values; k++) l.wide_in.push_back(constant(n.values[k], is128 ? n.values_hi[k] : 0));
+      std::sort(l.wide_in.begin(), l.wide_in.end());
+      l.wide_in.erase(std::unique(l.wide_in.begin(), l.wide_in.end()), l.wide_in.end());
+      if (l.wide_in.empty()) closed(1, 0);
+      else if (l.wide_in.size() == 1) { closed(l.wide_in[0], l.wide_in[0]); l.wide_in.clear(); }
+      else l.op = device::kLeafWideIn;
+      break;
+    default: throw InvalidInputException("unknown filter op " + std::to_string(n.op));
+  }
+  return l;
+}
+
+FilterLeaf LeafOf(const mi_filter_node& n, const std::vector<ScanColumn>* columns) {
   if (!n.column || !*n.column) throw InvalidInputException("filter leaf without a column name");
   FilterLeaf l;
   l.column = n.column;
   l.op = device::kLeafRange;
   l.lo = kMin;
   l.hi = kMax;
-  const int64_t c = n.value;
+  // What the constants are compared as: by the column where it is known (an unknown one is refused when the filter is
+  // bound), else by their kind
+  const bool has_constant = n.op != MI_F_IS_NULL && n.op != MI_F_IS_NOT_NULL && !n.str_value && !n.str_values;
+  FilterValueClass cls = FilterValueClass::kOther;
+  if (has_constant) {
+    if (n.value_kind != MI_FV_INT64 && n.value_kind != MI_FV_DOUBLE && n.value_kind != MI_FV_INT128)
+      throw InvalidInputException("filter on column '" + l.column + "': unknown value_kind " + std::to_string(n.value_kind));
+    const ScanColumn* sc = nullptr;
+    if (columns)
+      for (auto& c : *columns)
+        if (c.name == l.column) sc = &c;
+    if (sc && !sc->is_constant()) {
+      cls = FilterClassOf(sc->field);
+      const bool is_float = cls == FilterValueClass::kFloat32 || cls == FilterValueClass::kFloat64;
+      const std::string what = "filter on column '" + l.column + "' (" + sc->field.DuckType() + "): ";
+      if (n.value_kind == MI_FV_DOUBLE && !is_float) throw InvalidInputException(what + "a double constant (MI_FV_DOUBLE) needs a FLOAT / DOUBLE column");
+      if (n.value_kind != MI_FV_DOUBLE && is_float) throw InvalidInputException(what + "a FLOAT / DOUBLE column needs double constants (MI_FV_DOUBLE)");
+      if (n.value_kind == MI_FV_INT128 && cls != FilterValueClass::kWide)
+        throw InvalidInputException(what + "a 128-bit constant (MI_FV_INT128) needs a HUGEINT / DECIMAL(19..38) column");
+    } else {
+      cls = n.value_kind == MI_FV_DOUBLE ? FilterValueClass::kFloat64 : n.value_kind == MI_FV_INT128 ? FilterValueClass::kWide : FilterValueClass::kOther;
+    }
+  }
+  if (cls == FilterValueClass::kWide) return WideLeafOf(n, l);
+  // FLOAT / DOUBLE: the constants become their order-preserving keys, everything below works on keys unchanged
+  if (cls != FilterValueClass::kOther) l.float_width = cls == FilterValueClass::kFloat32 ? 4 : 8;
+  auto constant = [&](int64_t v) {
+    if (!l.float_width) return v;
+    double d;
+    std::memcpy(&d, &v, 8);
+    return filterkey::FloatKeyOfDouble(d, l.float_width);
+  };
+  const int64_t c = constant(n.value);
   auto closed = [&](int64_t lo, int64_t hi) { l.lo = lo; l.hi = hi; l.lo_open = l.hi_open = false; };
   if (n.str_value || n.str_values) {   // byte-string constants: a VARCHAR / BLOB column
     l.is_string = true;
@@ -96,7 +182,7 @@ FilterLeaf LeafOf(const mi_filter_node& n) {
     case MI_F_IN:
       if (n.n_values < 0 || (n.n_values > 0 && !n.values)) throw InvalidInputException("IN filter without values");
       if (n.n_values > 256) throw NotImplementedException("IN-list with more than 256 values is not pushed down");
-      l.in_values.assign(n.values, n.values + n.n_values);
+      for (int32_t k = 0; k < n.n_values; k++) l.in_values.push_back(constant(n.values[k]));
       std::sort(l.in_values.begin(), l.in_values.end());
       l.in_values.erase(std::unique(l.in_values.begin(), l.in_values.end()), l.in_values.end());
       if (l.in_values.empty()) closed(1, 0);                                  // IN () keeps nothing
@@ -114,23 +200,23 @@ size_t LeafCount(const FilterCnf& cnf) {
   return n;
 }
 
-FilterCnf ToCnf(const mi_filter_node* nodes, int32_t n_nodes, int32_t at, int depth) {
+FilterCnf ToCnf(const mi_filter_node* nodes, int32_t n_nodes, int32_t at, int depth, const std::vector<ScanColumn>* columns) {
   if (at < 0 || at >= n_nodes) throw InvalidInputException("filter node index out of range");
   if (depth > 32) throw InvalidInputException("filter tree too deep");
   const mi_filter_node& n = nodes[at];
-  if (n.op != MI_F_AND && n.op != MI_F_OR) return FilterCnf{{LeafOf(n)}};
+  if (n.op != MI_F_AND && n.op != MI_F_OR) return FilterCnf{{LeafOf(n, columns)}};
   if (n.n_children <= 0 || n.first_child < 0 || n.first_child > n_nodes - n.n_children) throw InvalidInputException("AND / OR filter node without children");
   FilterCnf out;
   if (n.op == MI_F_AND) {
     for (int32_t k = 0; k < n.n_children; k++) {
-      FilterCnf c = ToCnf(nodes, n_nodes, n.first_child + k, depth + 1);
+      FilterCnf c = ToCnf(nodes, n_nodes, n.first_child + k, depth + 1, columns);
       out.insert(out.end(), c.begin(), c.end());
     }
   } else {
     // (A1 & A2) | (B1 & B2) = (A1|B1) & (A1|B2) & (A2|B1) & (A2|B2): distribute child by child
     out = FilterCnf{{}};
     for (int32_t k = 0; k < n.n_children; k++) {
-      FilterCnf c = ToCnf(nodes, n_nodes, n.first_child + k, depth + 1);
+      FilterCnf c = ToCnf(nodes, n_nodes, n.first_child + k, depth + 1, columns);
       FilterCnf next;
       for (auto& left : out)
         for (auto& right : c) {
@@ -145,9 +231,9 @@ FilterCnf ToCnf(const mi_filter_node* nodes, int32_t n_nodes, int32_t at, int de
 }
 }  // namespace
 
-FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root) {
+FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root, const std::vector<ScanColumn>* columns) {
   if (!nodes || n_nodes <= 0) throw InvalidInputException("empty filter");
-  FilterCnf cnf = ToCnf(nodes, n_nodes, root, 0);
+  FilterCnf cnf = ToCnf(nodes, n_nodes, root, 0, columns);
   // single-leaf range clauses on one column intersect (lo <= v AND v < hi -> one leaf)
   FilterCnf merged;
   for (auto& clause : cnf) {
@@ -214,9 +300,20 @@ void BoundFilter::Resolve(const std::vector<ScanColumn>& all_columns, const std:
                                         ") needs a utf8 / large_utf8 / binary / fixed_size_binary column (dictionary-encoded or not)");
         continue;
       }
+      if (leaf.is_wide || leaf.float_width) {
+        // FLOAT / DOUBLE / 128-bit constants: the column must be what they were made for (dictionary-encoded or not)
+        const FilterValueClass cls = FilterClassOf(sc.field);
+        const FilterValueClass want = leaf.is_wide ? FilterValueClass::kWide : leaf.float_width == 4 ? FilterValueClass::kFloat32 : FilterValueClass::kFloat64;
+        if (cls != want)
+          throw NotImplementedException("filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() + "): its constants are " +
+                                        (leaf.is_wide ? "128-bit integers" : leaf.float_width == 4 ? "FLOAT keys" : "DOUBLE keys"));
+        continue;
+      }
       if (!(vf.Plan(&kind, &param, &w) && !vf.has_dictionary && IsIntegerLike(kind, w, vf, /*allow_bool*/ true)))
         throw NotImplementedException("filter pushdown on column '" + sc.name + "' (" + sc.field.DuckType() +
-                                      ") needs an integer / boolean / date / time / timestamp / decimal(<=18) column");
+                                      ") with integer constants needs an integer / boolean / date / time / timestamp / decimal(<=18) column; FLOAT / "
+                                      "DOUBLE and HUGEINT / DECIMAL(19..38) columns take constants of their own kind, VARCHAR / BLOB byte strings; "
+                                      "intervals, nested types and string views are not compared in the scan");
     }
   }
 }
@@ -229,6 +326,14 @@ void BoundFilter::UploadConstants() {
       if (leaf.op == device::kLeafIn) {
         list = DeviceBuffer(leaf.in_values.size() * 8);
         MI_HIP_CHECK(hipMemcpy(list.get(), leaf.in_values.data(), leaf.in_values.size() * 8, hipMemcpyHostToDevice));
+      } else if (leaf.is_wide) {
+        // kLeafWideRange: {lo.lower, lo.upper, hi.lower, hi.upper}; kLeafWideIn: {lower, upper} per constant
+        std::vector<int64_t> words;
+        auto add = [&](wide_t v) { words.push_back(static_cast<int64_t>(LowerOf(v))); words.push_back(UpperOf(v)); };
+        if (leaf.op == device::kLeafWideRange) { add(leaf.wide_lo); add(leaf.wide_hi); }
+        else for (wide_t v : leaf.wide_in) add(v);
+        list = DeviceBuffer(words.size() * 8);
+        MI_HIP_CHECK(hipMemcpy(list.get(), words.data(), words.size() * 8, hipMemcpyHostToDevice));
       } else if ((leaf.op == device::kLeafStrIn || leaf.op == device::kLeafStrRange) && !leaf.str_values.empty()) {
         // 3 words per constant (its string_t image + the device address of its bytes), the bytes behind the table
         const size_t nc = leaf.str_values.size();
@@ -258,7 +363,32 @@ void BoundFilter::UploadConstants() {
 }
 
 namespace {
-// Which entries of a string-valued dictionary version pass `leaf` (one byte per entry: 0 no, 1 yes, 2 NULL), in HBM.
+// Does dictionary value `p` (decoded, `width` bytes) pass the FLOAT / DOUBLE / 128-bit leaf?  The kernel's comparison, once
+// per entry; a negated leaf is negated by the look-up (kLeafDictMap mode 1), so that a NULL entry fails both.
+bool ValuePasses(const FilterLeaf& leaf, const uint8_t* p, int32_t width) {
+  if (leaf.is_wide) {
+    uint64_t lower;
+    int64_t upper;
+    std::memcpy(&lower, p, 8);
+    std::memcpy(&upper, p + 8, 8);
+    if (leaf.op == device::kLeafWideIn) return std::binary_search(leaf.wide_in.begin(), leaf.wide_in.end(), WideOf(static_cast<int64_t>(lower), upper));
+    return filterkey::WideInRange(upper, lower, UpperOf(leaf.wide_lo), LowerOf(leaf.wide_lo), UpperOf(leaf.wide_hi), LowerOf(leaf.wide_hi));
+  }
+  int64_t key;
+  if (width == 4) {
+    int32_t b;
+    std::memcpy(&b, p, 4);
+    key = filterkey::FloatKey(b);
+  } else {
+    int64_t b;
+    std::memcpy(&b, p, 8);
+    key = filterkey::FloatKey(b);
+  }
+  if (leaf.op == device::kLeafIn) return std::binary_search(leaf.in_values.begin(), leaf.in_values.end(), key);
+  return key >= leaf.lo && key <= leaf.hi;   // open ends are kMin / kMax
+}
+
+// Which entries of a dictionary version pass `leaf` (one byte per entry: 0 no, 1 yes, 2 NULL), in HBM.
 // Made once per (version, leaf); the upload rides `stream` in front of the filter kernel that reads it.
 const void* DictMatchMap(DictState* dict, size_t li, const FilterLeaf& leaf, hipStream_t stream) {
   auto it = dict->match_maps.find(li);
@@ -280,8 +410,12 @@ const void* DictMatchMap(DictState* dict, size_t li, const FilterLeaf& leaf, hip
     }
     return true;
   };
+  const bool by_value = leaf.is_wide || leaf.float_width != 0;
+  const bool null_test = leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull;
+  const size_t vw = static_cast<size_t>(dict->out_width);
   for (int64_t e = 0; e < dict->dict_len; e++)
     codes[static_cast<size_t>(e)] = !dict->host_valid[static_cast<size_t>(e)] ? 2
+                                    : (by_value && !null_test) ? (ValuePasses(leaf, dict->host_values.data() + static_cast<size_t>(e) * vw, dict->out_width) ? 1 : 0)
                                     : (leaf.is_string && passes(dict->host_strings[static_cast<size_t>(e)])) ? 1 : 0;
   codes[static_cast<size_t>(dict->dict_len)] = 2;   // the NULL entry rows without a value point at
   // device copy + its pinned source
@@ -307,7 +441,7 @@ device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_co
       L.lo = leaf.lo;
       L.hi = leaf.hi;
       L.in_values = d_in_lists[li].get<int64_t>();
-      L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.in_values.size());
+      L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.is_wide ? leaf.wide_in.size() : leaf.in_values.size());
       if (leaf.op == device::kLeafStrRange)
         L.n_in = (leaf.lo_open ? 0 : 1) | (leaf.lo_incl ? 2 : 0) | (leaf.hi_open ? 0 : 4) | (leaf.hi_incl ? 8 : 0);
       L.width = 1;
@@ -331,12 +465,17 @@ device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_co
       L.validity = pn.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(b.d_out + pn.valid_off) : nullptr;
       L.width = std::max(pn.width, 1);
       const bool null_test = leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull;
-      if (pn.kind == MI_K_DICT && (leaf.is_string || null_test)) {
+      const bool by_value = !null_test && (leaf.is_wide || leaf.float_width != 0);
+      if (pn.kind == MI_K_DICT && (leaf.is_string || null_test || by_value)) {
         // dictionary-encoded: match the dictionary version this batch uses once (host), the rows by index.  IS [NOT] NULL
         // goes the same way: a row is NULL when its index or its dictionary entry is
         const std::shared_ptr<DictState>& dict = b.node_dict[static_cast<size_t>(root)];
         if (!dict || (leaf.is_string && static_cast<int64_t>(dict->host_strings.size()) != dict->dict_len))
           throw NotImplementedException("string filter on the dictionary-encoded column '" + leaf.column + "': its dictionary values are not strings");
+        if (by_value && (dict->out_width != (leaf.is_wide ? 16 : leaf.float_width) ||
+                         dict->host_values.size() != static_cast<size_t>(dict->dict_len) * static_cast<size_t>(dict->out_width)))
+          throw NotImplementedException("filter on the dictionary-encoded column '" + leaf.column + "': its dictionary values are not " +
+                                        (leaf.is_wide ? "128-bit integers" : leaf.float_width == 4 ? "FLOAT" : "DOUBLE"));
         L.op = device::kLeafDictMap;
         L.in_values = static_cast<const int64_t*>(DictMatchMap(dict.get(), li, leaf, stream));
         L.n_in = static_cast<int32_t>(std::min<int64_t>(dict->dict_len + 1, 0x7FFFFFFF));
@@ -355,6 +494,15 @@ device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_co
         const size_t data_span = vkind == MI_K_FIXED_BINARY ? 1 : 2;
         L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(b.d_in + (dn.spans.size() > data_span ? dn.spans[data_span].offset : 0)));
         L.hi = static_cast<int64_t>(pn.ptr_base);
+        continue;
+      }
+      if (leaf.is_wide) {
+        if (pn.width != 16) throw InternalException("128-bit filter leaf on column '" + leaf.column + "' of width " + std::to_string(pn.width));
+        continue;   // op and constants are set above
+      }
+      if (leaf.float_width && !null_test) {
+        if (pn.width != leaf.float_width) throw InternalException("floating-point filter leaf on column '" + leaf.column + "' of width " + std::to_string(pn.width));
+        L.flags |= device::kLeafFloat;
         continue;
       }
       const ArrowField& vf = ValueField(Column(static_cast<size_t>(leaf.out_col), out_columns).field);

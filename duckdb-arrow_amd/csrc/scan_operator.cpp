@@ -388,6 +388,35 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
       }
       d->host_strings.push_back(std::move(v));
     }
+  } else if (FilterClassOf(f) != FilterValueClass::kOther) {
+    // FLOAT / DOUBLE / 128-bit dictionaries keep their decoded values on the host for the same reason.  The Arrow values are
+    // the decoded ones (float16 widened, exactly); the validity bitmap above says which of them count
+    const mi_buffer_span* sp = &b.buffers[0];
+    const size_t vw = static_cast<size_t>(w), sw = kind == MI_K_HALF_FLOAT ? 2 : vw;
+    if (sp[1].length < n_new * static_cast<int64_t>(sw)) throw InternalException("Arrow IPC validation failed: dictionary values buffer is too short");
+    if (delta) d->host_values = old->host_values;
+    d->host_values.resize(static_cast<size_t>(n) * vw, 0);
+    uint8_t* dst = d->host_values.data() + static_cast<size_t>(n_old) * vw;
+    const uint8_t* src = b.body + sp[1].offset;
+    if (kind != MI_K_HALF_FLOAT) {
+      std::memcpy(dst, src, static_cast<size_t>(n_new) * vw);
+    } else {
+      for (int64_t i = 0; i < n_new; i++) {
+        uint16_t h;
+        std::memcpy(&h, src + 2 * i, 2);
+        const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16, exp = (h >> 10) & 0x1Fu;
+        uint32_t man = h & 0x3FFu, bits;
+        if (exp == 0x1F) bits = sign | 0x7F800000u | (man << 13);
+        else if (exp != 0) bits = sign | ((exp + 112u) << 23) | (man << 13);
+        else if (man == 0) bits = sign;
+        else {   // subnormal half: normalise
+          uint32_t e = 113;
+          while (!(man & 0x400u)) { man <<= 1; e--; }
+          bits = sign | (e << 23) | ((man & 0x3FFu) << 13);
+        }
+        std::memcpy(dst + 4 * i, &bits, 4);
+      }
+    }
   }
   set_bit(n, false);  // the extra NULL entry at index dict_len (ColumnArrowToDuckDBDictionary)
   MI_HIP_CHECK(hipMemcpyAsync(d->d_validity.get(), words, valid_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -1496,7 +1525,9 @@ int mi_scan_init(mi_scan* s, const char* const* projected_names, int32_t n_proje
 int mi_scan_set_filter(mi_scan* s, const mi_filter_node* nodes, int32_t n_nodes, int32_t root) {
   return WrapC([&] {
     if (!s || !nodes) throw InvalidInputException("mi_scan_set_filter: NULL argument");
-    s->scan->SetFilter(NormaliseFilter(nodes, n_nodes, root));
+    // the bind result tells what each leaf's constants are compared as (FLOAT / DOUBLE keys, 128-bit integers)
+    const std::vector<ScanColumn>& columns = s->scan->Bind();
+    s->scan->SetFilter(NormaliseFilter(nodes, n_nodes, root, &columns));
   });
 }
 

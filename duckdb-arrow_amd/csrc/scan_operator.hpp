@@ -67,11 +67,24 @@ struct FilterLeaf {
   std::vector<std::string> str_values;   // ... these byte strings (negate: none of them)
   //! kLeafStrRange: str_values = {lower, upper}; lo_open / hi_open = no such bound, the two below = the bound itself passes
   bool lo_incl = false, hi_incl = false;
+  //! FLOAT / DOUBLE column (width 4 / 8): an integer leaf as above (kLeafRange / kLeafIn) whose lo / hi / in_values are the
+  //! order-preserving keys of the constants (filter_key.hpp); the kernel maps every value the same way (kLeafFloat)
+  int32_t float_width = 0;
+  //! kLeafWideRange / kLeafWideIn: the column is HUGEINT / DECIMAL(19..38), a form of its own as strings are
+  bool is_wide = false;
+  __int128 wide_lo = 0, wide_hi = 0;     // wide_lo <= v <= wide_hi (negate: outside)
+  std::vector<__int128> wide_in;         // sorted, distinct
   int32_t out_col = -1;           // resolved at Init: index into the scan's filter columns
 };
 //! Conjunctive normal form: every clause is an OR of leaves, the filter is the AND of its clauses.
 using FilterCnf = std::vector<std::vector<FilterLeaf>>;
-FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root);  // scan_filter.cpp
+//! `columns` (the scan's bind result) tells what each leaf's constants are compared as: a FLOAT / DOUBLE column takes
+//! doubles, a 128-bit one 128-bit integers, and a constant kind that does not fit its column is refused naming the column.
+//! Without it (mi_scan_set_filter_range) every constant is a stored int64.
+FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root, const std::vector<ScanColumn>* columns = nullptr);  // scan_filter.cpp
+//! what a column's values are compared as by a pushed-down filter
+enum class FilterValueClass { kOther, kFloat32, kFloat64, kWide };
+FilterValueClass FilterClassOf(const ArrowField& field);
 
 //! One immutable version of a decoded dictionary (dict_len + 1 entries, the last one NULL).  Record batches keep the
 //! version they were enqueued with, so a later replacement / delta never changes what an in-flight batch sees.
@@ -92,6 +105,8 @@ struct DictState {
   //! predicates -- the dictionary is matched once, on the host, the rows by index (K6, kLeafDictMap)
   std::vector<std::string> host_strings;
   std::vector<char> host_valid;
+  //! FLOAT / DOUBLE / 128-bit dictionaries: the decoded values (out_width bytes each), for the same purpose
+  std::vector<uint8_t> host_values;
   std::map<size_t, std::shared_ptr<void>> match_maps;   // filter leaf -> device byte per entry: 0 no, 1 yes, 2 NULL
 };
 

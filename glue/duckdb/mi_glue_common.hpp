@@ -346,7 +346,37 @@ inline bool MiConstantToInt(const Value& v, int64_t& out) {
       return true;
     }
     default:
-      return false;  // floats, hugeints, intervals: compared by DuckDB above the scan
+      return false;  // intervals and the rest: compared by DuckDB above the scan (floats and hugeints: MiConstantToNumber)
+  }
+}
+
+//! A numeric constant as mi_filter_node carries it: FLOAT / DOUBLE as the bits of a double (MI_FV_DOUBLE; the scan rounds a
+//! FLOAT column's constant back to float32, exactly), HUGEINT / DECIMAL(19..38) as two words (MI_FV_INT128), everything
+//! MiConstantToInt takes as the stored int64 (MI_FV_INT64).
+inline bool MiConstantToNumber(const Value& v, int32_t& kind, int64_t& low, int64_t& high) {
+  if (v.IsNull()) {
+    return false;
+  }
+  high = 0;
+  switch (v.type().InternalType()) {
+    case PhysicalType::FLOAT:
+    case PhysicalType::DOUBLE: {
+      const double d = v.type().InternalType() == PhysicalType::FLOAT ? static_cast<double>(v.GetValueUnsafe<float>())
+                                                                      : v.GetValueUnsafe<double>();
+      memcpy(&low, &d, sizeof(double));
+      kind = MI_FV_DOUBLE;
+      return true;
+    }
+    case PhysicalType::INT128: {
+      const auto h = v.GetValueUnsafe<hugeint_t>();
+      memcpy(&low, &h.lower, sizeof(int64_t));
+      high = h.upper;
+      kind = MI_FV_INT128;
+      return true;
+    }
+    default:
+      kind = MI_FV_INT64;
+      return MiConstantToInt(v, low);
   }
 }
 
@@ -428,7 +458,7 @@ class MiFilterTranslator {
       n.str_len = NumericCast<int32_t>(out.strings.back()->size());
       return true;
     }
-    return MiConstantToInt(v, n.value);
+    return MiConstantToNumber(v, n.value_kind, n.value, n.value_hi);
   }
 
   static int32_t FlipComparison(int32_t op) {
@@ -518,6 +548,7 @@ class MiFilterTranslator {
         } else {
           out.in_lists.push_back(make_uniq<vector<int64_t>>());
         }
+        auto highs = make_uniq<vector<int64_t>>();  // MI_FV_INT128: the high words of the list
         for (idx_t i = 1; i < opx.children.size(); i++) {
           if (opx.children[i]->GetExpressionClass() != ExpressionClass::BOUND_CONSTANT) {
             return false;
@@ -531,11 +562,14 @@ class MiFilterTranslator {
             out.str_ptrs.back()->push_back(out.strings.back()->data());
             out.str_lens.back()->push_back(NumericCast<int32_t>(out.strings.back()->size()));
           } else {
-            int64_t x;
-            if (!MiConstantToInt(v, x)) {
+            int32_t kind;
+            int64_t low, high;
+            if (!MiConstantToNumber(v, kind, low, high) || (i > 1 && kind != tree[at].value_kind)) {
               return false;
             }
-            out.in_lists.back()->push_back(x);
+            tree[at].value_kind = kind;
+            out.in_lists.back()->push_back(low);
+            highs->push_back(high);
           }
         }
         if (strings) {
@@ -543,6 +577,10 @@ class MiFilterTranslator {
           tree[at].str_lens = out.str_lens.back()->data();
         } else {
           tree[at].values = out.in_lists.back()->data();
+          if (tree[at].value_kind == MI_FV_INT128) {
+            out.in_lists.push_back(std::move(highs));
+            tree[at].values_hi = out.in_lists.back()->data();
+          }
         }
         return true;
       }

@@ -442,6 +442,12 @@ int mi_hbm_fetch(mi_hbm* h, int32_t from_stream, int64_t offset, int64_t length,
  * vectors.  sel_out[window*2048 ...] holds ascending window-relative row indices, count_out[window] their number. */
 int mi_filter_range(mi_ctx* ctx, const void* values, int32_t width, const void* validity, int64_t nrows, int64_t lo,
                     int64_t hi, mi_sel_t* sel_out, uint32_t* count_out, void* stream);
+/* The same one-leaf launch for the typed leaves of mi_scan_set_filter: lo <= v <= hi (both inclusive) on a FLOAT / DOUBLE
+ * vector (value_kind MI_FV_DOUBLE, width 4 / 8, bounds[2] = the bits of two doubles, DuckDB's total order) or on a
+ * hugeint_t vector (MI_FV_INT128, width 16, bounds[4] = lo low, lo high, hi low, hi high).  The 128-bit bounds travel to
+ * the device and the call waits for the kernel; the floating-point form is asynchronous like mi_filter_range. */
+int mi_filter_between(mi_ctx* ctx, const void* values, int32_t width, const void* validity, int64_t nrows, int32_t value_kind,
+                      const int64_t* bounds, mi_sel_t* sel_out, uint32_t* count_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Scan operator.  Replaces the TableFunction bodies: read_arrow (src/scanner/read_arrow.cpp:43-86 via
@@ -551,7 +557,10 @@ typedef struct mi_data_chunk {
  * hands a scan: col <op> constant with = <> < <= > >=, IS NULL, IS NOT NULL, IN (list), combined
  * by AND / OR trees over any number of columns.  Comparison columns are fixed-width integer-like after the scan
  * (integers, BOOLEAN, DATE, TIME / TIMESTAMP, DECIMAL(<=18)) and constants are the stored integers (DECIMAL(15,2) 0.05
- * is 5), or VARCHAR / BLOB columns with = <> < <= > >= IN and MI_F_STARTS_WITH against byte strings (byte-wise order,
+ * is 5); FLOAT / DOUBLE columns against IEEE doubles (MI_FV_DOUBLE) in DuckDB's total order -- every NaN equals every
+ * other NaN and is greater than everything else, +inf included, and -0.0 = +0.0; a constant for a FLOAT column is rounded
+ * to float32 first, as DuckDB casts it to the column's type; HUGEINT / DECIMAL(19..38) columns against 128-bit stored
+ * integers (MI_FV_INT128, or MI_FV_INT64 sign-extended); or VARCHAR / BLOB columns with = <> < <= > >= IN and MI_F_STARTS_WITH against byte strings (byte-wise order,
  * a proper prefix sorts first: DuckDB's default collation); IS [NOT] NULL takes any column.  SQL semantics: a comparison with NULL is not true, so the row is dropped
  * unless another branch of an OR keeps it.  A filter column need not be projected.  The tree is normalised to at most
  * 24 leaves in conjunctive normal form; larger ones are refused with MI_ENOTSUP (DuckDB then keeps the filter above the
@@ -562,6 +571,15 @@ enum mi_filter_op {
   MI_F_IN = 9, MI_F_STARTS_WITH = 10 /* VARCHAR / BLOB: the row begins with str_value (LIKE 'abc%', prefix()) */,
   MI_F_AND = 16, MI_F_OR = 17
 };
+/* What mi_filter_node.value / values[] hold.  A kind that does not fit the column (a double against an integer column, an
+ * int64 against a DOUBLE column, 128 bits against a narrow column) is MI_EINVAL naming the column. */
+enum mi_filter_value_kind {
+  MI_FV_INT64 = 0,   /* the stored integers (every caller that leaves the field zero, as all did while it was padding) */
+  MI_FV_DOUBLE = 1,  /* the bits of IEEE doubles (FLOAT / DOUBLE columns) */
+  MI_FV_INT128 = 2   /* the low words of 128-bit integers, their high words in value_hi / values_hi[] (HUGEINT, DECIMAL(19..38)) */
+};
+/* The struct grew by value_hi / values_hi behind str_lens: callers are recompiled with this header and zero their nodes
+ * (memset), as the DuckDB glue does; the Python binding's _ffi.FilterNode mirrors it field by field. */
 typedef struct mi_filter_node {
   int32_t op;             /* enum mi_filter_op */
   int32_t first_child;    /* MI_F_AND / MI_F_OR: the children are nodes[first_child .. first_child + n_children) */
@@ -575,9 +593,11 @@ typedef struct mi_filter_node {
    * takes str_values / str_lens; byte-wise comparison like DuckDB's.  Leave NULL for the integer forms above. */
   const char* str_value;
   int32_t str_len;
-  int32_t _pad;
+  int32_t value_kind;     /* enum mi_filter_value_kind: what value / values[] hold; 0 = stored integers */
   const char* const* str_values;
   const int32_t* str_lens;
+  int64_t value_hi;          /* MI_FV_INT128: the high word of `value` (two's complement) */
+  const int64_t* values_hi;  /* MI_FV_INT128 with MI_F_IN: the high words of values[] */
 } mi_filter_node;
 int mi_scan_set_filter(mi_scan* s, const mi_filter_node* nodes, int32_t n_nodes, int32_t root);
 /* Shorthand for lo <= column < hi. */
@@ -722,6 +742,14 @@ int mi_ipc_serialize_chunks(mi_writer* w, const mi_data_chunk* chunks, int32_t n
  * kernel (csrc/lz4_encode_format.hpp), whose bytes the kernel's equal.  *size = bytes written; when `out` is NULL or
  * `cap` is too small nothing is written and *size = the room a call needs. */
 int mi_lz4_frame_compress_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t cap, int64_t* size);
+
+/* Test and verification hook, host only: the order-preserving key the filter kernel (K6) compares a FLOAT (width 4: `v` is
+ * rounded to float32 first) or DOUBLE (width 8) value by -- the function the kernel compiles (csrc/filter_key.hpp).  Keys
+ * compare as signed integers the way DuckDB orders the values: all NaNs equal and greatest, -0.0 = +0.0. */
+int mi_filter_float_key(double v, int32_t width, int64_t* key);
+/* Debug getter: launches of the filter kernel by this process so far.  *base counts the instance every program of integer,
+ * string and dictionary leaves runs, *extended the one launched for programs with a FLOAT / DOUBLE / 128-bit leaf. */
+int mi_filter_launch_counts(int64_t* base, int64_t* extended);
 
 #ifdef __cplusplus
 }

@@ -1,47 +1,76 @@
-"""Kernel-level timing of K6 on resident int32 / int64 values: the one-leaf range (mi_filter_range) and, through the scan
-operator's own entry points, a compacting gather (transcode_gather) behind it.  HIP-event-free: wall clock around 20 launches."""
-import sys, os, time, json
+"""Kernel-level timing of K6 on resident values: the one-leaf range (mi_filter_range on int32 / int64, mi_filter_between on
+float32 / float64 / int128 -- the same rows pass in every dtype) and, for int32, a compacting gather (transcode_gather)
+behind it through the scan operator's own entry points; for int128, transcode_copy over the same column as its yardstick.
+HIP-event-free: wall clock around 20 launches."""
+import argparse, sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import duckdb_arrow_amd as da
 from duckdb_arrow_amd import _ffi
+ap = argparse.ArgumentParser()
+ap.add_argument("--dtype", choices=["int32", "int64", "float32", "float64", "int128"], default="int32")
+ap.add_argument("--rows", type=int, default=240_000_000)
+args = ap.parse_args()
 ctx = da.Context(0)
-n = 240_000_000
+n = args.rows
 out = {"rows": n}
-vals = torch.randint(8036, 10562, (n,), dtype=torch.int32, device="cuda")
+width = {"int32": 4, "int64": 8, "float32": 4, "float64": 8, "int128": 16}[args.dtype]
+ints = torch.randint(8036, 10562, (n,), dtype=torch.int64 if width > 4 else torch.int32, device="cuda")
+if args.dtype == "int128":     # hugeint_t{uint64 lower; int64 upper}, upper = 0
+    vals = torch.zeros((n, 2), dtype=torch.int64, device="cuda")
+    vals[:, 0] = ints
+    del ints
+elif args.dtype.startswith("float"):
+    vals = ints.to(torch.float32 if width == 4 else torch.float64)
+    del ints
+else:
+    vals = ints
 sel = torch.empty(n, dtype=torch.int32, device="cuda")
 cnt = torch.zeros((n + 2047) // 2048, dtype=torch.int32, device="cuda")
 s = torch.cuda.current_stream().cuda_stream
-for _ in range(3):
-    da.filter_range(ctx, vals.data_ptr(), 4, 0, n, 8766, 9131, sel.data_ptr(), cnt.data_ptr(), s)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(20):
-    da.filter_range(ctx, vals.data_ptr(), 4, 0, n, 8766, 9131, sel.data_ptr(), cnt.data_ptr(), s)
-torch.cuda.synchronize()
-ms = (time.perf_counter() - t0) / 20 * 1e3
+if args.dtype in ("int32", "int64"):
+    launch = lambda: da.filter_range(ctx, vals.data_ptr(), width, 0, n, 8766, 9131, sel.data_ptr(), cnt.data_ptr(), s)
+else:   # lo <= v <= hi: the rows of 8766 <= v < 9131
+    launch = lambda: da.filter_between(ctx, vals.data_ptr(), width, 0, n, 8766, 9130, sel.data_ptr(), cnt.data_ptr(), s)
+
+
+def timed(fn, reps=20):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+ms = timed(launch)
 k = int(cnt.sum().item())
-alg = 4 * n + 4 * k + cnt.numel() * 4
-out["filter_program_range_int32"] = {"ms": ms, "G_rows_per_s": n / ms / 1e6, "selectivity": k / n, "algorithmic_bytes": alg, "GBps": alg / ms / 1e6}
-# late materialisation behind it: an int64 column gathered through the selection vector into a dense array
-src = torch.randint(0, 1 << 40, (n,), dtype=torch.int64, device="cuda")
-dst = torch.empty(k + 64, dtype=torch.int64, device="cuda")
-task = da.make_task(_ffi.K_COPY, n, src.data_ptr(), dst.data_ptr(), param=8, null_count=0, sel=sel.data_ptr(), sel_count=cnt.data_ptr())
-plan = da.Plan(ctx, [task])
-for _ in range(3):
-    plan.launch(s)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(20):
-    plan.launch(s)
-torch.cuda.synchronize()
-ms = (time.perf_counter() - t0) / 20 * 1e3
-assert plan.status() == 0
-# spot check against torch
-w0 = int(cnt[0].item())
-want = src[:2048][sel[:w0].long()]
-assert torch.equal(dst[:w0], want)
-alg = 4 * k + 8 * k + 8 * k + cnt.numel() * 4   # sel + the selected values in and out
-out["transcode_gather_int64"] = {"ms": ms, "selected": k, "algorithmic_bytes": alg, "GBps": alg / ms / 1e6,
-                                 "note": "the source column is touched sector-wise: at 14 % selectivity nearly every 64-byte line holds a selected row"}
+alg = width * n + 4 * k + cnt.numel() * 4
+out["filter_program_range_" + args.dtype] = {"ms": ms, "G_rows_per_s": n / ms / 1e6, "selectivity": k / n, "algorithmic_bytes": alg, "GBps": alg / ms / 1e6}
+out["filter_launches_base_extended"] = list(da.filter_launch_counts())
+if args.dtype == "int128":
+    out["filter_program_range_int128"]["note"] = "every launch uploads its 32 bytes of bounds and waits for the kernel (mi_filter_between)"
+    # the yardstick: the flat copy of the same column (16 bytes in, 16 bytes out per row)
+    dst = torch.empty((n, 2), dtype=torch.int64, device="cuda")
+    plan = da.Plan(ctx, [da.make_task(_ffi.K_COPY, n, vals.data_ptr(), dst.data_ptr(), param=16, null_count=0)])
+    ms = timed(lambda: plan.launch(s))
+    assert plan.status() == 0 and torch.equal(dst[:4096], vals[:4096])
+    out["transcode_copy_int128"] = {"ms": ms, "algorithmic_bytes": 32 * n, "GBps": 32 * n / ms / 1e6}
+if args.dtype == "int32":
+    # late materialisation behind it: an int64 column gathered through the selection vector into a dense array
+    src = torch.randint(0, 1 << 40, (n,), dtype=torch.int64, device="cuda")
+    dst = torch.empty(k + 64, dtype=torch.int64, device="cuda")
+    task = da.make_task(_ffi.K_COPY, n, src.data_ptr(), dst.data_ptr(), param=8, null_count=0, sel=sel.data_ptr(), sel_count=cnt.data_ptr())
+    plan = da.Plan(ctx, [task])
+    ms = timed(lambda: plan.launch(s))
+    assert plan.status() == 0
+    # spot check against torch
+    w0 = int(cnt[0].item())
+    want = src[:2048][sel[:w0].long()]
+    assert torch.equal(dst[:w0], want)
+    alg = 4 * k + 8 * k + 8 * k + cnt.numel() * 4   # sel + the selected values in and out
+    out["transcode_gather_int64"] = {"ms": ms, "selected": k, "algorithmic_bytes": alg, "GBps": alg / ms / 1e6,
+                                     "note": "the source column is touched sector-wise: at 14 % selectivity nearly every 64-byte line holds a selected row"}
 print(json.dumps(out))

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-kernel register / LDS / occupancy table of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage)."""
+"""Per-kernel register / LDS / occupancy table of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage).  Template
+instances are listed one line each under their own names: transcode_dec128<NULLS>, and filter_program<false> (integer, string
+and dictionary leaves) beside filter_program<true> (with the FLOAT / DOUBLE / 128-bit leaves)."""
 import glob, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "duckdb-arrow_amd", "csrc")

@@ -146,7 +146,7 @@ class HbmStream {
   }
 
   ~HbmStream() {
-    try { ctx->Bind(); } catch (...) {}
+    try { ctx->Bind(); } catch (...) { (void)hipGetLastError(); }   // nothing to report to; leave no stale error to the host's next HIP call
     plan.reset();
   }
 

@@ -170,16 +170,20 @@ __device__ __forceinline__ void encode_string_tile_generic(const mi_col_task& t,
     if (k * kBlockThreads >= n) break;  // uniform
     u32x4 s = {0u, 0u, 0u, 0u};
     uint32_t len = 0;
+    int64_t len64 = 0;  // a list_entry_t's length is all 64 bits of its second word; a string_t's the dword in front
     if (r < n) {
       s = str[r];
-      len = enc_row_valid(valid, has, row0 + r) ? (t.kind == MI_K_ENC_LIST32 ? s.z : s.x) : 0u;
+      if (enc_row_valid(valid, has, row0 + r)) {
+        if (t.kind == MI_K_ENC_LIST32) len64 = static_cast<int64_t>(static_cast<uint64_t>(s.z) | (static_cast<uint64_t>(s.w) << 32));
+        else len64 = len = s.x;
+      }
     }
     int64_t total;
-    const int64_t ex = block_exclusive_scan(static_cast<int64_t>(len), &total, lds4);
+    const int64_t ex = block_exclusive_scan(len64, &total, lds4);
     const int64_t pos = base + ex;
     if (r < n) {
-      if (large) off64[row0 + r + 1] = pos + len;
-      else off[row0 + r + 1] = static_cast<int32_t>(pos + len);
+      if (large) off64[row0 + r + 1] = pos + len64;
+      else off[row0 + r + 1] = static_cast<int32_t>(pos + len64);
     }
     if (t.kind == MI_K_ENC_LIST32) {  // offsets only
       base += total;
@@ -406,8 +410,8 @@ __global__ __launch_bounds__(kBlockThreads, 8) void encode_string_1p(const mi_co
   const bool large = (t.flags & 1) != 0;  // LargeUtf8 / LargeList: int64 offsets (arrow_large_buffer_size)
   // The length pass reads two dwords per row (the length field: dword 0 of a string_t, the low dword of a list_entry_t's
   // length; and the dword behind it: a string_t's first four bytes, all there is to a string of <= 4 bytes -- a tile of
-  // flags or codes is encoded below from these registers alone).  The loads leave before the validity words are even
-  // asked for: the length of a NULL row is read and then ignored.
+  // flags or codes is encoded below from these registers alone --, the high dword of a list_entry_t's length).  The loads
+  // leave before the validity words are even asked for: the length of a NULL row is read and then ignored.
   uint32_t pre_len[kTileRows / kBlockThreads], pre_bytes[kTileRows / kBlockThreads];
   {
     gptr<const u32x2> lens = (gptr<const u32x2>)(GC<uint32_t>(t.buf1) + 4 * row0 + (is_list ? 2 : 0));
@@ -433,8 +437,10 @@ __global__ __launch_bounds__(kBlockThreads, 8) void encode_string_1p(const mi_co
 #pragma unroll
     for (int k = 0; k < kTileRows / kBlockThreads; k++) {
       const int r = static_cast<int>(threadIdx.x) + k * kBlockThreads;
-      const uint32_t l = (r < n && ((s_valid[r >> 6] >> (r & 63)) & 1)) ? pre_len[k] : 0u;
+      const bool row_ok = r < n && ((s_valid[r >> 6] >> (r & 63)) & 1);
+      const uint32_t l = row_ok ? pre_len[k] : 0u;
       local += l;
+      if (is_list && row_ok) local += static_cast<unsigned long long>(pre_bytes[k]) << 32;  // uniform: list lengths are 64 bits
       longest = longest > l ? longest : l;
       const uint32_t incl = wave_inclusive_scan_u32(l);
       if (lane == 63) s_wtot[k * kWaves + wave] = incl;

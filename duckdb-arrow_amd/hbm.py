@@ -7,6 +7,7 @@ over, launching, and turning the layout into numpy views for the tests.  Device 
 `memory="torch"` asks for torch tensors (tests that want to poke at the buffers with torch).
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -19,7 +20,9 @@ class _PlanView:
     """The stream's plan seen through mi_hbm_* (stats / timed launches), shaped like duckdb_arrow_amd.Plan."""
 
     def __init__(self, owner):
-        self._o = owner
+        # a weak reference: with a strong one every HbmStream is a reference cycle, freed only by the cycle collector, which
+        # finalises it and its Context in any order (the library then closes a stream whose context is gone)
+        self._o = weakref.proxy(owner)
 
     @property
     def n_tasks(self):

@@ -288,7 +288,8 @@ typedef struct mi_col_task {
                              will lie in the Arrow data buffer (an Arrow data buffer itself, or a heap staged in row order
                              with the slots of inline strings left open) they are moved as one coalesced copy. */
   void* out_data;         /* DuckDB vector data, nrows * out_width bytes (encode: Arrow buffer 1) */
-  void* out_validity;     /* mi_validity_t[ceil(nrows/64)] or NULL to skip (encode: Arrow bitmap) */
+  void* out_validity;     /* mi_validity_t[ceil(nrows/64)] or NULL to skip (encode: Arrow bitmap, ceil(nrows/8) bytes at any
+                             byte alignment) */
   void* out_aux;          /* encode: Arrow buffer 2 (string data); decode: validity words of the PARENT vector when NULLs
                              propagate from it (struct / fixed_size_list parents), else NULL */
   uint64_t ptr_base;      /* address the consumer will see for byte 0 of buf2 (string_t long-string pointers) */

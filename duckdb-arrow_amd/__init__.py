@@ -304,6 +304,13 @@ def filter_launch_counts():
     return base.value, ext.value
 
 
+def writer_fused_counts():
+    """(row groups the fused COPY pump encoded where the scan decoded them, string-view columns among them) by this process."""
+    groups, views = C.c_int64(), C.c_int64()
+    _ffi.check(_ffi.lib().mi_writer_fused_counts(C.byref(groups), C.byref(views)))
+    return groups.value, views.value
+
+
 # ---------------------------------------------------------------------------------------------------- logical views
 def _valid_bits(validity_ptr, n, shift=0):
     """`shift`: bit of the first word that belongs to row 0 (mi_vector.validity_shift, nested children only)."""
@@ -899,19 +906,22 @@ class Connection:
         finally:
             L.mi_writer_close(w)
 
-    def copy_to(self, table, path, preserve_insertion_order=True, file_size_bytes=None, arrow_large_buffer_size=False, **options):
+    def copy_to(self, table, path, preserve_insertion_order=True, file_size_bytes=None, arrow_large_buffer_size=False,
+                produce_arrow_string_view=False, **options):
         """COPY table TO 'path' (FORMAT ARROWS, row_group_size ..., chunk_size ..., row_group_size_bytes ...,
         row_groups_per_file ..., kv_metadata {...}, compression ...).  With row_groups_per_file / file_size_bytes `path`
         becomes a directory of data_<i>.arrows files, like DuckDB's file rotation.  compression (or codec) = "lz4" /
         "lz4_frame" writes record batches with BodyCompression LZ4_FRAME, compressed on the GPU -- any Arrow reader takes
         them, and a device-resident read_arrow expands them in HBM; "none" / "uncompressed" is the default; "zstd" is
         refused (ZSTD bodies are read, not written).  File sizes that rotation counts are compressed sizes.  Returns the
-        list of files written."""
+        list of files written.  produce_arrow_string_view is DuckDB's setting of that name: VARCHAR fields at any depth are
+        written as Arrow string views (Utf8View), whatever arrow_large_buffer_size says, which BLOB and LIST keep following."""
         L = _ffi.lib()
         o = _ffi.WriteOptions()
         _ffi.check(L.mi_write_options_init(C.byref(o)))
         o.preserve_insertion_order = int(preserve_insertion_order)
         o.arrow_large_buffer_size = int(arrow_large_buffer_size)   # SET arrow_large_buffer_size=true
+        o.produce_arrow_string_view = int(produce_arrow_string_view)   # SET produce_arrow_string_view=true
         for k, v in options.items():
             if k.lower() == "kv_metadata":
                 if not isinstance(v, dict):

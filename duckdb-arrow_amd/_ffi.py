@@ -18,7 +18,7 @@ K_COPY, K_BOOL, K_DEC128, K_DATE64, K_MUL_I32, K_MUL_I64, K_DIV_I64, K_STR32, K_
     K_DURATION, K_INTERVAL_MONTHS, K_INTERVAL_MDN, K_NARROW, K_HALF_FLOAT, K_NULL, K_STRVIEW, K_LIST32, K_LIST64, \
     K_STRUCT = range(1, 22)
 K_RUN_END = 22
-K_ENC_COPY, K_ENC_DEC128, K_ENC_BOOL, K_ENC_STR32, K_ENC_VALIDITY, K_ENC_LIST32 = 32, 33, 34, 35, 36, 37
+K_ENC_COPY, K_ENC_DEC128, K_ENC_BOOL, K_ENC_STR32, K_ENC_VALIDITY, K_ENC_LIST32, K_ENC_STRVIEW = 32, 33, 34, 35, 36, 37, 38
 
 ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL_RANGE, ST_OFFSET_OVERFLOW, ST_DICT_INDEX, ST_INTERNAL = \
     1, 2, 4, 8, 16, 32, 64, 128
@@ -160,7 +160,8 @@ class WriteOptions(C.Structure):
                 ("row_group_size_bytes_set", C.c_int32), ("preserve_insertion_order", C.c_int32),
                 ("n_kv_metadata", C.c_int32), ("kv_keys", (C.c_char * 64) * MAX_KV),
                 ("kv_values", (C.c_char * 256) * MAX_KV), ("kv_value_lens", C.c_int32 * MAX_KV),
-                ("arrow_large_buffer_size", C.c_int32), ("compression", C.c_int32)]
+                ("arrow_large_buffer_size", C.c_int32), ("produce_arrow_string_view", C.c_int32),
+                ("reserved_view", C.c_int32), ("compression", C.c_int32)]
 
 
 class ScanStats(C.Structure):
@@ -217,6 +218,7 @@ SIGNATURES = {
     "mi_filter_between": (C.c_int, [P, P, C.c_int32, P, C.c_int64, C.c_int32, C.POINTER(C.c_int64), P, P, P]),
     "mi_filter_float_key": (C.c_int, [C.c_double, C.c_int32, C.POINTER(C.c_int64)]),
     "mi_filter_launch_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mi_writer_fused_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mi_scan_set_filter_range": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64]),
     "mi_scan_set_filter": (C.c_int, [P, C.POINTER(FilterNode), C.c_int32, C.c_int32]),
     "mi_scan_open_files_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32,

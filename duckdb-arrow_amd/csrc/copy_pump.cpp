@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -233,7 +235,9 @@ bool FusedSinkPossible(mi_writer* w, ArrowScan* scan) {
     if (cols[c].is_constant()) return false;
     const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
     if (!wc.children.empty()) return false;
-    if (wc.enc_kind != MI_K_ENC_COPY && wc.enc_kind != MI_K_ENC_DEC128 && wc.enc_kind != MI_K_ENC_BOOL && wc.enc_kind != MI_K_ENC_STR32) return false;
+    if (wc.enc_kind != MI_K_ENC_COPY && wc.enc_kind != MI_K_ENC_DEC128 && wc.enc_kind != MI_K_ENC_BOOL && wc.enc_kind != MI_K_ENC_STR32 &&
+        wc.enc_kind != MI_K_ENC_STRVIEW)
+      return false;
   }
   return true;
 }
@@ -305,7 +309,9 @@ void FusedPump::FinishEncoded(WriteJob* job) {
   const std::vector<int64_t> nulls = e.plan->MapNullCounts(e.h_nulls.get<int64_t>());
   std::vector<std::pair<int64_t, int64_t>> nodes;
   for (size_t c = 0; c < n_cols; c++) nodes.emplace_back(e.nrows, nulls[c]);
-  job->header = EncodeRecordBatchMessage(e.nrows, nodes, e.file_spans, e.file_body_size, compressed ? 0 : -1);
+  int64_t n_view_fields = 0;
+  for (size_t c = 0; c < n_cols; c++) n_view_fields += WriterColumn(c).enc_kind == MI_K_ENC_STRVIEW;
+  job->header = EncodeRecordBatchMessage(e.nrows, nodes, e.file_spans, e.file_body_size, compressed ? 0 : -1, n_view_fields);
   job->body = e.h_body.get();
   job->body_size = static_cast<size_t>(e.file_body_size);
 }
@@ -358,6 +364,37 @@ int64_t PayloadOf(const DeviceColumnView& v, int64_t r0, int64_t m) {
   return total;
 }
 
+// row groups the fused pump has encoded where they lay in HBM, and string-view columns among them (mi_writer_fused_counts)
+std::atomic<int64_t> g_fused_row_groups{0}, g_fused_view_columns{0};
+
+// bytes of the valid strings of more than 12 bytes among rows [r0, r0 + m): the size of a view column's data buffer.  Always a
+// pass over the offsets (timed: MI_WRITER_TIMING reports it as "view sizing").
+int64_t LongPayloadOf(const DeviceColumnView& v, int64_t r0, int64_t m) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool nulls = v.null_count != 0 && v.h_validity;
+  int64_t total = 0;
+  auto sum = [&](auto zero) {
+    using T = decltype(zero);
+    T prev;
+    std::memcpy(&prev, v.h_offsets + r0 * static_cast<int64_t>(sizeof(T)), sizeof(T));
+    for (int64_t i = r0; i < r0 + m; i++) {
+      T next;
+      std::memcpy(&next, v.h_offsets + (i + 1) * static_cast<int64_t>(sizeof(T)), sizeof(T));
+      const int64_t len = static_cast<int64_t>(next) - static_cast<int64_t>(prev);
+      prev = next;
+      if (len > 12 && (!nulls || ((v.h_validity[i >> 3] >> (i & 7)) & 1))) total += len;
+    }
+  };
+  if (v.offset_width == 8) sum(int64_t{0});
+  else sum(int32_t{0});
+  if (Timers().on) {
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(Timers().mu);
+    Timers().view_sizing += dt;
+  }
+  return total;
+}
+
 // can rows of this batch be encoded where they lie?
 bool FusedPump::ViewsOf(const BatchRef& ref, std::vector<DeviceColumnView>* views) {
   views->resize(n_cols);
@@ -367,7 +404,7 @@ bool FusedPump::ViewsOf(const BatchRef& ref, std::vector<DeviceColumnView>* view
     if (!v.flat) return false;
     const auto& wc = WriterColumn(c);
     const bool is_string = v.kind == MI_K_STR32 || v.kind == MI_K_STR64;
-    if (wc.enc_kind == MI_K_ENC_STR32) {
+    if (wc.enc_kind == MI_K_ENC_STR32 || wc.enc_kind == MI_K_ENC_STRVIEW) {
       if (!is_string) return false;
     } else if (is_string || v.width != wc.width || v.kind == MI_K_STRVIEW || v.kind == MI_K_FIXED_BINARY) {
       return false;
@@ -399,8 +436,11 @@ void FusedPump::EncodeOnGpu(int tok, const std::vector<DeviceColumnView>& views,
   std::vector<EncodeNode> nodes(n_cols);
   for (size_t c = 0; c < n_cols; c++) {
     const auto& wc = WriterColumn(c);
-    nodes[c] = EncodeNode{wc.enc_kind, wc.param, wc.large_offsets, m, wc.enc_kind == MI_K_ENC_STR32 ? PayloadOf(views[c], r0, m) : 0};
+    const int64_t payload = wc.enc_kind == MI_K_ENC_STR32 ? PayloadOf(views[c], r0, m) : wc.enc_kind == MI_K_ENC_STRVIEW ? LongPayloadOf(views[c], r0, m) : 0;
+    nodes[c] = EncodeNode{wc.enc_kind, wc.param, wc.large_offsets, m, payload};
   }
+  g_fused_row_groups++;
+  for (size_t c = 0; c < n_cols; c++) g_fused_view_columns += nodes[c].kind == MI_K_ENC_STRVIEW;
   LayOutBody(nodes, &e.layout);
   const size_t body_bytes = static_cast<size_t>(e.layout.body_size);
   Fit(e.d_body, body_bytes + 256);
@@ -561,5 +601,12 @@ extern "C" int mi_writer_sink_scan(mi_writer* w, mi_scan* scan, int64_t* rows) {
     n += ch.size;
   }
   if (rows) *rows = n;
+  return MI_OK;
+}
+
+extern "C" int mi_writer_fused_counts(int64_t* row_groups, int64_t* view_columns) {
+  if (!row_groups || !view_columns) return WrapC([] { throw InvalidInputException("mi_writer_fused_counts: NULL argument"); });
+  *row_groups = g_fused_row_groups.load();
+  *view_columns = g_fused_view_columns.load();
   return MI_OK;
 }

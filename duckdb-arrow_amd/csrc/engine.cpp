@@ -112,7 +112,7 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
   auto fail = [&](const std::string& what) {
     throw InvalidInputException("task " + std::to_string(i) + ": " + what);
   };
-  if (t.kind != MI_K_RUN_END && device::ClassOfKind(t.kind) < 0) fail("unknown kind " + std::to_string(t.kind));
+  if (t.kind != MI_K_RUN_END && t.kind != MI_K_ENC_STRVIEW && device::ClassOfKind(t.kind) < 0) fail("unknown kind " + std::to_string(t.kind));
   if (t.sel != nullptr) {  // gather mode: decode only the rows a selection vector names, compacted per 2048-row window
     if (!device::KindCanGather(t.kind)) fail("kind " + std::to_string(t.kind) + " cannot be decoded through a selection vector");
     if (t.sel_count == nullptr) fail("gather tasks need sel_count (rows selected per 2048-row window)");
@@ -198,6 +198,7 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
       if (t.param != 2 && t.param != 4 && t.param != 8) fail("ENC_DEC128 in width must be 2,4,8");
       break;
     case MI_K_ENC_STR32:
+    case MI_K_ENC_STRVIEW:
       if (t.out_aux == nullptr) fail("out_aux (string data) is NULL");
       if (reinterpret_cast<uintptr_t>(t.buf1) % 16 != 0) fail("string_t vector must be 16-byte aligned");
       break;
@@ -212,6 +213,8 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
 
 // staging key of run-end tasks in Plan::Set (not a kernel class: they launch transcode_run_end, kernels_run_end.hip)
 constexpr int kRunEndSlot = device::kNumClasses;
+// ... and of string-view encode tasks (encode_string_view, kernels_encode_view.hip); their bytes count under kClassEncString
+constexpr int kEncViewSlot = device::kNumClasses + 1;
 
 static int64_t TaskBytesRead(const mi_col_task& t) {
   const int64_t n = t.nrows;
@@ -246,10 +249,10 @@ static int64_t TaskBytesRead(const mi_col_task& t) {
     switch (t.kind) {
       case MI_K_ENC_COPY: case MI_K_ENC_DEC128: b += n * t.param; break;
       case MI_K_ENC_BOOL: b += n; break;
-      case MI_K_ENC_STR32: case MI_K_ENC_LIST32: b += n * 16; break;  // + payload, known only after the scan (reported via buf2_len if given)
+      case MI_K_ENC_STR32: case MI_K_ENC_LIST32: case MI_K_ENC_STRVIEW: b += n * 16; break;  // + payload, known only after the scan (reported via buf2_len if given)
       default: break;
     }
-    if (t.kind == MI_K_ENC_STR32) b += t.buf2_len;
+    if (t.kind == MI_K_ENC_STR32 || t.kind == MI_K_ENC_STRVIEW) b += t.buf2_len;   // (views: the long strings alone)
   }
   return b;
 }
@@ -266,6 +269,7 @@ static int64_t TaskBytesWritten(const mi_col_task& t) {
     case MI_K_ENC_BOOL: b += (n + 7) / 8; break;
     case MI_K_ENC_STR32: b += (n + 1) * ((t.flags & 1) ? 8 : 4) + t.buf2_len; break;
     case MI_K_ENC_LIST32: b += (n + 1) * ((t.flags & 1) ? 8 : 4); break;
+    case MI_K_ENC_STRVIEW: b += n * 16 + t.buf2_len; break;
     default: break;
   }
   return b;
@@ -316,8 +320,8 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
     ValidateTask(in_tasks[i], static_cast<size_t>(i));
     mi_col_task t = in_tasks[i];
     // run-end expansion lives outside kernels_decode.hip: its bytes count under the misc class, its slices go last
-    const bool run_end = t.kind == MI_K_RUN_END;
-    const int cls = run_end ? static_cast<int>(device::kClassMisc) : device::ClassOfTask(t);
+    const bool run_end = t.kind == MI_K_RUN_END, enc_view = t.kind == MI_K_ENC_STRVIEW;
+    const int cls = run_end ? static_cast<int>(device::kClassMisc) : enc_view ? static_cast<int>(device::kClassEncString) : device::ClassOfTask(t);
     if (t.kind >= MI_K_ENC_COPY) {
       is_encode = true;
       t.depth = 0;
@@ -331,20 +335,23 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
     class_rows[cls] += t.nrows;
     max_depth = std::max(max_depth, t.depth);
     staged.push_back(t);
-    staged_cls.push_back(run_end ? kRunEndSlot : cls);
+    staged_cls.push_back(run_end ? kRunEndSlot : enc_view ? kEncViewSlot : cls);
   }
   n_null_counts = null_counter;
   order.assign(static_cast<size_t>(n_tasks), {0, 0});
   // depth-major, shallow first (a child sees its parent's finished validity); then, in a slice of their own per depth after
-  // every other slice, the run-end expansions: they read the decoded vector of their values child, which is deeper than they are
-  for (int pass = 0; pass < 2; pass++)
+  // every other slice, the run-end expansions: they read the decoded vector of their values child, which is deeper than they are;
+  // last, the string-view encode tasks (a kernel of their own, launched only by plans that have such tasks)
+  for (int pass = 0; pass < 3; pass++)
   for (int depth = 0; depth <= max_depth; depth++) {
     for (int c = 0; c < device::kNumClasses; c++) {
       if (pass == 1 && c != device::kClassMisc) continue;
-      const int want = pass == 0 ? c : kRunEndSlot;
+      if (pass == 2 && c != device::kClassEncString) continue;
+      const int want = pass == 0 ? c : pass == 1 ? kRunEndSlot : kEncViewSlot;
       ClassSlice sl;
       sl.cls = c;
       sl.run_end = pass == 1;
+      sl.enc_view = pass == 2;
       sl.depth = depth;
       sl.first_task = static_cast<int32_t>(tasks.size());
       sl.tile_begin_at = static_cast<int32_t>(tile_begin.size());
@@ -428,6 +435,10 @@ void Plan::LaunchSlice(const ClassSlice& cs, hipStream_t s) {
   int64_t* null_counts = d_null_counts.get<int64_t>();
   if (cs.run_end) {
     MI_HIP_CHECK(device::LaunchRunEnd(t, tb, tt, cs.n_tasks, cs.total_tiles, status, s));
+    return;
+  }
+  if (cs.enc_view) {   // the look-back words are those of encode_string_1p's slice, which has run by now (same stream)
+    MI_HIP_CHECK(device::LaunchEncodeStringView(t, tb, tt, cs.n_tasks, cs.total_tiles, d_tile_sums.get<int64_t>(), null_counts, status, s));
     return;
   }
   switch (cs.cls) {

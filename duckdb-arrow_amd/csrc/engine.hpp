@@ -54,6 +54,9 @@ struct ClassSlice {
   int32_t tile_begin_at = 0;  // index into Plan::tile_begin / d_tile_begin (n_tasks + 1 entries)
   uint32_t total_tiles = 0;
   bool run_end = false;       // MI_K_RUN_END tasks: launched by LaunchRunEnd (accounted under the misc class)
+  bool enc_view = false;      // MI_K_ENC_STRVIEW tasks: launched by LaunchEncodeStringView (accounted under the encode-string class:
+                              // class_bytes_*, class_tiles and LaunchTimed add encode_string_view to encode_string_1p's line when a plan
+                              // has both -- time a kernel alone with a plan of its tasks alone, as tools/encode_bench.py does)
   uint32_t misc_groups = 0;   // which kernels of the class have work.  misc: bit 0 common flat kinds, bit 1 nested kinds
                               // (list / string view / struct), bit 2 rare flat kinds; enc_string: bit 0 strings, bit 1 lists
 };

@@ -597,7 +597,8 @@ std::vector<uint8_t> EncodeSchemaMessage(const ArrowSchemaModel& schema) {
 }
 
 std::vector<uint8_t> EncodeRecordBatchMessage(int64_t length, const std::vector<std::pair<int64_t, int64_t>>& nodes,
-                                              const std::vector<mi_buffer_span>& buffers, int64_t body_length, int32_t compression) {
+                                              const std::vector<mi_buffer_span>& buffers, int64_t body_length, int32_t compression,
+                                              int64_t n_view_fields) {
   fb::Builder fbb(1024 + 16 * (nodes.size() + buffers.size()));
   static_assert(sizeof(mi_buffer_span) == 16, "Buffer struct layout");
   static_assert(sizeof(mi_string_t) == 16, "string_t layout");
@@ -611,11 +612,17 @@ std::vector<uint8_t> EncodeRecordBatchMessage(int64_t length, const std::vector<
     fbb.AddScalar<int8_t>(1, 0, 0);
     body_compression = fbb.EndTable();
   }
+  fb::Builder::Offset variadic = 0;   // one data buffer per view field; absent without view fields, as the messages always were
+  if (n_view_fields > 0) {
+    const std::vector<int64_t> ones(static_cast<size_t>(n_view_fields), 1);
+    variadic = fbb.CreateStructVector(ones.data(), ones.size(), 8, 8);
+  }
   fbb.StartTable();
   fbb.AddScalar<int64_t>(0, length, 0);
   fbb.AddOffset(1, nds);
   fbb.AddOffset(2, bufs);
   fbb.AddOffset(3, body_compression);
+  fbb.AddOffset(4, variadic);
   auto rb = fbb.EndTable();
   fbb.StartTable();
   fbb.AddScalar<int16_t>(0, 4, 0);   // V5

@@ -157,7 +157,8 @@ bool DecodeFooter(const uint8_t* file_tail, int64_t tail_len, int64_t file_size,
 std::vector<uint8_t> EncodeSchemaMessage(const ArrowSchemaModel& schema);
 std::vector<uint8_t> EncodeRecordBatchMessage(int64_t length, const std::vector<std::pair<int64_t, int64_t>>& nodes,
                                               const std::vector<mi_buffer_span>& buffers, int64_t body_length,
-                                              int32_t compression = -1 /* RecordBatchMeta::compression: -1 none, 0 LZ4_FRAME */);
+                                              int32_t compression = -1 /* RecordBatchMeta::compression: -1 none, 0 LZ4_FRAME */,
+                                              int64_t n_view_fields = 0 /* variadicBufferCounts: that many entries of 1; 0 = no such field */);
 
 // DuckDB logical type name ("BIGINT", "DECIMAL(15,2)", ...) -> Arrow field as ArrowConverter::ToArrowSchema
 // exports it (arrow_stream_writer.cpp:22-24). Throws NotImplementedException for types outside the path.

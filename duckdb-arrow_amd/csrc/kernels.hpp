@@ -169,6 +169,11 @@ hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_
 hipError_t LaunchEncodeString(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
                               int32_t n_tasks, uint32_t total_tiles, int64_t* d_tile_state, int64_t* d_null_counts,
                               uint32_t* d_status, bool has_lists, hipStream_t stream);
+// MI_K_ENC_STRVIEW tasks only (kernels_encode_view.hip): string_t -> Arrow string views, one workgroup per 2048-row tile, a
+// look-back of its own over `total_tiles` state words (zeroed by the launch).  The kind is in no kernel class: a plan stages
+// such tasks in a slice of their own, as it does run-end tasks, and launches this kernel only when it has one.
+hipError_t LaunchEncodeStringView(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task, int32_t n_tasks,
+                                  uint32_t total_tiles, int64_t* d_tile_state, int64_t* d_null_counts, uint32_t* d_status, hipStream_t stream);
 
 // The writer's LZ4_FRAME compressor (kernels_lz4_encode.hip).  One wave per block of `d_blocks`: block b of the encoded body
 // `d_body` is compressed into d_slots + b * lz4enc::kSlotStride and d_words[b] becomes its size word (the compressed size,

@@ -54,6 +54,7 @@ void EncodePlanFor(const ArrowField& f, int32_t* enc_kind, int64_t* param, int32
       return;
     case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY:
       *enc_kind = MI_K_ENC_STR32; *param = 0; *width = 16; return;
+    case MI_AT_UTF8_VIEW: *enc_kind = MI_K_ENC_STRVIEW; *param = 0; *width = 16; return;   // produce_arrow_string_view
     default: throw NotImplementedException("Arrow type " + f.Format() + " is not encoded by the MI355X writer path");
   }
 }
@@ -144,7 +145,8 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
   int64_t extra_heap = 0, payload = 0;
   bool one_copy = false;
   uint64_t region_lo = 0, region_hi = 0;
-  if (columns[static_cast<size_t>(ni)].enc_kind == MI_K_ENC_STR32) {
+  const bool as_views = columns[static_cast<size_t>(ni)].enc_kind == MI_K_ENC_STRVIEW;
+  if (columns[static_cast<size_t>(ni)].enc_kind == MI_K_ENC_STR32 || as_views) {
     const mi_string_t* s = static_cast<const mi_string_t*>(v.data) + start;
     const uint64_t heap_lo = reinterpret_cast<uint64_t>(v.heap), heap_hi = heap_lo + static_cast<uint64_t>(v.heap_size > 0 ? v.heap_size : 0);
     bool ascending_inside = v.heap != nullptr;
@@ -168,6 +170,7 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
       one_copy = ascending_inside && region_hi - region_lo <= static_cast<uint64_t>(long_bytes) + 16ull * static_cast<uint64_t>(n);
       extra_heap = one_copy ? static_cast<int64_t>(region_hi - region_lo) : long_bytes;
     }
+    if (as_views) payload = long_bytes;   // the data buffer of a view column holds the long strings alone
   }
   Reserve(columns[static_cast<size_t>(ni)], columns[static_cast<size_t>(ni)].count + n, extra_heap);
   Column& c = columns[static_cast<size_t>(ni)];  // (children are appended after this block: `columns` never grows here)
@@ -214,7 +217,7 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
   std::memcpy(c.data.get() + static_cast<size_t>(c.count) * static_cast<size_t>(c.width),
               static_cast<const uint8_t*>(v.data) + static_cast<size_t>(start) * static_cast<size_t>(c.width),
               static_cast<size_t>(n) * static_cast<size_t>(c.width));
-  if (c.enc_kind == MI_K_ENC_STR32) {
+  if (c.enc_kind == MI_K_ENC_STR32 || c.enc_kind == MI_K_ENC_STRVIEW) {
     c.payload_bytes += payload;
     if (extra_heap > 0) {
       mi_string_t* dst = reinterpret_cast<mi_string_t*>(c.data.get()) + c.count;
@@ -346,7 +349,9 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   std::vector<std::pair<int64_t, int64_t>> node_counts;
   for (size_t ci = 0; ci < n_nodes; ci++)
     node_counts.emplace_back(buffer.columns[ci].count, validity_task[ci] >= 0 ? null_counts[static_cast<size_t>(validity_task[ci])] : 0);
-  header = EncodeRecordBatchMessage(n_top, node_counts, *spans, body_size, compression == MI_WRITE_COMPRESSION_LZ4_FRAME ? 0 : -1);
+  int64_t n_view_fields = 0;   // RecordBatch.variadicBufferCounts: one data buffer per view field, rows or not
+  for (auto& c : buffer.columns) n_view_fields += c.enc_kind == MI_K_ENC_STRVIEW;
+  header = EncodeRecordBatchMessage(n_top, node_counts, *spans, body_size, compression == MI_WRITE_COMPRESSION_LZ4_FRAME ? 0 : -1, n_view_fields);
   return 1;
 }
 
@@ -503,6 +508,8 @@ void ArrowStreamWriter::Finalize() {
   if (Timers().on)
     std::fprintf(stderr, "[mi_writer] append %.3f s, serialize (H2D + K7 + D2H) %.3f s, write (I/O thread) %.3f s\n", Timers().append,
                  Timers().serialize, Timers().write);
+  if (Timers().on && Timers().view_sizing > 0)
+    std::fprintf(stderr, "[mi_writer] view sizing (host pass over the offsets, pump thread) %.3f s\n", Timers().view_sizing);
 }
 
 std::unique_ptr<mi_writer_local> MakeLocal(mi_writer* w) {
@@ -592,11 +599,19 @@ void MakeLarge(ArrowField& f) {
   for (auto& c : f.children) MakeLarge(c);
 }
 
-std::vector<ArrowField> FieldsFromC(const mi_field* fields, int32_t n_fields, bool large = false) {
+// produce_arrow_string_view: VARCHAR at any depth exports as Utf8View, whatever arrow_large_buffer_size says (ArrowConverter::
+// ToArrowSchema asks for the view property first); BLOB is not touched (DuckDB writes no binary views)
+void MakeView(ArrowField& f) {
+  if (f.type == MI_AT_UTF8) f.type = MI_AT_UTF8_VIEW;
+  for (auto& c : f.children) MakeView(c);
+}
+
+std::vector<ArrowField> FieldsFromC(const mi_field* fields, int32_t n_fields, bool large = false, bool views = false) {
   if (!fields || n_fields <= 0) throw InvalidInputException("writer needs at least one column");
   std::vector<ArrowField> out;
   for (int32_t i = 0; i < n_fields; i++) {
     out.push_back(FieldFromDuckType(fields[i].name, fields[i].duck_type));
+    if (views) MakeView(out.back());
     if (large) MakeLarge(out.back());
   }
   return out;
@@ -635,7 +650,8 @@ int mi_write_options_set(mi_write_options* o, const char* name, const char* valu
       else if (codec == "zstd") throw NotImplementedException("COMPRESSION zstd: ZSTD bodies are read but not written by this path (use lz4 or uncompressed)");
       else throw BinderException("Unknown COMPRESSION '" + std::string(value) + "' for FORMAT ARROWS: expected uncompressed, none, lz4 or lz4_frame");
     }
-    // other options are not ours: the bind loop ignores them (write_arrow_stream.cpp:62-105)
+    // other options are not ours: the bind loop ignores them (write_arrow_stream.cpp:62-105) -- produce_arrow_string_view and
+    // arrow_large_buffer_size among them: those are settings, which reach the struct's fields from the client's properties
   });
 }
 
@@ -693,7 +709,7 @@ int mi_writer_open(mi_ctx* ctx, const char* path, const mi_field* fields, int32_
       mi_write_options_finalize(&w->opts);
     }
     if (w->opts.row_group_size_bytes <= 0) w->opts.row_group_size_bytes = w->opts.row_group_size * 1024;
-    w->fields = FieldsFromC(fields, n_fields, w->opts.arrow_large_buffer_size != 0);
+    w->fields = FieldsFromC(fields, n_fields, w->opts.arrow_large_buffer_size != 0, w->opts.produce_arrow_string_view != 0);
     std::vector<std::pair<std::string, std::string>> kv;
     for (int32_t i = 0; i < w->opts.n_kv_metadata; i++)
       kv.emplace_back(w->opts.kv_keys[i], std::string(w->opts.kv_values[i], static_cast<size_t>(w->opts.kv_value_lens[i])));

@@ -12,6 +12,7 @@ namespace miarrow {
 // MI_WRITER_TIMING=1: cumulative seconds per stage of the COPY sink, printed when a writer is finalized
 struct SinkTimers {
   double append = 0, serialize = 0, write = 0;
+  double view_sizing = 0;   // fused pump, produce_arrow_string_view: the host pass over the Arrow offsets that sizes the data buffers
   bool on = std::getenv("MI_WRITER_TIMING") != nullptr;
   std::mutex mu;  // several sink threads add their stage times
 };

@@ -35,6 +35,16 @@ void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out) {
         add_span((n + 1) * off_width);
         add_span(c.payload_bytes);
         break;
+      case MI_K_ENC_STRVIEW:   // views, then the one data buffer: present (length 0) even when no row is longer than 12 bytes
+        if (c.payload_bytes > 0x7FFFFFFFll) {
+          throw InvalidInputException(
+              "Arrow Appender: The maximum total string size for a string view buffer is 2147483647 but the strings of more than 12 "
+              "bytes of this record batch take " + std::to_string(c.payload_bytes) +
+              " bytes.\n* Write smaller row groups, or SET produce_arrow_string_view=false and arrow_large_buffer_size=true");
+        }
+        add_span(n * 16);
+        add_span(c.payload_bytes);
+        break;
       default: break;   // struct / fixed-size list: the bitmap alone
     }
   }
@@ -53,11 +63,11 @@ mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, cons
     t.out_data = body + spans[0].offset;
     return t;
   }
-  t.flags = node.large_offsets ? 1 : 0;
+  t.flags = node.large_offsets && node.kind != MI_K_ENC_STRVIEW ? 1 : 0;
   t.out_data = body + spans[1].offset;
   if (node.kind == MI_K_ENC_LIST32) return t;   // bitmap + int32 (or int64) offsets from the staged list_entry_t rows
   t.param = node.param;
-  if (node.kind == MI_K_ENC_STR32) {
+  if (node.kind == MI_K_ENC_STR32 || node.kind == MI_K_ENC_STRVIEW) {
     t.buf2 = in.heap;
     t.buf2_len = node.payload_bytes;
     t.ptr_base = in.ptr_base;

@@ -28,7 +28,8 @@ struct EncodeNode {
   int64_t param = 0;            // leaf: vector element width (or decimal physical width)
   bool large_offsets = false;   // int64 Arrow offsets
   int64_t rows = 0;
-  int64_t payload_bytes = 0;    // MI_K_ENC_STR32: size of the Arrow data buffer
+  int64_t payload_bytes = 0;    // size of the Arrow data buffer: MI_K_ENC_STR32 the bytes of the valid rows, MI_K_ENC_STRVIEW of
+                                // those among them that are longer than 12 bytes
 };
 struct BodyLayout {
   std::vector<mi_buffer_span> spans;   // RecordBatch.buffers
@@ -37,14 +38,15 @@ struct BodyLayout {
 };
 //! Field nodes depth first, per node validity (always emitted, ArrowAppender::FinalizeChild), then offsets / data -- the
 //! order ArrowIpcEncoderEncodeSimpleRecordBatch walks the ArrowArray tree; every buffer starts on a multiple of
-//! kBufferAlign.  Throws when a node has more than INT32_MAX rows or int32 offsets cannot address its string bytes.
+//! kBufferAlign.  A string-view node (MI_K_ENC_STRVIEW) has three: bitmap, 16 bytes of view per row, one data buffer.
+//! Throws when a node has more than INT32_MAX rows or int32 offsets cannot address its string bytes.
 void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out);
 
 //! Where the K7 kernels read one node (device addresses)
 struct EncodeInput {
   const void* data = nullptr;       // DuckDB vector data; list: list_entry_t rows; struct / fixed-size list: its validity words
   const void* validity = nullptr;   // validity words, NULL when every row is valid
-  const void* heap = nullptr;       // MI_K_ENC_STR32: the bytes long string_t rows point into ...
+  const void* heap = nullptr;       // MI_K_ENC_STR32 / MI_K_ENC_STRVIEW: the bytes long string_t rows point into ...
   uint64_t ptr_base = 0;            // ... and the pointer value its byte 0 has inside them
 };
 //! The encode task of `node`: `spans` are the node's own (BodyLayout::first_span), `body` is where the body starts in HBM

@@ -61,6 +61,7 @@ unique_ptr<FunctionData> MiWriteBind(ClientContext& context, CopyFunctionBindInp
   MiCheck(mi_write_options_init(&bind->options));
   bind->options.preserve_insertion_order = DBConfig::GetConfig(context).options.preserve_insertion_order ? 1 : 0;
   bind->options.arrow_large_buffer_size = context.GetClientProperties().arrow_offset_size == ArrowOffsetSize::LARGE ? 1 : 0;
+  bind->options.produce_arrow_string_view = context.GetClientProperties().produce_arrow_string_view ? 1 : 0;
   for (auto& option : input.info.options) {
     const auto loption = StringUtil::Lower(option.first);
     if (loption == "kv_metadata" && option.second.size() == 1) {

@@ -109,9 +109,12 @@ enum mi_kind {
   MI_K_ENC_BOOL = 34,     /* K7c byte -> bit, bits start as 1 */
   MI_K_ENC_STR32 = 35,    /* K7d string_t -> int32 offsets + data (flags bit 0: int64 offsets, LargeUtf8 / LargeList) */
   MI_K_ENC_VALIDITY = 36, /* K7a alone: validity words -> always-present bitmap + NULL count (struct / fixed_size_list node) */
-  MI_K_ENC_LIST32 = 37    /* list_entry_t{u64 offset, u64 length} rows -> bitmap + int32 Arrow offsets (running sum of the
+  MI_K_ENC_LIST32 = 37,   /* list_entry_t{u64 offset, u64 length} rows -> bitmap + int32 Arrow offsets (running sum of the
                            * lengths of the valid rows, NULL rows repeat the offset: ArrowListData::AppendOffsets); the
                            * child rows are a node of their own, gathered in list order */
+  MI_K_ENC_STRVIEW = 38   /* K7e string_t -> Arrow string views (Utf8View, produce_arrow_string_view): out_data = 16 bytes per row,
+                           * out_aux = the ONE data buffer (the strings of more than 12 bytes of the valid rows, back to back in
+                           * row order; int32 offsets, no large variant) */
 };
 
 typedef struct mi_field {
@@ -664,6 +667,15 @@ typedef struct mi_write_options {
   int32_t arrow_large_buffer_size; /* DuckDB's setting of the same name (ClientProperties.arrow_offset_size, passed to the
                                     * serializer at arrow_stream_writer.cpp:11-13): VARCHAR / BLOB / LIST export as
                                     * LargeUtf8 / LargeBinary / LargeList with int64 offsets; default 0 */
+  int32_t produce_arrow_string_view; /* DuckDB's setting of the same name (ClientProperties.produce_arrow_string_view, which the
+                                    * reference hands to its serializer with the rest of the properties): every VARCHAR field, at
+                                    * any depth, exports as Utf8View -- 16-byte views + one data buffer for the strings of more than
+                                    * 12 bytes -- and wins over arrow_large_buffer_size there (BLOB and LIST keep following that
+                                    * one); default 0.  A setting, not a COPY option: mi_write_options_set ignores the name */
+  int32_t reserved_view;         /* 0.  A deliberate departure from "new fields go at the end": `compression` is pinned as the
+                                    * struct's last int32, so the setting sits in front of it and this int32 keeps the size a
+                                    * multiple of 8.  `compression` therefore moved by 8 bytes and the struct grew by 8: every
+                                    * client compiled against the older header has to be rebuilt */
   int32_t compression;           /* MI_WRITE_COMPRESSION_*: COMPRESSION / CODEC, default none */
 } mi_write_options;
 #define MI_WRITE_COMPRESSION_NONE 0
@@ -676,7 +688,10 @@ typedef struct mi_write_options {
  * codec; a NULL value is "<NAME> requires exactly one argument"; every other name is ignored).  compression / codec takes
  * uncompressed | none | lz4 | lz4_frame; zstd is MI_ENOTSUP (ZSTD bodies are read but not written), anything else
  * MI_EINVAL naming the value.  The option holds for mi_writer_sink, mi_writer_local_*, mi_writer_sink_scan and rotation
- * (mi_writer_file_size counts compressed bytes); mi_ipc_serialize_chunks and mi_writer_append_message stay uncompressed; _add_kv appends one kv_metadata entry; _finalize applies the cross-option
+ * (mi_writer_file_size counts compressed bytes); mi_ipc_serialize_chunks and mi_writer_append_message stay uncompressed.
+ * produce_arrow_string_view holds for the same entry points (both pumps of mi_writer_sink_scan, rotation, COMPRESSION lz4);
+ * mi_ipc_serializer_create / mi_ipc_serialize_chunks and mi_writer_append_message take no options and stay as they are: offsets,
+ * never views.  _add_kv appends one kv_metadata entry; _finalize applies the cross-option
  * rules.  Errors are MI_EINVAL with the reference's BinderException texts: "ROW_GROUP_SIZE and ROW_GROUP_SIZE_BYTES are
  * mutually exclusive", "ROW_GROUP_SIZE_BYTES does not work while preserving insertion order. Use \"SET
  * preserve_insertion_order=false;\" to disable preserving insertion order.". */
@@ -751,6 +766,9 @@ int mi_filter_float_key(double v, int32_t width, int64_t* key);
 /* Debug getter: launches of the filter kernel by this process so far.  *base counts the instance every program of integer,
  * string and dictionary leaves runs, *extended the one launched for programs with a FLOAT / DOUBLE / 128-bit leaf. */
 int mi_filter_launch_counts(int64_t* base, int64_t* extended);
+/* Debug getter: row groups mi_writer_sink_scan's fused pump has encoded where the scan decoded them (no host staging) in this
+ * process so far, and how many string-view columns (produce_arrow_string_view) they held, summed over those row groups. */
+int mi_writer_fused_counts(int64_t* row_groups, int64_t* view_columns);
 
 #ifdef __cplusplus
 }

@@ -86,13 +86,10 @@ class _DeviceBytes:
         self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
 
 
-def native_heap_leg(torch, da, _ffi, ctx, hs, buf, info, rounds=5):
-    """encode_string_1p on DuckDB-NATIVE string heaps: the long strings of a vector back to back in the heap, strings of <= 12
-    bytes inline only (they leave no gap in the heap).  The decoded vectors of `hs` point into the Arrow data buffer, where a
-    wave's long strings already lie as they will lie in the output (one coalesced copy per wave); here every (record batch,
-    string column) gets a heap of its own with only the long strings in it and rewritten pointers, so a wave's long strings
-    are contiguous in the heap but NOT at a constant distance from their places in the output: the kernel's per-row path.
-    Same output as the source stream's buffers (checked on the first record batch)."""
+def native_heaps(torch, _ffi, hs):
+    """Every (record batch, string column) of `hs` with a DuckDB-native heap: only the long strings in it, back to back, and the
+    string_t rows rewritten to point there (ptr_base 0).  -> (heaps, vectors, [(layout, column, rows, address of its string_t
+    rows, its long bytes)], long bytes in all); `heaps` and `vectors` own the memory."""
     d_in = torch.as_tensor(_DeviceBytes(hs.in_ptr, hs.host.size + 64), device="cuda")
     d_out = torch.as_tensor(_DeviceBytes(hs.out_ptr, hs.out_bytes), device="cuda")
     cols = [(lay, e) for lay in hs.layout for e in lay["columns"] if e["kind"] == _ffi.K_STR32]
@@ -100,8 +97,7 @@ def native_heap_leg(torch, da, _ffi, ctx, hs, buf, info, rounds=5):
     heaps = torch.zeros(heap_total + 256, dtype=torch.uint8, device="cuda")
     rows_total = sum(lay["nrows"] for lay, _ in cols)
     vectors = torch.empty(rows_total * 16 + 256, dtype=torch.uint8, device="cuda")   # the rewritten string_t rows
-    total = 0
-    spans, tasks = [], []
+    made = []
     hb = vb = 0
     long_bytes = 0
     for lay, e in cols:
@@ -121,15 +117,31 @@ def native_heap_leg(torch, da, _ffi, ctx, hs, buf, info, rounds=5):
             heaps[hb: hb + nbytes] = d_in[src]
             s64[:, 1][rows_long] = hb + new_off[rows_long]     # pointer = position in `heaps` (ptr_base 0)
         long_bytes += nbytes
+        made.append((lay, e, n, vectors.data_ptr() + vb, nbytes))
+        hb += (nbytes + 63) // 64 * 64
+        vb += 16 * n
+    return heaps, vectors, made, long_bytes
+
+
+def native_heap_leg(torch, da, _ffi, ctx, hs, buf, info, rounds=5):
+    """encode_string_1p on DuckDB-NATIVE string heaps: the long strings of a vector back to back in the heap, strings of <= 12
+    bytes inline only (they leave no gap in the heap).  The decoded vectors of `hs` point into the Arrow data buffer, where a
+    wave's long strings already lie as they will lie in the output (one coalesced copy per wave); here every (record batch,
+    string column) gets a heap of its own with only the long strings in it and rewritten pointers, so a wave's long strings
+    are contiguous in the heap but NOT at a constant distance from their places in the output: the kernel's per-row path.
+    Same output as the source stream's buffers (checked on the first record batch)."""
+    heaps, vectors, made, long_bytes = native_heaps(torch, _ffi, hs)
+    cols = [(lay, e) for lay, e, _, _, _ in made]
+    total = 0
+    spans, tasks = [], []
+    for lay, e, n, vptr, _ in made:
         sz = [(n + 7) // 8, e["buffers"][1][1], e["buffers"][2][1]]
         offs = []
         for x in sz:
             offs.append(total)
             total += (x + 63) // 64 * 64 + 64
         spans.append((lay, e, offs, sz))
-        tasks.append((n, vectors.data_ptr() + vb, offs, sz, e))
-        hb += (nbytes + 63) // 64 * 64
-        vb += 16 * n
+        tasks.append((n, vptr, offs, sz, e))
     arena = torch.zeros(total + 256, dtype=torch.uint8, device="cuda")
     ab = arena.data_ptr()
     out_base = hs.out_ptr
@@ -158,12 +170,58 @@ def native_heap_leg(torch, da, _ffi, ctx, hs, buf, info, rounds=5):
     return out
 
 
+def string_view_leg(torch, da, _ffi, ctx, hs, info, rounds=5):
+    """encode_string_view per string column, on both heap layouts: "decoded" (the string_t rows point into the Arrow data buffer, the
+    inline strings lie between the long ones) and "native" (native_heaps).  Beside it, same column and layout, encode_string_1p
+    (offsets + data) and, as the ceiling of a column without long strings, encode_fixed's 16-byte copy of the same rows.  HIP-event
+    time of one plan per column over every record batch, median of `rounds`.  Algorithmic bytes of a view column: 16 in + 16 out
+    per row + 2 x the long bytes."""
+    heaps, vectors, made, _ = native_heaps(torch, _ffi, hs)
+    stream = torch.cuda.current_stream().cuda_stream
+    rows = sum(n for _, e, n, _, _ in made if e["name"] == made[0][1]["name"])
+    room = max(sum(16 * n + 64 + (n + 7) // 8 + 64 + e["buffers"][2][1] + 64 + 4 * n + 128 for _, e, n, _, _ in made if e["name"] == nm) for nm in {e["name"] for _, e, _, _, _ in made})
+    arena = torch.zeros(room + 4096, dtype=torch.uint8, device="cuda")
+
+    def timed(tasks):
+        plan = da.Plan(ctx, tasks)
+        plan.launch(stream)
+        assert plan.status() == 0
+        ms = float(np.median([sum(plan.launch_timed(stream)) for _ in range(rounds)]))
+        plan.close()
+        return ms
+
+    out = {"rows": rows, "columns": {}}
+    for nm in dict.fromkeys(e["name"] for _, e, _, _, _ in made):
+        mine = [(lay, e, n, vptr, nb) for lay, e, n, vptr, nb in made if e["name"] == nm]
+        long_bytes = sum(nb for _, _, _, _, nb in mine)
+        col = {"long_bytes": long_bytes, "algorithmic_bytes": 32 * rows + 2 * long_bytes}
+        for layout in ("decoded", "native"):
+            at, tv, ts, tc = arena.data_ptr(), [], [], []
+            for lay, e, n, vptr, nb in mine:
+                src = vptr if layout == "native" else hs.out_ptr + e["data_off"]
+                heap = heaps.data_ptr() if layout == "native" else hs.in_ptr
+                bitmap, data, aux = at, at + ((n + 7) // 8 + 127) // 64 * 64, 0
+                aux = data + (16 * n + 127) // 64 * 64
+                at = aux + (e["buffers"][2][1] + 127) // 64 * 64
+                common = dict(validity=hs.out_ptr + e["valid_off"], out_validity=bitmap)
+                tv.append(da.make_task(_ffi.K_ENC_STRVIEW, n, src, data, out_aux=aux, buf2=heap, ptr_base=0, buf2_len=nb, **common))
+                ts.append(da.make_task(_ffi.K_ENC_STR32, n, src, data, out_aux=aux, buf2=heap, ptr_base=0, buf2_len=e["buffers"][2][1], **common))
+                tc.append(da.make_task(_ffi.K_ENC_COPY, n, src, data, param=16, **common))
+            ms = timed(tv)
+            col[layout] = {"encode_string_view_ms": ms, "TBps": col["algorithmic_bytes"] / ms / 1e9, "encode_string_1p_ms": timed(ts)}
+            if layout == "decoded":
+                col["encode_fixed_16_byte_copy_ms"] = timed(tc)
+        out["columns"][nm] = col
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sf", type=float, default=1.0)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--per-column", action="store_true", help="also time one plan per column (diagnostic)")
     ap.add_argument("--native-heap", action="store_true", help="also: encode_string_1p over DuckDB-native string heaps (long strings back to back)")
+    ap.add_argument("--string-view", action="store_true", help="also: encode_string_view per string column on both heap layouts, beside encode_string_1p and the 16-byte copy")
     args = ap.parse_args()
     import torch
     import duckdb_arrow_amd as da
@@ -179,8 +237,9 @@ def main():
     out = encode_leg(torch, da, _ffi, ctx, hs, buf, info, args.rounds, args.per_column)
     if args.native_heap:
         out["native_heap"] = native_heap_leg(torch, da, _ffi, ctx, hs, buf, info, args.rounds)
+    if args.string_view:
+        out["string_view"] = string_view_leg(torch, da, _ffi, ctx, hs, info, args.rounds)
     print(json.dumps(out))
-
 
 
 if __name__ == "__main__":

@@ -304,6 +304,37 @@ def filter_launch_counts():
     return base.value, ext.value
 
 
+def filter_string(ctx, rows_ptr, validity_ptr, nrows, heap_ptr, ptr_base, op, constant, sel_ptr, count_ptr, launches=1):
+    """One string leaf ("=", "<", "starts_with", "contains", "ends_with", "like", "not like", ...) over a resident string_t vector
+    (mi_filter_string): uploads the constant, launches the filter kernel `launches` times and waits.  Returns the mean kernel
+    time in ms, from device events."""
+    codes = {"=": _ffi.F_EQ, "<>": _ffi.F_NE, "<": _ffi.F_LT, "<=": _ffi.F_LE, ">": _ffi.F_GT, ">=": _ffi.F_GE, "starts_with": _ffi.F_STARTS_WITH,
+             "contains": _ffi.F_CONTAINS, "ends_with": _ffi.F_ENDS_WITH, "like": _ffi.F_LIKE, "not like": _ffi.F_NOT_LIKE}
+    constant = constant.encode() if isinstance(constant, str) else bytes(constant)
+    ms = C.c_float()
+    _ffi.check(_ffi.lib().mi_filter_string(ctx._h, rows_ptr, validity_ptr or None, nrows, heap_ptr or None, ptr_base, codes[op.lower()], constant,
+                                           len(constant), sel_ptr, count_ptr, launches, C.byref(ms)))
+    return ms.value
+
+
+def filter_like_match(op, pattern, row):
+    """Does the byte string `row` pass `op` ("contains", "ends_with", "like", "not like") with this needle / suffix / pattern:
+    the matcher the filter kernel compiles, on the host (mi_filter_like_match).  Raises MiError where Relation.filter would."""
+    as_bytes = lambda v: v.encode() if isinstance(v, str) else bytes(v)
+    code = op if isinstance(op, int) else {"contains": _ffi.F_CONTAINS, "ends_with": _ffi.F_ENDS_WITH, "like": _ffi.F_LIKE,
+                                           "not like": _ffi.F_NOT_LIKE}[op.lower()]
+    pattern, row, result = as_bytes(pattern), as_bytes(row), C.c_int32()
+    _ffi.check(_ffi.lib().mi_filter_like_match(code, pattern, len(pattern), row, len(row), C.byref(result)))
+    return bool(result.value)
+
+
+def filter_pattern_launches():
+    """Launches of the filter kernel's contains / ends_with / LIKE instance by this process (mi_filter_pattern_launches)."""
+    n = C.c_int64()
+    _ffi.check(_ffi.lib().mi_filter_pattern_launches(C.byref(n)))
+    return n.value
+
+
 def writer_fused_counts():
     """(row groups the fused COPY pump encoded where the scan decoded them, string-view columns among them) by this process."""
     groups, views = C.c_int64(), C.c_int64()
@@ -499,15 +530,19 @@ class Relation:
     def filter(self, expr):
         """Pushed-down predicate tree (mi_scan_set_filter).  `expr` is nested tuples:
             ("and", e1, e2, ...) | ("or", e1, e2, ...) | (column, op, value) with op in = <> != < <= > >= |
-            (column, "in", [values]) | (column, "is null") | (column, "is not null") | (column, "starts_with", prefix)
+            (column, "in", [values]) | (column, "is null") | (column, "is not null") | (column, "starts_with", prefix) |
+            (column, "contains", needle) | (column, "ends_with", suffix) | (column, "like", pattern) | (column, "not like", pattern)
         Constants are the stored integers, or str / bytes for VARCHAR / BLOB columns (byte-wise order).  The column's DuckDB
         type picks what a number is sent as: FLOAT / DOUBLE columns take Python floats (float('nan'), inf; ints are converted)
         in DuckDB's total order -- NaN = NaN, NaN greatest, -0.0 = +0.0; HUGEINT / DECIMAL(19..38) columns take ints of up to
         128 bits; a decimal.Decimal on any DECIMAL column is scaled to the stored integer.  A float against an integer column
-        is refused.  NULL semantics are SQL's: a comparison with NULL is not true."""
+        is refused.  NULL semantics are SQL's: a comparison with NULL is not true.  Needles and suffixes are literal bytes; in a
+        LIKE pattern `%` is the only wildcard (`_` and more than 8 literal segments are refused with MI_ENOTSUP, there is no
+        escape character), and a NULL row passes neither "like" nor "not like"."""
         ops = {"=": _ffi.F_EQ, "==": _ffi.F_EQ, "<>": _ffi.F_NE, "!=": _ffi.F_NE, "<": _ffi.F_LT, "<=": _ffi.F_LE,
                ">": _ffi.F_GT, ">=": _ffi.F_GE, "is null": _ffi.F_IS_NULL, "is not null": _ffi.F_IS_NOT_NULL, "in": _ffi.F_IN,
-               "starts_with": _ffi.F_STARTS_WITH}
+               "starts_with": _ffi.F_STARTS_WITH, "contains": _ffi.F_CONTAINS, "ends_with": _ffi.F_ENDS_WITH, "like": _ffi.F_LIKE,
+               "not like": _ffi.F_NOT_LIKE}
         nodes, keep = [None], []
         duck = {f["name"]: f["duck_type"] for f in self.fields}
 

@@ -93,6 +93,7 @@ class FilterNode(C.Structure):
 
 FV_INT64, FV_DOUBLE, FV_INT128 = 0, 1, 2
 F_EQ, F_NE, F_LT, F_LE, F_GT, F_GE, F_IS_NULL, F_IS_NOT_NULL, F_IN, F_STARTS_WITH, F_AND, F_OR = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 16, 17
+F_CONTAINS, F_ENDS_WITH, F_LIKE, F_NOT_LIKE = 11, 12, 13, 14
 
 
 class HbmOptions(C.Structure):
@@ -218,6 +219,9 @@ SIGNATURES = {
     "mi_filter_between": (C.c_int, [P, P, C.c_int32, P, C.c_int64, C.c_int32, C.POINTER(C.c_int64), P, P, P]),
     "mi_filter_float_key": (C.c_int, [C.c_double, C.c_int32, C.POINTER(C.c_int64)]),
     "mi_filter_launch_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mi_filter_string": (C.c_int, [P, P, P, C.c_int64, P, C.c_uint64, C.c_int32, C.c_char_p, C.c_int32, P, P, C.c_int32, C.POINTER(C.c_float)]),
+    "mi_filter_like_match": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "mi_filter_pattern_launches": (C.c_int, [C.POINTER(C.c_int64)]),
     "mi_writer_fused_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mi_scan_set_filter_range": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64]),
     "mi_scan_set_filter": (C.c_int, [P, C.POINTER(FilterNode), C.c_int32, C.c_int32]),

@@ -15,6 +15,7 @@
 #include "filter_key.hpp"
 #include "ipc_format.hpp"
 #include "ipc_stream_reader.hpp"
+#include "like_match.hpp"
 #include "scan_operator.hpp"
 #include "writer.hpp"
 
@@ -362,6 +363,44 @@ int mi_filter_between(mi_ctx* ctx, const void* values, int32_t width, const void
   });
 }
 
+int mi_filter_string(mi_ctx* ctx, const void* rows, const void* validity, int64_t nrows, const void* heap, uint64_t ptr_base, int32_t op,
+                     const char* str_value, int32_t str_len, mi_sel_t* sel_out, uint32_t* count_out, int32_t launches, float* ms) {
+  return Wrap([&] {
+    if (!ctx || !rows || !sel_out || !count_out || launches < 1) throw InvalidInputException("mi_filter_string: NULL argument or no launch");
+    if (op == MI_F_IN || op == MI_F_AND || op == MI_F_OR || op == MI_F_IS_NULL || op == MI_F_IS_NOT_NULL || !str_value)
+      throw InvalidInputException("mi_filter_string: one comparison of a string_t vector with one byte string");
+    ctx->ctx->Bind();
+    mi_filter_node node;
+    std::memset(&node, 0, sizeof(node));
+    node.op = op;
+    node.column = "rows";
+    node.str_value = str_value;
+    node.str_len = str_len;
+    BoundFilter filter;
+    filter.cnf = NormaliseFilter(&node, 1, 0);
+    filter.UploadConstants();
+    device::FilterProgram prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_leaves = 1;
+    device::FilterLeafDev& L = prog.leaves[0];
+    LeafConstants(filter.cnf[0][0], filter.d_in_lists[0], true, L);
+    L.data = rows;
+    L.validity = static_cast<const uint64_t*>(validity);
+    L.width = 16;
+    L.lo = static_cast<int64_t>(reinterpret_cast<uintptr_t>(heap));
+    L.hi = static_cast<int64_t>(ptr_base);
+    hipStream_t s = ctx->ctx->stream;
+    const HipEvent begin = HipEvent::CreateTimed(), end = HipEvent::CreateTimed();
+    MI_HIP_CHECK(hipEventRecord(begin, s));
+    for (int32_t i = 0; i < launches; i++) MI_HIP_CHECK(device::LaunchFilterProgram(prog, nrows, sel_out, count_out, s));
+    MI_HIP_CHECK(hipEventRecord(end, s));
+    MI_HIP_CHECK(hipStreamSynchronize(s));   // the constants die with this call
+    float total = 0;
+    MI_HIP_CHECK(hipEventElapsedTime(&total, begin, end));
+    if (ms) *ms = total / static_cast<float>(launches);
+  });
+}
+
 int mi_filter_float_key(double v, int32_t width, int64_t* key) {
   return Wrap([&] {
     if (!key || (width != 4 && width != 8)) throw InvalidInputException("mi_filter_float_key: width must be 4 or 8");
@@ -376,6 +415,24 @@ int mi_filter_launch_counts(int64_t* base, int64_t* extended) {
     device::FilterLaunchCounts(n);
     *base = n[0];
     *extended = n[1];
+  });
+}
+
+int mi_filter_like_match(int32_t op, const char* pattern, int32_t pattern_len, const char* row, int32_t row_len, int32_t* result) {
+  return Wrap([&] {
+    if (!result || pattern_len < 0 || row_len < 0 || (!pattern && pattern_len > 0) || (!row && row_len > 0))
+      throw InvalidInputException("mi_filter_like_match: NULL argument or negative length");
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(pattern);
+    likematch::Pattern pat;
+    CheckPattern(likematch::Compile(op, bytes, static_cast<uint32_t>(pattern_len), &pat), op, std::string());
+    *result = likematch::Passes(pat, bytes, reinterpret_cast<const uint8_t*>(row), static_cast<uint32_t>(row_len)) ? 1 : 0;
+  });
+}
+
+int mi_filter_pattern_launches(int64_t* n) {
+  return Wrap([&] {
+    if (!n) throw InvalidInputException("mi_filter_pattern_launches: NULL argument");
+    *n = device::FilterPatternLaunches();
   });
 }
 

@@ -95,6 +95,11 @@ class HipEvent : public HipHandle<hipEvent_t, hipEventDestroy> {
     MI_HIP_CHECK(hipEventCreateWithFlags(&e.h_, hipEventDisableTiming));
     return e;
   }
+  static HipEvent CreateTimed() {   // for the entry points that report a kernel time
+    HipEvent e;
+    MI_HIP_CHECK(hipEventCreate(&e.h_));
+    return e;
+  }
 };
 
 class HipStream : public HipHandle<hipStream_t, hipStreamDestroy> {

@@ -133,6 +133,8 @@ constexpr int kLeafStrRange = 7;    // string_t column: lower bound <(=) row <(=
 constexpr int kLeafWideRange = 8;   // 16-byte column (hugeint_t{uint64 lower; int64 upper}: HUGEINT, DECIMAL(19..38)): lo <= v <= hi, `upper`
                                     // signed, then `lower` unsigned.  in_values = {lo.lower, lo.upper, hi.lower, hi.upper}
 constexpr int kLeafWideIn = 9;      // 16-byte column: v is one of n_in constants, in_values = {lower, upper} pairs
+constexpr int kLeafStrMatch = 10;   // string_t column: contains / ends_with / %-pattern LIKE (like_match.hpp).  in_values: the literal segments in
+                                    // kLeafStrIn's layout, in pattern order; n_in = their number (1 .. 8) | anchored at the head << 8 | at the tail << 9
 constexpr int kLeafUnsigned = 1;    // flags: the column holds unsigned integers
 constexpr int kLeafNegate = 2;      //        NOT (range / in-list); NULL still fails
 constexpr int kLeafEndsClause = 4;
@@ -154,10 +156,13 @@ struct FilterProgram {
 };
 // Two instances of one kernel: programs of the leaves kLeafRange .. kLeafStrRange without kLeafFloat launch filter_program<false>,
 // which compiles none of the code of the others; a program that holds a kLeafFloat / kLeafWideRange / kLeafWideIn leaf
-// launches filter_program<true>.
+// launches filter_program<true>.  A third one, filter_program<true, true>, knows every leaf form and kLeafStrMatch besides; it is
+// launched only for a program that holds such a leaf.
 hipError_t LaunchFilterProgram(const FilterProgram& prog, int64_t nrows, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream);
 //! launches of each instance by this process so far: [0] filter_program<false>, [1] filter_program<true>
 void FilterLaunchCounts(int64_t out[2]);
+//! launches of filter_program<true, true> by this process so far
+int64_t FilterPatternLaunches();
 // lo <= v < hi on one column (mi_filter_range)
 hipError_t LaunchFilterRange(const void* values, int32_t width, const void* validity, int64_t nrows, int64_t lo,
                              int64_t hi, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream);

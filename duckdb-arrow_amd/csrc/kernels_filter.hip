@@ -1,6 +1,7 @@
 // kernels_filter.hip -- K6: pushed-down predicates -> selection vectors, and the fused Q6-style consumer.
 #include "device_common.hpp"
 #include "filter_key.hpp"
+#include "like_match.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -182,6 +183,70 @@ __device__ __forceinline__ void leaf_strrange(const FilterLeafDev& L, int64_t fi
   }
 }
 
+// kLeafStrMatch: contains / ends_with / %-pattern LIKE (like_match.hpp holds the rule and the matcher; the host compiles the
+// same one).  The frame is leaf_strrange's: one window at a time, 8 rows per lane, rows past nrows never loaded.  The
+// segments are kLeafStrIn constants (in_values: 3 words each, uniform: scalar loads), n_in = the segment count | head
+// anchor << 8 | tail anchor << 9.  A row of <= 12 bytes -- a NULL row's canonical zero included -- is matched from its four
+// dwords in registers; a longer one from its heap bytes, by its own lane whatever its length, through the aligned dwords
+// that cover [p, p + len) and no other (Arrow buffers are 8-byte padded inside the body, so these stay inside the body's
+// allocation); the matcher asks for no byte at or behind p + len, where the next row's bytes lie.
+struct MatchSegments {
+  gptr<const int64_t> table;
+  __device__ __forceinline__ uint32_t len(int s) const { return static_cast<uint32_t>(static_cast<uint64_t>(table[3 * s])); }
+  __device__ __forceinline__ uint8_t byte(int s, uint32_t i) const {
+    return GC<uint8_t>(reinterpret_cast<const void*>(static_cast<uintptr_t>(table[3 * s + 2])))[i];
+  }
+};
+
+struct MatchRow {
+  u32x4 s;                        // the string_t
+  gptr<const uint32_t> words;     // len > 12: the aligned dword that holds the row's byte 0
+  uint32_t mis;                   //           and where in it that byte sits
+  mutable uint32_t have, word;    // the dword loaded last (scanning forward costs one load per four bytes)
+  __device__ __forceinline__ uint8_t operator[](uint32_t i) const {
+    if (s.x <= 12) return static_cast<uint8_t>((i < 4 ? s.y : i < 8 ? s.z : s.w) >> (8 * (i & 3)));
+    const uint32_t at = mis + i;
+    if ((at >> 2) != have) {
+      have = at >> 2;
+      word = words[have];
+    }
+    return static_cast<uint8_t>(word >> (8 * (at & 3)));
+  }
+};
+
+__device__ __forceinline__ void leaf_strmatch(const FilterLeafDev& L, int64_t first_window, int64_t nrows, int r, uint32_t (&m)[kFilterWindows]) {
+  gptr<const u32x4> rows = GC<u32x4>(L.data);
+  const uint64_t heap = static_cast<uint64_t>(L.lo), ptr_base = static_cast<uint64_t>(L.hi);
+  const MatchSegments segs = {GC<int64_t>(L.in_values)};
+  const int n_seg = L.n_in & 0xFF;
+  const bool head = (L.n_in & 0x100) != 0, tail = (L.n_in & 0x200) != 0;
+#pragma clang loop unroll(disable)
+  for (int w = 0; w < kFilterWindows; w++) {
+    const int64_t row0 = (first_window + w) * kTileRows;
+    const int64_t left = nrows - row0;
+    const int n = left < kTileRows ? static_cast<int>(left < 0 ? 0 : left) : kTileRows;
+    uint32_t mm = 0;
+#pragma clang loop unroll(disable)
+    for (int k = 0; k < 8; k++) {
+      if (r + k >= n) break;
+      MatchRow row;
+      row.s = __builtin_nontemporal_load(rows + row0 + r + k);
+      row.words = nullptr;
+      row.mis = 0;
+      row.have = 0xFFFFFFFFu;
+      row.word = 0;
+      if (row.s.x > 12) {
+        const uint64_t p = static_cast<uint64_t>(row.s.z) | (static_cast<uint64_t>(row.s.w) << 32);
+        const uint64_t a = heap + (p - ptr_base);
+        row.mis = static_cast<uint32_t>(a & 3u);
+        row.words = GC<uint32_t>(reinterpret_cast<const void*>(static_cast<uintptr_t>(a - row.mis)));
+      }
+      mm |= likematch::Matches(segs, n_seg, head, tail, row, row.s.x) ? (1u << k) : 0u;
+    }
+    m[w] = mm;
+  }
+}
+
 // kLeafDictMap: a string predicate on a dictionary-encoded column was evaluated once per dictionary (on the host: one byte per
 // entry: 0 no, 1 yes, 2 the entry is NULL); a row passes by looking its index up -- 4 bytes per row instead of a string_t and
 // its heap bytes.  Rows without a value point at the extra NULL entry (index dict_len), so the row validity is not needed, and
@@ -256,8 +321,10 @@ __device__ __forceinline__ void leaf_wide(const FilterLeafDev& L, int64_t first_
 }
 
 // EXT = false: the leaves the kernel has always had, and none of the code of the others.  EXT = true adds kLeafFloat on
-// range / IN leaves and the 16-byte leaves; launched only for a program that holds one (LaunchFilterProgram).
-template <bool EXT>
+// range / IN leaves and the 16-byte leaves; launched only for a program that holds one (LaunchFilterProgram).  PAT = true
+// (with EXT: trees mix every leaf form) adds kLeafStrMatch, launched only for a program that holds such a leaf.  Three
+// instances: filter_program<false>, <true> and <true, true>.
+template <bool EXT, bool PAT = false>
 __global__ __launch_bounds__(kBlockThreads) void filter_program(const FilterProgram prog, int64_t nrows,
                                                                 mi_sel_t* __restrict__ sel_out_p,
                                                                 uint32_t* __restrict__ count_out_p) {
@@ -291,6 +358,7 @@ __global__ __launch_bounds__(kBlockThreads) void filter_program(const FilterProg
       if (L.op == kLeafStrIn) leaf_strin(L, first_window, nrows, r, m);
       else if (L.op == kLeafStrRange) leaf_strrange(L, first_window, nrows, r, m);
       else if (L.op == kLeafDictMap) leaf_dictmap(L, first_window, nrows, r, m);
+      else if (PAT && L.op == kLeafStrMatch) leaf_strmatch(L, first_window, nrows, r, m);
       else if (EXT && (L.op == kLeafWideRange || L.op == kLeafWideIn)) leaf_wide(L, first_window, nrows, r, m);
       else if (EXT && (L.flags & kLeafFloat)) {
         if (L.width == 4) leaf_compare<int32_t, true>(L, first_window, nrows, r, m);
@@ -408,7 +476,7 @@ hipError_t LaunchAggSumProduct(const AggSumProductArgs& args, unsigned long long
 }
 
 namespace {
-std::atomic<int64_t> g_filter_launches[2];
+std::atomic<int64_t> g_filter_launches[3];   // filter_program<false>, <true>, <true, true>
 
 //! true when `prog` holds a leaf that only filter_program<true> knows
 bool FilterProgramIsExtended(const FilterProgram& prog) {
@@ -425,17 +493,30 @@ void FilterLaunchCounts(int64_t out[2]) {
   out[1] = g_filter_launches[1].load();
 }
 
+int64_t FilterPatternLaunches() { return g_filter_launches[2].load(); }
+
 hipError_t LaunchFilterProgram(const FilterProgram& prog, int64_t nrows, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream) {
   MI_DROP_STALE_ERROR();
   if (nrows <= 0) return hipSuccess;
   if (prog.n_leaves < 0 || prog.n_leaves > kMaxFilterLeaves) return hipErrorInvalidValue;
-  for (int l = 0; l < prog.n_leaves; l++) {   // what the 16-byte and float leaves may be bound to
+  bool pattern = false;
+  for (int l = 0; l < prog.n_leaves; l++) {   // what the 16-byte, float and pattern leaves may be bound to
     const FilterLeafDev& L = prog.leaves[l];
     if ((L.op == kLeafWideRange || L.op == kLeafWideIn) && (L.width != 16 || !L.in_values || !L.data)) return hipErrorInvalidValue;
     if ((L.op == kLeafRange || L.op == kLeafIn) && (L.flags & kLeafFloat) && L.width != 4 && L.width != 8) return hipErrorInvalidValue;
+    if (L.op == kLeafStrMatch) {   // 1 .. 8 segments in HBM over a string_t vector
+      const int n_seg = L.n_in & 0xFF;
+      if (n_seg < 1 || n_seg > likematch::kMaxSegments || (L.n_in & ~0x3FF) || !L.in_values || !L.data) return hipErrorInvalidValue;
+      pattern = true;
+    }
   }
   const int64_t windows = (nrows + kTileRows - 1) / kTileRows;
   const uint32_t grid = static_cast<uint32_t>((windows + kFilterWindows - 1) / kFilterWindows);
+  if (pattern) {
+    hipLaunchKernelGGL((filter_program<true, true>), dim3(grid), dim3(kBlockThreads), 0, stream, prog, nrows, sel_out, count_out);
+    g_filter_launches[2]++;
+    return hipGetLastError();
+  }
   const bool ext = FilterProgramIsExtended(prog);
   if (ext) hipLaunchKernelGGL(filter_program<true>, dim3(grid), dim3(kBlockThreads), 0, stream, prog, nrows, sel_out, count_out);
   else hipLaunchKernelGGL(filter_program<false>, dim3(grid), dim3(kBlockThreads), 0, stream, prog, nrows, sel_out, count_out);

@@ -9,6 +9,8 @@
 // DOUBLE columns go the same way on the order-preserving keys of filter_key.hpp (DuckDB's total order: NaN = NaN, NaN
 // greatest, -0.0 = +0.0; a strict bound is an inclusive one on key +- 1), so everything here works on keys unchanged;
 // HUGEINT / DECIMAL(19..38) columns are a leaf form of their own, as strings are, with 128-bit inclusive ranges.
+// contains / ends_with / LIKE with `%` (like_match.hpp) fold into the string leaves above where they can -- no `%` is =,
+// 'abc%' the prefix range, '%' IS NOT NULL -- and are kLeafStrMatch otherwise, opaque to range merging.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +18,7 @@
 #include <limits>
 
 #include "filter_key.hpp"
+#include "like_match.hpp"
 #include "scan_operator.hpp"
 
 namespace miarrow {
@@ -75,6 +78,21 @@ FilterLeaf WideLeafOf(const mi_filter_node& n, FilterLeaf l) {
   return l;
 }
 
+}  // namespace
+
+void CheckPattern(int compiled, int32_t op, const std::string& column) {
+  const std::string on = column.empty() ? std::string() : " (column '" + column + "')";
+  switch (compiled) {
+    case likematch::kCompiled: return;
+    case likematch::kHasUnderscore:
+      throw NotImplementedException("LIKE pattern with '_'" + on + ": '_' steps over UTF-8 characters, the scan compares bytes; the filter stays above the scan");
+    case likematch::kTooManySegments:
+      throw NotImplementedException("LIKE pattern with more than " + std::to_string(likematch::kMaxSegments) + " literal segments" + on + " is not pushed into the scan");
+    default: throw InvalidInputException("unknown filter op " + std::to_string(op));
+  }
+}
+
+namespace {
 FilterLeaf LeafOf(const mi_filter_node& n, const std::vector<ScanColumn>* columns) {
   if (!n.column || !*n.column) throw InvalidInputException("filter leaf without a column name");
   FilterLeaf l;
@@ -131,6 +149,33 @@ FilterLeaf LeafOf(const mi_filter_node& n, const std::vector<ScanColumn>* column
         if (n.n_values > 256) throw NotImplementedException("IN-list with more than 256 values is not pushed down");
         for (int32_t k = 0; k < n.n_values; k++) add(n.str_values[k], n.str_lens[k]);
         break;
+      case MI_F_CONTAINS: case MI_F_ENDS_WITH: case MI_F_LIKE: case MI_F_NOT_LIKE: {
+        if (!n.str_value || n.str_len < 0) throw InvalidInputException("string filter constant without bytes");
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(n.str_value);
+        likematch::Pattern pat;
+        CheckPattern(likematch::Compile(n.op, bytes, static_cast<uint32_t>(n.str_len), &pat), n.op, l.column);
+        // What the existing leaves already say.  No segment: '%' alone or an empty needle is IS NOT NULL (NOT LIKE '%' keeps
+        // nothing: an empty IN-list).  No '%': =.  'abc%': the prefix range.  Negated, the last two still drop NULL rows.
+        if (pat.n_seg == 0 && !(pat.head && pat.tail)) {
+          if (!pat.negate) l.op = device::kLeafIsNotNull;
+          return l;
+        }
+        if (pat.n_seg <= 1 && pat.head) {   // anchored at both ends: no '%' at all; at the head alone: 'abc%'
+          mi_filter_node folded = n;
+          folded.op = pat.tail ? MI_F_EQ : MI_F_STARTS_WITH;
+          folded.str_value = n.str_value + (pat.n_seg ? pat.off[0] : 0);
+          folded.str_len = static_cast<int32_t>(pat.n_seg ? pat.len[0] : 0);
+          FilterLeaf f = LeafOf(folded, columns);
+          f.negate = pat.negate;
+          return f;
+        }
+        l.op = device::kLeafStrMatch;
+        l.negate = pat.negate;
+        l.match_head = pat.head;
+        l.match_tail = pat.tail;
+        for (int s = 0; s < pat.n_seg; s++) l.str_values.emplace_back(n.str_value + pat.off[s], pat.len[s]);
+        return l;
+      }
       case MI_F_LT: case MI_F_LE: case MI_F_GT: case MI_F_GE: case MI_F_STARTS_WITH: {
         // ordering and prefix tests: one range leaf [lower, upper] with open / closed ends (byte-wise order)
         if (!n.str_value || n.str_len < 0) throw InvalidInputException("string filter constant without bytes");
@@ -170,6 +215,8 @@ FilterLeaf LeafOf(const mi_filter_node& n, const std::vector<ScanColumn>* column
     l.str_values.erase(std::unique(l.str_values.begin(), l.str_values.end()), l.str_values.end());
     return l;
   }
+  if (n.op == MI_F_STARTS_WITH || n.op == MI_F_CONTAINS || n.op == MI_F_ENDS_WITH || n.op == MI_F_LIKE || n.op == MI_F_NOT_LIKE)
+    throw InvalidInputException("filter on column '" + l.column + "': this operator takes a byte string (str_value)");
   switch (n.op) {
     case MI_F_EQ: closed(c, c); break;
     case MI_F_NE: closed(c, c); l.negate = true; break;
@@ -281,7 +328,7 @@ void BoundFilter::Resolve(const std::vector<ScanColumn>& all_columns, const std:
       leaf.out_col = static_cast<int32_t>(known - filter_names.begin());
       const ScanColumn& sc = Column(static_cast<size_t>(leaf.out_col), out_columns);
       if (sc.is_constant()) throw NotImplementedException("filter on the constant column '" + sc.name + "' is not pushed into the scan");
-      if (leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull) {
+      if ((leaf.op == device::kLeafIsNull || leaf.op == device::kLeafIsNotNull) && !leaf.is_string) {
         std::string why;
         if (!sc.field.Supported(&why)) throw NotImplementedException("Column '" + sc.name + "': " + why + " is not decoded by the MI355X scan path yet");
         continue;
@@ -334,7 +381,7 @@ void BoundFilter::UploadConstants() {
         else for (wide_t v : leaf.wide_in) add(v);
         list = DeviceBuffer(words.size() * 8);
         MI_HIP_CHECK(hipMemcpy(list.get(), words.data(), words.size() * 8, hipMemcpyHostToDevice));
-      } else if ((leaf.op == device::kLeafStrIn || leaf.op == device::kLeafStrRange) && !leaf.str_values.empty()) {
+      } else if ((leaf.op == device::kLeafStrIn || leaf.op == device::kLeafStrRange || leaf.op == device::kLeafStrMatch) && !leaf.str_values.empty()) {
         // 3 words per constant (its string_t image + the device address of its bytes), the bytes behind the table
         const size_t nc = leaf.str_values.size();
         size_t bytes = 0;
@@ -394,7 +441,15 @@ const void* DictMatchMap(DictState* dict, size_t li, const FilterLeaf& leaf, hip
   auto it = dict->match_maps.find(li);
   if (it != dict->match_maps.end()) return it->second.get();
   std::vector<uint8_t> codes(static_cast<size_t>(dict->dict_len) + 1, 0);
+  struct LeafSegments {   // the segments of a kLeafStrMatch leaf as likematch::Matches takes them
+    const std::vector<std::string>& v;
+    uint32_t len(int s) const { return static_cast<uint32_t>(v[static_cast<size_t>(s)].size()); }
+    uint8_t byte(int s, uint32_t i) const { return static_cast<uint8_t>(v[static_cast<size_t>(s)][i]); }
+  };
   auto passes = [&](const std::string& v) {   // std::string compares byte-wise (unsigned), a proper prefix first
+    if (leaf.op == device::kLeafStrMatch)
+      return likematch::Matches(LeafSegments{leaf.str_values}, static_cast<int>(leaf.str_values.size()), leaf.match_head, leaf.match_tail,
+                                reinterpret_cast<const uint8_t*>(v.data()), static_cast<uint32_t>(v.size()));
     if (leaf.op != device::kLeafStrRange) return std::binary_search(leaf.str_values.begin(), leaf.str_values.end(), v);
     auto cmp = [](const std::string& a, const std::string& b) {
       const int c = std::memcmp(a.data(), b.data(), std::min(a.size(), b.size()));
@@ -427,6 +482,19 @@ const void* DictMatchMap(DictState* dict, size_t li, const FilterLeaf& leaf, hip
 }
 }  // namespace
 
+void LeafConstants(const FilterLeaf& leaf, const DeviceBuffer& constants, bool ends_clause, device::FilterLeafDev& L) {
+  L.op = leaf.op;
+  L.flags = (ends_clause ? device::kLeafEndsClause : 0) | (leaf.negate ? device::kLeafNegate : 0);
+  L.lo = leaf.lo;
+  L.hi = leaf.hi;
+  L.in_values = constants.get<int64_t>();
+  L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.is_wide ? leaf.wide_in.size() : leaf.in_values.size());
+  if (leaf.op == device::kLeafStrRange)
+    L.n_in = (leaf.lo_open ? 0 : 1) | (leaf.lo_incl ? 2 : 0) | (leaf.hi_open ? 0 : 4) | (leaf.hi_incl ? 8 : 0);
+  if (leaf.op == device::kLeafStrMatch) L.n_in |= (leaf.match_head ? 0x100 : 0) | (leaf.match_tail ? 0x200 : 0);
+  L.width = 1;
+}
+
 device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_columns, const Batch& b, hipStream_t stream) const {
   device::FilterProgram prog;
   std::memset(&prog, 0, sizeof(prog));
@@ -436,15 +504,7 @@ device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_co
       const FilterLeaf& leaf = clause[j];
       device::FilterLeafDev& L = prog.leaves[prog.n_leaves++];
       const int32_t root = b.roots[static_cast<size_t>(leaf.out_col)];
-      L.op = leaf.op;
-      L.flags = (j + 1 == clause.size() ? device::kLeafEndsClause : 0) | (leaf.negate ? device::kLeafNegate : 0);
-      L.lo = leaf.lo;
-      L.hi = leaf.hi;
-      L.in_values = d_in_lists[li].get<int64_t>();
-      L.n_in = static_cast<int32_t>(leaf.is_string ? leaf.str_values.size() : leaf.is_wide ? leaf.wide_in.size() : leaf.in_values.size());
-      if (leaf.op == device::kLeafStrRange)
-        L.n_in = (leaf.lo_open ? 0 : 1) | (leaf.lo_incl ? 2 : 0) | (leaf.hi_open ? 0 : 4) | (leaf.hi_incl ? 8 : 0);
-      L.width = 1;
+      LeafConstants(leaf, d_in_lists[li], j + 1 == clause.size(), L);
       if (root < 0) {
         // the column is absent from this file (union_by_name): every row is NULL -- IS NULL keeps every row, everything
         // else keeps none (an empty, non-negated range over any readable bytes: the selection buffer itself)

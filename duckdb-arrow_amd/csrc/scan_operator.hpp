@@ -67,6 +67,9 @@ struct FilterLeaf {
   std::vector<std::string> str_values;   // ... these byte strings (negate: none of them)
   //! kLeafStrRange: str_values = {lower, upper}; lo_open / hi_open = no such bound, the two below = the bound itself passes
   bool lo_incl = false, hi_incl = false;
+  //! kLeafStrMatch (contains / ends_with / %-pattern LIKE, like_match.hpp): str_values = the literal segments in pattern
+  //! order, anchored at the head / the tail of the row; negate = NOT LIKE
+  bool match_head = false, match_tail = false;
   //! FLOAT / DOUBLE column (width 4 / 8): an integer leaf as above (kLeafRange / kLeafIn) whose lo / hi / in_values are the
   //! order-preserving keys of the constants (filter_key.hpp); the kernel maps every value the same way (kLeafFloat)
   int32_t float_width = 0;
@@ -82,6 +85,8 @@ using FilterCnf = std::vector<std::vector<FilterLeaf>>;
 //! doubles, a 128-bit one 128-bit integers, and a constant kind that does not fit its column is refused naming the column.
 //! Without it (mi_scan_set_filter_range) every constant is a stored int64.
 FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root, const std::vector<ScanColumn>* columns = nullptr);  // scan_filter.cpp
+//! what likematch::Compile answered -> nothing, or the refusal mi_scan_set_filter and mi_filter_like_match share (`column` may be empty)
+void CheckPattern(int compiled, int32_t op, const std::string& column);
 //! what a column's values are compared as by a pushed-down filter
 enum class FilterValueClass { kOther, kFloat32, kFloat64, kWide };
 FilterValueClass FilterClassOf(const ArrowField& field);
@@ -140,6 +145,10 @@ struct BoundFilter {
   //! versions do not have yet are made here and uploaded on `stream`, in front of the kernel that reads them.
   device::FilterProgram Program(const std::vector<ScanColumn>& out_columns, const Batch& b, hipStream_t stream) const;
 };
+
+//! What of a leaf does not depend on the record batch -- form, flags, bounds, the constants UploadConstants put into HBM --
+//! as the kernel takes it; the caller binds data, validity and width (BoundFilter::Program, mi_filter_string)
+void LeafConstants(const FilterLeaf& leaf, const DeviceBuffer& constants, bool ends_clause, device::FilterLeafDev& L);
 
 //! Vectors of one DataChunk (the storage behind mi_data_chunk.columns)
 struct ChunkStorage {

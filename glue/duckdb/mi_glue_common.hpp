@@ -22,6 +22,7 @@
 #include "duckdb/planner/expression/bound_comparison_expression.hpp"
 #include "duckdb/planner/expression/bound_conjunction_expression.hpp"
 #include "duckdb/planner/expression/bound_constant_expression.hpp"
+#include "duckdb/planner/expression/bound_function_expression.hpp"
 #include "duckdb/planner/expression/bound_operator_expression.hpp"
 #include "duckdb/planner/operator/logical_get.hpp"
 
@@ -580,6 +581,50 @@ class MiFilterTranslator {
           if (tree[at].value_kind == MI_FV_INT128) {
             out.in_lists.push_back(std::move(highs));
             tree[at].values_hi = out.in_lists.back()->data();
+          }
+        }
+        return true;
+      }
+      case ExpressionClass::BOUND_FUNCTION: {
+        // contains(col, 'x'), suffix / ends_with, prefix / starts_with and LIKE / NOT LIKE without an escape argument (`~~`,
+        // `!~~`; with ESCAPE the binder makes like_escape / not_like_escape of three arguments, which are not taken).  The
+        // optimizer rewrites LIKE '%x%', 'x%' and '%x' into the first three itself.  Function names are restated from
+        // upstream without DuckDB's source at hand: see INTEGRATION.md.
+        auto& fn = expr.Cast<BoundFunctionExpression>();
+        const string& fname = fn.function.name;
+        int32_t op;
+        if (fname == "contains") {
+          op = MI_F_CONTAINS;
+        } else if (fname == "suffix" || fname == "ends_with") {
+          op = MI_F_ENDS_WITH;
+        } else if (fname == "prefix" || fname == "starts_with") {
+          op = MI_F_STARTS_WITH;
+        } else if (fname == "~~") {
+          op = MI_F_LIKE;
+        } else if (fname == "!~~") {
+          op = MI_F_NOT_LIKE;
+        } else {
+          return false;
+        }
+        if (fn.children.size() != 2 || fn.children[1]->GetExpressionClass() != ExpressionClass::BOUND_CONSTANT) {
+          return false;
+        }
+        const char* name = ColumnOf(*fn.children[0]);
+        const auto& v = fn.children[1]->Cast<BoundConstantExpression>().value;
+        if (!name || v.IsNull() || (v.type().id() != LogicalTypeId::VARCHAR && v.type().id() != LogicalTypeId::BLOB)) {
+          return false;  // contains(list, x), a NULL pattern, ...
+        }
+        tree[at].op = op;
+        tree[at].column = name;
+        if (!SetConstant(tree[at], v)) {
+          return false;
+        }
+        if (op != MI_F_STARTS_WITH) {
+          // a pattern the library refuses (`_`, a ninth segment) stays above the scan: the host-side matcher answers
+          // exactly what mi_scan_set_filter would
+          int32_t unused = 0;
+          if (mi_filter_like_match(op, tree[at].str_value, tree[at].str_len, "", 0, &unused) != MI_OK) {
+            return false;
           }
         }
         return true;

@@ -565,7 +565,12 @@ typedef struct mi_data_chunk {
  * other NaN and is greater than everything else, +inf included, and -0.0 = +0.0; a constant for a FLOAT column is rounded
  * to float32 first, as DuckDB casts it to the column's type; HUGEINT / DECIMAL(19..38) columns against 128-bit stored
  * integers (MI_FV_INT128, or MI_FV_INT64 sign-extended); or VARCHAR / BLOB columns with = <> < <= > >= IN and MI_F_STARTS_WITH against byte strings (byte-wise order,
- * a proper prefix sorts first: DuckDB's default collation); IS [NOT] NULL takes any column.  SQL semantics: a comparison with NULL is not true, so the row is dropped
+ * a proper prefix sorts first: DuckDB's default collation), and with MI_F_CONTAINS, MI_F_ENDS_WITH, MI_F_LIKE and MI_F_NOT_LIKE: rows are byte
+ * strings, the constants of the first two are literal, and in a LIKE pattern `%` (any run of bytes) is the only special byte -- a pattern that
+ * holds `_` is MI_ENOTSUP (it steps over UTF-8 characters and stays above the scan; for `%` alone bytes and characters select the same rows of
+ * valid UTF-8), there is no ESCAPE, so `\` is a byte, no ILIKE and no collation; at most 8 literal segments between the `%` signs, more is
+ * MI_ENOTSUP.  A pattern without `%` is =, 'abc%' is MI_F_STARTS_WITH, '%' is IS NOT NULL; the empty needle of contains / ends_with matches
+ * every row that is not NULL.  String-view columns take none of the string forms; IS [NOT] NULL takes any column.  SQL semantics: a comparison with NULL is not true, so the row is dropped
  * unless another branch of an OR keeps it.  A filter column need not be projected.  The tree is normalised to at most
  * 24 leaves in conjunctive normal form; larger ones are refused with MI_ENOTSUP (DuckDB then keeps the filter above the
  * scan).  Chunks carry a selection vector (or only the selected rows: mi_scan_options.filter_compact).  Call between
@@ -573,6 +578,10 @@ typedef struct mi_data_chunk {
 enum mi_filter_op {
   MI_F_EQ = 1, MI_F_NE = 2, MI_F_LT = 3, MI_F_LE = 4, MI_F_GT = 5, MI_F_GE = 6, MI_F_IS_NULL = 7, MI_F_IS_NOT_NULL = 8,
   MI_F_IN = 9, MI_F_STARTS_WITH = 10 /* VARCHAR / BLOB: the row begins with str_value (LIKE 'abc%', prefix()) */,
+  MI_F_CONTAINS = 11,  /* VARCHAR / BLOB: str_value occurs in the row as a run of bytes (contains()); literal: % and _ are bytes */
+  MI_F_ENDS_WITH = 12, /* VARCHAR / BLOB: the row ends with str_value (suffix()); literal */
+  MI_F_LIKE = 13,      /* VARCHAR / BLOB: the row matches the pattern str_value, % = any run of bytes and the only wildcard */
+  MI_F_NOT_LIKE = 14,  /* ... does not match it; a NULL row passes neither */
   MI_F_AND = 16, MI_F_OR = 17
 };
 /* What mi_filter_node.value / values[] hold.  A kind that does not fit the column (a double against an integer column, an
@@ -593,7 +602,8 @@ typedef struct mi_filter_node {
   int64_t value;          /* comparison constant */
   const int64_t* values;  /* MI_F_IN */
   /* VARCHAR / BLOB columns (utf8, large_utf8, binary, fixed_size_binary, dictionary-encoded or not): MI_F_EQ / MI_F_NE /
-   * MI_F_LT / MI_F_LE / MI_F_GT / MI_F_GE / MI_F_STARTS_WITH take str_value (str_len bytes, no terminator needed), MI_F_IN
+   * MI_F_LT / MI_F_LE / MI_F_GT / MI_F_GE / MI_F_STARTS_WITH / MI_F_CONTAINS / MI_F_ENDS_WITH / MI_F_LIKE / MI_F_NOT_LIKE
+   * take str_value (str_len bytes, no terminator needed: a needle, a suffix or a pattern is bytes like any other constant), MI_F_IN
    * takes str_values / str_lens; byte-wise comparison like DuckDB's.  Leave NULL for the integer forms above. */
   const char* str_value;
   int32_t str_len;
@@ -766,6 +776,20 @@ int mi_filter_float_key(double v, int32_t width, int64_t* key);
 /* Debug getter: launches of the filter kernel by this process so far.  *base counts the instance every program of integer,
  * string and dictionary leaves runs, *extended the one launched for programs with a FLOAT / DOUBLE / 128-bit leaf. */
 int mi_filter_launch_counts(int64_t* base, int64_t* extended);
+/* Measurement entry (tools/filter_bench.py): one string leaf -- MI_F_EQ .. MI_F_GE, MI_F_STARTS_WITH, MI_F_CONTAINS, MI_F_ENDS_WITH,
+ * MI_F_LIKE, MI_F_NOT_LIKE with str_value -- over a resident string_t vector (16 bytes per row; rows longer than 12 bytes point
+ * at ptr_base + their position in `heap`, the device copy of the Arrow data buffer), folded and launched as mi_scan_set_filter
+ * would.  The call uploads the constant, launches the kernel `launches` times on the context's stream, waits, and writes the
+ * mean time of a launch between two device events to *ms (may be NULL). */
+int mi_filter_string(mi_ctx* ctx, const void* rows, const void* validity, int64_t nrows, const void* heap, uint64_t ptr_base, int32_t op,
+                     const char* str_value, int32_t str_len, mi_sel_t* sel_out, uint32_t* count_out, int32_t launches, float* ms);
+/* Test and verification hook, host only, no context: does a row that is not NULL pass `op` (MI_F_CONTAINS, MI_F_ENDS_WITH, MI_F_LIKE,
+ * MI_F_NOT_LIKE) with this needle / suffix / pattern -- the matcher the filter kernel compiles (csrc/like_match.hpp), for one row.
+ * *result = 1 or 0.  MI_ENOTSUP / MI_EINVAL exactly where mi_scan_set_filter answers so for that op and pattern. */
+int mi_filter_like_match(int32_t op, const char* pattern, int32_t pattern_len, const char* row, int32_t row_len, int32_t* result);
+/* Debug getter: launches by this process so far of the filter kernel's third instance, the one run for programs that hold a
+ * contains / ends_with / LIKE leaf which did not fold into another form.  mi_filter_launch_counts does not count them. */
+int mi_filter_pattern_launches(int64_t* n);
 /* Debug getter: row groups mi_writer_sink_scan's fused pump has encoded where the scan decoded them (no host staging) in this
  * process so far, and how many string-view columns (produce_arrow_string_view) they held, summed over those row groups. */
 int mi_writer_fused_counts(int64_t* row_groups, int64_t* view_columns);

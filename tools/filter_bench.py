@@ -1,19 +1,75 @@
 """Kernel-level timing of K6 on resident values: the one-leaf range (mi_filter_range on int32 / int64, mi_filter_between on
 float32 / float64 / int128 -- the same rows pass in every dtype) and, for int32, a compacting gather (transcode_gather)
 behind it through the scan operator's own entry points; for int128, transcode_copy over the same column as its yardstick.
-HIP-event-free: wall clock around 20 launches."""
+HIP-event-free: wall clock around 20 launches.
+--dtype string: one string leaf (--op contains | ends_with | like | not_like | starts_with, --pattern) over a VARCHAR column
+resident in HBM: --column l_comment or l_shipinstruct of the seeded lineitem (csrc/synth_lineitem.cpp), decoded once by
+transcode_string into string_t rows that point into the stream's HBM copy.  Times are device events around 20 launches
+(mi_filter_string); TB/s is over 16 bytes per row plus the payload bytes of the rows longer than 12, the bytes such a leaf
+has to read.  transcode_string over the same column (its own timed launch) is reported beside it as the ceiling: it reads the
+same rows' offsets and payload once and writes the 16 bytes the leaf reads."""
 import argparse, sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import duckdb_arrow_amd as da
 from duckdb_arrow_amd import _ffi
 ap = argparse.ArgumentParser()
-ap.add_argument("--dtype", choices=["int32", "int64", "float32", "float64", "int128"], default="int32")
-ap.add_argument("--rows", type=int, default=240_000_000)
+ap.add_argument("--dtype", choices=["int32", "int64", "float32", "float64", "int128", "string"], default="int32")
+ap.add_argument("--rows", type=int, default=None, help="default 240 M, 30 M for --dtype string")
+ap.add_argument("--op", choices=["contains", "ends_with", "like", "not_like", "starts_with"], default="contains")
+ap.add_argument("--pattern", default="special")
+ap.add_argument("--column", choices=["l_comment", "l_shipinstruct"], default="l_comment")
 args = ap.parse_args()
 ctx = da.Context(0)
-n = args.rows
+n = args.rows or (30_000_000 if args.dtype == "string" else 240_000_000)
 out = {"rows": n}
+
+
+def string_leaf():
+    from duckdb_arrow_amd.hbm import HbmStream
+    buf, info = da.synth_lineitem_stream(n_rows=n, rows_per_batch=n, seed=42, with_validity=False)   # one record batch
+    hs = HbmStream(ctx, buf, columns=[args.column], pointer_mode=_ffi.HBM_PTR_DEVICE)
+    del buf
+    hs.launch()
+    assert hs.status() == 0
+    col = hs.layout[0]["columns"][0]
+    assert col["name"] == args.column and col["nrows"] == n and col["width"] == 16 and col["valid_off"] < 0
+    rows = torch.from_numpy(hs._d2h(col["data_off"], 16 * n).view(np.uint32).reshape(n, 4).astype(np.int64))
+    lens = rows[:, 0]
+    long_rows = lens > 12
+    payload = int(lens[long_rows].sum().item())
+    heap = hs.in_ptr + col["body_off"] + col["buffers"][2][0]
+    sel = torch.empty(n, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros((n + 2047) // 2048, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    op = args.op.replace("_", " ") if args.op == "not_like" else args.op
+    launches = lambda: da.filter_pattern_launches() + sum(da.filter_launch_counts())
+    before = (da.filter_pattern_launches(), launches())
+    da.filter_string(ctx, hs.out_ptr + col["data_off"], 0, n, heap, col["ptr_base"], op, args.pattern, sel.data_ptr(), cnt.data_ptr(), launches=3)
+    ms = da.filter_string(ctx, hs.out_ptr + col["data_off"], 0, n, heap, col["ptr_base"], op, args.pattern, sel.data_ptr(), cnt.data_ptr(), launches=20)
+    k = int(cnt.sum().item())
+    alg = 16 * n + payload
+    out["column"] = {"name": args.column, "rows_longer_than_12": int(long_rows.sum().item()), "payload_bytes_of_those": payload,
+                     "mean_length": float(lens.double().mean().item())}
+    out["filter_program_string"] = {"op": op, "pattern": args.pattern, "ms": ms, "selected": k, "selectivity": k / n, "algorithmic_bytes": alg,
+                                    "TBps": alg / ms / 1e9, "pattern_instance": da.filter_pattern_launches() > before[0],
+                                    "launches": launches() - before[1]}
+    # the ceiling: the decode of the same column, timed by the plan (offsets and payload in, 16 bytes per row out)
+    hs.plan.launch_timed()
+    ms_classes = hs.plan.launch_timed()
+    stats = [c for c in hs.plan.class_stats() if c["rows"] > 0]
+    assert len(stats) == 1, stats
+    t_ms = max(ms_classes)
+    out["transcode_string"] = {"kernel": stats[0]["kernel"], "ms": t_ms, "bytes_read": stats[0]["bytes_read"], "bytes_written": stats[0]["bytes_written"],
+                               "TBps": (stats[0]["bytes_read"] + stats[0]["bytes_written"]) / t_ms / 1e9,
+                               "leaf_bytes_TBps": alg / t_ms / 1e9}
+    out["filter_ms_over_transcode_ms"] = ms / t_ms
+    print(json.dumps(out))
+
+
+if args.dtype == "string":
+    string_leaf()
+    sys.exit(0)
 width = {"int32": 4, "int64": 8, "float32": 4, "float64": 8, "int128": 16}[args.dtype]
 ints = torch.randint(8036, 10562, (n,), dtype=torch.int64 if width > 4 else torch.int32, device="cuda")
 if args.dtype == "int128":     # hugeint_t{uint64 lower; int64 upper}, upper = 0

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / occupancy table of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage).  Template
-instances are listed one line each under their own names: transcode_dec128<NULLS>, and filter_program<false> (integer, string
-and dictionary leaves) beside filter_program<true> (with the FLOAT / DOUBLE / 128-bit leaves)."""
+instances are listed one line each under their own names: transcode_dec128<NULLS>, and filter_program<false, false> (integer,
+string and dictionary leaves) beside filter_program<true, false> (with the FLOAT / DOUBLE / 128-bit leaves) and
+filter_program<true, true> (with the contains / ends_with / LIKE leaf besides)."""
 import glob, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "duckdb-arrow_amd", "csrc")

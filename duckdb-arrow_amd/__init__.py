@@ -290,6 +290,64 @@ def filter_between(ctx, values_ptr, width, validity_ptr, nrows, lo, hi, sel_ptr,
                                             C.c_void_p(stream or None)))
 
 
+_AGG_OPS = {"count_star": _ffi.AGG_COUNT_STAR, "count": _ffi.AGG_COUNT, "sum": _ffi.AGG_SUM, "sum_product": _ffi.AGG_SUM_PRODUCT,
+            "min": _ffi.AGG_MIN, "max": _ffi.AGG_MAX}
+_AGG_ARITY = {"count_star": 0, "count": 1, "sum": 1, "sum_product": 2, "min": 1, "max": 1}
+
+
+def _agg_check_specs(specs):
+    """What needs no library: 1 .. 8 specs, known operations, the right number of arguments -> [(name, args)]"""
+    specs = [tuple(sp) if isinstance(sp, (tuple, list)) else (sp,) for sp in specs]
+    if not 1 <= len(specs) <= _ffi.MAX_AGGREGATES:
+        raise MiError(_ffi.MI_EINVAL, "aggregate takes 1 to %d aggregates, not %d" % (_ffi.MAX_AGGREGATES, len(specs)))
+    out = []
+    for sp in specs:
+        name = str(sp[0]).lower() if sp else ""
+        if name not in _AGG_OPS:
+            raise MiError(_ffi.MI_EINVAL, "aggregate: unknown operation %r (one of %s)" % (sp[0] if sp else None, ", ".join(sorted(_AGG_OPS))))
+        if len(sp) - 1 != _AGG_ARITY[name]:
+            raise MiError(_ffi.MI_EINVAL, "aggregate: %s takes %d argument(s), not %d" % (name, _AGG_ARITY[name], len(sp) - 1))
+        out.append((name, sp[1:]))
+    return out
+
+
+def _agg_value(v):
+    """mi_agg_value -> int / float / None"""
+    if v.is_null:
+        return None
+    if v.kind == _ffi.AGG_VALUE_DOUBLE:
+        return struct.unpack("<d", struct.pack("<Q", v.lo))[0]
+    return (v.hi << 64) + v.lo
+
+
+def aggregate_vectors(ctx, specs, nrows, sel_ptr=0, count_ptr=0, stream=0, detail=False):
+    """Aggregates over resident vectors (mi_aggregate_vectors).  `specs` as Relation.aggregate takes them, a column being
+    (data_ptr, validity_ptr or 0, width, value_class) with value_class one of "signed", "unsigned", "float", "wide", "any";
+    sel_ptr / count_ptr: a selection vector in the filter's layout, or 0 for every row.  Returns ints / floats / None per
+    spec; with `detail` (value, contributing rows) pairs."""
+    classes = {"any": _ffi.AGG_CLASS_ANY, "signed": _ffi.AGG_CLASS_SIGNED, "unsigned": _ffi.AGG_CLASS_UNSIGNED,
+               "float": _ffi.AGG_CLASS_FLOAT, "wide": _ffi.AGG_CLASS_WIDE}
+    checked = _agg_check_specs(specs)
+    arr = (_ffi.AggVectorSpec * len(checked))()
+    for i, (name, cols) in enumerate(checked):
+        arr[i].op = _AGG_OPS[name]
+        for slot, col in zip((arr[i].a, arr[i].b), cols):
+            data, validity, width, cls = col
+            slot.data, slot.validity, slot.width, slot.value_class = data or None, validity or None, width, classes[cls]
+    out = (_ffi.AggValue * len(checked))()
+    _ffi.check(_ffi.lib().mi_aggregate_vectors(ctx._h, arr, len(checked), sel_ptr or None, count_ptr or None, nrows, out,
+                                               C.c_void_p(stream or None)))
+    return [(_agg_value(v), v.count) if detail else _agg_value(v) for v in out]
+
+
+def aggregate_counters():
+    """(agg_windows launches, agg_combine launches, agg_windows ms, agg_combine ms) of this process; the times are summed
+    over the mi_scan_aggregate calls that ran with MI_AGG_TIMING=1 in the environment."""
+    a, b, c, d = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    _ffi.check(_ffi.lib().mi_aggregate_counters(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
 def filter_float_key(value, width):
     """The order-preserving integer key the filter kernel compares a FLOAT (width 4) / DOUBLE (width 8) value by."""
     key = C.c_int64()
@@ -666,6 +724,31 @@ class Relation:
         _ffi.check(_ffi.lib().mi_scan_sum_product(self._h, a.encode(), b.encode(), arr, len(filters), C.byref(r)))
         self._initialised = True
         return (r.sum_hi << 64) + r.sum_lo, r.rows_selected, r.rows_scanned
+
+    def aggregate(self, specs, detail=False):
+        """SELECT agg_1, ..., agg_n (n <= 8) over the rows the pushed-down filter keeps, on the GPU in one pass
+        (mi_scan_aggregate); call it in place of chunks() / count().  `specs`: ("count_star",), ("count", c), ("sum", c),
+        ("sum_product", a, b), ("min", c), ("max", c).  Returns one Python value per spec -- an int (counts; sums, minima and
+        maxima of integer-like columns as the stored integers, exact in 128 bits), a float (FLOAT / DOUBLE columns) or None
+        (SUM / MIN / MAX over no row that is not NULL); with `detail` also the rows scanned and selected:
+        (values, rows_scanned, rows_selected)."""
+        checked = _agg_check_specs(specs)
+        arr = (_ffi.AggSpec * len(checked))()
+        keep = []
+        for i, (name, cols) in enumerate(checked):
+            arr[i].op = _AGG_OPS[name]
+            names = [c.encode() for c in cols]
+            keep.append(names)
+            if names:
+                arr[i].column_a = names[0]
+            if len(names) > 1:
+                arr[i].column_b = names[1]
+        out = (_ffi.AggValue * len(checked))()
+        scanned, selected = C.c_int64(), C.c_int64()
+        _ffi.check(_ffi.lib().mi_scan_aggregate(self._h, arr, len(checked), out, C.byref(scanned), C.byref(selected)))
+        self._initialised = True
+        values = [_agg_value(v) for v in out]
+        return (values, scanned.value, selected.value) if detail else values
 
     def progress(self):
         return _ffi.lib().mi_scan_progress(self._h)

@@ -23,6 +23,7 @@ K_ENC_COPY, K_ENC_DEC128, K_ENC_BOOL, K_ENC_STR32, K_ENC_VALIDITY, K_ENC_LIST32,
 ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL_RANGE, ST_OFFSET_OVERFLOW, ST_DICT_INDEX, ST_INTERNAL = \
     1, 2, 4, 8, 16, 32, 64, 128
 ST_BAD_RUN_ENDS = 512
+ST_SEL_RANGE = 1024
 
 
 class Field(C.Structure):
@@ -129,6 +130,30 @@ class HbmLayout(C.Structure):
 
 class SumProductResult(C.Structure):
     _fields_ = [("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("rows_scanned", C.c_int64), ("rows_selected", C.c_int64)]
+
+
+AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_SUM_PRODUCT, AGG_MIN, AGG_MAX = 1, 2, 3, 4, 5, 6
+MAX_AGGREGATES = 8
+AGG_VALUE_INT128, AGG_VALUE_DOUBLE = 0, 1
+AGG_CLASS_ANY, AGG_CLASS_SIGNED, AGG_CLASS_UNSIGNED, AGG_CLASS_FLOAT, AGG_CLASS_WIDE = 0, 1, 2, 3, 4
+
+
+class AggSpec(C.Structure):
+    _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("column_a", C.c_char_p), ("column_b", C.c_char_p),
+                ("reserved", C.c_int64 * 2)]
+
+
+class AggValue(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64), ("count", C.c_int64), ("kind", C.c_int32), ("is_null", C.c_int32),
+                ("reserved", C.c_int64 * 2)]
+
+
+class AggColumn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("validity", C.c_void_p), ("width", C.c_int32), ("value_class", C.c_int32)]
+
+
+class AggVectorSpec(C.Structure):
+    _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("a", AggColumn), ("b", AggColumn), ("reserved", C.c_int64 * 2)]
 
 
 class ArrowArrayStream(C.Structure):   # Arrow C stream interface: 4 callbacks + private_data
@@ -241,6 +266,9 @@ SIGNATURES = {
     "mi_scan_next": (C.c_int, [P, C.POINTER(DataChunk)]),
     "mi_scan_count": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mi_scan_sum_product": (C.c_int, [P, C.c_char_p, C.c_char_p, C.POINTER(RangeFilter), C.c_int32, C.POINTER(SumProductResult)]),
+    "mi_scan_aggregate": (C.c_int, [P, C.POINTER(AggSpec), C.c_int32, C.POINTER(AggValue), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mi_aggregate_vectors": (C.c_int, [P, C.POINTER(AggVectorSpec), C.c_int32, P, P, C.c_int64, C.POINTER(AggValue), P]),
+    "mi_aggregate_counters": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mi_scan_progress": (C.c_double, [P]),
     "mi_scan_get_stats": (C.c_int, [P, P]),
     "mi_write_options_init": (C.c_int, [C.POINTER(WriteOptions)]),

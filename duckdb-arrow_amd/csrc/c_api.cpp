@@ -401,6 +401,55 @@ int mi_filter_string(mi_ctx* ctx, const void* rows, const void* validity, int64_
   });
 }
 
+int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel, const uint32_t* sel_count,
+                         int64_t nrows, mi_agg_value* out, void* stream) {
+  return Wrap([&] {
+    if (!ctx || !aggs || !out) throw InvalidInputException("mi_aggregate_vectors: NULL argument");
+    if (n_aggs < 1 || n_aggs > MI_MAX_AGGREGATES)
+      throw InvalidInputException("mi_aggregate_vectors takes 1 to " + std::to_string(MI_MAX_AGGREGATES) + " aggregates, not " + std::to_string(n_aggs));
+    if ((sel == nullptr) != (sel_count == nullptr)) throw InvalidInputException("mi_aggregate_vectors: sel and sel_count go together");
+    if (nrows < 0) throw InvalidInputException("mi_aggregate_vectors: negative row count");
+    device::AggProgram prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_aggs = n_aggs;
+    auto column = [](const mi_agg_column& c) {
+      device::AggColumnDev d;
+      d.data = c.data;
+      d.validity = static_cast<const uint64_t*>(c.validity);
+      d.width = c.width;
+      d.cls = c.value_class;
+      return d;
+    };
+    for (int32_t i = 0; i < n_aggs; i++) {
+      prog.aggs[i].op = aggs[i].op;
+      prog.aggs[i].a = column(aggs[i].a);
+      prog.aggs[i].b = column(aggs[i].b);
+    }
+    if (!device::AggProgramIsValid(prog))
+      throw InvalidInputException("mi_aggregate_vectors: an operation, value class or width that does not fit (SUM takes integers of width 1 / 2 / 4 / 8 "
+                                  "or floats of width 4 / 8, MIN / MAX also width 16, a product two integers or two floats)");
+    ctx->ctx->Bind();
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
+    const int64_t n_windows = (nrows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
+    const size_t n = static_cast<size_t>(n_aggs);
+    DeviceBuffer d_partials((static_cast<size_t>(n_windows) * n + n) * sizeof(aggmerge::Partial));   // [window][aggregate], then the accumulators
+    aggmerge::Partial* partials = d_partials.get<aggmerge::Partial>();
+    aggmerge::Partial* acc = partials + static_cast<size_t>(n_windows) * n;
+    MI_HIP_CHECK(hipMemsetAsync(acc, 0, n * sizeof(aggmerge::Partial), s));
+    MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, nrows, partials, s));
+    MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, acc, s));
+    std::vector<aggmerge::Partial> host(n);
+    MI_HIP_CHECK(hipMemcpyAsync(host.data(), acc, n * sizeof(aggmerge::Partial), hipMemcpyDeviceToHost, s));
+    MI_HIP_CHECK(hipStreamSynchronize(s));
+    uint32_t flags = 0;
+    for (size_t i = 0; i < n; i++) {
+      FillAggValue(prog.aggs[i].op, prog.aggs[i].a.cls, host[i], &out[i]);
+      flags |= static_cast<uint32_t>(host[i].flags);
+    }
+    ThrowForStatus(flags);
+  });
+}
+
 int mi_filter_float_key(double v, int32_t width, int64_t* key) {
   return Wrap([&] {
     if (!key || (width != 4 && width != 8)) throw InvalidInputException("mi_filter_float_key: width must be 4 or 8");

@@ -545,6 +545,7 @@ void ThrowForStatus(uint32_t bits) {
   if (bits & MI_ST_DECOMPRESS)
     throw IOException("LZ4_FRAME compressed buffer is malformed or does not decompress to its declared size (Expected decompressed size mismatch)");
   if (bits & MI_ST_INTERNAL) throw InternalException("a kernel gave up waiting for another workgroup (bounded spin exceeded)");
+  if (bits & MI_ST_SEL_RANGE) throw InvalidInputException("aggregate: a selection index names no row of its 2048-row window (skipped: the results are not valid)");
   if (bits & MI_ST_OFFSET_OVERFLOW)
     throw InvalidInputException(
         "Arrow Appender: The maximum total string size for regular string buffers is 2147483647 but the offset exceeds this.\n"

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/mi_arrow_ipc.h"
+#include "agg_merge.hpp"
 #include "lz4_encode_format.hpp"
 
 namespace miarrow {
@@ -166,6 +167,38 @@ int64_t FilterPatternLaunches();
 // lo <= v < hi on one column (mi_filter_range)
 hipError_t LaunchFilterRange(const void* values, int32_t width, const void* validity, int64_t nrows, int64_t lo,
                              int64_t hi, mi_sel_t* sel_out, uint32_t* count_out, hipStream_t stream);
+
+// K9: aggregates over decoded vectors under the filter's selection vectors (kernels_aggregate.hip; the rules of a merge are
+// agg_merge.hpp).  The program -- at most aggmerge::kMaxAggregates descriptors -- is a kernel argument, as FilterProgram is.
+struct AggColumnDev {
+  const void* data;                 // decoded vector (device); may be NULL for COUNT, which reads the validity alone
+  const uint64_t* validity;         // validity words (device) or NULL = all valid
+  int32_t width;                    // bytes per row
+  int32_t cls;                      // aggmerge::kClass*
+};
+struct AggDescDev {
+  AggColumnDev a, b;                // b: the second factor of kOpSumProduct
+  int32_t op;                       // aggmerge::kOp*
+  int32_t _pad;
+};
+struct AggProgram {
+  int32_t n_aggs;
+  int32_t _pad;
+  AggDescDev aggs[aggmerge::kMaxAggregates];
+};
+//! what the launchers accept: 1 .. 8 aggregates, widths that fit their class, no SUM over 16-byte values, products of two
+//! integers or two floats
+bool AggProgramIsValid(const AggProgram& prog);
+//! agg_windows: one partial per window and aggregate to d_partials[window * n_aggs + aggregate].  sel / sel_count in the
+//! filter's layout (2048 slots per window, the first sel_count[w] read), or both NULL = every row.
+hipError_t LaunchAggWindows(const AggProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
+                            aggmerge::Partial* d_partials, hipStream_t stream);
+//! agg_combine: folds the partials of n_windows windows, in ascending order, into d_acc[0 .. n_aggs)
+hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_partials, int64_t n_windows, aggmerge::Partial* d_acc,
+                            hipStream_t stream);
+
+//! launches by this process so far: [0] agg_windows, [1] agg_combine
+void AggLaunchCounts(int64_t out[2]);
 
 // K7 launches.  The string / list kernel is a single pass (decoupled look-back across the tiles of a column); it needs
 // 2 * total_tiles + 1 state words (zeroed by the launch).

@@ -1,0 +1,255 @@
+// kernels_aggregate.hip -- K9: up to 8 aggregates (COUNT(*), COUNT, SUM, SUM of a product, MIN, MAX) over decoded vectors,
+// under the selection vectors of the pushed-down filter (K6) or over every row (mi_scan_aggregate, mi_aggregate_vectors).
+//
+// agg_windows: one 256-thread workgroup per 2048-row window.  With a selection vector the lanes read sel[0 .. count)
+// coalesced and gather the rows it names (ascending inside the window, as kernels_gather.hip reads them); without one they
+// stream the window's rows.  Per aggregate: a lane-local partial, a wave reduction by shuffles, the four wave results
+// through LDS, one record to partials[window][aggregate].  The aggregate loop is OUTSIDE the row loop: a lane holds one
+// partial (4 words) at a time whatever the program's length, at the price of reading the window's <= 8 KiB of `sel` again
+// per aggregate -- from L2 / the vector L1, the first aggregate brought it in -- so 8 aggregates cost no more registers
+// than one and nothing spills.
+// agg_combine: one workgroup, lane a folds partials[0 .. n_windows)[a] in ascending window order into the running
+// accumulator of aggregate a.
+// No atomics, no waiting on another workgroup: the only reduction across workgroups is the launch boundary between the
+// two kernels, so every sum -- the double sums included -- is folded in one fixed order.  How two partials become one is
+// agg_merge.hpp, shared with the host.
+// No loaded value is used as an address except a selection index, which may come from memory the caller filled: the count
+// of a window is clamped to the rows the window has, and an index at or past them is skipped and raises MI_ST_SEL_RANGE in
+// the partial's flags, so nothing outside the vectors is read.
+#include "device_common.hpp"
+#include "agg_merge.hpp"
+
+#include <atomic>
+
+namespace miarrow {
+namespace device {
+
+namespace {
+
+using aggmerge::Partial;
+
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+typedef u64x2 u64x2_a8 __attribute__((aligned(8)));   // a zero-copy alias of the Arrow body is 8-byte aligned only (leaf_wide)
+
+__device__ __forceinline__ bool row_is_valid(const uint64_t* validity, int64_t row) {
+  return validity == nullptr || ((GC<uint64_t>(validity)[row >> 6] >> (row & 63)) & 1ull) != 0;
+}
+
+// one integer of any class as a 128-bit two's-complement integer
+__device__ __forceinline__ void load_integer(const AggColumnDev& c, int64_t row, uint64_t* lo, uint64_t* hi) {
+  if (c.cls == aggmerge::kClassWide) {
+    const u64x2 v = GC<u64x2_a8>(c.data)[row];
+    *lo = v.x;
+    *hi = v.y;
+    return;
+  }
+  uint64_t u;
+  int64_t s;
+  switch (c.width) {
+    case 1: u = GC<uint8_t>(c.data)[row]; s = static_cast<int8_t>(u); break;
+    case 2: u = GC<uint16_t>(c.data)[row]; s = static_cast<int16_t>(u); break;
+    case 4: u = GC<uint32_t>(c.data)[row]; s = static_cast<int32_t>(u); break;
+    default: u = GC<uint64_t>(c.data)[row]; s = static_cast<int64_t>(u); break;
+  }
+  if (c.cls == aggmerge::kClassUnsigned) {
+    *lo = u;
+    *hi = 0;
+  } else {
+    *lo = static_cast<uint64_t>(s);
+    *hi = s < 0 ? ~0ull : 0ull;
+  }
+}
+
+__device__ __forceinline__ Partial load_partial(gptr<const Partial> p) {
+  const u64x2 x = ((gptr<const u64x2_a8>)p)[0], y = ((gptr<const u64x2_a8>)p)[1];
+  return Partial{x.x, x.y, y.x, y.y};
+}
+__device__ __forceinline__ void store_partial(gptr<Partial> p, const Partial& v) {
+  const u64x2 x = {v.lo, v.hi}, y = {v.count, v.flags};
+  ((gptr<u64x2_a8>)p)[0] = x;
+  ((gptr<u64x2_a8>)p)[1] = y;
+}
+
+__device__ __forceinline__ double load_double(const AggColumnDev& c, int64_t row) {
+  return c.width == 4 ? static_cast<double>(GC<float>(c.data)[row]) : GC<double>(c.data)[row];
+}
+
+template <bool HAS_SEL>
+__global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram prog, const mi_sel_t* __restrict__ sel_p,
+                                                             const uint32_t* __restrict__ sel_count_p, int64_t nrows,
+                                                             Partial* __restrict__ partials_p) {
+  __shared__ Partial wave_part[kBlockThreads / 64];
+  const int64_t window = blockIdx.x;
+  const int64_t row0 = window * kTileRows;
+  const int64_t left = nrows - row0;
+  const uint32_t n = left < kTileRows ? static_cast<uint32_t>(left < 0 ? 0 : left) : static_cast<uint32_t>(kTileRows);
+  uint32_t cnt = n;
+  if (HAS_SEL) {
+    const uint32_t c = GC<uint32_t>(sel_count_p)[window];
+    cnt = c < n ? c : n;   // a count past the window's rows is clamped: sel[] is read inside the window's slots only
+  }
+  gptr<const mi_sel_t> sel = GC<mi_sel_t>(sel_p) + row0;
+  gptr<Partial> partials = GM<Partial>(partials_p) + window * prog.n_aggs;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma clang loop unroll(disable)
+  for (int a = 0; a < prog.n_aggs; a++) {
+    const AggDescDev& d = prog.aggs[a];
+    const int op = d.op, cls = d.a.cls;
+    const bool is_sum = op == aggmerge::kOpSum || op == aggmerge::kOpSumProduct;
+    Partial p = {0ull, 0ull, 0ull, 0ull};
+    for (uint32_t i = threadIdx.x; i < cnt; i += kBlockThreads) {
+      uint32_t r = i;
+      if (HAS_SEL) {
+        r = sel[i];
+        if (r >= n) {   // not a row of this window: never dereferenced
+          p.flags |= MI_ST_SEL_RANGE;
+          continue;
+        }
+      }
+      const int64_t row = row0 + r;
+      if (op == aggmerge::kOpCountStar) {
+        p.count++;
+        continue;
+      }
+      bool valid = row_is_valid(d.a.validity, row);
+      if (op == aggmerge::kOpSumProduct) valid = valid && row_is_valid(d.b.validity, row);
+      if (!valid) continue;
+      if (op == aggmerge::kOpCount) {
+        p.count++;
+      } else if (cls == aggmerge::kClassFloat) {
+        double v = load_double(d.a, row);
+        if (op == aggmerge::kOpSumProduct) v = __dmul_rn(v, load_double(d.b, row));   // rounded product, then the sum: no fma
+        if (is_sum) {
+          p.lo = aggmerge::BitsOf(p.count ? __dadd_rn(aggmerge::DoubleOf(p.lo), v) : v);
+          p.count++;
+        } else {
+          aggmerge::Fold(op, cls, &p, aggmerge::CanonicalBits(v), 0ull);
+        }
+      } else {
+        uint64_t lo, hi;
+        load_integer(d.a, row, &lo, &hi);
+        if (op == aggmerge::kOpSumProduct) {
+          uint64_t blo, bhi;
+          load_integer(d.b, row, &blo, &bhi);
+          const unsigned __int128 x = (static_cast<unsigned __int128>(hi) << 64) | lo, y = (static_cast<unsigned __int128>(bhi) << 64) | blo;
+          const unsigned __int128 prod = x * y;   // modulo 2^128: the two's-complement product
+          lo = static_cast<uint64_t>(prod);
+          hi = static_cast<uint64_t>(prod >> 64);
+        }
+        if (is_sum) {
+          aggmerge::Add128(&p.lo, &p.hi, lo, hi);
+          p.count++;
+        } else {
+          aggmerge::Fold(op, cls, &p, lo, hi);
+        }
+      }
+    }
+    // wave reduction: lane l takes lane l + d while that lane exists (a lane whose partner would lie past the wave keeps its
+    // partial as it is: __shfl_down hands such a lane its own value back, which must not be folded in a second time)
+#pragma unroll
+    for (int dist = 32; dist >= 1; dist >>= 1) {
+      Partial o;
+      o.lo = __shfl_down(p.lo, dist, 64);
+      o.hi = __shfl_down(p.hi, dist, 64);
+      o.count = __shfl_down(p.count, dist, 64);
+      o.flags = __shfl_down(p.flags, dist, 64);
+      if (lane + dist < 64) aggmerge::Merge(op, cls, &p, o);
+    }
+    if (lane == 0) wave_part[wave] = p;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      Partial q = wave_part[0];
+#pragma unroll
+      for (int k = 1; k < kBlockThreads / 64; k++) aggmerge::Merge(op, cls, &q, wave_part[k]);
+      store_partial(partials + a, q);
+    }
+    __syncthreads();   // wave_part is written again by the next aggregate
+  }
+}
+
+// ops / classes: 4 bits per aggregate (a lane picks its own: no indexing of the kernel argument by a lane's number)
+__global__ __launch_bounds__(64) void agg_combine(uint32_t ops, uint32_t classes, int32_t n_aggs, const Partial* __restrict__ partials_p,
+                                                  int64_t n_windows, Partial* __restrict__ acc_p) {
+  const int a = threadIdx.x;
+  if (a >= n_aggs) return;
+  const int op = static_cast<int>((ops >> (4 * a)) & 15u), cls = static_cast<int>((classes >> (4 * a)) & 15u);
+  gptr<const Partial> partials = GC<Partial>(partials_p);
+  gptr<Partial> acc = GM<Partial>(acc_p);
+  Partial p = load_partial(acc + a);
+#pragma unroll 4
+  for (int64_t w = 0; w < n_windows; w++) {
+    const Partial q = load_partial(partials + (w * n_aggs + a));
+    aggmerge::Merge(op, cls, &p, q);
+  }
+  store_partial(acc + a, p);
+}
+
+bool ColumnOk(const AggColumnDev& c, bool needs_values) {
+  if (!needs_values) return true;
+  if (!c.data) return false;
+  switch (c.cls) {
+    case aggmerge::kClassSigned: case aggmerge::kClassUnsigned: return c.width == 1 || c.width == 2 || c.width == 4 || c.width == 8;
+    case aggmerge::kClassFloat: return c.width == 4 || c.width == 8;
+    case aggmerge::kClassWide: return c.width == 16;
+    default: return false;
+  }
+}
+
+}  // namespace
+
+namespace {
+std::atomic<int64_t> g_agg_launches[2];   // agg_windows, agg_combine
+}  // namespace
+
+void AggLaunchCounts(int64_t out[2]) {
+  out[0] = g_agg_launches[0].load();
+  out[1] = g_agg_launches[1].load();
+}
+
+bool AggProgramIsValid(const AggProgram& prog) {
+  if (prog.n_aggs < 1 || prog.n_aggs > aggmerge::kMaxAggregates) return false;
+  for (int a = 0; a < prog.n_aggs; a++) {
+    const AggDescDev& d = prog.aggs[a];
+    if (d.op < aggmerge::kOpCountStar || d.op > aggmerge::kOpMax) return false;
+    const bool values = d.op != aggmerge::kOpCountStar && d.op != aggmerge::kOpCount;
+    if (!ColumnOk(d.a, values)) return false;
+    if (d.op == aggmerge::kOpSum && d.a.cls == aggmerge::kClassWide) return false;
+    if (d.op == aggmerge::kOpSumProduct) {
+      if (!ColumnOk(d.b, true) || d.a.cls == aggmerge::kClassWide || d.b.cls == aggmerge::kClassWide) return false;
+      if ((d.a.cls == aggmerge::kClassFloat) != (d.b.cls == aggmerge::kClassFloat)) return false;
+    }
+  }
+  return true;
+}
+
+hipError_t LaunchAggWindows(const AggProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
+                            aggmerge::Partial* d_partials, hipStream_t stream) {
+  MI_DROP_STALE_ERROR();
+  if (nrows <= 0) return hipSuccess;
+  if (!AggProgramIsValid(prog) || (sel == nullptr) != (sel_count == nullptr) || !d_partials) return hipErrorInvalidValue;
+  const int64_t windows = (nrows + kTileRows - 1) / kTileRows;
+  if (windows > 0x7FFFFFFFll) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<uint32_t>(windows)), block(kBlockThreads);
+  if (sel) hipLaunchKernelGGL(agg_windows<true>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials);
+  else hipLaunchKernelGGL(agg_windows<false>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials);
+  g_agg_launches[0]++;
+  return hipGetLastError();
+}
+
+hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_partials, int64_t n_windows, aggmerge::Partial* d_acc,
+                            hipStream_t stream) {
+  MI_DROP_STALE_ERROR();
+  if (n_windows <= 0) return hipSuccess;
+  if (!AggProgramIsValid(prog) || !d_partials || !d_acc) return hipErrorInvalidValue;
+  uint32_t ops = 0, classes = 0;
+  for (int a = 0; a < prog.n_aggs; a++) {
+    ops |= static_cast<uint32_t>(prog.aggs[a].op) << (4 * a);
+    classes |= static_cast<uint32_t>(prog.aggs[a].a.cls) << (4 * a);
+  }
+  hipLaunchKernelGGL(agg_combine, dim3(1), dim3(64), 0, stream, ops, classes, prog.n_aggs, d_partials, n_windows, d_acc);
+  g_agg_launches[1]++;
+  return hipGetLastError();
+}
+
+}  // namespace device
+}  // namespace miarrow

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -195,7 +196,7 @@ void ArrowScan::Init(const std::vector<std::string>& projected) {
   if (has_filter) {
     filter.Resolve(all_columns, out_columns);
     filter.UploadConstants();
-    if (opts.filter_compact) {
+    if (opts.filter_compact && !aggn.on) {   // mi_scan_aggregate materialises nothing for a consumer
       for (auto& c : out_columns) {
         if (c.is_constant()) continue;
         int32_t kind, w;
@@ -517,7 +518,8 @@ void ArrowScan::EnqueueBatch(Slot& s) {
   const bool zero_copy = opts.zero_copy_direct >= 0 && (opts.device_resident || !keep_on_device);
   // a host consumer of a body that only exists decompressed in HBM: string_t rows point into a pinned mirror of the body
   const bool mirror = b.deferred && !opts.device_resident;
-  po.zero_copy_direct = zero_copy && !agg.on && !s.compact && !mirror;
+  // (mi_scan_aggregate reads the vectors in HBM: a host consumer's alias would be the pinned host body)
+  po.zero_copy_direct = zero_copy && !agg.on && !s.compact && !mirror && !(aggn.on && !opts.device_resident);
   if (mirror) Retire(Grow(s.h_mirror, in_bytes, GrownCapacity(in_bytes, s.h_mirror.size(), 1 << 16)));
   po.unset_all_valid = opts.unset_all_valid != 0;
   s.planner.opts = po;
@@ -553,11 +555,17 @@ void ArrowScan::EnqueueBatch(Slot& s) {
       else s.col_root[c] = s.planner.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
     }
   }
+  if (aggn.on) {   // refused before anything of this record batch is queued on the GPU
+    for (const auto& a : aggn.aggs)
+      for (const int32_t c : {a.col_a, a.col_b})
+        if (c >= 0 && src.out_to_file_column[static_cast<size_t>(c)] < 0)
+          throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
+  }
   if (has_filter) {
     s.sel_off = s.planner.Reserve(static_cast<size_t>(n) * 4 + 16);
     s.sel_count_off = s.planner.Reserve(static_cast<size_t>(n_windows) * 4 + 16);
   }
-  s.d2h_bytes = s.compact ? 0 : s.planner.arena_bytes;
+  s.d2h_bytes = (s.compact || aggn.on) ? 0 : s.planner.arena_bytes;   // (the aggregates' vectors never leave HBM)
   if (has_filter) {
     for (size_t k = 0; k < filter.columns.size(); k++) {
       const int32_t wc = filter.columns[k];
@@ -665,6 +673,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     MI_HIP_CHECK(device::LaunchAggSumProduct(a, agg.d_acc.get<unsigned long long>(), ctx->num_cus, ctx->stream));
     agg.rows_scanned += n;
   }
+  if (aggn.on && n > 0) EnqueueAggregates(s);
   MI_HIP_CHECK(hipEventRecord(s.compute_done, ctx->stream));
   MI_HIP_CHECK(hipStreamWaitEvent(ctx->d2h_stream, s.compute_done, 0));
   if (has_filter && n > 0)  // the per-window counts always come back (tiny): chunk sizes, Count(), the stage-B layout
@@ -674,7 +683,7 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     s.needs_stage_b = true;
     return;
   }
-  s.host_vectors = !opts.device_resident && !agg.on && s.d2h_bytes > 0 && !keep_on_device;
+  s.host_vectors = !opts.device_resident && !agg.on && !aggn.on && s.d2h_bytes > 0 && !keep_on_device;
   if (s.host_vectors) {
     MI_HIP_CHECK(hipMemcpyAsync(s.h_out.get(), s.d_out.get(), s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
     stats.d2h_bytes += static_cast<int64_t>(s.d2h_bytes);
@@ -1301,6 +1310,203 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
   agg.on = false;
 }
 
+// ------------------------------------------------------------------------------------------------ fused aggregates
+// mi_scan_aggregate: SELECT agg_1 .. agg_n over the rows the pushed-down filter keeps.  The columns are validated at bind
+// time (messages name the column and the operation), the call projects exactly the aggregate columns, and every record
+// batch gets agg_windows + agg_combine behind its filter on the compute stream (EnqueueAggregates): nothing but the
+// filter's counts comes back per batch, the accumulator block once at the end.
+namespace {
+std::atomic<int64_t> g_agg_events_ns[2];   // MI_AGG_TIMING=1: device time of agg_windows / agg_combine, nanoseconds
+
+//! aggmerge::kClass* of the values SUM / MIN / MAX read from `c`, kClassAny when they read none of its kind
+int32_t AggClassOf(const ScanColumn& c) {
+  if (c.is_constant() || c.field.has_dictionary) return aggmerge::kClassAny;
+  const ArrowField& vf = ValueField(c.field);
+  int32_t kind, w;
+  int64_t param;
+  if (vf.has_dictionary || !c.field.Plan(&kind, &param, &w)) return aggmerge::kClassAny;
+  switch (FilterClassOf(c.field)) {
+    case FilterValueClass::kFloat32: case FilterValueClass::kFloat64: return aggmerge::kClassFloat;
+    case FilterValueClass::kWide: return aggmerge::kClassWide;
+    default: break;
+  }
+  if (vf.Plan(&kind, &param, &w) && IsIntegerLike(kind, w, vf, /*allow_bool*/ false))
+    return vf.type == MI_AT_INT && !vf.is_signed ? aggmerge::kClassUnsigned : aggmerge::kClassSigned;
+  return aggmerge::kClassAny;
+}
+}  // namespace
+
+const char* AggOpName(int32_t op) {
+  switch (op) {
+    case aggmerge::kOpCountStar: return "COUNT(*)";
+    case aggmerge::kOpCount: return "COUNT";
+    case aggmerge::kOpSum: return "SUM";
+    case aggmerge::kOpSumProduct: return "SUM_PRODUCT";
+    case aggmerge::kOpMin: return "MIN";
+    case aggmerge::kOpMax: return "MAX";
+    default: return "?";
+  }
+}
+
+void AggTimingTotals(double out_ms[2]) {
+  out_ms[0] = static_cast<double>(g_agg_events_ns[0].load()) * 1e-6;
+  out_ms[1] = static_cast<double>(g_agg_events_ns[1].load()) * 1e-6;
+}
+
+void ArrowScan::Aggregate(const std::vector<AggSpec>& specs, AggResult* out) {
+  if (initialized) throw InvalidInputException("mi_scan_aggregate replaces mi_scan_init / mi_scan_next: call it right after bind");
+  if (specs.empty() || specs.size() > static_cast<size_t>(aggmerge::kMaxAggregates))
+    throw InvalidInputException("mi_scan_aggregate takes 1 to " + std::to_string(aggmerge::kMaxAggregates) + " aggregates, not " + std::to_string(specs.size()));
+  Bind();
+  // ---- bind-time validation, and the projection: exactly the columns the aggregates read
+  std::vector<std::string> proj;
+  auto slot_of = [&](const std::string& name) {
+    for (size_t i = 0; i < proj.size(); i++)
+      if (proj[i] == name) return static_cast<int32_t>(i);
+    proj.push_back(name);
+    return static_cast<int32_t>(proj.size() - 1);
+  };
+  auto column_of = [&](const std::string& name, int32_t op) -> const ScanColumn& {
+    auto it = std::find_if(all_columns.begin(), all_columns.end(), [&](const ScanColumn& sc) { return sc.name == name; });
+    if (it == all_columns.end()) throw InvalidInputException(std::string(AggOpName(op)) + ": Field '" + name + "' does not exist in IPC file schema");
+    if (it->is_constant()) throw NotImplementedException(std::string(AggOpName(op)) + " on the constant column '" + name + "' is not computed in the scan");
+    std::string why;
+    if (!it->field.Supported(&why)) throw NotImplementedException("Column '" + name + "': " + why + " is not decoded by the MI355X scan path yet");
+    if (it->field.has_dictionary || ValueField(it->field).has_dictionary)
+      throw NotImplementedException(std::string(AggOpName(op)) + " on the dictionary-encoded column '" + name + "' is not computed in the scan");
+    return *it;
+  };
+  aggn.aggs.clear();
+  for (const AggSpec& sp : specs) {
+    AggregateState::Bound b;
+    b.op = sp.op;
+    if (sp.op == aggmerge::kOpCountStar) {
+      aggn.aggs.push_back(b);
+      continue;
+    }
+    if (sp.op < aggmerge::kOpCountStar || sp.op > aggmerge::kOpMax) throw InvalidInputException("mi_scan_aggregate: unknown operation " + std::to_string(sp.op));
+    const ScanColumn& ca = column_of(sp.a, sp.op);
+    if (sp.op != aggmerge::kOpCount) {
+      b.cls = AggClassOf(ca);
+      const bool sums = sp.op == aggmerge::kOpSum || sp.op == aggmerge::kOpSumProduct;
+      if (b.cls == aggmerge::kClassAny || (sums && b.cls == aggmerge::kClassWide))
+        throw NotImplementedException(std::string(AggOpName(sp.op)) + " on column '" + sp.a + "' (" + ca.field.DuckType() + "): SUM takes integers, DATE, TIME / "
+                                      "TIMESTAMP, DECIMAL(<=18), FLOAT and DOUBLE columns, MIN / MAX those and HUGEINT / DECIMAL(19..38)");
+      if (sp.op == aggmerge::kOpSumProduct) {
+        const ScanColumn& cb = column_of(sp.b, sp.op);
+        b.cls_b = AggClassOf(cb);
+        if (b.cls_b == aggmerge::kClassAny || b.cls_b == aggmerge::kClassWide)
+          throw NotImplementedException(std::string(AggOpName(sp.op)) + " on column '" + sp.b + "' (" + cb.field.DuckType() + "): a factor is an integer, DATE, TIME / "
+                                        "TIMESTAMP, DECIMAL(<=18), FLOAT or DOUBLE column");
+        if ((b.cls == aggmerge::kClassFloat) != (b.cls_b == aggmerge::kClassFloat))
+          throw NotImplementedException(std::string(AggOpName(sp.op)) + " of '" + sp.a + "' (" + ca.field.DuckType() + ") and '" + sp.b + "' (" + cb.field.DuckType() +
+                                        "): both factors must be integer-like or both floating point");
+      }
+    }
+    b.col_a = slot_of(sp.a);
+    if (sp.op == aggmerge::kOpSumProduct) b.col_b = slot_of(sp.b);
+    aggn.aggs.push_back(b);
+  }
+  if (proj.empty()) {
+    // COUNT(*) alone reads no column, but a scan decodes at least one: the narrowest fixed-width column, else the first it can decode
+    const ScanColumn* pick = nullptr;
+    int32_t pick_w = 0;
+    for (const ScanColumn& c : all_columns) {
+      std::string why;
+      if (c.is_constant() || c.field.has_dictionary || !c.field.Supported(&why)) continue;
+      int32_t kind, w = 0;
+      int64_t param;
+      const bool fixed = AggClassOf(c) != aggmerge::kClassAny && c.field.Plan(&kind, &param, &w);
+      if (!pick || (fixed && (pick_w == 0 || w < pick_w))) {
+        pick = &c;
+        pick_w = fixed ? w : 0;
+      }
+    }
+    if (!pick) throw NotImplementedException("COUNT(*): the scan has no column it decodes without a dictionary");
+    proj.push_back(pick->name);
+  }
+  ctx->Bind();
+  aggn.on = true;
+  aggn.rows_scanned = 0;
+  const char* timing = std::getenv("MI_AGG_TIMING");
+  aggn.timed = timing && timing[0] == '1';
+  aggn.events.clear();
+  try {
+    Init(proj);
+    const size_t n_aggs = aggn.aggs.size();
+    aggn.d_acc = DeviceBuffer(aggmerge::kMaxAggregates * sizeof(aggmerge::Partial));
+    MI_HIP_CHECK(hipMemsetAsync(aggn.d_acc.get(), 0, aggn.d_acc.size(), ctx->stream));   // count 0: the identity of every merge
+    BatchRef ref;
+    int64_t selected = 0;
+    while (AcquireBatch(&ref)) {   // the pull loop only recycles slots and adds up the filter's counts
+      selected += ref.selected;
+      ReleaseBatch(ref);
+    }
+    std::vector<aggmerge::Partial> acc(static_cast<size_t>(aggmerge::kMaxAggregates));
+    MI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MI_HIP_CHECK(hipMemcpy(acc.data(), aggn.d_acc.get(), acc.size() * sizeof(aggmerge::Partial), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e + 2 < aggn.events.size(); e += 3) {
+      float w_ms = 0, c_ms = 0;
+      MI_HIP_CHECK(hipEventElapsedTime(&w_ms, aggn.events[e], aggn.events[e + 1]));
+      MI_HIP_CHECK(hipEventElapsedTime(&c_ms, aggn.events[e + 1], aggn.events[e + 2]));
+      g_agg_events_ns[0] += static_cast<int64_t>(static_cast<double>(w_ms) * 1e6);
+      g_agg_events_ns[1] += static_cast<int64_t>(static_cast<double>(c_ms) * 1e6);
+    }
+    aggn.events.clear();
+    uint32_t flags = 0;
+    for (size_t a = 0; a < n_aggs; a++) flags |= static_cast<uint32_t>(acc[a].flags);
+    ThrowForStatus(flags);
+    out->values.assign(acc.begin(), acc.begin() + static_cast<std::ptrdiff_t>(n_aggs));
+    out->classes.clear();
+    for (auto& b : aggn.aggs) out->classes.push_back(b.cls);
+    out->rows_scanned = aggn.rows_scanned;
+    out->rows_selected = selected;
+  } catch (...) {
+    aggn.on = false;
+    throw;
+  }
+  aggn.on = false;
+}
+
+void ArrowScan::EnqueueAggregates(Slot& s) {
+  const int64_t n = s.nrows;
+  const int64_t n_windows = (n + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
+  device::AggProgram prog;
+  std::memset(&prog, 0, sizeof(prog));
+  auto column = [&](int32_t c, int32_t cls, device::AggColumnDev* out) {
+    // (a column that this file lacks was refused by EnqueueBatch before anything was queued: col_root is a node here)
+    const PlannedNode& o = s.planner.nodes[static_cast<size_t>(s.col_root[static_cast<size_t>(c)])];
+    out->data = o.alias_body_off >= 0 ? static_cast<const void*>(s.d_in.get() + o.alias_body_off) : static_cast<const void*>(s.d_out.get() + o.data_off);
+    out->validity = o.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out.get() + o.valid_off) : nullptr;
+    out->width = o.width;
+    out->cls = cls;
+  };
+  prog.n_aggs = static_cast<int32_t>(aggn.aggs.size());
+  for (size_t a = 0; a < aggn.aggs.size(); a++) {
+    const AggregateState::Bound& b = aggn.aggs[a];
+    device::AggDescDev& d = prog.aggs[a];
+    d.op = b.op;
+    if (b.col_a >= 0) column(b.col_a, b.cls, &d.a);
+    if (b.col_b >= 0) column(b.col_b, b.cls_b, &d.b);
+  }
+  const size_t bytes = static_cast<size_t>(n_windows) * aggn.aggs.size() * sizeof(aggmerge::Partial);
+  Retire(Grow(aggn.d_partials, bytes, GrownCapacity(bytes, aggn.d_partials.size(), 1 << 12)));
+  aggmerge::Partial* partials = aggn.d_partials.get<aggmerge::Partial>();
+  const mi_sel_t* sel = has_filter ? reinterpret_cast<const mi_sel_t*>(s.d_out.get() + s.sel_off) : nullptr;
+  const uint32_t* sel_count = has_filter ? reinterpret_cast<const uint32_t*>(s.d_out.get() + s.sel_count_off) : nullptr;
+  auto stamp = [&] {
+    if (!aggn.timed) return;
+    aggn.events.push_back(HipEvent::CreateTimed());
+    MI_HIP_CHECK(hipEventRecord(aggn.events.back(), ctx->stream));
+  };
+  stamp();
+  MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, n, partials, ctx->stream));
+  stamp();
+  MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, aggn.d_acc.get<aggmerge::Partial>(), ctx->stream));
+  stamp();
+  aggn.rows_scanned += n;
+}
+
 double ArrowScan::Progress() { return readahead.Progress(); }
 
 // ------------------------------------------------------------------------------------------------ multi-device
@@ -1407,6 +1613,20 @@ void MultiDeviceScan::SumProduct(const std::string& a, const std::string& b, con
   }
   out->sum_lo = static_cast<uint64_t>(sum);
   out->sum_hi = static_cast<int64_t>(static_cast<uint64_t>(sum >> 64));
+}
+
+void MultiDeviceScan::Aggregate(const std::vector<AggSpec>& specs, AggResult* out) {
+  std::vector<AggResult> parts(subs.size());
+  ForEachParallel([&](size_t i) { subs[i]->Aggregate(specs, &parts[i]); });
+  // sub-scan order, by the rules the kernels merge by: the double sums come out the same for the same device count
+  *out = AggResult();
+  out->values.assign(specs.size(), aggmerge::Partial{0, 0, 0, 0});
+  out->classes = parts[0].classes;
+  for (auto& p : parts) {
+    for (size_t a = 0; a < specs.size(); a++) aggmerge::Merge(specs[a].op, out->classes[a], &out->values[a], p.values[a]);
+    out->rows_scanned += p.rows_scanned;
+    out->rows_selected += p.rows_selected;
+  }
 }
 
 void ArrowScan::Stats(mi_scan_stats* out) {
@@ -1577,6 +1797,43 @@ int mi_scan_sum_product(mi_scan* s, const char* column_a, const char* column_b, 
     }
     std::memset(out, 0, sizeof(*out));
     s->scan->SumProduct(column_a, column_b, cols, lo, hi, out);
+  });
+}
+
+int mi_scan_aggregate(mi_scan* s, const mi_agg_spec* aggs, int32_t n_aggs, mi_agg_value* out, int64_t* rows_scanned, int64_t* rows_selected) {
+  return WrapC([&] {
+    if (!s || !aggs || !out) throw InvalidInputException("mi_scan_aggregate: NULL argument");
+    if (n_aggs < 1 || n_aggs > MI_MAX_AGGREGATES)
+      throw InvalidInputException("mi_scan_aggregate takes 1 to " + std::to_string(MI_MAX_AGGREGATES) + " aggregates, not " + std::to_string(n_aggs));
+    std::vector<AggSpec> specs;
+    for (int32_t i = 0; i < n_aggs; i++) {
+      AggSpec sp;
+      sp.op = aggs[i].op;
+      if (sp.op < MI_AGG_COUNT_STAR || sp.op > MI_AGG_MAX) throw InvalidInputException("mi_scan_aggregate: unknown operation " + std::to_string(sp.op));
+      if (sp.op != MI_AGG_COUNT_STAR && !aggs[i].column_a) throw InvalidInputException(std::string("mi_scan_aggregate: ") + AggOpName(sp.op) + " without a column");
+      if (sp.op == MI_AGG_SUM_PRODUCT && !aggs[i].column_b) throw InvalidInputException("mi_scan_aggregate: SUM_PRODUCT without a second column");
+      if (sp.op != MI_AGG_COUNT_STAR) sp.a = aggs[i].column_a;
+      if (sp.op == MI_AGG_SUM_PRODUCT) sp.b = aggs[i].column_b;
+      specs.push_back(std::move(sp));
+    }
+    AggResult r;
+    s->scan->Aggregate(specs, &r);
+    for (int32_t i = 0; i < n_aggs; i++) FillAggValue(specs[static_cast<size_t>(i)].op, r.classes[static_cast<size_t>(i)], r.values[static_cast<size_t>(i)], &out[i]);
+    if (rows_scanned) *rows_scanned = r.rows_scanned;
+    if (rows_selected) *rows_selected = r.rows_selected;
+  });
+}
+
+int mi_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, double* windows_ms, double* combine_ms) {
+  return WrapC([&] {
+    int64_t n[2];
+    double ms[2];
+    device::AggLaunchCounts(n);
+    AggTimingTotals(ms);
+    if (window_launches) *window_launches = n[0];
+    if (combine_launches) *combine_launches = n[1];
+    if (windows_ms) *windows_ms = ms[0];
+    if (combine_ms) *combine_ms = ms[1];
   });
 }
 

@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstring>
 #include <deque>
 #include <map>
 #include <mutex>
@@ -182,6 +183,38 @@ struct DeviceColumnView {
   int32_t offset_width = 0;
 };
 
+//! One aggregate of mi_scan_aggregate by column name, and what a draining call returns: the accumulators, the value class
+//! each is merged by (aggmerge::kClass*: what the host's merge of several devices needs), the rows seen
+struct AggSpec {
+  int32_t op = 0;            // aggmerge::kOp*
+  std::string a, b;
+};
+struct AggResult {
+  std::vector<aggmerge::Partial> values;
+  std::vector<int32_t> classes;
+  int64_t rows_scanned = 0, rows_selected = 0;
+};
+
+//! a finished accumulator as the C ABI returns it (mi_scan_aggregate, mi_aggregate_vectors)
+inline void FillAggValue(int32_t op, int32_t cls, const aggmerge::Partial& p, mi_agg_value* v) {
+  std::memset(v, 0, sizeof(*v));
+  v->count = static_cast<int64_t>(p.count);
+  if (op == aggmerge::kOpCountStar || op == aggmerge::kOpCount) {
+    v->kind = MI_AGG_VALUE_INT128;
+    v->lo = p.count;
+    return;
+  }
+  v->kind = cls == aggmerge::kClassFloat ? MI_AGG_VALUE_DOUBLE : MI_AGG_VALUE_INT128;
+  v->is_null = aggmerge::IsNull(op, p) ? 1 : 0;
+  if (v->is_null) return;
+  v->lo = p.lo;
+  v->hi = static_cast<int64_t>(p.hi);
+}
+//! "SUM", "MIN", ... for messages
+const char* AggOpName(int32_t op);
+//! MI_AGG_TIMING=1: device milliseconds of agg_windows / agg_combine summed over this process's calls of mi_scan_aggregate
+void AggTimingTotals(double out_ms[2]);
+
 class ScanBase {
  public:
   virtual ~ScanBase() = default;
@@ -192,6 +225,8 @@ class ScanBase {
   virtual void Count(int64_t* rows, int64_t* selected, int64_t* chunks) = 0;
   virtual void SumProduct(const std::string& a, const std::string& b, const std::vector<std::string>& filter_columns,
                           const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) = 0;
+  //! mi_scan_aggregate: `out` receives one partial per spec (agg_merge.hpp), ops / classes what each is merged by
+  virtual void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) = 0;
   virtual double Progress() = 0;
   virtual void Stats(mi_scan_stats* out) = 0;   // adds to *out
 };
@@ -218,6 +253,9 @@ class ArrowScan : public ScanBase {
   //! sum(a * b) over rows passing the range filters, all on the GPU; drains the scan (mi_scan_sum_product)
   void SumProduct(const std::string& a, const std::string& b, const std::vector<std::string>& filter_columns,
                   const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) override;
+
+  //! up to 8 aggregates over the rows the pushed-down filter keeps, all on the GPU; drains the scan (mi_scan_aggregate)
+  void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) override;
 
   // ---- batch-level pull (what Next() is built on; the COPY pump and the multi-device scan use it directly) ----
   //! Waits for the next record batch in order; false when the scan is exhausted.  The batch stays valid (its slot is
@@ -350,6 +388,23 @@ class ArrowScan : public ScanBase {
     DeviceBuffer d_acc;                    // unsigned long long {sum lo, sum hi, rows selected}
     int64_t rows_scanned = 0;
   } agg;
+  // fused aggregates (mi_scan_aggregate): a state of its own beside `agg`
+  struct AggregateState {
+    bool on = false;
+    struct Bound {
+      int32_t op = 0, cls = 0;
+      int32_t col_a = -1, col_b = -1;        // output columns
+      int32_t cls_b = 0;
+    };
+    std::vector<Bound> aggs;
+    DeviceBuffer d_acc;                      // aggmerge::Partial per aggregate: lives as long as the call
+    DeviceBuffer d_partials;                 // partials[window][aggregate] of the record batch in flight (one stream: in order)
+    int64_t rows_scanned = 0;
+    bool timed = false;                      // MI_AGG_TIMING=1: HIP events around every launch
+    std::vector<HipEvent> events;            // timed: {before agg_windows, between, after agg_combine} per record batch
+  } aggn;
+  //! agg_windows + agg_combine over the slot's decoded vectors and selection vectors, behind the filter on the compute stream
+  void EnqueueAggregates(Slot& s);
   // constant columns (filename / hive): 2048 string_t each per source, host
   std::map<std::pair<int32_t, size_t>, std::vector<mi_string_t>> const_vectors;
   std::mutex const_mu;
@@ -389,6 +444,7 @@ class MultiDeviceScan : public ScanBase {
   void Count(int64_t* rows, int64_t* selected, int64_t* chunks) override;
   void SumProduct(const std::string& a, const std::string& b, const std::vector<std::string>& filter_columns,
                   const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) override;
+  void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) override;
   double Progress() override;
   void Stats(mi_scan_stats* out) override;
 

@@ -325,6 +325,7 @@ typedef struct mi_col_task {
 #define MI_ST_DECOMPRESS 256u     /* a compressed buffer is malformed or does not expand to its declared length (EIO,
                                    * base_stream_reader.cpp:24-29) */
 #define MI_ST_BAD_RUN_ENDS 512u   /* run ends not positive and strictly increasing, or short of the array (FULL validation) */
+#define MI_ST_SEL_RANGE 1024u     /* aggregates: a selection index names no row of its 2048-row window (skipped, never read) */
 
 /* Uploads the task table to HBM (descriptor table + tile index) and returns a reusable plan.  One plan =
  * any number of (batch, column) tasks = ONE fused kernel launch per mi_plan_launch. */
@@ -793,6 +794,103 @@ int mi_filter_pattern_launches(int64_t* n);
 /* Debug getter: row groups mi_writer_sink_scan's fused pump has encoded where the scan decoded them (no host staging) in this
  * process so far, and how many string-view columns (produce_arrow_string_view) they held, summed over those row groups. */
 int mi_writer_fused_counts(int64_t* row_groups, int64_t* view_columns);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Fused aggregates over the pushed-down filter (an ABI extension, as mi_scan_sum_product is: the reference has no
+ * counterpart and DuckDB no hook for it):
+ *   SELECT agg_1, ..., agg_n FROM scan WHERE <whatever mi_scan_set_filter / mi_scan_set_filter_range accepted>   (n <= 8)
+ * evaluated on the GPU in one pass over the decoded vectors of every record batch, which never leave HBM; only the
+ * results do.  Call right after bind, in place of init / next (as mi_scan_sum_product): the call projects the aggregate
+ * columns itself -- a filter column that is not aggregated is decoded for the filter alone -- honours the filter that
+ * was set (without one every row is selected), ignores mi_scan_options.filter_compact and drains the scan.
+ * Semantics are SQL's and DuckDB's:
+ *   MI_AGG_COUNT_STAR   the selected rows.
+ *   MI_AGG_COUNT        the selected rows whose value is not NULL, for any top-level column the scan decodes (VARCHAR,
+ *                       BLOB, INTERVAL, nested and run-end encoded ones included); a dictionary-encoded column and a
+ *                       constant (filename / hive) column are MI_ENOTSUP.  A COUNT is never NULL.
+ *   MI_AGG_SUM, MI_AGG_SUM_PRODUCT
+ *                       integer-like columns (integers, DATE, TIME / TIMESTAMP, DECIMAL(<=18); the stored integers,
+ *                       unsigned types zero-extended, so a uint64 of 2^63 or more is positive): exact in 128 bits.
+ *                       Overflow is not detected: the sum wraps modulo 2^128, exactly as mi_scan_sum_product's does.
+ *                       FLOAT / DOUBLE columns (both factors of a product must be floating point, anything mixed is
+ *                       MI_ENOTSUP): accumulated in double, FLOAT and float16 values widened first (DuckDB's sum(FLOAT)
+ *                       is a DOUBLE too); NaN and infinities propagate as IEEE addition does.  A double sum is folded in
+ *                       one fixed order: the same file, options and device count give the same bits; its rounding error
+ *                       is that of some summation order, not of the row order.
+ *                       A NULL input -- a NULL in either factor -- contributes nothing; no contributor: NULL.
+ *   MI_AGG_MIN, MI_AGG_MAX
+ *                       integer-like columns: the stored integers, respecting signedness.  FLOAT / DOUBLE: DuckDB's total
+ *                       order (NaN greatest, -0.0 = +0.0); -0.0 comes back as +0.0, any NaN as the quiet NaN
+ *                       0x7FF8000000000000.  HUGEINT / DECIMAL(19..38): `upper` signed, then `lower` unsigned.  No
+ *                       contributor: NULL.
+ * BOOLEAN, strings, intervals and nested types under SUM / MIN / MAX, and SUM over a 128-bit column, are MI_ENOTSUP with
+ * a message that names the column and the operation; an unknown column, more than 8 aggregates and a call after init are
+ * MI_EINVAL, as is an aggregate column that a file of the scan lacks (union_by_name).
+ * With mi_scan_options.rank / world every rank returns its share: COUNT and SUM results add up, MIN and MAX merge (the
+ * smaller / greater of the ranks' values that are not NULL).  A multi-device scan merges its devices' results itself, in
+ * device order. */
+enum mi_agg_op {
+  MI_AGG_COUNT_STAR = 1,   /* no column */
+  MI_AGG_COUNT = 2,        /* column_a */
+  MI_AGG_SUM = 3,          /* column_a */
+  MI_AGG_SUM_PRODUCT = 4,  /* column_a * column_b */
+  MI_AGG_MIN = 5,          /* column_a */
+  MI_AGG_MAX = 6           /* column_a */
+};
+#define MI_MAX_AGGREGATES 8
+typedef struct mi_agg_spec {
+  int32_t op;              /* enum mi_agg_op */
+  int32_t reserved0;
+  const char* column_a;
+  const char* column_b;    /* MI_AGG_SUM_PRODUCT */
+  int64_t reserved[2];     /* zero */
+} mi_agg_spec;
+enum mi_agg_value_kind {
+  MI_AGG_VALUE_INT128 = 0, /* lo / hi: a 128-bit two's-complement integer (counts, integer sums, integer and 128-bit MIN / MAX) */
+  MI_AGG_VALUE_DOUBLE = 1  /* lo: the bits of an IEEE double, hi = 0 (FLOAT / DOUBLE sums, MIN / MAX) */
+};
+typedef struct mi_agg_value {
+  uint64_t lo;
+  int64_t hi;
+  int64_t count;           /* selected rows that contributed (for a COUNT: the count itself) */
+  int32_t kind;            /* enum mi_agg_value_kind */
+  int32_t is_null;         /* SUM / MIN / MAX without a contributing row; lo = hi = 0 then */
+  int64_t reserved[2];
+} mi_agg_value;
+int mi_scan_aggregate(mi_scan* s, const mi_agg_spec* aggs, int32_t n_aggs, mi_agg_value* out /* [n_aggs] */,
+                      int64_t* rows_scanned, int64_t* rows_selected);
+/* The kernel-level entry, over resident vectors as mi_filter_range / mi_filter_between are: the same kernels on columns the
+ * caller describes.  sel / sel_count: a selection vector in the filter's layout -- 2048 slots per 2048-row window, the first
+ * sel_count[w] of window w are read, each a row number inside its window -- or both NULL for every row.  A count beyond the
+ * rows its window has is clamped; an index that names no row of its window is skipped, never dereferenced, and makes the
+ * call fail with MI_EINVAL (MI_ST_SEL_RANGE): the values of that call are not to be trusted.  16-byte columns need 8-byte
+ * alignment only, every other width its own.  Fills out[0 .. n_aggs) and waits for the stream (NULL = the context's). */
+enum mi_agg_value_class {
+  MI_AGG_CLASS_ANY = 0,      /* MI_AGG_COUNT only: the validity alone is read, data may be NULL */
+  MI_AGG_CLASS_SIGNED = 1,   /* width 1 / 2 / 4 / 8 */
+  MI_AGG_CLASS_UNSIGNED = 2, /* width 1 / 2 / 4 / 8 */
+  MI_AGG_CLASS_FLOAT = 3,    /* width 4 / 8 */
+  MI_AGG_CLASS_WIDE = 4      /* width 16: mi_hugeint_t (MIN / MAX / COUNT) */
+};
+typedef struct mi_agg_column {
+  const void* data;          /* device: one value of `width` bytes per row */
+  const void* validity;      /* device: validity words (uint64_t, bit r & 63 of word r >> 6), or NULL = all valid */
+  int32_t width;
+  int32_t value_class;       /* enum mi_agg_value_class */
+} mi_agg_column;
+typedef struct mi_agg_vector_spec {
+  int32_t op;                /* enum mi_agg_op */
+  int32_t reserved0;
+  mi_agg_column a, b;        /* b: the second factor of MI_AGG_SUM_PRODUCT */
+  int64_t reserved[2];
+} mi_agg_vector_spec;
+int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel, const uint32_t* sel_count,
+                         int64_t nrows, mi_agg_value* out /* [n_aggs] */, void* stream);
+/* Debug and measurement facility, not part of the query surface (as mi_filter_launch_counts / mi_filter_pattern_launches are):
+ * launches of agg_windows / agg_combine by this process so far, and the device time of both kernels summed over the calls of
+ * mi_scan_aggregate that ran with the environment variable MI_AGG_TIMING=1 (HIP events around every launch; milliseconds, 0
+ * without it -- no event is created then).  DESIGN section 10's kernel times come from here.  Any pointer may be NULL. */
+int mi_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, double* windows_ms, double* combine_ms);
 
 #ifdef __cplusplus
 }

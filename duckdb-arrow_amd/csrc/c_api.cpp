@@ -320,7 +320,7 @@ int mi_filter_range(mi_ctx* ctx, const void* values, int32_t width, const void* 
                     int64_t hi, mi_sel_t* sel_out, uint32_t* count_out, void* stream) {
   return Wrap([&] {
     if (!ctx || !values || !sel_out || !count_out) throw InvalidInputException("mi_filter_range: NULL argument");
-    if (width != 2 && width != 4 && width != 8) throw InvalidInputException("mi_filter_range: width must be 2, 4 or 8");
+    if (width != 1 && width != 2 && width != 4 && width != 8) throw InvalidInputException("mi_filter_range: width must be 1, 2, 4 or 8");
     ctx->ctx->Bind();
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
     MI_HIP_CHECK(device::LaunchFilterRange(values, width, validity, nrows, lo, hi, sel_out, count_out, s));

@@ -222,7 +222,8 @@ FilterLeaf LeafOf(const mi_filter_node& n, const std::vector<ScanColumn>* column
     case MI_F_NE: closed(c, c); l.negate = true; break;
     case MI_F_LT: if (c == kMin) closed(1, 0); else { l.hi = c - 1; l.hi_open = false; } break;   // nothing is < MIN: an empty range
     case MI_F_LE: l.hi = c; l.hi_open = false; break;
-    case MI_F_GT: if (c == kMax) closed(1, 0); else { l.lo = c + 1; l.lo_open = false; } break;
+    // nothing signed is > MAX, but a uint64 column reaches past it: Program decides (keys of FLOAT / DOUBLE end at NaN's)
+    case MI_F_GT: if (c == kMax) { closed(1, 0); l.above_int64_max = !l.float_width; } else { l.lo = c + 1; l.lo_open = false; } break;
     case MI_F_GE: l.lo = c; l.lo_open = false; break;
     case MI_F_IS_NULL: l.op = device::kLeafIsNull; break;
     case MI_F_IS_NOT_NULL: l.op = device::kLeafIsNotNull; break;
@@ -285,9 +286,9 @@ FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t 
   FilterCnf merged;
   for (auto& clause : cnf) {
     bool folded = false;
-    if (clause.size() == 1 && clause[0].op == device::kLeafRange && !clause[0].negate) {
+    if (clause.size() == 1 && clause[0].op == device::kLeafRange && !clause[0].negate && !clause[0].above_int64_max) {
       for (auto& m : merged) {
-        if (m.size() == 1 && m[0].op == device::kLeafRange && !m[0].negate && m[0].column == clause[0].column) {
+        if (m.size() == 1 && m[0].op == device::kLeafRange && !m[0].negate && !m[0].above_int64_max && m[0].column == clause[0].column) {
           if (!clause[0].lo_open) { m[0].lo = m[0].lo_open ? clause[0].lo : std::max(m[0].lo, clause[0].lo); m[0].lo_open = false; }
           if (!clause[0].hi_open) { m[0].hi = m[0].hi_open ? clause[0].hi : std::min(m[0].hi, clause[0].hi); m[0].hi_open = false; }
           folded = true;
@@ -573,15 +574,25 @@ device::FilterProgram BoundFilter::Program(const std::vector<ScanColumn>& out_co
           // negative one is below every value of the column.
           L.flags |= device::kLeafBias;
           const int64_t bias = static_cast<int64_t>(0x8000000000000000ull);
-          if (leaf.op == device::kLeafRange) {
+          if (leaf.op == device::kLeafRange && leaf.above_int64_max) {
+            L.lo = 0;                                                  // v > INT64_MAX: the images of 2^63 ..
+            L.hi = static_cast<int64_t>(0x7FFFFFFFFFFFFFFFull);        // .. UINT64_MAX
+          } else if (leaf.op == device::kLeafRange) {
             if (!leaf.hi_open && leaf.hi < 0) { L.lo = 1; L.hi = 0; }   // empty (its negation keeps every valid row, as it must)
             else {
               L.lo = (leaf.lo_open || leaf.lo < 0) ? bias : (leaf.lo ^ bias);            // bias = the image of 0
               L.hi = leaf.hi_open ? static_cast<int64_t>(0x7FFFFFFFFFFFFFFFull) : (leaf.hi ^ bias);   // image of UINT64_MAX
             }
           }
-          // IN-lists of uint64 columns are uploaded unbiased: compare them unbiased too
-          if (leaf.op == device::kLeafIn) L.flags &= ~device::kLeafBias;
+          // IN-lists of uint64 columns are uploaded unbiased: compare them unbiased too.  That compares bit patterns, and
+          // a negative constant is no value of the column: the list is sorted, so those are its head and are stepped over
+          if (leaf.op == device::kLeafIn) {
+            L.flags &= ~device::kLeafBias;
+            const int32_t negative = static_cast<int32_t>(std::lower_bound(leaf.in_values.begin(), leaf.in_values.end(), int64_t(0)) - leaf.in_values.begin());
+            L.in_values += negative;
+            L.n_in -= negative;
+            if (L.n_in == 0) { L.op = device::kLeafRange; L.lo = 1; L.hi = 0; }   // none is left: the leaf keeps nothing
+          }
         }
       }
     }

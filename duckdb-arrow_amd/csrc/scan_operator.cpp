@@ -1288,6 +1288,10 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
     int32_t kind, w;
     int64_t param;
     if (!(!c.is_constant() && c.field.Plan(&kind, &param, &w) && IsIntegerLike(kind, w, c.field, /*allow_bool*/ false))) throw InvalidInputException("Column '" + name + "' (" + c.field.DuckType() + ") is not a fixed-width integer-like column: the fused aggregate takes integers, DATE, TIME/TIMESTAMP and DECIMAL(<=18)");
+    // the kernel loads every value sign-extended: a uint16 60000 would be summed and range-tested as -5536
+    if (c.field.type == MI_AT_INT && !c.field.is_signed)
+      throw NotImplementedException("Column '" + name + "' (" + c.field.DuckType() + ") is unsigned: mi_scan_sum_product reads signed columns only; "
+                                    "mi_scan_aggregate (MI_AGG_SUM_PRODUCT over mi_scan_set_filter) handles unsigned columns at the same speed");
   }
   agg.d_acc = DeviceBuffer(4 * sizeof(unsigned long long));
   MI_HIP_CHECK(hipMemsetAsync(agg.d_acc.get(), 0, agg.d_acc.size(), ctx->stream));

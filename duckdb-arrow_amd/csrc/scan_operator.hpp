@@ -62,6 +62,9 @@ struct FilterLeaf {
   int32_t op = 0;                 // device::kLeaf*
   int64_t lo = 0, hi = 0;         // kLeafRange: lo <= v <= hi ...
   bool lo_open = true, hi_open = true;  // ... where an open end has no bound at all (uint64 columns reach past INT64_MAX)
+  //! kLeafRange from `v > INT64_MAX`: the empty range (1, 0) on every column but a uint64 one, where it keeps the values
+  //! >= 2^63 (BoundFilter::Program knows the column's signedness).  Such a leaf is never merged with another range.
+  bool above_int64_max = false;
   bool negate = false;
   std::vector<int64_t> in_values;
   bool is_string = false;         // kLeafStrIn: the column is VARCHAR / BLOB, the row passes when it equals one of ...

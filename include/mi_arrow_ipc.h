@@ -562,7 +562,9 @@ typedef struct mi_data_chunk {
  * hands a scan: col <op> constant with = <> < <= > >=, IS NULL, IS NOT NULL, IN (list), combined
  * by AND / OR trees over any number of columns.  Comparison columns are fixed-width integer-like after the scan
  * (integers, BOOLEAN, DATE, TIME / TIMESTAMP, DECIMAL(<=18)) and constants are the stored integers (DECIMAL(15,2) 0.05
- * is 5); FLOAT / DOUBLE columns against IEEE doubles (MI_FV_DOUBLE) in DuckDB's total order -- every NaN equals every
+ * is 5) as int64, compared by value: on an unsigned column a negative constant is below every row (> and >= keep every row
+ * that is not NULL, an IN-list never matches it), `> INT64_MAX` keeps the UBIGINT rows >= 2^63 and no row of any other
+ * column, and a UBIGINT constant >= 2^63 is not expressible (as MI_FV_INT128 it is MI_EINVAL, see below); FLOAT / DOUBLE columns against IEEE doubles (MI_FV_DOUBLE) in DuckDB's total order -- every NaN equals every
  * other NaN and is greater than everything else, +inf included, and -0.0 = +0.0; a constant for a FLOAT column is rounded
  * to float32 first, as DuckDB casts it to the column's type; HUGEINT / DECIMAL(19..38) columns against 128-bit stored
  * integers (MI_FV_INT128, or MI_FV_INT64 sign-extended); or VARCHAR / BLOB columns with = <> < <= > >= IN and MI_F_STARTS_WITH against byte strings (byte-wise order,
@@ -625,7 +627,9 @@ int mi_scan_count(mi_scan* s, int64_t* rows, int64_t* selected, int64_t* chunks)
  *   SELECT sum(a * b), count(*) FROM scan WHERE lo_k <= f_k < hi_k  (k < n_filters <= 4)
  * evaluated on the GPU over the decoded vectors of every record batch, which never leave HBM: the only D2H traffic is
  * this 32-byte result.  Columns must be fixed-width integer-like after the scan (integers, DATE, TIME/TIMESTAMP,
- * DECIMAL(<=18)); values are the stored integers (DECIMAL(15,2) 0.05 is 5).  NULL in a filter column drops the row,
+ * DECIMAL(<=18)) and signed: the kernel reads every value sign-extended, so an unsigned factor or filter column (UTINYINT ..
+ * UBIGINT) is MI_ENOTSUP naming the column -- mi_scan_aggregate below handles unsigned columns and runs at the same speed.
+ * Values are the stored integers (DECIMAL(15,2) 0.05 is 5).  NULL in a filter column drops the row,
  * NULL in a or b contributes nothing (SQL SUM).  Call after bind instead of init/next: it projects the columns it
  * needs itself and drains the scan. */
 typedef struct mi_range_filter {

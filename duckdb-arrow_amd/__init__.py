@@ -348,6 +348,73 @@ def aggregate_counters():
     return a.value, b.value, c.value, d.value
 
 
+def _group_check_keys(keys):
+    """What needs no library: 1 .. 4 keys -> list"""
+    keys = [keys] if isinstance(keys, (str, bytes)) else list(keys)
+    if not 1 <= len(keys) <= _ffi.MAX_GROUP_KEYS:
+        raise MiError(_ffi.MI_EINVAL, "group_aggregate takes 1 to %d key columns, not %d" % (_ffi.MAX_GROUP_KEYS, len(keys)))
+    return keys
+
+
+def _group_key_value(v, as_text):
+    """mi_group_key_value -> int / str (as_text) / bytes / None"""
+    if v.is_null:
+        return None
+    raw = bytes(v.bytes)
+    if v.kind == _ffi.GROUP_KEY_STRING:
+        body = raw[4: 4 + int.from_bytes(raw[:4], "little")]
+        return body.decode("utf-8", "surrogateescape") if as_text else body
+    return int.from_bytes(raw, "little", signed=True)
+
+
+def _group_rows(out_keys, out_values, n_groups, n_keys, n_aggs, text, detail):
+    rows = []
+    for g in range(n_groups):
+        key = tuple(_group_key_value(out_keys[g * n_keys + k], text[k]) for k in range(n_keys))
+        vals = [out_values[g * n_aggs + a] for a in range(n_aggs)]
+        rows.append((key, [(_agg_value(v), v.count) if detail else _agg_value(v) for v in vals]))
+    return rows
+
+
+def group_aggregate_vectors(ctx, keys, specs, nrows, sel_ptr=0, count_ptr=0, capacity=_ffi.MAX_GROUPS, stream=0, detail=False):
+    """GROUP BY over resident vectors (mi_group_aggregate_vectors).  `keys`: 1 .. 4 columns (data_ptr, validity_ptr or 0,
+    width, key_class) with key_class one of "signed", "unsigned", "wide", "string" (16-byte string_t rows; they come back as
+    bytes) ; `specs`, sel_ptr / count_ptr as aggregate_vectors takes them.  Returns [(key_tuple, [values...]), ...] sorted
+    ascending by key, NULLS LAST; with `detail` every value is a (value, contributing rows) pair."""
+    classes = {"signed": _ffi.GROUP_KEY_CLASS_SIGNED, "unsigned": _ffi.GROUP_KEY_CLASS_UNSIGNED, "wide": _ffi.GROUP_KEY_CLASS_WIDE,
+               "string": _ffi.GROUP_KEY_CLASS_STRING}
+    agg_classes = {"any": _ffi.AGG_CLASS_ANY, "signed": _ffi.AGG_CLASS_SIGNED, "unsigned": _ffi.AGG_CLASS_UNSIGNED,
+                   "float": _ffi.AGG_CLASS_FLOAT, "wide": _ffi.AGG_CLASS_WIDE}
+    keys = _group_check_keys(keys)
+    checked = _agg_check_specs(specs)
+    karr = (_ffi.GroupKeyColumn * len(keys))()
+    for i, (data, validity, width, cls) in enumerate(keys):
+        if cls not in classes:
+            raise MiError(_ffi.MI_EINVAL, "group_aggregate_vectors: unknown key class %r (one of %s)" % (cls, ", ".join(sorted(classes))))
+        karr[i].data, karr[i].validity, karr[i].width, karr[i].key_class = data or None, validity or None, width, classes[cls]
+    arr = (_ffi.AggVectorSpec * len(checked))()
+    for i, (name, cols) in enumerate(checked):
+        arr[i].op = _AGG_OPS[name]
+        for slot, col in zip((arr[i].a, arr[i].b), cols):
+            data, validity, width, cls = col
+            slot.data, slot.validity, slot.width, slot.value_class = data or None, validity or None, width, agg_classes[cls]
+    capacity = max(int(capacity), 0)
+    out_keys = (_ffi.GroupKeyValue * max(capacity * len(keys), 1))()
+    out_values = (_ffi.AggValue * max(capacity * len(checked), 1))()
+    n_groups = C.c_int32()
+    _ffi.check(_ffi.lib().mi_group_aggregate_vectors(ctx._h, karr, len(keys), arr, len(checked), sel_ptr or None, count_ptr or None, nrows,
+                                                     out_keys, out_values, capacity, C.byref(n_groups), C.c_void_p(stream or None)))
+    return _group_rows(out_keys, out_values, n_groups.value, len(keys), len(checked), [False] * len(keys), detail)
+
+
+def group_aggregate_counters():
+    """(group_windows launches, group_combine launches, group_windows ms, group_combine ms) of this process; the times are
+    summed over the mi_scan_group_aggregate calls that ran with MI_AGG_TIMING=1 in the environment."""
+    a, b, c, d = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    _ffi.check(_ffi.lib().mi_group_aggregate_counters(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
 def filter_float_key(value, width):
     """The order-preserving integer key the filter kernel compares a FLOAT (width 4) / DOUBLE (width 8) value by."""
     key = C.c_int64()
@@ -749,6 +816,37 @@ class Relation:
         self._initialised = True
         values = [_agg_value(v) for v in out]
         return (values, scanned.value, selected.value) if detail else values
+
+    def group_aggregate(self, keys, specs, detail=False, capacity=_ffi.MAX_GROUPS):
+        """SELECT k_1 .. k_m, agg_1 .. agg_n ... GROUP BY k_1 .. k_m (m <= 4, n <= 8) over the rows the pushed-down filter
+        keeps, on the GPU (mi_scan_group_aggregate), for few groups: at most 256 distinct keys per 2048-row window and 4096
+        in the scan.  `keys`: column names; `specs` as aggregate() takes them.  Returns [(key_tuple, [values...]), ...]
+        sorted ascending by key, NULLS LAST; a key comes back as an int (the stored integer), a str (VARCHAR), bytes (BLOB)
+        or None.  With `detail`: (rows, rows_scanned, rows_selected)."""
+        keys = _group_check_keys(keys)
+        checked = _agg_check_specs(specs)
+        arr = (_ffi.AggSpec * len(checked))()
+        keep = []
+        for i, (name, cols) in enumerate(checked):
+            arr[i].op = _AGG_OPS[name]
+            names = [c.encode() for c in cols]
+            keep.append(names)
+            if names:
+                arr[i].column_a = names[0]
+            if len(names) > 1:
+                arr[i].column_b = names[1]
+        karr = (C.c_char_p * len(keys))(*[k.encode() if isinstance(k, str) else k for k in keys])
+        capacity = max(int(capacity), 0)
+        out_keys = (_ffi.GroupKeyValue * max(capacity * len(keys), 1))()
+        out_values = (_ffi.AggValue * max(capacity * len(checked), 1))()
+        n_groups, scanned, selected = C.c_int32(), C.c_int64(), C.c_int64()
+        _ffi.check(_ffi.lib().mi_scan_group_aggregate(self._h, karr, len(keys), arr, len(checked), out_keys, out_values, capacity,
+                                                      C.byref(n_groups), C.byref(scanned), C.byref(selected)))
+        self._initialised = True
+        types = {f["name"]: f["duck_type"] for f in self.fields}
+        text = [str(types.get(k if isinstance(k, str) else k.decode(), "")).upper().startswith("VARCHAR") for k in keys]
+        rows = _group_rows(out_keys, out_values, n_groups.value, len(keys), len(checked), text, False)
+        return (rows, scanned.value, selected.value) if detail else rows
 
     def progress(self):
         return _ffi.lib().mi_scan_progress(self._h)

@@ -24,6 +24,7 @@ ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL
     1, 2, 4, 8, 16, 32, 64, 128
 ST_BAD_RUN_ENDS = 512
 ST_SEL_RANGE = 1024
+ST_GROUP_LIMIT, ST_GROUP_KEY_LONG = 2048, 4096
 
 
 class Field(C.Structure):
@@ -156,6 +157,19 @@ class AggVectorSpec(C.Structure):
     _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("a", AggColumn), ("b", AggColumn), ("reserved", C.c_int64 * 2)]
 
 
+MAX_GROUP_KEYS, GROUP_WINDOW_LIMIT, MAX_GROUPS = 4, 256, 4096
+GROUP_KEY_INT128, GROUP_KEY_STRING = 0, 1
+GROUP_KEY_CLASS_SIGNED, GROUP_KEY_CLASS_UNSIGNED, GROUP_KEY_CLASS_WIDE, GROUP_KEY_CLASS_STRING = 1, 2, 3, 4
+
+
+class GroupKeyValue(C.Structure):
+    _fields_ = [("bytes", C.c_uint8 * 16), ("kind", C.c_int32), ("is_null", C.c_int32)]
+
+
+class GroupKeyColumn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("validity", C.c_void_p), ("width", C.c_int32), ("key_class", C.c_int32)]
+
+
 class ArrowArrayStream(C.Structure):   # Arrow C stream interface: 4 callbacks + private_data
     _fields_ = [("get_schema", C.c_void_p), ("get_next", C.c_void_p), ("get_last_error", C.c_void_p),
                 ("release", C.c_void_p), ("private_data", C.c_void_p)]
@@ -269,6 +283,11 @@ SIGNATURES = {
     "mi_scan_aggregate": (C.c_int, [P, C.POINTER(AggSpec), C.c_int32, C.POINTER(AggValue), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mi_aggregate_vectors": (C.c_int, [P, C.POINTER(AggVectorSpec), C.c_int32, P, P, C.c_int64, C.POINTER(AggValue), P]),
     "mi_aggregate_counters": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mi_scan_group_aggregate": (C.c_int, [P, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(AggSpec), C.c_int32, C.POINTER(GroupKeyValue),
+                                          C.POINTER(AggValue), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mi_group_aggregate_vectors": (C.c_int, [P, C.POINTER(GroupKeyColumn), C.c_int32, C.POINTER(AggVectorSpec), C.c_int32, P, P, C.c_int64,
+                                             C.POINTER(GroupKeyValue), C.POINTER(AggValue), C.c_int32, C.POINTER(C.c_int32), P]),
+    "mi_group_aggregate_counters": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mi_scan_progress": (C.c_double, [P]),
     "mi_scan_get_stats": (C.c_int, [P, P]),
     "mi_write_options_init": (C.c_int, [C.POINTER(WriteOptions)]),

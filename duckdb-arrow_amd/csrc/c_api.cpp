@@ -450,6 +450,65 @@ int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_
   });
 }
 
+int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int32_t n_keys, const mi_agg_vector_spec* aggs, int32_t n_aggs,
+                               const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows, mi_group_key_value* out_keys,
+                               mi_agg_value* out_values, int32_t capacity, int32_t* n_groups, void* stream) {
+  return Wrap([&] {
+    if (n_groups) *n_groups = 0;
+    if (!ctx || !keys || !aggs || !out_keys || !out_values || !n_groups) throw InvalidInputException("mi_group_aggregate_vectors: NULL argument");
+    if (n_keys < 1 || n_keys > MI_MAX_GROUP_KEYS)
+      throw InvalidInputException("mi_group_aggregate_vectors takes 1 to " + std::to_string(MI_MAX_GROUP_KEYS) + " key columns, not " + std::to_string(n_keys));
+    if (n_aggs < 1 || n_aggs > MI_MAX_AGGREGATES)
+      throw InvalidInputException("mi_group_aggregate_vectors takes 1 to " + std::to_string(MI_MAX_AGGREGATES) + " aggregates, not " + std::to_string(n_aggs));
+    if ((sel == nullptr) != (sel_count == nullptr)) throw InvalidInputException("mi_group_aggregate_vectors: sel and sel_count go together");
+    if (nrows < 0 || capacity < 0) throw InvalidInputException("mi_group_aggregate_vectors: negative row count or capacity");
+    device::GroupProgram prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_keys = n_keys;
+    GroupResult r;
+    for (int32_t k = 0; k < n_keys; k++) {
+      prog.keys[k].data = keys[k].data;
+      prog.keys[k].validity = static_cast<const uint64_t*>(keys[k].validity);
+      prog.keys[k].width = keys[k].width;
+      prog.keys[k].cls = keys[k].key_class;
+      r.kinds.push_back(groupkey::KindOfClass(keys[k].key_class));
+    }
+    prog.aggs.n_aggs = n_aggs;
+    auto column = [](const mi_agg_column& c) {
+      device::AggColumnDev d;
+      d.data = c.data;
+      d.validity = static_cast<const uint64_t*>(c.validity);
+      d.width = c.width;
+      d.cls = c.value_class;
+      return d;
+    };
+    std::vector<int32_t> ops;
+    for (int32_t i = 0; i < n_aggs; i++) {
+      prog.aggs.aggs[i].op = aggs[i].op;
+      prog.aggs.aggs[i].a = column(aggs[i].a);
+      prog.aggs.aggs[i].b = column(aggs[i].b);
+      ops.push_back(aggs[i].op);
+      r.classes.push_back(aggs[i].a.value_class);
+    }
+    if (!device::GroupProgramIsValid(prog))
+      throw InvalidInputException("mi_group_aggregate_vectors: a key class, operation, value class or width that does not fit (keys: signed / unsigned of width "
+                                  "1 / 2 / 4 / 8, wide or string of width 16; aggregates as mi_aggregate_vectors takes them)");
+    ctx->ctx->Bind();
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
+    const int64_t n_windows = (nrows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
+    const size_t table_bytes = (device::GroupTableBytes(n_keys, n_aggs) + 15) & ~static_cast<size_t>(15);
+    DeviceBuffer d_all(table_bytes + device::GroupWindowsBytes(n_windows, n_keys, n_aggs) + 16);   // the table, then the windows' records
+    const device::GroupTableDev table = device::GroupTableAt(d_all.get(), n_keys, n_aggs);
+    const device::GroupWindowsOut win = device::GroupWindowsAt(d_all.get() + table_bytes, n_windows, n_keys, n_aggs);
+    MI_HIP_CHECK(device::GroupTableClear(d_all.get(), n_keys, n_aggs, s));
+    MI_HIP_CHECK(device::LaunchGroupWindows(prog, sel, sel_count, nrows, win, s));
+    MI_HIP_CHECK(device::LaunchGroupCombine(prog, win, n_windows, table, s));
+    ReadGroupTable(d_all.get(), n_keys, n_aggs, s, &r);
+    SortGroups(&r);
+    FillGroupOutputs(r, ops, out_keys, out_values, capacity, n_groups);
+  });
+}
+
 int mi_filter_float_key(double v, int32_t width, int64_t* key) {
   return Wrap([&] {
     if (!key || (width != 4 && width != 8)) throw InvalidInputException("mi_filter_float_key: width must be 4 or 8");

@@ -546,6 +546,10 @@ void ThrowForStatus(uint32_t bits) {
     throw IOException("LZ4_FRAME compressed buffer is malformed or does not decompress to its declared size (Expected decompressed size mismatch)");
   if (bits & MI_ST_INTERNAL) throw InternalException("a kernel gave up waiting for another workgroup (bounded spin exceeded)");
   if (bits & MI_ST_SEL_RANGE) throw InvalidInputException("aggregate: a selection index names no row of its 2048-row window (skipped: the results are not valid)");
+  if (bits & MI_ST_GROUP_KEY_LONG) throw NotImplementedException("a VARCHAR / BLOB group key longer than 12 bytes stays above the scan");
+  if (bits & MI_ST_GROUP_LIMIT)
+    throw NotImplementedException("GROUP BY with more than " + std::to_string(MI_GROUP_WINDOW_LIMIT) + " groups among the selected rows of a 2048-row window or more than " +
+                                  std::to_string(MI_MAX_GROUPS) + " groups in a scan stays above the scan");
   if (bits & MI_ST_OFFSET_OVERFLOW)
     throw InvalidInputException(
         "Arrow Appender: The maximum total string size for regular string buffers is 2147483647 but the offset exceeds this.\n"

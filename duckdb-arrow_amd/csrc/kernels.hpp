@@ -200,6 +200,55 @@ hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_p
 //! launches by this process so far: [0] agg_windows, [1] agg_combine
 void AggLaunchCounts(int64_t out[2]);
 
+// K10: GROUP BY over decoded vectors (kernels_group.hip; the rules of a key are group_key.hpp).  Few groups: at most
+// groupkey::kWindowLimit distinct keys among the selected rows of one window, groupkey::kMaxGroups in a scan.
+struct GroupKeyColumnDev {
+  const void* data;                 // decoded vector (device)
+  const uint64_t* validity;         // validity words (device) or NULL = all valid
+  int32_t width;                    // bytes per row
+  int32_t cls;                      // groupkey::kKey*
+};
+struct GroupProgram {
+  int32_t n_keys;
+  int32_t _pad;
+  GroupKeyColumnDev keys[4];        // groupkey::kMaxKeys
+  AggProgram aggs;
+};
+//! what group_windows writes per window and group_combine reads: heads[2 w] = the window's local groups, heads[2 w + 1] =
+//! MI_ST_* bits it raised; record (w * kWindowLimit + g) of nulls / keys (n_keys x {lo, hi}) / partials (n_aggs) is local group g
+struct GroupWindowsOut {
+  uint32_t* heads;
+  uint32_t* nulls;
+  uint64_t* keys;
+  aggmerge::Partial* partials;
+};
+size_t GroupWindowsBytes(int64_t n_windows, int n_keys, int n_aggs);
+GroupWindowsOut GroupWindowsAt(void* base, int64_t n_windows, int n_keys, int n_aggs);
+//! the scan-wide table, in HBM for the whole call: head = {groups, MI_ST_* bits}, kGroupTableSlots slots that name a record,
+//! kMaxGroups records of nulls / keys / accumulators
+constexpr uint32_t kGroupTableSlots = 8192;
+struct GroupTableDev {
+  uint32_t* head;
+  uint32_t* slots;
+  uint32_t* nulls;
+  uint64_t* keys;
+  aggmerge::Partial* acc;
+};
+size_t GroupTableBytes(int n_keys, int n_aggs);
+GroupTableDev GroupTableAt(void* base, int n_keys, int n_aggs);
+//! an empty table (asynchronous)
+hipError_t GroupTableClear(void* base, int n_keys, int n_aggs, hipStream_t stream);
+//! 1 .. 4 key columns of a class and width that fit, and a valid aggregate program
+bool GroupProgramIsValid(const GroupProgram& prog);
+//! group_windows: the local groups of every window of `nrows` rows; sel / sel_count as LaunchAggWindows takes them
+hipError_t LaunchGroupWindows(const GroupProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
+                              const GroupWindowsOut& out, hipStream_t stream);
+//! group_combine: merges the windows, in ascending order, into the table
+hipError_t LaunchGroupCombine(const GroupProgram& prog, const GroupWindowsOut& in, int64_t n_windows, const GroupTableDev& table,
+                              hipStream_t stream);
+//! launches by this process so far: [0] group_windows, [1] group_combine
+void GroupLaunchCounts(int64_t out[2]);
+
 // K7 launches.  The string / list kernel is a single pass (decoupled look-back across the tiles of a column); it needs
 // 2 * total_tiles + 1 state words (zeroed by the launch).
 hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,

@@ -19,8 +19,10 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <memory>
@@ -29,6 +31,7 @@
 
 #include "batch_planner.hpp"
 #include "engine.hpp"
+#include "group_key.hpp"
 #include "ipc_stream_reader.hpp"
 #include "scan_readahead.hpp"
 
@@ -198,6 +201,26 @@ struct AggResult {
   int64_t rows_scanned = 0, rows_selected = 0;
 };
 
+//! What mi_scan_group_aggregate returns: the groups' normalised keys (group_key.hpp) and one partial per group and
+//! aggregate, values[g * classes.size() + a]; kinds: groupkey::kKind* per key part.  In the result order once SortGroups ran.
+struct GroupResult {
+  std::vector<int32_t> kinds;
+  std::vector<int32_t> classes;
+  std::vector<groupkey::Key> keys;
+  std::vector<aggmerge::Partial> values;
+  int64_t rows_scanned = 0, rows_selected = 0;
+};
+//! copies the scan-wide table of K10 back (one copy: keys, accumulators, group count, flags), throws for the MI_ST_* bits it
+//! carries and appends its groups to out->keys / out->values
+void ReadGroupTable(const void* d_table, int n_keys, int n_aggs, hipStream_t stream, GroupResult* out);
+//! the result order: ascending by key, NULLS LAST (groupkey::KeyLess)
+void SortGroups(GroupResult* r);
+//! a sorted result as the C ABI returns it; more groups than `capacity` is MI_EINVAL with *n_groups set
+void FillGroupOutputs(const GroupResult& r, const std::vector<int32_t>& ops, mi_group_key_value* out_keys, mi_agg_value* out_values,
+                      int32_t capacity, int32_t* n_groups);
+//! MI_AGG_TIMING=1: device milliseconds of group_windows / group_combine summed over this process's calls of mi_scan_group_aggregate
+void GroupTimingTotals(double out_ms[2]);
+
 //! a finished accumulator as the C ABI returns it (mi_scan_aggregate, mi_aggregate_vectors)
 inline void FillAggValue(int32_t op, int32_t cls, const aggmerge::Partial& p, mi_agg_value* v) {
   std::memset(v, 0, sizeof(*v));
@@ -230,6 +253,8 @@ class ScanBase {
                           const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) = 0;
   //! mi_scan_aggregate: `out` receives one partial per spec (agg_merge.hpp), ops / classes what each is merged by
   virtual void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) = 0;
+  //! mi_scan_group_aggregate: the groups of this scan, sorted
+  virtual void GroupAggregate(const std::vector<std::string>& keys, const std::vector<AggSpec>& specs, GroupResult* out) = 0;
   virtual double Progress() = 0;
   virtual void Stats(mi_scan_stats* out) = 0;   // adds to *out
 };
@@ -259,6 +284,8 @@ class ArrowScan : public ScanBase {
 
   //! up to 8 aggregates over the rows the pushed-down filter keeps, all on the GPU; drains the scan (mi_scan_aggregate)
   void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) override;
+  //! the same aggregates per group of up to 4 key columns, for few groups (mi_scan_group_aggregate)
+  void GroupAggregate(const std::vector<std::string>& keys, const std::vector<AggSpec>& specs, GroupResult* out) override;
 
   // ---- batch-level pull (what Next() is built on; the COPY pump and the multi-device scan use it directly) ----
   //! Waits for the next record batch in order; false when the scan is exhausted.  The batch stays valid (its slot is
@@ -400,14 +427,28 @@ class ArrowScan : public ScanBase {
       int32_t cls_b = 0;
     };
     std::vector<Bound> aggs;
+    struct KeyBound {
+      int32_t col = -1, cls = 0;             // output column, groupkey::kKey*
+    };
+    std::vector<KeyBound> keys;              // mi_scan_group_aggregate: not empty
+    DeviceBuffer d_table;                    // K10's scan-wide table (device::GroupTableAt): lives as long as the call
+    DeviceBuffer d_windows;                  // what group_windows writes for the record batch in flight (device::GroupWindowsAt)
     DeviceBuffer d_acc;                      // aggmerge::Partial per aggregate: lives as long as the call
     DeviceBuffer d_partials;                 // partials[window][aggregate] of the record batch in flight (one stream: in order)
     int64_t rows_scanned = 0;
     bool timed = false;                      // MI_AGG_TIMING=1: HIP events around every launch
     std::vector<HipEvent> events;            // timed: {before agg_windows, between, after agg_combine} per record batch
   } aggn;
-  //! agg_windows + agg_combine over the slot's decoded vectors and selection vectors, behind the filter on the compute stream
+  //! agg_windows + agg_combine (with keys: group_windows + group_combine) over the slot's decoded vectors and selection
+  //! vectors, behind the filter on the compute stream
   void EnqueueAggregates(Slot& s);
+  //! bind-time validation shared by Aggregate and GroupAggregate: a column an aggregate (or GROUP BY, `what`) may read
+  const ScanColumn& AggregateColumn(const std::string& name, const std::string& what) const;
+  //! validates `specs` into aggn.aggs and adds the columns they read to `proj`
+  void BindAggregateSpecs(const std::vector<AggSpec>& specs, const char* api, std::vector<std::string>* proj);
+  //! runs the scan over `proj` with aggn.on: `begin` after Init (allocates the accumulators), then every record batch;
+  //! returns the selected rows once the stream is idle and adds the launches' device time to `timing_ns` (MI_AGG_TIMING=1)
+  int64_t DrainAggregates(const std::vector<std::string>& proj, const std::function<void()>& begin, std::atomic<int64_t>* timing_ns);
   // constant columns (filename / hive): 2048 string_t each per source, host
   std::map<std::pair<int32_t, size_t>, std::vector<mi_string_t>> const_vectors;
   std::mutex const_mu;
@@ -448,6 +489,7 @@ class MultiDeviceScan : public ScanBase {
   void SumProduct(const std::string& a, const std::string& b, const std::vector<std::string>& filter_columns,
                   const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) override;
   void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) override;
+  void GroupAggregate(const std::vector<std::string>& keys, const std::vector<AggSpec>& specs, GroupResult* out) override;
   double Progress() override;
   void Stats(mi_scan_stats* out) override;
 

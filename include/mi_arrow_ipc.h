@@ -326,6 +326,8 @@ typedef struct mi_col_task {
                                    * base_stream_reader.cpp:24-29) */
 #define MI_ST_BAD_RUN_ENDS 512u   /* run ends not positive and strictly increasing, or short of the array (FULL validation) */
 #define MI_ST_SEL_RANGE 1024u     /* aggregates: a selection index names no row of its 2048-row window (skipped, never read) */
+#define MI_ST_GROUP_LIMIT 2048u   /* GROUP BY: more than MI_GROUP_WINDOW_LIMIT distinct keys in a window or MI_MAX_GROUPS in a scan */
+#define MI_ST_GROUP_KEY_LONG 4096u /* GROUP BY: a selected row's VARCHAR / BLOB key is longer than 12 bytes */
 
 /* Uploads the task table to HBM (descriptor table + tile index) and returns a reusable plan.  One plan =
  * any number of (batch, column) tasks = ONE fused kernel launch per mi_plan_launch. */
@@ -895,6 +897,67 @@ int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_
  * mi_scan_aggregate that ran with the environment variable MI_AGG_TIMING=1 (HIP events around every launch; milliseconds, 0
  * without it -- no event is created then).  DESIGN section 10's kernel times come from here.  Any pointer may be NULL. */
 int mi_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, double* windows_ms, double* combine_ms);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Grouped fused aggregates (an ABI extension, as mi_scan_aggregate is):
+ *   SELECT k_1 .. k_m, agg_1 .. agg_n FROM scan WHERE <the filter that was set> GROUP BY k_1 .. k_m
+ * with 1 <= m <= MI_MAX_GROUP_KEYS and 1 <= n <= MI_MAX_AGGREGATES, for FEW groups: at most MI_GROUP_WINDOW_LIMIT distinct
+ * keys among the selected rows of one 2048-row window and MI_MAX_GROUPS in a scan (TPC-H Q1, `group by fruit`); it is not
+ * a general hash aggregate.  The aggregates, their classes, their NULL rule and their arithmetic are exactly those of
+ * mi_scan_aggregate, per group.
+ * Key columns are top-level columns the scan decodes to an integer-like vector of 1 / 2 / 4 / 8 bytes (the integers, BOOLEAN
+ * as its byte, DATE, TIME / TIMESTAMP, DECIMAL(<=18)), to a 16-byte integer (HUGEINT, DECIMAL(19..38)) or to VARCHAR / BLOB.
+ * Every key value is normalised to 16 bytes plus a NULL bit: integers sign- or zero-extended to 128 bits; a string to its
+ * inline image (uint32 length, then the bytes, the padding behind them masked to zero by the kernel).  A string key of
+ * more than 12 bytes in a selected row makes the call fail with MI_ENOTSUP ("a VARCHAR / BLOB group key longer than 12
+ * bytes stays above the scan"); rows the filter dropped are never looked at.  A NULL key is a value of its own (NULLs group
+ * together, the bytes under a NULL are ignored); '' and NULL differ, 'a' and 'a\0' differ.
+ * MI_ENOTSUP at bind, naming the column: FLOAT / DOUBLE, INTERVAL, nested, string-view, dictionary-encoded and constant
+ * (filename / hive) key columns.  MI_EINVAL: no key or more than MI_MAX_GROUP_KEYS, a key column named twice, an unknown
+ * column.  More groups than a limit allows: MI_ENOTSUP ("GROUP BY with more than ... groups stays above the scan").
+ * The result is one row per group that has a selected row (a group whose every aggregate is NULL included), sorted
+ * ascending by k_1, then k_2 ...: integers by value, strings bytewise and then shorter first, NULLS LAST -- a function of
+ * the data alone.  out_keys[g * n_keys + k] / out_values[g * n_aggs + a] describe row g.  More groups than `capacity`:
+ * *n_groups is set to their number and the call fails with MI_EINVAL.
+ * Call right after bind, in place of init / next: the call projects the key and aggregate columns itself, honours the
+ * filter that was set, ignores mi_scan_options.filter_compact and drains the scan.  With rank / world every rank returns
+ * its share's groups; a multi-device scan merges its devices' group lists itself by key, in device order. */
+#define MI_MAX_GROUP_KEYS 4
+#define MI_GROUP_WINDOW_LIMIT 256
+#define MI_MAX_GROUPS 4096
+enum mi_group_key_kind {
+  MI_GROUP_KEY_INT128 = 0, /* bytes: a 128-bit two's-complement integer, little-endian (low 8 bytes, then high 8) */
+  MI_GROUP_KEY_STRING = 1  /* bytes: uint32 length (<= 12), then the string's bytes, zero padded */
+};
+typedef struct mi_group_key_value {
+  uint8_t bytes[16];
+  int32_t kind;            /* enum mi_group_key_kind */
+  int32_t is_null;         /* bytes are zero then */
+} mi_group_key_value;
+int mi_scan_group_aggregate(mi_scan* s, const char* const* key_columns, int32_t n_keys, const mi_agg_spec* aggs, int32_t n_aggs,
+                            mi_group_key_value* out_keys /* [capacity * n_keys] */, mi_agg_value* out_values /* [capacity * n_aggs] */,
+                            int32_t capacity, int32_t* n_groups, int64_t* rows_scanned, int64_t* rows_selected);
+/* The kernel-level entry, over resident vectors as mi_aggregate_vectors is, with the same sel / sel_count contract (counts
+ * clamped; an index past its window skipped, MI_EINVAL through MI_ST_SEL_RANGE).  A string key column holds 16-byte string_t
+ * rows; only length and inline bytes are read.  16-byte columns need 8-byte alignment only. */
+enum mi_group_key_class {
+  MI_GROUP_KEY_CLASS_SIGNED = 1,   /* width 1 / 2 / 4 / 8 */
+  MI_GROUP_KEY_CLASS_UNSIGNED = 2, /* width 1 / 2 / 4 / 8 */
+  MI_GROUP_KEY_CLASS_WIDE = 3,     /* width 16: mi_hugeint_t */
+  MI_GROUP_KEY_CLASS_STRING = 4    /* width 16: string_t */
+};
+typedef struct mi_group_key_column {
+  const void* data;          /* device: one value of `width` bytes per row */
+  const void* validity;      /* device: validity words, or NULL = all valid */
+  int32_t width;
+  int32_t key_class;         /* enum mi_group_key_class */
+} mi_group_key_column;
+int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int32_t n_keys, const mi_agg_vector_spec* aggs, int32_t n_aggs,
+                               const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows, mi_group_key_value* out_keys,
+                               mi_agg_value* out_values, int32_t capacity, int32_t* n_groups, void* stream);
+/* Debug and measurement facility, the counterpart of mi_aggregate_counters: launches of group_windows / group_combine by this
+ * process so far, and their device time summed over the calls of mi_scan_group_aggregate that ran with MI_AGG_TIMING=1. */
+int mi_group_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, double* windows_ms, double* combine_ms);
 
 #ifdef __cplusplus
 }

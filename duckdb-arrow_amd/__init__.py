@@ -166,6 +166,8 @@ class Context:
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
+        self._users = 0          # open relations that scan on this context
+        self._orphaned = False
         _ffi.check(_ffi.lib().mi_ctx_create(device, C.byref(self._h)))
         self.device = device
 
@@ -174,7 +176,22 @@ class Context:
             _ffi.lib().mi_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
-    __del__ = close
+    def __del__(self):
+        # A relation holds its context, so reference counting frees the relation first.  The cycle collector finalises a group
+        # of objects in any order (a traceback that holds a frame with both is such a group): a context finalised before a
+        # relation that is still open stays alive, and the last such relation to close destroys it.
+        if self._users:
+            self._orphaned = True
+        else:
+            self.close()
+
+    def _retain(self):
+        self._users += 1
+
+    def _release(self):
+        self._users -= 1
+        if self._orphaned and not self._users:
+            self.close()
 
     def numa(self):
         """(NUMA node of the GPU or -1, the node's CPUs as a set) -- mi_ctx_numa."""
@@ -621,6 +638,9 @@ class Relation:
         self._conn = conn
         self._h = handle
         self._keep = keep
+        self._contexts = [c for c in [conn.ctx] + (keep if isinstance(keep, list) else []) if isinstance(c, Context)]
+        for c in self._contexts:
+            c._retain()
         n = C.c_int32(0)
         _ffi.check(_ffi.lib().mi_scan_bind(self._h, None, 0, C.byref(n)))
         fields = (_ffi.Field * max(n.value, 1))()
@@ -861,6 +881,8 @@ class Relation:
         if self._h:
             _ffi.lib().mi_scan_close(self._h)
             self._h = C.c_void_p()
+            for c in self._contexts:
+                c._release()
 
     __del__ = close
 

@@ -462,6 +462,9 @@ __device__ __forceinline__ void light_map(gptr<const IN> src, gptr<OUT> out, int
       } else {
 #pragma unroll
         for (int k = 0; k < V; k++) vin[p][k] = base + k < n ? src[base + k] : IN(0);
+        // the rows a tile is padded with are no rows: f sees them as NULL, never as a valid 0 (an index into an empty
+        // dictionary, which has no entry 0)
+        ok[p] &= base < n ? (1u << (n - base)) - 1u : 0u;
       }
     }
 #pragma unroll

@@ -42,3 +42,37 @@ def test_hbm_stream_is_freed_by_its_reference_count_before_its_context():
         assert gone() is None and ctx_gone() is None
     finally:
         gc.enable()
+
+
+class _CountingLib:
+    """stands in for the library: records the order in which handles are destroyed"""
+
+    def __init__(self):
+        self.calls = []
+
+    def mi_ctx_destroy(self, h):
+        self.calls.append("ctx")
+
+    def mi_scan_close(self, h):
+        self.calls.append("scan")
+
+
+@pytest.mark.parametrize("context_first", [True, False])
+def test_a_relation_finalised_after_its_context_still_finds_it_alive(monkeypatch, context_first):
+    """the cycle collector may finalise a context before a relation that is still open on it (both hang on the frame a
+    traceback keeps): the scan is closed first all the same, and the context is destroyed exactly once"""
+    import ctypes as C
+    lib = _CountingLib()
+    monkeypatch.setattr(da._ffi, "lib", lambda: lib)
+    ctx = da.Context.__new__(da.Context)
+    ctx._h, ctx._users, ctx._orphaned = C.c_void_p(1), 0, False
+    con = da.Connection.__new__(da.Connection)
+    con.ctx = ctx
+    rel = da.Relation.__new__(da.Relation)
+    rel._conn, rel._h, rel._keep, rel._contexts = con, C.c_void_p(2), None, [ctx]
+    ctx._retain()
+    for finalise in ((ctx.__del__, rel.__del__) if context_first else (rel.__del__, ctx.__del__)):
+        finalise()
+    assert lib.calls == ["scan", "ctx"]
+    rel.close(), ctx.close()
+    assert lib.calls == ["scan", "ctx"]

@@ -308,8 +308,8 @@ def filter_between(ctx, values_ptr, width, validity_ptr, nrows, lo, hi, sel_ptr,
 
 
 _AGG_OPS = {"count_star": _ffi.AGG_COUNT_STAR, "count": _ffi.AGG_COUNT, "sum": _ffi.AGG_SUM, "sum_product": _ffi.AGG_SUM_PRODUCT,
-            "min": _ffi.AGG_MIN, "max": _ffi.AGG_MAX}
-_AGG_ARITY = {"count_star": 0, "count": 1, "sum": 1, "sum_product": 2, "min": 1, "max": 1}
+            "min": _ffi.AGG_MIN, "max": _ffi.AGG_MAX, "sum_expr": _ffi.AGG_SUM_EXPR}
+_AGG_ARITY = {"count_star": 0, "count": 1, "sum": 1, "sum_product": 2, "min": 1, "max": 1}   # (sum_expr: 1 .. 4 factors)
 
 
 def _agg_check_specs(specs):
@@ -322,10 +322,109 @@ def _agg_check_specs(specs):
         name = str(sp[0]).lower() if sp else ""
         if name not in _AGG_OPS:
             raise MiError(_ffi.MI_EINVAL, "aggregate: unknown operation %r (one of %s)" % (sp[0] if sp else None, ", ".join(sorted(_AGG_OPS))))
+        if name == "sum_expr":
+            if not 1 <= len(sp) - 1 <= _ffi.MAX_EXPR_FACTORS:
+                raise MiError(_ffi.MI_EINVAL, "aggregate: sum_expr takes 1 to %d factors, not %d" % (_ffi.MAX_EXPR_FACTORS, len(sp) - 1))
+            factors = [_agg_factor(f) for f in sp[1:]]
+            if all(f[0] is None for f in factors):
+                raise MiError(_ffi.MI_EINVAL, "aggregate: sum_expr needs at least one factor with a column")
+            out.append((name, tuple(factors)))
+            continue
         if len(sp) - 1 != _AGG_ARITY[name]:
             raise MiError(_ffi.MI_EINVAL, "aggregate: %s takes %d argument(s), not %d" % (name, _AGG_ARITY[name], len(sp) - 1))
         out.append((name, sp[1:]))
     return out
+
+
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _agg_factor(f):
+    """One factor of a sum_expr -> (column or None, mul, add).  The forms: a column; (column, mul, add); (None, add) or a
+    bare number for a constant.  What a column is -- a name for a scan, a (data, validity, width, class) tuple for the
+    *_vectors calls -- is the caller's business: anything that is neither a number nor a 2- / 3-tuple of one of these
+    forms is taken as a column."""
+    def int64(*constants):
+        for v in constants:
+            if isinstance(v, int) and not -(1 << 63) <= v < (1 << 63):
+                raise MiError(_ffi.MI_EINVAL, "aggregate: the sum_expr constant %d does not fit an int64" % v)
+
+    if _is_number(f):
+        int64(f)
+        return (None, 1, f)
+    if isinstance(f, (tuple, list)):
+        if len(f) == 2 and f[0] is None and _is_number(f[1]):
+            int64(f[1])
+            return (None, 1, f[1])
+        if len(f) == 3 and f[0] is not None and _is_number(f[1]) and _is_number(f[2]):
+            int64(f[1], f[2])
+            return (f[0], f[1], f[2])
+        if len(f) in (2, 3) and f[0] is None:
+            raise MiError(_ffi.MI_EINVAL, "aggregate: a constant sum_expr factor is (None, number) or a number, not %r" % (f,))
+    if f is None or isinstance(f, bool):
+        raise MiError(_ffi.MI_EINVAL, "aggregate: a sum_expr factor is a column, (column, mul, add), (None, add) or a number, not %r" % (f,))
+    return (f, 1, 0)
+
+
+def _agg_fill_constants(slot, mul, add):
+    """mul / add into a mi_agg_factor or mi_agg_vector_factor: Python ints are MI_AGG_CONST_INT, a float makes both doubles"""
+    if isinstance(mul, float) or isinstance(add, float):
+        slot.constants, slot.fmul, slot.fadd = _ffi.AGG_CONST_DOUBLE, float(mul), float(add)
+        slot.mul, slot.add = 1, 0
+        return
+    slot.constants, slot.mul, slot.add, slot.fmul, slot.fadd = _ffi.AGG_CONST_INT, mul, add, 1.0, 0.0
+
+
+def _agg_scan_specs(checked):
+    """[(name, args)] -> (mi_agg_spec array, what must stay alive while it is used)"""
+    arr = (_ffi.AggSpec * len(checked))()
+    keep = []
+    for i, (name, cols) in enumerate(checked):
+        arr[i].op = _AGG_OPS[name]
+        if name == "sum_expr":
+            expr = _ffi.AggExpr()
+            expr.n_factors = len(cols)
+            for slot, (col, mul, add) in zip(expr.factors, cols):
+                if col is not None:
+                    keep.append(col.encode() if isinstance(col, str) else col)
+                    slot.column = keep[-1]
+                _agg_fill_constants(slot, mul, add)
+            keep.append(expr)
+            arr[i].expr = C.pointer(expr)
+            continue
+        names = [c.encode() if isinstance(c, str) else c for c in cols]
+        keep.append(names)
+        if names:
+            arr[i].column_a = names[0]
+        if len(names) > 1:
+            arr[i].column_b = names[1]
+    return arr, keep
+
+
+def _agg_vector_specs(checked, classes):
+    """[(name, args)] -> (mi_agg_vector_spec array, what must stay alive while it is used)"""
+    def fill(slot, col):
+        data, validity, width, cls = col
+        slot.data, slot.validity, slot.width, slot.value_class = data or None, validity or None, width, classes[cls]
+
+    arr = (_ffi.AggVectorSpec * len(checked))()
+    keep = []
+    for i, (name, cols) in enumerate(checked):
+        arr[i].op = _AGG_OPS[name]
+        if name == "sum_expr":
+            expr = _ffi.AggVectorExpr()
+            expr.n_factors = len(cols)
+            for slot, (col, mul, add) in zip(expr.factors, cols):
+                if col is not None:
+                    fill(slot.column, col)
+                _agg_fill_constants(slot, mul, add)
+            keep.append(expr)
+            arr[i].expr = C.pointer(expr)
+            continue
+        for slot, col in zip((arr[i].a, arr[i].b), cols):
+            fill(slot, col)
+    return arr, keep
 
 
 def _agg_value(v):
@@ -345,12 +444,7 @@ def aggregate_vectors(ctx, specs, nrows, sel_ptr=0, count_ptr=0, stream=0, detai
     classes = {"any": _ffi.AGG_CLASS_ANY, "signed": _ffi.AGG_CLASS_SIGNED, "unsigned": _ffi.AGG_CLASS_UNSIGNED,
                "float": _ffi.AGG_CLASS_FLOAT, "wide": _ffi.AGG_CLASS_WIDE}
     checked = _agg_check_specs(specs)
-    arr = (_ffi.AggVectorSpec * len(checked))()
-    for i, (name, cols) in enumerate(checked):
-        arr[i].op = _AGG_OPS[name]
-        for slot, col in zip((arr[i].a, arr[i].b), cols):
-            data, validity, width, cls = col
-            slot.data, slot.validity, slot.width, slot.value_class = data or None, validity or None, width, classes[cls]
+    arr, _keep = _agg_vector_specs(checked, classes)
     out = (_ffi.AggValue * len(checked))()
     _ffi.check(_ffi.lib().mi_aggregate_vectors(ctx._h, arr, len(checked), sel_ptr or None, count_ptr or None, nrows, out,
                                                C.c_void_p(stream or None)))
@@ -409,12 +503,7 @@ def group_aggregate_vectors(ctx, keys, specs, nrows, sel_ptr=0, count_ptr=0, cap
         if cls not in classes:
             raise MiError(_ffi.MI_EINVAL, "group_aggregate_vectors: unknown key class %r (one of %s)" % (cls, ", ".join(sorted(classes))))
         karr[i].data, karr[i].validity, karr[i].width, karr[i].key_class = data or None, validity or None, width, classes[cls]
-    arr = (_ffi.AggVectorSpec * len(checked))()
-    for i, (name, cols) in enumerate(checked):
-        arr[i].op = _AGG_OPS[name]
-        for slot, col in zip((arr[i].a, arr[i].b), cols):
-            data, validity, width, cls = col
-            slot.data, slot.validity, slot.width, slot.value_class = data or None, validity or None, width, agg_classes[cls]
+    arr, _keep = _agg_vector_specs(checked, agg_classes)
     capacity = max(int(capacity), 0)
     out_keys = (_ffi.GroupKeyValue * max(capacity * len(keys), 1))()
     out_values = (_ffi.AggValue * max(capacity * len(checked), 1))()
@@ -815,21 +904,14 @@ class Relation:
     def aggregate(self, specs, detail=False):
         """SELECT agg_1, ..., agg_n (n <= 8) over the rows the pushed-down filter keeps, on the GPU in one pass
         (mi_scan_aggregate); call it in place of chunks() / count().  `specs`: ("count_star",), ("count", c), ("sum", c),
-        ("sum_product", a, b), ("min", c), ("max", c).  Returns one Python value per spec -- an int (counts; sums, minima and
+        ("sum_product", a, b), ("min", c), ("max", c), ("sum_expr", factor, ...) -- the sum of a product of 1 .. 4 factors,
+        a factor being a column name, (column, mul, add) for add + mul * column, or (None, add) / a bare number for a
+        constant; Python ints are exact int64 constants, floats doubles (floating-point columns only).  Returns one Python value per spec -- an int (counts; sums, minima and
         maxima of integer-like columns as the stored integers, exact in 128 bits), a float (FLOAT / DOUBLE columns) or None
         (SUM / MIN / MAX over no row that is not NULL); with `detail` also the rows scanned and selected:
         (values, rows_scanned, rows_selected)."""
         checked = _agg_check_specs(specs)
-        arr = (_ffi.AggSpec * len(checked))()
-        keep = []
-        for i, (name, cols) in enumerate(checked):
-            arr[i].op = _AGG_OPS[name]
-            names = [c.encode() for c in cols]
-            keep.append(names)
-            if names:
-                arr[i].column_a = names[0]
-            if len(names) > 1:
-                arr[i].column_b = names[1]
+        arr, _keep = _agg_scan_specs(checked)
         out = (_ffi.AggValue * len(checked))()
         scanned, selected = C.c_int64(), C.c_int64()
         _ffi.check(_ffi.lib().mi_scan_aggregate(self._h, arr, len(checked), out, C.byref(scanned), C.byref(selected)))
@@ -845,16 +927,7 @@ class Relation:
         or None.  With `detail`: (rows, rows_scanned, rows_selected)."""
         keys = _group_check_keys(keys)
         checked = _agg_check_specs(specs)
-        arr = (_ffi.AggSpec * len(checked))()
-        keep = []
-        for i, (name, cols) in enumerate(checked):
-            arr[i].op = _AGG_OPS[name]
-            names = [c.encode() for c in cols]
-            keep.append(names)
-            if names:
-                arr[i].column_a = names[0]
-            if len(names) > 1:
-                arr[i].column_b = names[1]
+        arr, _keep = _agg_scan_specs(checked)
         karr = (C.c_char_p * len(keys))(*[k.encode() if isinstance(k, str) else k for k in keys])
         capacity = max(int(capacity), 0)
         out_keys = (_ffi.GroupKeyValue * max(capacity * len(keys), 1))()

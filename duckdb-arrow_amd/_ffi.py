@@ -133,15 +133,26 @@ class SumProductResult(C.Structure):
     _fields_ = [("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("rows_scanned", C.c_int64), ("rows_selected", C.c_int64)]
 
 
-AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_SUM_PRODUCT, AGG_MIN, AGG_MAX = 1, 2, 3, 4, 5, 6
+AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_SUM_PRODUCT, AGG_MIN, AGG_MAX, AGG_SUM_EXPR = 1, 2, 3, 4, 5, 6, 7
 MAX_AGGREGATES = 8
+MAX_EXPR_FACTORS = 4
+AGG_CONST_INT, AGG_CONST_DOUBLE = 0, 1
 AGG_VALUE_INT128, AGG_VALUE_DOUBLE = 0, 1
 AGG_CLASS_ANY, AGG_CLASS_SIGNED, AGG_CLASS_UNSIGNED, AGG_CLASS_FLOAT, AGG_CLASS_WIDE = 0, 1, 2, 3, 4
 
 
+class AggFactor(C.Structure):
+    _fields_ = [("column", C.c_char_p), ("mul", C.c_int64), ("add", C.c_int64), ("fmul", C.c_double), ("fadd", C.c_double),
+                ("constants", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class AggExpr(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("reserved0", C.c_int32), ("factors", AggFactor * MAX_EXPR_FACTORS)]
+
+
 class AggSpec(C.Structure):
     _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("column_a", C.c_char_p), ("column_b", C.c_char_p),
-                ("reserved", C.c_int64 * 2)]
+                ("expr", C.POINTER(AggExpr)), ("reserved", C.c_int64 * 1)]
 
 
 class AggValue(C.Structure):
@@ -153,8 +164,18 @@ class AggColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("validity", C.c_void_p), ("width", C.c_int32), ("value_class", C.c_int32)]
 
 
+class AggVectorFactor(C.Structure):
+    _fields_ = [("column", AggColumn), ("mul", C.c_int64), ("add", C.c_int64), ("fmul", C.c_double), ("fadd", C.c_double),
+                ("constants", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class AggVectorExpr(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("reserved0", C.c_int32), ("factors", AggVectorFactor * MAX_EXPR_FACTORS)]
+
+
 class AggVectorSpec(C.Structure):
-    _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("a", AggColumn), ("b", AggColumn), ("reserved", C.c_int64 * 2)]
+    _fields_ = [("op", C.c_int32), ("reserved0", C.c_int32), ("a", AggColumn), ("b", AggColumn), ("expr", C.POINTER(AggVectorExpr)),
+                ("reserved", C.c_int64 * 1)]
 
 
 MAX_GROUP_KEYS, GROUP_WINDOW_LIMIT, MAX_GROUPS = 4, 256, 4096

@@ -5,8 +5,9 @@
 //
 // A partial is {lo, hi, count, flags}:
 //   count   rows that contributed (COUNT(*): the selected rows; COUNT(col): the selected rows that are not NULL; the
-//           others: the selected rows whose input -- both factors of a product -- is not NULL).  count == 0 is the NULL
-//           rule: "no contributor", the partial is the identity of every merge, and SUM / MIN / MAX of it is NULL.
+//           others: the selected rows whose input -- both factors of a product, every column an expression names -- is
+//           not NULL).  count == 0 is the NULL rule: "no contributor", the partial is the identity of every merge, and
+//           SUM / MIN / MAX of it is NULL.
 //   lo, hi  integer classes: a 128-bit two's-complement integer -- the sum (wrapping modulo 2^128), or the minimum /
 //           maximum sign- or zero-extended; kClassWide orders by `hi` signed, then `lo` unsigned, which is the order of
 //           the extended narrow integers too.  kClassFloat: lo = the bits of a double (hi = 0) -- the sum, or the
@@ -26,6 +27,8 @@ namespace aggmerge {
 
 // the operations (== MI_AGG_* of mi_arrow_ipc.h)
 constexpr int kOpCountStar = 1, kOpCount = 2, kOpSum = 3, kOpSumProduct = 4, kOpMin = 5, kOpMax = 6;
+constexpr int kOpSumExpr = 7;       // SUM of a product of 1 .. kMaxExprFactors affine factors, each add + mul * column or a constant
+constexpr int kMaxExprFactors = 4;  // (== MI_MAX_EXPR_FACTORS)
 // what a column's values are (== MI_AGG_CLASS_* of mi_arrow_ipc.h)
 constexpr int kClassAny = 0;        // COUNT alone: only the validity is read
 constexpr int kClassSigned = 1;     // width 1 / 2 / 4 / 8, sign-extended
@@ -72,7 +75,11 @@ MI_KEY_FN bool Less(bool is_float, uint64_t alo, uint64_t ahi, uint64_t blo, uin
   return filterkey::WideLess(static_cast<int64_t>(ahi), alo, static_cast<int64_t>(bhi), blo);
 }
 
-//! into = into (+) from for the aggregate `op` over values of class `cls` (for a product: kClassFloat or an integer class)
+//! into = into (+) from for the aggregate `op` over values of class `cls` (for a product: kClassFloat or an integer class).
+//! kOpSumExpr merges as the two other sums do.  WITH_EXPR = false is for a caller that never holds a kOpSumExpr -- the
+//! kernel instantiations for programs without an expression, and the combine kernels, whose launchers hand an expression
+//! sum over as kOpSum -- and compiles the test for it away, so those kernels are the code they were before expressions.
+template <bool WITH_EXPR = true>
 MI_KEY_FN void Merge(int op, int cls, Partial* into, const Partial& from) {
   into->flags |= from.flags;
   if (from.count == 0) return;   // the NULL rule: nothing contributed, nothing changes
@@ -83,7 +90,7 @@ MI_KEY_FN void Merge(int op, int cls, Partial* into, const Partial& from) {
     return;
   }
   const bool is_float = cls == kClassFloat;
-  if (op == kOpSum || op == kOpSumProduct) {
+  if (op == kOpSum || op == kOpSumProduct || (WITH_EXPR && op == kOpSumExpr)) {
     if (is_float) into->lo = BitsOf(DoubleOf(into->lo) + DoubleOf(from.lo));
     else Add128(&into->lo, &into->hi, from.lo, from.hi);
   } else if (op == kOpMin) {
@@ -95,9 +102,59 @@ MI_KEY_FN void Merge(int op, int cls, Partial* into, const Partial& from) {
 }
 
 //! one contributing value folded into a partial: the same as Merge with a partial of count 1
+template <bool WITH_EXPR = true>
 MI_KEY_FN void Fold(int op, int cls, Partial* into, uint64_t lo, uint64_t hi) {
   const Partial one = {lo, hi, 1ull, 0ull};
-  Merge(op, cls, into, one);
+  Merge<WITH_EXPR>(op, cls, into, one);
+}
+
+// ---- the expression of kOpSumExpr: f_0 * f_1 * ... * f_{F-1}, a factor add + mul * v or the constant add.  One step takes the
+// product of the factors before it (`first`: there is none) and returns it times this factor.
+
+//! integer expressions: v sign- or zero-extended to {vlo, vhi} by the caller, mul and add sign-extended here; the factor
+//! and the product modulo 2^128, in unsigned arithmetic throughout (nothing signed can overflow)
+MI_KEY_FN void ExprStepInt(bool first, bool has_column, int64_t mul, int64_t add, uint64_t vlo, uint64_t vhi, uint64_t* lo, uint64_t* hi) {
+  typedef unsigned __int128 u128;
+  const u128 a = (static_cast<u128>(add < 0 ? ~0ull : 0ull) << 64) | static_cast<uint64_t>(add);
+  u128 f = a;
+  if (has_column) {
+    const u128 m = (static_cast<u128>(mul < 0 ? ~0ull : 0ull) << 64) | static_cast<uint64_t>(mul);
+    const u128 v = (static_cast<u128>(vhi) << 64) | vlo;
+    f = a + m * v;
+  }
+  if (!first) f = ((static_cast<u128>(*hi) << 64) | *lo) * f;
+  *lo = static_cast<uint64_t>(f);
+  *hi = static_cast<uint64_t>(f >> 64);
+}
+
+//! a * b and a + b rounded once each, never contracted into an fma (the host compiler may contract `a * b + c` otherwise)
+MI_KEY_FN double MulRn(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __dmul_rn(a, b);
+#else
+  volatile double r = a * b;
+  return r;
+#endif
+}
+MI_KEY_FN double AddRn(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __dadd_rn(a, b);
+#else
+  volatile double r = a + b;
+  return r;
+#endif
+}
+
+//! floating-point expressions: the factor is (mul * v) + add, each rounded once; a mul of exactly 1.0 skips the
+//! multiplication and an add of exactly +0.0 the addition, so a plain column is its value bit for bit (-0.0, NaN payloads);
+//! the product is taken left to right, each step rounded once
+MI_KEY_FN double ExprStepDouble(bool first, bool has_column, double mul, double add, double v, double product) {
+  double f = add;
+  if (has_column) {
+    f = mul == 1.0 ? v : MulRn(mul, v);
+    if (BitsOf(add) != 0ull) f = AddRn(f, add);
+  }
+  return first ? f : MulRn(product, f);
 }
 
 //! SUM / MIN / MAX over no contributor is NULL; a COUNT never is

@@ -401,6 +401,39 @@ int mi_filter_string(mi_ctx* ctx, const void* rows, const void* validity, int64_
   });
 }
 
+namespace {
+//! the expression of vector spec `a` into exprs->exprs[a] and desc->a (the first column factor's column: its class is the
+//! expression's), for the call `api` names in its messages; what is left to check is device::AggProgramIsValid's
+void VectorExprOf(const char* api, const mi_agg_vector_spec& spec, device::AggDescDev* desc, device::AggExprDev* out) {
+  const mi_agg_vector_expr* e = spec.expr;
+  if (!e) throw InvalidInputException(std::string(api) + ": SUM_EXPR without an expression");
+  if (e->n_factors < 1 || e->n_factors > MI_MAX_EXPR_FACTORS)
+    throw InvalidInputException(std::string(api) + ": SUM_EXPR takes 1 to " + std::to_string(MI_MAX_EXPR_FACTORS) + " factors, not " + std::to_string(e->n_factors));
+  auto is_constant = [](const mi_agg_vector_factor& f) { return f.column.data == nullptr && f.column.value_class == MI_AGG_CLASS_ANY; };
+  const mi_agg_vector_factor* first = nullptr;
+  for (int32_t f = 0; f < e->n_factors && !first; f++)
+    if (!is_constant(e->factors[f])) first = &e->factors[f];
+  if (!first) throw InvalidInputException(std::string(api) + ": SUM_EXPR needs at least one factor with a column");
+  const bool is_float = first->column.value_class == MI_AGG_CLASS_FLOAT;
+  std::memset(out, 0, sizeof(*out));
+  out->n_factors = e->n_factors;
+  for (int32_t f = 0; f < e->n_factors; f++) {
+    const mi_agg_vector_factor& in = e->factors[f];
+    device::AggFactorDev& fd = out->factors[f];
+    ExprFactorConstants(std::string(api) + ": SUM_EXPR factor " + std::to_string(f), is_float, in.constants, in.mul, in.add, in.fmul, in.fadd, &fd.mul, &fd.add);
+    if (is_constant(in)) continue;
+    fd.col.data = in.column.data;
+    fd.col.validity = static_cast<const uint64_t*>(in.column.validity);
+    fd.col.width = in.column.width;
+    fd.col.cls = in.column.value_class;
+    if (&in == first) desc->a = fd.col;
+    else if ((in.column.value_class == MI_AGG_CLASS_FLOAT) != is_float)
+      throw NotImplementedException(std::string(api) + ": SUM_EXPR factors " + std::to_string(static_cast<int>(first - e->factors)) + " and " + std::to_string(f) +
+                                    ": both factors must be integer-like or both floating point");
+  }
+}
+}  // namespace
+
 int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel, const uint32_t* sel_count,
                          int64_t nrows, mi_agg_value* out, void* stream) {
   return Wrap([&] {
@@ -420,12 +453,22 @@ int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_
       d.cls = c.value_class;
       return d;
     };
+    device::AggExprTable exprs_table;
+    const device::AggExprTable* exprs = nullptr;
     for (int32_t i = 0; i < n_aggs; i++) {
       prog.aggs[i].op = aggs[i].op;
+      if (aggs[i].op == MI_AGG_SUM_EXPR) {
+        if (!exprs) {
+          std::memset(&exprs_table, 0, sizeof(exprs_table));
+          exprs = &exprs_table;
+        }
+        VectorExprOf("mi_aggregate_vectors", aggs[i], &prog.aggs[i], &exprs_table.exprs[i]);
+        continue;
+      }
       prog.aggs[i].a = column(aggs[i].a);
       prog.aggs[i].b = column(aggs[i].b);
     }
-    if (!device::AggProgramIsValid(prog))
+    if (!device::AggProgramIsValid(prog, exprs))
       throw InvalidInputException("mi_aggregate_vectors: an operation, value class or width that does not fit (SUM takes integers of width 1 / 2 / 4 / 8 "
                                   "or floats of width 4 / 8, MIN / MAX also width 16, a product two integers or two floats)");
     ctx->ctx->Bind();
@@ -436,8 +479,8 @@ int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_
     aggmerge::Partial* partials = d_partials.get<aggmerge::Partial>();
     aggmerge::Partial* acc = partials + static_cast<size_t>(n_windows) * n;
     MI_HIP_CHECK(hipMemsetAsync(acc, 0, n * sizeof(aggmerge::Partial), s));
-    MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, nrows, partials, s));
-    MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, acc, s));
+    MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, nrows, partials, s, exprs));
+    MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, acc, s, exprs));
     std::vector<aggmerge::Partial> host(n);
     MI_HIP_CHECK(hipMemcpyAsync(host.data(), acc, n * sizeof(aggmerge::Partial), hipMemcpyDeviceToHost, s));
     MI_HIP_CHECK(hipStreamSynchronize(s));
@@ -483,14 +526,25 @@ int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int
       return d;
     };
     std::vector<int32_t> ops;
+    device::AggExprTable exprs_table;
+    const device::AggExprTable* exprs = nullptr;
     for (int32_t i = 0; i < n_aggs; i++) {
       prog.aggs.aggs[i].op = aggs[i].op;
+      ops.push_back(aggs[i].op);
+      if (aggs[i].op == MI_AGG_SUM_EXPR) {
+        if (!exprs) {
+          std::memset(&exprs_table, 0, sizeof(exprs_table));
+          exprs = &exprs_table;
+        }
+        VectorExprOf("mi_group_aggregate_vectors", aggs[i], &prog.aggs.aggs[i], &exprs_table.exprs[i]);
+        r.classes.push_back(prog.aggs.aggs[i].a.cls);
+        continue;
+      }
       prog.aggs.aggs[i].a = column(aggs[i].a);
       prog.aggs.aggs[i].b = column(aggs[i].b);
-      ops.push_back(aggs[i].op);
       r.classes.push_back(aggs[i].a.value_class);
     }
-    if (!device::GroupProgramIsValid(prog))
+    if (!device::GroupProgramIsValid(prog, exprs))
       throw InvalidInputException("mi_group_aggregate_vectors: a key class, operation, value class or width that does not fit (keys: signed / unsigned of width "
                                   "1 / 2 / 4 / 8, wide or string of width 16; aggregates as mi_aggregate_vectors takes them)");
     ctx->ctx->Bind();
@@ -501,8 +555,8 @@ int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int
     const device::GroupTableDev table = device::GroupTableAt(d_all.get(), n_keys, n_aggs);
     const device::GroupWindowsOut win = device::GroupWindowsAt(d_all.get() + table_bytes, n_windows, n_keys, n_aggs);
     MI_HIP_CHECK(device::GroupTableClear(d_all.get(), n_keys, n_aggs, s));
-    MI_HIP_CHECK(device::LaunchGroupWindows(prog, sel, sel_count, nrows, win, s));
-    MI_HIP_CHECK(device::LaunchGroupCombine(prog, win, n_windows, table, s));
+    MI_HIP_CHECK(device::LaunchGroupWindows(prog, sel, sel_count, nrows, win, s, exprs));
+    MI_HIP_CHECK(device::LaunchGroupCombine(prog, win, n_windows, table, s, exprs));
     ReadGroupTable(d_all.get(), n_keys, n_aggs, s, &r);
     SortGroups(&r);
     FillGroupOutputs(r, ops, out_keys, out_values, capacity, n_groups);

@@ -186,16 +186,35 @@ struct AggProgram {
   int32_t _pad;
   AggDescDev aggs[aggmerge::kMaxAggregates];
 };
+// The expressions of a program's kOpSumExpr aggregates: a table of its own, a kernel argument of the EXPR instantiations of
+// agg_windows / group_windows alone, so a program without an expression launches the kernels it always launched with the
+// arguments it always had.  exprs[a] belongs to aggs[a]; for such an aggregate aggs[a].a is the first column factor's
+// column (its class is the expression's: what the combine kernels and the host merge by).
+struct AggFactorDev {
+  AggColumnDev col;                 // cls == aggmerge::kClassAny: a constant factor (`add` alone, nothing is read)
+  uint64_t mul, add;                // integer expression: int64 two's complement; float expression: the bits of a double
+};
+struct AggExprDev {
+  int32_t n_factors;                // 1 .. aggmerge::kMaxExprFactors
+  int32_t _pad;
+  AggFactorDev factors[aggmerge::kMaxExprFactors];
+};
+struct AggExprTable {
+  AggExprDev exprs[aggmerge::kMaxAggregates];
+};
 //! what the launchers accept: 1 .. 8 aggregates, widths that fit their class, no SUM over 16-byte values, products of two
-//! integers or two floats
-bool AggProgramIsValid(const AggProgram& prog);
+//! integers or two floats; a kOpSumExpr needs `exprs`: 1 .. 4 factors, at least one column, every column factor with data,
+//! width 1 / 2 / 4 / 8 (integers) or 4 / 8 (floats), all integer-like or all floating point, none of 16 bytes
+bool AggProgramIsValid(const AggProgram& prog, const AggExprTable* exprs = nullptr);
 //! agg_windows: one partial per window and aggregate to d_partials[window * n_aggs + aggregate].  sel / sel_count in the
-//! filter's layout (2048 slots per window, the first sel_count[w] read), or both NULL = every row.
+//! filter's layout (2048 slots per window, the first sel_count[w] read), or both NULL = every row.  `exprs` is read only
+//! when the program holds a kOpSumExpr, and only then the expression instantiation is launched.
 hipError_t LaunchAggWindows(const AggProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
-                            aggmerge::Partial* d_partials, hipStream_t stream);
-//! agg_combine: folds the partials of n_windows windows, in ascending order, into d_acc[0 .. n_aggs)
+                            aggmerge::Partial* d_partials, hipStream_t stream, const AggExprTable* exprs = nullptr);//! agg_combine: folds the partials of n_windows windows, in ascending order, into d_acc[0 .. n_aggs)
 hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_partials, int64_t n_windows, aggmerge::Partial* d_acc,
-                            hipStream_t stream);
+                            hipStream_t stream, const AggExprTable* exprs = nullptr);
+//! whether the program holds a kOpSumExpr (and its launches therefore need the table)
+bool AggProgramHasExpr(const AggProgram& prog);
 
 //! launches by this process so far: [0] agg_windows, [1] agg_combine
 void AggLaunchCounts(int64_t out[2]);
@@ -238,14 +257,14 @@ size_t GroupTableBytes(int n_keys, int n_aggs);
 GroupTableDev GroupTableAt(void* base, int n_keys, int n_aggs);
 //! an empty table (asynchronous)
 hipError_t GroupTableClear(void* base, int n_keys, int n_aggs, hipStream_t stream);
-//! 1 .. 4 key columns of a class and width that fit, and a valid aggregate program
-bool GroupProgramIsValid(const GroupProgram& prog);
-//! group_windows: the local groups of every window of `nrows` rows; sel / sel_count as LaunchAggWindows takes them
+//! 1 .. 4 key columns of a class and width that fit, and a valid aggregate program (`exprs` as AggProgramIsValid takes it)
+bool GroupProgramIsValid(const GroupProgram& prog, const AggExprTable* exprs = nullptr);
+//! group_windows: the local groups of every window of `nrows` rows; sel / sel_count / exprs as LaunchAggWindows takes them
 hipError_t LaunchGroupWindows(const GroupProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
-                              const GroupWindowsOut& out, hipStream_t stream);
+                              const GroupWindowsOut& out, hipStream_t stream, const AggExprTable* exprs = nullptr);
 //! group_combine: merges the windows, in ascending order, into the table
 hipError_t LaunchGroupCombine(const GroupProgram& prog, const GroupWindowsOut& in, int64_t n_windows, const GroupTableDev& table,
-                              hipStream_t stream);
+                              hipStream_t stream, const AggExprTable* exprs = nullptr);
 //! launches by this process so far: [0] group_windows, [1] group_combine
 void GroupLaunchCounts(int64_t out[2]);
 

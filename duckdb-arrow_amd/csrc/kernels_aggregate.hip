@@ -1,4 +1,5 @@
-// kernels_aggregate.hip -- K9: up to 8 aggregates (COUNT(*), COUNT, SUM, SUM of a product, MIN, MAX) over decoded vectors,
+// kernels_aggregate.hip -- K9: up to 8 aggregates (COUNT(*), COUNT, SUM, SUM of a product, MIN, MAX, SUM of a product of up
+// to 4 affine factors: kernels_agg_expr.inl) over decoded vectors,
 // under the selection vectors of the pushed-down filter (K6) or over every row (mi_scan_aggregate, mi_aggregate_vectors).
 //
 // agg_windows: one 256-thread workgroup per 2048-row window.  With a selection vector the lanes read sel[0 .. count)
@@ -74,10 +75,13 @@ __device__ __forceinline__ double load_double(const AggColumnDev& c, int64_t row
   return c.width == 4 ? static_cast<double>(GC<float>(c.data)[row]) : GC<double>(c.data)[row];
 }
 
-template <bool HAS_SEL>
-__global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram prog, const mi_sel_t* __restrict__ sel_p,
-                                                             const uint32_t* __restrict__ sel_count_p, int64_t nrows,
-                                                             Partial* __restrict__ partials_p) {
+#include "kernels_agg_expr.inl"
+
+// The kernel's text, once.  EXPR: the program may hold kOpSumExpr aggregates and `exprs` is their table; without it the
+// branch is not compiled and `exprs` not looked at, so agg_windows<HAS_SEL> below is the kernel it was before expressions.
+template <bool HAS_SEL, bool EXPR>
+__device__ __forceinline__ void agg_windows_body(const AggProgram& prog, const AggExprTable* exprs, const mi_sel_t* __restrict__ sel_p,
+                                                 const uint32_t* __restrict__ sel_count_p, int64_t nrows, Partial* __restrict__ partials_p) {
   __shared__ Partial wave_part[kBlockThreads / 64];
   const int64_t window = blockIdx.x;
   const int64_t row0 = window * kTileRows;
@@ -111,6 +115,10 @@ __global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram pr
         p.count++;
         continue;
       }
+      if (EXPR && op == aggmerge::kOpSumExpr) {   // validity, values and the sum: kernels_agg_expr.inl
+        fold_expr_row(exprs->exprs[a], cls, row, &p);
+        continue;
+      }
       bool valid = row_is_valid(d.a.validity, row);
       if (op == aggmerge::kOpSumProduct) valid = valid && row_is_valid(d.b.validity, row);
       if (!valid) continue;
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram pr
           p.lo = aggmerge::BitsOf(p.count ? __dadd_rn(aggmerge::DoubleOf(p.lo), v) : v);
           p.count++;
         } else {
-          aggmerge::Fold(op, cls, &p, aggmerge::CanonicalBits(v), 0ull);
+          aggmerge::Fold<false>(op, cls, &p, aggmerge::CanonicalBits(v), 0ull);
         }
       } else {
         uint64_t lo, hi;
@@ -140,7 +148,7 @@ __global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram pr
           aggmerge::Add128(&p.lo, &p.hi, lo, hi);
           p.count++;
         } else {
-          aggmerge::Fold(op, cls, &p, lo, hi);
+          aggmerge::Fold<false>(op, cls, &p, lo, hi);
         }
       }
     }
@@ -153,18 +161,33 @@ __global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram pr
       o.hi = __shfl_down(p.hi, dist, 64);
       o.count = __shfl_down(p.count, dist, 64);
       o.flags = __shfl_down(p.flags, dist, 64);
-      if (lane + dist < 64) aggmerge::Merge(op, cls, &p, o);
+      if (lane + dist < 64) aggmerge::Merge<EXPR>(op, cls, &p, o);
     }
     if (lane == 0) wave_part[wave] = p;
     __syncthreads();
     if (threadIdx.x == 0) {
       Partial q = wave_part[0];
 #pragma unroll
-      for (int k = 1; k < kBlockThreads / 64; k++) aggmerge::Merge(op, cls, &q, wave_part[k]);
+      for (int k = 1; k < kBlockThreads / 64; k++) aggmerge::Merge<EXPR>(op, cls, &q, wave_part[k]);
       store_partial(partials + a, q);
     }
     __syncthreads();   // wave_part is written again by the next aggregate
   }
+}
+
+template <bool HAS_SEL>
+__global__ __launch_bounds__(kBlockThreads) void agg_windows(const AggProgram prog, const mi_sel_t* __restrict__ sel_p,
+                                                             const uint32_t* __restrict__ sel_count_p, int64_t nrows,
+                                                             Partial* __restrict__ partials_p) {
+  agg_windows_body<HAS_SEL, false>(prog, nullptr, sel_p, sel_count_p, nrows, partials_p);
+}
+
+// launched only for a program that holds a kOpSumExpr: the expression table rides behind the arguments of agg_windows
+template <bool HAS_SEL>
+__global__ __launch_bounds__(kBlockThreads) void agg_windows_expr(const AggProgram prog, const mi_sel_t* __restrict__ sel_p,
+                                                                  const uint32_t* __restrict__ sel_count_p, int64_t nrows,
+                                                                  Partial* __restrict__ partials_p, const AggExprTable exprs) {
+  agg_windows_body<HAS_SEL, true>(prog, &exprs, sel_p, sel_count_p, nrows, partials_p);
 }
 
 // ops / classes: 4 bits per aggregate (a lane picks its own: no indexing of the kernel argument by a lane's number)
@@ -179,7 +202,7 @@ __global__ __launch_bounds__(64) void agg_combine(uint32_t ops, uint32_t classes
 #pragma unroll 4
   for (int64_t w = 0; w < n_windows; w++) {
     const Partial q = load_partial(partials + (w * n_aggs + a));
-    aggmerge::Merge(op, cls, &p, q);
+    aggmerge::Merge<false>(op, cls, &p, q);
   }
   store_partial(acc + a, p);
 }
@@ -206,11 +229,39 @@ void AggLaunchCounts(int64_t out[2]) {
   out[1] = g_agg_launches[1].load();
 }
 
-bool AggProgramIsValid(const AggProgram& prog) {
+namespace {
+// a kOpSumExpr: 1 .. 4 factors, at least one column; every column factor has data and a width of its class, none of 16 bytes;
+// all integer-like or all floating point, and aggs[a].a is the first column factor's column
+bool ExprOk(const AggDescDev& d, const AggExprDev& e) {
+  if (e.n_factors < 1 || e.n_factors > aggmerge::kMaxExprFactors) return false;
+  int columns = 0;
+  for (int f = 0; f < e.n_factors; f++) {
+    const AggColumnDev& c = e.factors[f].col;
+    if (c.cls == aggmerge::kClassAny) continue;   // a constant
+    if (c.cls == aggmerge::kClassWide || !ColumnOk(c, true)) return false;
+    if (columns == 0 && (c.data != d.a.data || c.validity != d.a.validity || c.width != d.a.width || c.cls != d.a.cls)) return false;
+    if ((c.cls == aggmerge::kClassFloat) != (d.a.cls == aggmerge::kClassFloat)) return false;
+    columns++;
+  }
+  return columns > 0;
+}
+}  // namespace
+
+bool AggProgramHasExpr(const AggProgram& prog) {
+  for (int a = 0; a < prog.n_aggs && a < aggmerge::kMaxAggregates; a++)
+    if (prog.aggs[a].op == aggmerge::kOpSumExpr) return true;
+  return false;
+}
+
+bool AggProgramIsValid(const AggProgram& prog, const AggExprTable* exprs) {
   if (prog.n_aggs < 1 || prog.n_aggs > aggmerge::kMaxAggregates) return false;
   for (int a = 0; a < prog.n_aggs; a++) {
     const AggDescDev& d = prog.aggs[a];
-    if (d.op < aggmerge::kOpCountStar || d.op > aggmerge::kOpMax) return false;
+    if (d.op < aggmerge::kOpCountStar || d.op > aggmerge::kOpSumExpr) return false;
+    if (d.op == aggmerge::kOpSumExpr) {
+      if (!exprs || !ExprOk(d, exprs->exprs[a])) return false;
+      continue;
+    }
     const bool values = d.op != aggmerge::kOpCountStar && d.op != aggmerge::kOpCount;
     if (!ColumnOk(d.a, values)) return false;
     if (d.op == aggmerge::kOpSum && d.a.cls == aggmerge::kClassWide) return false;
@@ -223,27 +274,31 @@ bool AggProgramIsValid(const AggProgram& prog) {
 }
 
 hipError_t LaunchAggWindows(const AggProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
-                            aggmerge::Partial* d_partials, hipStream_t stream) {
+                            aggmerge::Partial* d_partials, hipStream_t stream, const AggExprTable* exprs) {
   MI_DROP_STALE_ERROR();
   if (nrows <= 0) return hipSuccess;
-  if (!AggProgramIsValid(prog) || (sel == nullptr) != (sel_count == nullptr) || !d_partials) return hipErrorInvalidValue;
+  if (!AggProgramIsValid(prog, exprs) || (sel == nullptr) != (sel_count == nullptr) || !d_partials) return hipErrorInvalidValue;
   const int64_t windows = (nrows + kTileRows - 1) / kTileRows;
   if (windows > 0x7FFFFFFFll) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>(windows)), block(kBlockThreads);
-  if (sel) hipLaunchKernelGGL(agg_windows<true>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials);
+  if (AggProgramHasExpr(prog)) {
+    if (sel) hipLaunchKernelGGL(agg_windows_expr<true>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials, *exprs);
+    else hipLaunchKernelGGL(agg_windows_expr<false>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials, *exprs);
+  } else if (sel) hipLaunchKernelGGL(agg_windows<true>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials);
   else hipLaunchKernelGGL(agg_windows<false>, grid, block, 0, stream, prog, sel, sel_count, nrows, d_partials);
   g_agg_launches[0]++;
   return hipGetLastError();
 }
 
 hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_partials, int64_t n_windows, aggmerge::Partial* d_acc,
-                            hipStream_t stream) {
+                            hipStream_t stream, const AggExprTable* exprs) {
   MI_DROP_STALE_ERROR();
   if (n_windows <= 0) return hipSuccess;
-  if (!AggProgramIsValid(prog) || !d_partials || !d_acc) return hipErrorInvalidValue;
+  if (!AggProgramIsValid(prog, exprs) || !d_partials || !d_acc) return hipErrorInvalidValue;
   uint32_t ops = 0, classes = 0;
   for (int a = 0; a < prog.n_aggs; a++) {
-    ops |= static_cast<uint32_t>(prog.aggs[a].op) << (4 * a);
+    const int op = prog.aggs[a].op == aggmerge::kOpSumExpr ? aggmerge::kOpSum : prog.aggs[a].op;   // partials of either merge as sums
+    ops |= static_cast<uint32_t>(op) << (4 * a);
     classes |= static_cast<uint32_t>(prog.aggs[a].a.cls) << (4 * a);
   }
   hipLaunchKernelGGL(agg_combine, dim3(1), dim3(64), 0, stream, ops, classes, prog.n_aggs, d_partials, n_windows, d_acc);

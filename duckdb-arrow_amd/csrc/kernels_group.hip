@@ -1,5 +1,5 @@
 // kernels_group.hip -- K10: GROUP BY over decoded vectors (mi_scan_group_aggregate, mi_group_aggregate_vectors): up to 4
-// key columns, up to 8 aggregates of K9's kinds per group, under the selection vectors of the pushed-down filter (K6) or
+// key columns, up to 8 aggregates of K9's kinds (the expression sum of kernels_agg_expr.inl included) per group, under the selection vectors of the pushed-down filter (K6) or
 // over every row.  Scope: few groups -- at most groupkey::kWindowLimit distinct keys among the selected rows of one
 // 2048-row window, groupkey::kMaxGroups in a scan; more raises MI_ST_GROUP_LIMIT.  The rules of a key are group_key.hpp,
 // the rules of a merge agg_merge.hpp, both shared with the host.
@@ -112,7 +112,7 @@ __device__ __forceinline__ void fold_row(const AggDescDev& d, int op, int cls, i
       p->lo = aggmerge::BitsOf(p->count ? __dadd_rn(aggmerge::DoubleOf(p->lo), v) : v);
       p->count++;
     } else {
-      aggmerge::Fold(op, cls, p, aggmerge::CanonicalBits(v), 0ull);
+      aggmerge::Fold<false>(op, cls, p, aggmerge::CanonicalBits(v), 0ull);
     }
   } else {
     uint64_t lo, hi;
@@ -129,10 +129,12 @@ __device__ __forceinline__ void fold_row(const AggDescDev& d, int op, int cls, i
       aggmerge::Add128(&p->lo, &p->hi, lo, hi);
       p->count++;
     } else {
-      aggmerge::Fold(op, cls, p, lo, hi);
+      aggmerge::Fold<false>(op, cls, p, lo, hi);
     }
   }
 }
+
+#include "kernels_agg_expr.inl"
 
 // one part of the key of `row`: 0, MI_ST_GROUP_KEY_LONG for a string that has no inline image, or kPartNull
 constexpr uint32_t kPartNull = 1u;
@@ -161,10 +163,11 @@ __device__ __forceinline__ uint32_t load_key_part(const GroupKeyColumnDev& c, in
   return 0;
 }
 
-template <bool HAS_SEL>
-__global__ __launch_bounds__(kBlockThreads) void group_windows(const GroupProgram prog, const mi_sel_t* __restrict__ sel_p,
-                                                               const uint32_t* __restrict__ sel_count_p, int64_t nrows,
-                                                               const GroupWindowsOut out) {
+// The kernel's text, once.  EXPR: the program may hold kOpSumExpr aggregates and `exprs` is their table; without it the
+// branch is not compiled and `exprs` not looked at, so group_windows<HAS_SEL> below is the kernel it was before expressions.
+template <bool HAS_SEL, bool EXPR>
+__device__ __forceinline__ void group_windows_body(const GroupProgram& prog, const AggExprTable* exprs, const mi_sel_t* __restrict__ sel_p,
+                                                   const uint32_t* __restrict__ sel_count_p, int64_t nrows, const GroupWindowsOut& out) {
   extern __shared__ __attribute__((aligned(16))) uint64_t s_keys[];   // [kWinSlots][n_keys]{lo, hi}
   __shared__ uint32_t s_tag[kWinSlots];          // 0: free, else 0x100 | the key's NULL bits
   __shared__ uint32_t s_sort[kTileRows];         // slot << 11 | row in window; kNoRow behind the selected rows
@@ -341,7 +344,12 @@ __global__ __launch_bounds__(kBlockThreads) void group_windows(const GroupProgra
     for (uint32_t g = wave; g < n_local; g += kBlockThreads / 64) {
       const uint32_t begin = s_start[g], end = s_start[g + 1];
       Partial p = {0ull, 0ull, 0ull, 0ull};
-      for (uint32_t j = begin + lane; j < end; j += 64) fold_row(d, op, cls, row0 + (s_sort[j] & (kTileRows - 1)), &p);
+      if (EXPR && op == aggmerge::kOpSumExpr) {   // validity, values and the sum: kernels_agg_expr.inl
+        const AggExprDev& e = exprs->exprs[a];
+        for (uint32_t j = begin + lane; j < end; j += 64) fold_expr_row(e, cls, row0 + (s_sort[j] & (kTileRows - 1)), &p);
+      } else {
+        for (uint32_t j = begin + lane; j < end; j += 64) fold_row(d, op, cls, row0 + (s_sort[j] & (kTileRows - 1)), &p);
+      }
 #pragma unroll
       for (int dist = 32; dist >= 1; dist >>= 1) {   // as agg_windows: lane l takes lane l + dist while that lane exists
         Partial o;
@@ -349,11 +357,26 @@ __global__ __launch_bounds__(kBlockThreads) void group_windows(const GroupProgra
         o.hi = __shfl_down(p.hi, dist, 64);
         o.count = __shfl_down(p.count, dist, 64);
         o.flags = __shfl_down(p.flags, dist, 64);
-        if (lane + dist < 64) aggmerge::Merge(op, cls, &p, o);
+        if (lane + dist < 64) aggmerge::Merge<EXPR>(op, cls, &p, o);
       }
       if (lane == 0) store_partial(partials + (static_cast<size_t>(g) * n_aggs + a), p);
     }
   }
+}
+
+template <bool HAS_SEL>
+__global__ __launch_bounds__(kBlockThreads) void group_windows(const GroupProgram prog, const mi_sel_t* __restrict__ sel_p,
+                                                               const uint32_t* __restrict__ sel_count_p, int64_t nrows,
+                                                               const GroupWindowsOut out) {
+  group_windows_body<HAS_SEL, false>(prog, nullptr, sel_p, sel_count_p, nrows, out);
+}
+
+// launched only for a program that holds a kOpSumExpr: the expression table rides behind the arguments of group_windows
+template <bool HAS_SEL>
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void group_windows_expr(const GroupProgram prog, const mi_sel_t* __restrict__ sel_p,
+                                                                    const uint32_t* __restrict__ sel_count_p, int64_t nrows,
+                                                                    const GroupWindowsOut out, const AggExprTable exprs) {
+  group_windows_body<HAS_SEL, true>(prog, &exprs, sel_p, sel_count_p, nrows, out);
 }
 
 __device__ __forceinline__ uint32_t slot_load(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -452,7 +475,7 @@ __global__ __launch_bounds__(kBlockThreads) void group_combine(int32_t n_keys, i
       const int op = static_cast<int>((ops >> (4 * a)) & 15u), cls = static_cast<int>((classes >> (4 * a)) & 15u);
       gptr<Partial> rec = acc + (static_cast<size_t>(s_gidx[t]) * n_aggs + a);
       Partial into = load_partial(rec);
-      aggmerge::Merge(op, cls, &into, load_partial(wparts + p));
+      aggmerge::Merge<false>(op, cls, &into, load_partial(wparts + p));
       store_partial(rec, into);
     }
     __syncthreads();   // the next window may meet the same groups, and writes s_gidx again
@@ -484,11 +507,11 @@ void GroupLaunchCounts(int64_t out[2]) {
   out[1] = g_group_launches[1].load();
 }
 
-bool GroupProgramIsValid(const GroupProgram& prog) {
+bool GroupProgramIsValid(const GroupProgram& prog, const AggExprTable* exprs) {
   if (prog.n_keys < 1 || prog.n_keys > groupkey::kMaxKeys) return false;
   for (int k = 0; k < prog.n_keys; k++)
     if (!KeyColumnOk(prog.keys[k])) return false;
-  return AggProgramIsValid(prog.aggs);
+  return AggProgramIsValid(prog.aggs, exprs);
 }
 
 size_t GroupWindowsBytes(int64_t n_windows, int n_keys, int n_aggs) {
@@ -539,29 +562,33 @@ hipError_t GroupTableClear(void* base, int n_keys, int n_aggs, hipStream_t strea
 }
 
 hipError_t LaunchGroupWindows(const GroupProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
-                              const GroupWindowsOut& out, hipStream_t stream) {
+                              const GroupWindowsOut& out, hipStream_t stream, const AggExprTable* exprs) {
   MI_DROP_STALE_ERROR();
   if (nrows <= 0) return hipSuccess;
-  if (!GroupProgramIsValid(prog) || (sel == nullptr) != (sel_count == nullptr) || !out.heads || !out.keys || !out.nulls || !out.partials)
+  if (!GroupProgramIsValid(prog, exprs) || (sel == nullptr) != (sel_count == nullptr) || !out.heads || !out.keys || !out.nulls || !out.partials)
     return hipErrorInvalidValue;
   const int64_t windows = (nrows + kTileRows - 1) / kTileRows;
   if (windows > 0x7FFFFFFFll) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>(windows)), block(kBlockThreads);
   const size_t lds = static_cast<size_t>(kWinSlots) * static_cast<size_t>(prog.n_keys) * 16;
-  if (sel) hipLaunchKernelGGL(group_windows<true>, grid, block, lds, stream, prog, sel, sel_count, nrows, out);
+  if (AggProgramHasExpr(prog.aggs)) {
+    if (sel) hipLaunchKernelGGL(group_windows_expr<true>, grid, block, lds, stream, prog, sel, sel_count, nrows, out, *exprs);
+    else hipLaunchKernelGGL(group_windows_expr<false>, grid, block, lds, stream, prog, sel, sel_count, nrows, out, *exprs);
+  } else if (sel) hipLaunchKernelGGL(group_windows<true>, grid, block, lds, stream, prog, sel, sel_count, nrows, out);
   else hipLaunchKernelGGL(group_windows<false>, grid, block, lds, stream, prog, sel, sel_count, nrows, out);
   g_group_launches[0]++;
   return hipGetLastError();
 }
 
 hipError_t LaunchGroupCombine(const GroupProgram& prog, const GroupWindowsOut& in, int64_t n_windows, const GroupTableDev& table,
-                              hipStream_t stream) {
+                              hipStream_t stream, const AggExprTable* exprs) {
   MI_DROP_STALE_ERROR();
   if (n_windows <= 0) return hipSuccess;
-  if (!GroupProgramIsValid(prog) || !in.heads || !table.head) return hipErrorInvalidValue;
+  if (!GroupProgramIsValid(prog, exprs) || !in.heads || !table.head) return hipErrorInvalidValue;
   uint32_t ops = 0, classes = 0;
   for (int a = 0; a < prog.aggs.n_aggs; a++) {
-    ops |= static_cast<uint32_t>(prog.aggs.aggs[a].op) << (4 * a);
+    const int op = prog.aggs.aggs[a].op == aggmerge::kOpSumExpr ? aggmerge::kOpSum : prog.aggs.aggs[a].op;   // partials of either merge as sums
+    ops |= static_cast<uint32_t>(op) << (4 * a);
     classes |= static_cast<uint32_t>(prog.aggs.aggs[a].a.cls) << (4 * a);
   }
   hipLaunchKernelGGL(group_combine, dim3(1), dim3(kBlockThreads), 0, stream, prog.n_keys, prog.aggs.n_aggs, ops, classes, in, n_windows, table);

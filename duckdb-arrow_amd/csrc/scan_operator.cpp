@@ -556,10 +556,15 @@ void ArrowScan::EnqueueBatch(Slot& s) {
     }
   }
   if (aggn.on) {   // refused before anything of this record batch is queued on the GPU
-    for (const auto& a : aggn.aggs)
-      for (const int32_t c : {a.col_a, a.col_b})
-        if (c >= 0 && src.out_to_file_column[static_cast<size_t>(c)] < 0)
-          throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
+    auto present = [&](int32_t c) {
+      if (c >= 0 && src.out_to_file_column[static_cast<size_t>(c)] < 0)
+        throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
+    };
+    for (const auto& a : aggn.aggs) {
+      present(a.col_a);
+      present(a.col_b);
+      for (const auto& f : a.factors) present(f.col);
+    }
     for (const auto& k : aggn.keys)
       if (src.out_to_file_column[static_cast<size_t>(k.col)] < 0)
         throw InvalidInputException("GROUP BY column '" + out_columns[static_cast<size_t>(k.col)].name + "' is absent from a file of the scan");
@@ -1352,8 +1357,35 @@ const char* AggOpName(int32_t op) {
     case aggmerge::kOpSumProduct: return "SUM_PRODUCT";
     case aggmerge::kOpMin: return "MIN";
     case aggmerge::kOpMax: return "MAX";
+    case aggmerge::kOpSumExpr: return "SUM_EXPR";
     default: return "?";
   }
+}
+
+void ExprFactorConstants(const std::string& what, bool is_float, int32_t constants, int64_t mul, int64_t add, double fmul, double fadd,
+                         uint64_t* mul_bits, uint64_t* add_bits) {
+  if (constants != MI_AGG_CONST_INT && constants != MI_AGG_CONST_DOUBLE)
+    throw InvalidInputException(what + ": constants must be MI_AGG_CONST_INT or MI_AGG_CONST_DOUBLE, not " + std::to_string(constants));
+  if (!is_float) {
+    if (constants == MI_AGG_CONST_DOUBLE)
+      throw NotImplementedException(what + ": double constants on an expression over integer-like columns are not computed in the scan (give int64 constants)");
+    *mul_bits = static_cast<uint64_t>(mul);
+    *add_bits = static_cast<uint64_t>(add);
+    return;
+  }
+  if (constants == MI_AGG_CONST_INT) {
+    // exact when the double, which then lies inside int64's range, converts back to the same integer
+    auto exact = [&](int64_t v) {
+      const double d = static_cast<double>(v);
+      if (!(d >= -9223372036854775808.0 && d < 9223372036854775808.0) || static_cast<int64_t>(d) != v)
+        throw InvalidInputException(what + ": the integer constant " + std::to_string(v) + " is not exactly representable in a double");
+      return d;
+    };
+    fmul = exact(mul);
+    fadd = exact(add);
+  }
+  *mul_bits = aggmerge::BitsOf(fmul);
+  *add_bits = aggmerge::BitsOf(fadd);
 }
 
 void AggTimingTotals(double out_ms[2]) {
@@ -1393,7 +1425,42 @@ void ArrowScan::BindAggregateSpecs(const std::vector<AggSpec>& specs, const char
       aggn.aggs.push_back(b);
       continue;
     }
-    if (sp.op < aggmerge::kOpCountStar || sp.op > aggmerge::kOpMax) throw InvalidInputException(std::string(api) + ": unknown operation " + std::to_string(sp.op));
+    if (sp.op < aggmerge::kOpCountStar || sp.op > aggmerge::kOpSumExpr) throw InvalidInputException(std::string(api) + ": unknown operation " + std::to_string(sp.op));
+    if (sp.op == aggmerge::kOpSumExpr) {
+      // every named column is validated and classified, then projected once; the class of the first is the expression's
+      if (sp.factors.empty() || sp.factors.size() > static_cast<size_t>(aggmerge::kMaxExprFactors))
+        throw InvalidInputException(std::string(api) + ": SUM_EXPR takes 1 to " + std::to_string(aggmerge::kMaxExprFactors) + " factors, not " + std::to_string(sp.factors.size()));
+      const ScanColumn* first = nullptr;
+      for (const AggFactorSpec& f : sp.factors) {
+        if (!f.has_column) continue;
+        const ScanColumn& c = AggregateColumn(f.column, AggOpName(sp.op));
+        const int32_t cls = AggClassOf(c);
+        if (cls == aggmerge::kClassAny || cls == aggmerge::kClassWide)
+          throw NotImplementedException(std::string(AggOpName(sp.op)) + " on column '" + f.column + "' (" + c.field.DuckType() + "): a factor is an integer, DATE, TIME / "
+                                        "TIMESTAMP, DECIMAL(<=18), FLOAT or DOUBLE column");
+        if (!first) {
+          first = &c;
+          b.cls = cls;
+        } else if ((b.cls == aggmerge::kClassFloat) != (cls == aggmerge::kClassFloat)) {
+          throw NotImplementedException(std::string(AggOpName(sp.op)) + " of '" + first->name + "' (" + first->field.DuckType() + ") and '" + f.column + "' (" + c.field.DuckType() +
+                                        "): both factors must be integer-like or both floating point");
+        }
+      }
+      if (!first) throw InvalidInputException(std::string(api) + ": SUM_EXPR needs at least one factor with a column");
+      for (const AggFactorSpec& f : sp.factors) {
+        AggregateState::Bound::Factor fb;
+        ExprFactorConstants(std::string(AggOpName(sp.op)) + (f.has_column ? " on column '" + f.column + "'" : std::string(" constant factor")), b.cls == aggmerge::kClassFloat,
+                            f.constants, f.mul, f.add, f.fmul, f.fadd, &fb.mul, &fb.add);
+        if (f.has_column) {
+          fb.cls = AggClassOf(AggregateColumn(f.column, AggOpName(sp.op)));
+          fb.col = SlotOf(proj, f.column);
+          if (b.col_a < 0) b.col_a = fb.col;
+        }
+        b.factors.push_back(fb);
+      }
+      aggn.aggs.push_back(b);
+      continue;
+    }
     const ScanColumn& ca = AggregateColumn(sp.a, AggOpName(sp.op));
     if (sp.op != aggmerge::kOpCount) {
       b.cls = AggClassOf(ca);
@@ -1630,6 +1697,8 @@ void ArrowScan::EnqueueAggregates(Slot& s) {
   device::GroupProgram gprog;
   std::memset(&gprog, 0, sizeof(gprog));
   device::AggProgram& prog = gprog.aggs;
+  device::AggExprTable exprs_table;   // (filled, and handed to the launches, only when an aggregate is an expression)
+  const device::AggExprTable* exprs = nullptr;
   prog.n_aggs = static_cast<int32_t>(aggn.aggs.size());
   for (size_t a = 0; a < aggn.aggs.size(); a++) {
     const AggregateState::Bound& b = aggn.aggs[a];
@@ -1639,6 +1708,20 @@ void ArrowScan::EnqueueAggregates(Slot& s) {
     d.b.cls = b.cls_b;
     if (b.col_a >= 0) column(b.col_a, &d.a.data, &d.a.validity, &d.a.width);
     if (b.col_b >= 0) column(b.col_b, &d.b.data, &d.b.validity, &d.b.width);
+    if (b.op != aggmerge::kOpSumExpr) continue;
+    if (!exprs) {
+      std::memset(&exprs_table, 0, sizeof(exprs_table));
+      exprs = &exprs_table;
+    }
+    device::AggExprDev& e = exprs_table.exprs[a];
+    e.n_factors = static_cast<int32_t>(b.factors.size());
+    for (size_t f = 0; f < b.factors.size(); f++) {
+      device::AggFactorDev& fd = e.factors[f];
+      fd.mul = b.factors[f].mul;
+      fd.add = b.factors[f].add;
+      fd.col.cls = b.factors[f].cls;
+      if (b.factors[f].col >= 0) column(b.factors[f].col, &fd.col.data, &fd.col.validity, &fd.col.width);
+    }
   }
   const mi_sel_t* sel = has_filter ? reinterpret_cast<const mi_sel_t*>(s.d_out.get() + s.sel_off) : nullptr;
   const uint32_t* sel_count = has_filter ? reinterpret_cast<const uint32_t*>(s.d_out.get() + s.sel_count_off) : nullptr;
@@ -1658,9 +1741,9 @@ void ArrowScan::EnqueueAggregates(Slot& s) {
     Retire(Grow(aggn.d_windows, bytes, GrownCapacity(bytes, aggn.d_windows.size(), 1 << 16)));
     const device::GroupWindowsOut win = device::GroupWindowsAt(aggn.d_windows.get(), n_windows, gprog.n_keys, prog.n_aggs);
     stamp();
-    MI_HIP_CHECK(device::LaunchGroupWindows(gprog, sel, sel_count, n, win, ctx->stream));
+    MI_HIP_CHECK(device::LaunchGroupWindows(gprog, sel, sel_count, n, win, ctx->stream, exprs));
     stamp();
-    MI_HIP_CHECK(device::LaunchGroupCombine(gprog, win, n_windows, device::GroupTableAt(aggn.d_table.get(), gprog.n_keys, prog.n_aggs), ctx->stream));
+    MI_HIP_CHECK(device::LaunchGroupCombine(gprog, win, n_windows, device::GroupTableAt(aggn.d_table.get(), gprog.n_keys, prog.n_aggs), ctx->stream, exprs));
     stamp();
     aggn.rows_scanned += n;
     return;
@@ -1669,9 +1752,9 @@ void ArrowScan::EnqueueAggregates(Slot& s) {
   Retire(Grow(aggn.d_partials, bytes, GrownCapacity(bytes, aggn.d_partials.size(), 1 << 12)));
   aggmerge::Partial* partials = aggn.d_partials.get<aggmerge::Partial>();
   stamp();
-  MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, n, partials, ctx->stream));
+  MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, n, partials, ctx->stream, exprs));
   stamp();
-  MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, aggn.d_acc.get<aggmerge::Partial>(), ctx->stream));
+  MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, aggn.d_acc.get<aggmerge::Partial>(), ctx->stream, exprs));
   stamp();
   aggn.rows_scanned += n;
 }
@@ -1885,7 +1968,27 @@ std::vector<AggSpec> SpecsOf(const char* api, const mi_agg_spec* aggs, int32_t n
   for (int32_t i = 0; i < n_aggs; i++) {
     AggSpec sp;
     sp.op = aggs[i].op;
-    if (sp.op < MI_AGG_COUNT_STAR || sp.op > MI_AGG_MAX) throw InvalidInputException(std::string(api) + ": unknown operation " + std::to_string(sp.op));
+    if (sp.op < MI_AGG_COUNT_STAR || sp.op > MI_AGG_SUM_EXPR) throw InvalidInputException(std::string(api) + ": unknown operation " + std::to_string(sp.op));
+    if (sp.op == MI_AGG_SUM_EXPR) {
+      const mi_agg_expr* e = aggs[i].expr;
+      if (!e) throw InvalidInputException(std::string(api) + ": SUM_EXPR without an expression");
+      if (e->n_factors < 1 || e->n_factors > MI_MAX_EXPR_FACTORS)
+        throw InvalidInputException(std::string(api) + ": SUM_EXPR takes 1 to " + std::to_string(MI_MAX_EXPR_FACTORS) + " factors, not " + std::to_string(e->n_factors));
+      for (int32_t f = 0; f < e->n_factors; f++) {
+        const mi_agg_factor& in = e->factors[f];
+        AggFactorSpec fs;
+        fs.has_column = in.column != nullptr;
+        if (in.column) fs.column = in.column;
+        fs.mul = in.mul;
+        fs.add = in.add;
+        fs.fmul = in.fmul;
+        fs.fadd = in.fadd;
+        fs.constants = in.constants;
+        sp.factors.push_back(std::move(fs));
+      }
+      specs.push_back(std::move(sp));
+      continue;
+    }
     if (sp.op != MI_AGG_COUNT_STAR && !aggs[i].column_a) throw InvalidInputException(std::string(api) + ": " + AggOpName(sp.op) + " without a column");
     if (sp.op == MI_AGG_SUM_PRODUCT && !aggs[i].column_b) throw InvalidInputException(std::string(api) + ": SUM_PRODUCT without a second column");
     if (sp.op != MI_AGG_COUNT_STAR) sp.a = aggs[i].column_a;

@@ -191,10 +191,23 @@ struct DeviceColumnView {
 
 //! One aggregate of mi_scan_aggregate by column name, and what a draining call returns: the accumulators, the value class
 //! each is merged by (aggmerge::kClass*: what the host's merge of several devices needs), the rows seen
+struct AggFactorSpec {
+  bool has_column = false;   // false: the constant `add`
+  std::string column;
+  int64_t mul = 1, add = 0;  // MI_AGG_CONST_INT
+  double fmul = 1.0, fadd = 0.0;   // MI_AGG_CONST_DOUBLE
+  int32_t constants = MI_AGG_CONST_INT;
+};
 struct AggSpec {
   int32_t op = 0;            // aggmerge::kOp*
   std::string a, b;
+  std::vector<AggFactorSpec> factors;   // kOpSumExpr
 };
+//! the constants of one factor as the kernels take them: int64 two's complement for an integer expression, the bits of a
+//! double for a floating-point one.  Double constants on an integer expression are MI_ENOTSUP; integer constants a double
+//! does not hold exactly are MI_EINVAL.  `what` begins the message.
+void ExprFactorConstants(const std::string& what, bool is_float, int32_t constants, int64_t mul, int64_t add, double fmul, double fadd,
+                         uint64_t* mul_bits, uint64_t* add_bits);
 struct AggResult {
   std::vector<aggmerge::Partial> values;
   std::vector<int32_t> classes;
@@ -425,6 +438,11 @@ class ArrowScan : public ScanBase {
       int32_t op = 0, cls = 0;
       int32_t col_a = -1, col_b = -1;        // output columns
       int32_t cls_b = 0;
+      struct Factor {
+        int32_t col = -1, cls = 0;             // output column (-1: a constant), its class
+        uint64_t mul = 0, add = 0;             // as device::AggFactorDev takes them
+      };
+      std::vector<Factor> factors;             // kOpSumExpr; col_a is then the first column factor's column
     };
     std::vector<Bound> aggs;
     struct KeyBound {

@@ -1,10 +1,11 @@
-/* TPC-H Q6 and four more aggregates in one pass over lineitem.arrows, through the C ABI alone: the predicates go to
+/* TPC-H Q6 and five more aggregates in one pass over lineitem.arrows, through the C ABI alone: the predicates go to
  * mi_scan_set_filter, the aggregates to mi_scan_aggregate, and only the results leave the GPU.
  *
  *   gcc -std=c99 -Iinclude examples/agg.c -Lduckdb-arrow_amd -lmi_arrow_ipc -Wl,-rpath,$PWD/duckdb-arrow_amd -o agg
  *   ./agg lineitem.arrows [more files...]
  *
- * SELECT sum(l_extendedprice * l_discount), count(*), min(l_shipdate), max(l_shipdate), sum(l_quantity)
+ * SELECT sum(l_extendedprice * l_discount), count(*), min(l_shipdate), max(l_shipdate), sum(l_quantity),
+ *        sum(l_extendedprice * (1 - l_discount))
  *   FROM read_arrow(files)
  *  WHERE l_shipdate >= DATE '1994-01-01' AND l_shipdate < DATE '1995-01-01'
  *    AND l_discount BETWEEN 0.05 AND 0.07 AND l_quantity < 24
@@ -60,7 +61,18 @@ int main(int argc, char** argv) {
   nodes[5] = leaf(MI_F_LT, "l_quantity", 2400);
   check(mi_scan_set_filter(scan, nodes, 6, 0), "mi_scan_set_filter");
 
-  mi_agg_spec aggs[5];
+  /* an expression: the product of up to four factors add + mul * column over the stored integers; at scale 2,
+   * 1 - l_discount is 100 + (-1) * l_discount */
+  mi_agg_expr net;
+  memset(&net, 0, sizeof(net));
+  net.n_factors = 2;
+  net.factors[0].column = "l_extendedprice";
+  net.factors[0].mul = 1;
+  net.factors[1].column = "l_discount";
+  net.factors[1].mul = -1;
+  net.factors[1].add = 100;
+
+  mi_agg_spec aggs[6];
   memset(aggs, 0, sizeof(aggs));
   aggs[0].op = MI_AGG_SUM_PRODUCT;
   aggs[0].column_a = "l_extendedprice";
@@ -72,9 +84,11 @@ int main(int argc, char** argv) {
   aggs[3].column_a = "l_shipdate";
   aggs[4].op = MI_AGG_SUM;
   aggs[4].column_a = "l_quantity";
-  mi_agg_value v[5];
+  aggs[5].op = MI_AGG_SUM_EXPR;
+  aggs[5].expr = &net;
+  mi_agg_value v[6];
   int64_t scanned = 0, selected = 0;
-  check(mi_scan_aggregate(scan, aggs, 5, v, &scanned, &selected), "mi_scan_aggregate");
+  check(mi_scan_aggregate(scan, aggs, 6, v, &scanned, &selected), "mi_scan_aggregate");
 
   if (v[0].is_null) {
     printf("revenue = NULL  (0 of %" PRId64 " rows pass)\n", scanned);
@@ -87,6 +101,8 @@ int main(int argc, char** argv) {
   printf("count(*) = %" PRIu64 "\n", v[1].lo);
   if (!v[2].is_null) printf("l_shipdate in [%" PRId64 ", %" PRId64 "] days since 1970-01-01\n", (int64_t)v[2].lo, (int64_t)v[3].lo);
   if (!v[4].is_null) printf("sum(l_quantity) = %" PRId64 ".%02" PRId64 " over %" PRId64 " rows\n", (int64_t)v[4].lo / 100, (int64_t)v[4].lo % 100, v[4].count);
+  if (!v[5].is_null && (v[5].hi == 0 || v[5].hi == -1))
+    printf("sum(l_extendedprice * (1 - l_discount)) = %" PRId64 ".%04" PRId64 "\n", (int64_t)v[5].lo / 10000, (int64_t)v[5].lo % 10000);
   mi_scan_close(scan);
   mi_ctx_destroy(ctx);
   return 0;

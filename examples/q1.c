@@ -10,9 +10,9 @@
  *  WHERE l_shipdate <= DATE '1998-09-02'
  *  GROUP BY l_returnflag, l_linestatus ORDER BY l_returnflag, l_linestatus
  *
- * Q1's sum_disc_price = sum(price * (1 - discount)) comes from the two sums printed here: sum(price) - sum(price *
- * discount).  Its sum_charge = sum(price * (1 - discount) * (1 + tax)) needs the three-factor product sum(price *
- * discount * tax), which the scan does not compute: that stays out of scope.
+ * This is the shape of Q1 with every kind of aggregate in it (sums, products, a count, a minimum, a maximum, a COUNT of
+ * a string column).  Q1 itself, whole -- sum_disc_price = sum(price * (1 - discount)), sum_charge = sum(price * (1 -
+ * discount) * (1 + tax)) and the three averages, in one call -- is examples/q1_full.c, through MI_AGG_SUM_EXPR.
  */
 #include <inttypes.h>
 #include <stdio.h>

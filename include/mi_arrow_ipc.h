@@ -829,6 +829,33 @@ int mi_writer_fused_counts(int64_t* row_groups, int64_t* view_columns);
  *                       order (NaN greatest, -0.0 = +0.0); -0.0 comes back as +0.0, any NaN as the quiet NaN
  *                       0x7FF8000000000000.  HUGEINT / DECIMAL(19..38): `upper` signed, then `lower` unsigned.  No
  *                       contributor: NULL.
+ *   MI_AGG_SUM_EXPR     SUM( f_0 * f_1 * ... * f_{F-1} ) over the selected rows, 1 <= F <= MI_MAX_EXPR_FACTORS.  A factor is
+ *                       add + mul * column, or the constant add (no column); at least one factor names a column, and
+ *                       the same column may appear in several factors.  TPC-H's revenue expression
+ *                       l_extendedprice * (1 - l_discount) * (1 + l_tax) over DECIMAL(., 2) columns is the three factors
+ *                       {l_extendedprice}, {100 + (-1) * l_discount}, {100 + 1 * l_tax} (a sum at scale 6); sum(x * x) is
+ *                       {x}, {x}; a constant factor rescales a sum.
+ *                       A row contributes when every column a factor names is not NULL in that row; `count` is the number
+ *                       of contributing rows and count == 0 is NULL, as for SUM.  (An average is the caller's division of
+ *                       a sum by its count: there is no AVG operation.)
+ *                       Integer expressions -- every named column integer-like, the classes SUM takes, signed and
+ *                       unsigned: each value is sign- or zero-extended to 128 bits, mul and add (int64) are sign-extended,
+ *                       and the factor, the product and the sum are computed modulo 2^128 in unsigned arithmetic.
+ *                       Overflow is not detected, as for MI_AGG_SUM_PRODUCT: the caller bounds
+ *                       rows * max|f_0| * ... * max|f_{F-1}| below 2^127.
+ *                       Floating-point expressions -- every named column FLOAT, float16 or DOUBLE, widened to double: the
+ *                       constants are doubles, a factor is (mul * v) + add with each operation rounded once; a mul of
+ *                       exactly 1.0 skips the multiplication and an add of exactly +0.0 the addition, so a plain column
+ *                       is its value bit for bit (-0.0 included).  The product is taken left to right, each step rounded
+ *                       once, never fused; the sum is folded exactly as SUM's is.  MI_AGG_CONST_INT constants are converted,
+ *                       and MI_EINVAL if a double does not hold them exactly.
+ *                       SUM_EXPR[a] equals SUM(a) and SUM_EXPR[a, b] equals SUM_PRODUCT(a, b) bit for bit, double sums
+ *                       included.  The value's kind is INT128 or DOUBLE by the expression's class.
+ *                       MI_ENOTSUP: integer-like and floating-point columns mixed in one expression (naming both),
+ *                       MI_AGG_CONST_DOUBLE constants on an integer expression, and -- naming the column -- a 128-bit
+ *                       (HUGEINT, DECIMAL(19..38)), BOOLEAN, string, interval, nested, dictionary-encoded or constant
+ *                       (filename / hive) factor column.  MI_EINVAL: F outside 1 .. 4, no factor with a column, a NULL
+ *                       `expr`, an unknown column, a column that a file of the scan lacks.
  * BOOLEAN, strings, intervals and nested types under SUM / MIN / MAX, and SUM over a 128-bit column, are MI_ENOTSUP with
  * a message that names the column and the operation; an unknown column, more than 8 aggregates and a call after init are
  * MI_EINVAL, as is an aggregate column that a file of the scan lacks (union_by_name).
@@ -841,15 +868,35 @@ enum mi_agg_op {
   MI_AGG_SUM = 3,          /* column_a */
   MI_AGG_SUM_PRODUCT = 4,  /* column_a * column_b */
   MI_AGG_MIN = 5,          /* column_a */
-  MI_AGG_MAX = 6           /* column_a */
+  MI_AGG_MAX = 6,          /* column_a */
+  MI_AGG_SUM_EXPR = 7      /* expr; column_a / column_b are ignored */
 };
 #define MI_MAX_AGGREGATES 8
+#define MI_MAX_EXPR_FACTORS 4
+enum mi_agg_constants {
+  MI_AGG_CONST_INT = 0,    /* mul / add hold the factor's constants */
+  MI_AGG_CONST_DOUBLE = 1  /* fmul / fadd do */
+};
+typedef struct mi_agg_factor {
+  const char* column;      /* NULL: the constant `add` (or fadd) */
+  int64_t mul, add;        /* a plain column is mul = 1, add = 0 */
+  double fmul, fadd;
+  int32_t constants;       /* enum mi_agg_constants */
+  int32_t reserved0;
+} mi_agg_factor;
+typedef struct mi_agg_expr {
+  int32_t n_factors;       /* 1 .. MI_MAX_EXPR_FACTORS */
+  int32_t reserved0;
+  mi_agg_factor factors[MI_MAX_EXPR_FACTORS];
+} mi_agg_expr;
 typedef struct mi_agg_spec {
   int32_t op;              /* enum mi_agg_op */
   int32_t reserved0;
   const char* column_a;
   const char* column_b;    /* MI_AGG_SUM_PRODUCT */
-  int64_t reserved[2];     /* zero */
+  const mi_agg_expr* expr; /* MI_AGG_SUM_EXPR; ignored by every other operation (the library is 64-bit only: the pointer fills
+                              what was the first of two reserved words) */
+  int64_t reserved[1];     /* zero */
 } mi_agg_spec;
 enum mi_agg_value_kind {
   MI_AGG_VALUE_INT128 = 0, /* lo / hi: a 128-bit two's-complement integer (counts, integer sums, integer and 128-bit MIN / MAX) */
@@ -884,11 +931,24 @@ typedef struct mi_agg_column {
   int32_t width;
   int32_t value_class;       /* enum mi_agg_value_class */
 } mi_agg_column;
+typedef struct mi_agg_vector_factor {
+  mi_agg_column column;      /* data NULL and value_class MI_AGG_CLASS_ANY: the constant `add` (or fadd) */
+  int64_t mul, add;
+  double fmul, fadd;
+  int32_t constants;         /* enum mi_agg_constants */
+  int32_t reserved0;
+} mi_agg_vector_factor;
+typedef struct mi_agg_vector_expr {
+  int32_t n_factors;         /* 1 .. MI_MAX_EXPR_FACTORS */
+  int32_t reserved0;
+  mi_agg_vector_factor factors[MI_MAX_EXPR_FACTORS];
+} mi_agg_vector_expr;
 typedef struct mi_agg_vector_spec {
   int32_t op;                /* enum mi_agg_op */
   int32_t reserved0;
-  mi_agg_column a, b;        /* b: the second factor of MI_AGG_SUM_PRODUCT */
-  int64_t reserved[2];
+  mi_agg_column a, b;        /* b: the second factor of MI_AGG_SUM_PRODUCT; MI_AGG_SUM_EXPR ignores both */
+  const mi_agg_vector_expr* expr;   /* MI_AGG_SUM_EXPR; ignored by every other operation */
+  int64_t reserved[1];
 } mi_agg_vector_spec;
 int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel, const uint32_t* sel_count,
                          int64_t nrows, mi_agg_value* out /* [n_aggs] */, void* stream);
@@ -902,7 +962,8 @@ int mi_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, d
  * Grouped fused aggregates (an ABI extension, as mi_scan_aggregate is):
  *   SELECT k_1 .. k_m, agg_1 .. agg_n FROM scan WHERE <the filter that was set> GROUP BY k_1 .. k_m
  * with 1 <= m <= MI_MAX_GROUP_KEYS and 1 <= n <= MI_MAX_AGGREGATES, for FEW groups: at most MI_GROUP_WINDOW_LIMIT distinct
- * keys among the selected rows of one 2048-row window and MI_MAX_GROUPS in a scan (TPC-H Q1, `group by fruit`); it is not
+ * keys among the selected rows of one 2048-row window and MI_MAX_GROUPS in a scan (TPC-H Q1 -- whole, its three-factor
+ * sum_charge through MI_AGG_SUM_EXPR: examples/q1.c -- or `group by fruit`); it is not
  * a general hash aggregate.  The aggregates, their classes, their NULL rule and their arithmetic are exactly those of
  * mi_scan_aggregate, per group.
  * Key columns are top-level columns the scan decodes to an integer-like vector of 1 / 2 / 4 / 8 bytes (the integers, BOOLEAN

@@ -3,13 +3,17 @@
 l_returnflag, l_linestatus, eight aggregates, l_shipdate <= 1998-09-02 -- over lineitem SF as 8 files, device-resident scan, one
 process, against the ungrouped call with the same eight aggregates and the same filter; the variants alternate, --runs runs each
 after one warm-up, MI_AGG_TIMING=1 (wall time per run, device time per launch of the kernels).  Then the window-limit case: a
-synthetic table whose every 2048-row window holds 256 distinct keys, grouped and ungrouped.  Prints one JSON line."""
+synthetic table whose every 2048-row window holds 256 distinct keys, grouped and ungrouped.  --q1 adds a third variant to the
+first part, alternating with the other two: TPC-H Q1 whole, the same keys and filter with Q1's own six aggregates, two of them
+expression sums of two and three factors (MI_AGG_SUM_EXPR).  Prints one JSON line."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["MI_AGG_TIMING"] = "1"
 
 AGGS = [("sum", "l_quantity"), ("sum", "l_extendedprice"), ("sum_product", "l_extendedprice", "l_discount"), ("sum_product", "l_extendedprice", "l_tax"),
         ("count_star",), ("min", "l_shipdate"), ("max", "l_shipdate"), ("count", "l_comment")]
+Q1_AGGS = [("sum", "l_quantity"), ("sum", "l_extendedprice"), ("sum_expr", "l_extendedprice", ("l_discount", -1, 100)),
+           ("sum_expr", "l_extendedprice", ("l_discount", -1, 100), ("l_tax", 1, 100)), ("sum", "l_discount"), ("count_star",)]
 KEYS = ["l_returnflag", "l_linestatus"]
 CUTOFF = 10471      # DATE '1998-09-02'
 
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--dir", default="/dev/shm")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--limit-rows", type=int, default=122880 * 130)
+    ap.add_argument("--q1", action="store_true", help="also run TPC-H Q1 whole: six aggregates, two of them expression sums")
     args = ap.parse_args()
     import numpy as np
     import pyarrow as pa
@@ -71,8 +76,12 @@ def main():
         con = da.Connection(0)
         expr = ("l_shipdate", "<=", CUTOFF)
         make = lambda: con.read_arrow(paths, device_resident=True).filter(expr)
-        q1 = alternate({"ungrouped": (make, lambda r: r.aggregate(AGGS, detail=True), da.aggregate_counters),
-                        "grouped": (make, lambda r: r.group_aggregate(KEYS, AGGS, detail=True), da.group_aggregate_counters)}, args.runs)
+        variants = {"ungrouped": (make, lambda r: r.aggregate(AGGS, detail=True), da.aggregate_counters),
+                    "grouped": (make, lambda r: r.group_aggregate(KEYS, AGGS, detail=True), da.group_aggregate_counters)}
+        if args.q1:
+            variants["q1_whole"] = (make, lambda r: r.group_aggregate(KEYS, Q1_AGGS, detail=True), da.group_aggregate_counters)
+        q1 = alternate(variants, args.runs)
+        whole = q1["q1_whole"].pop("result") if args.q1 else None
         groups, scanned, selected = q1["grouped"].pop("result")
         totals, scanned_u, selected_u = q1["ungrouped"].pop("result")
         assert (scanned, selected) == (scanned_u, selected_u)
@@ -81,6 +90,13 @@ def main():
             assert sum(g[1][a] for g in groups) == totals[a], (a, totals[a])
         assert min(g[1][5] for g in groups) == totals[5] and max(g[1][6] for g in groups) == totals[6]
         out["q1"] = dict(q1, scanned=scanned, selected=selected, groups=[[list(k), v] for k, v in groups])
+        if whole is not None:
+            wgroups, wscanned, wselected = whole
+            assert (wscanned, wselected) == (scanned, selected) and [k for k, _ in wgroups] == [k for k, _ in groups]
+            # sum(price * (100 - disc)) is 100 sum(price) - sum(price * disc), group by group; the counts are the other variant's
+            for (_, w), (_, g) in zip(wgroups, groups):
+                assert w[0] == g[0] and w[1] == g[1] and w[2] == 100 * g[1] - g[2] and w[5] == g[4], (w, g)
+            out["q1"]["whole_groups"] = [[list(k), v] for k, v in wgroups]
 
         # ---- the window-limit case: 256 distinct keys in every 2048-row window
         n = args.limit_rows

@@ -16,6 +16,7 @@
 #include "ipc_format.hpp"
 #include "ipc_stream_reader.hpp"
 #include "like_match.hpp"
+#include "scan_aggregate.hpp"
 #include "scan_operator.hpp"
 #include "writer.hpp"
 
@@ -432,6 +433,37 @@ void VectorExprOf(const char* api, const mi_agg_vector_spec& spec, device::AggDe
                                     ": both factors must be integer-like or both floating point");
   }
 }
+
+//! the vector specs of the call `api` as the launchers take them: prog (zeroed by the caller), the expressions of its
+//! SUM_EXPR aggregates in *table with *exprs pointing at it (else NULL), and each aggregate's class appended to `classes` (when given)
+void VectorProgramOf(const char* api, const mi_agg_vector_spec* aggs, int32_t n_aggs, device::AggProgram* prog, device::AggExprTable* table,
+                     const device::AggExprTable** exprs, std::vector<int32_t>* classes) {
+  auto column = [](const mi_agg_column& c) {
+    device::AggColumnDev d;
+    d.data = c.data;
+    d.validity = static_cast<const uint64_t*>(c.validity);
+    d.width = c.width;
+    d.cls = c.value_class;
+    return d;
+  };
+  prog->n_aggs = n_aggs;
+  *exprs = nullptr;
+  for (int32_t i = 0; i < n_aggs; i++) {
+    device::AggDescDev& d = prog->aggs[i];
+    d.op = aggs[i].op;
+    if (aggs[i].op == MI_AGG_SUM_EXPR) {
+      if (!*exprs) {
+        std::memset(table, 0, sizeof(*table));
+        *exprs = table;
+      }
+      VectorExprOf(api, aggs[i], &d, &table->exprs[i]);
+    } else {
+      d.a = column(aggs[i].a);
+      d.b = column(aggs[i].b);
+    }
+    if (classes) classes->push_back(d.a.cls);
+  }
+}
 }  // namespace
 
 int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel, const uint32_t* sel_count,
@@ -444,30 +476,9 @@ int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_
     if (nrows < 0) throw InvalidInputException("mi_aggregate_vectors: negative row count");
     device::AggProgram prog;
     std::memset(&prog, 0, sizeof(prog));
-    prog.n_aggs = n_aggs;
-    auto column = [](const mi_agg_column& c) {
-      device::AggColumnDev d;
-      d.data = c.data;
-      d.validity = static_cast<const uint64_t*>(c.validity);
-      d.width = c.width;
-      d.cls = c.value_class;
-      return d;
-    };
     device::AggExprTable exprs_table;
-    const device::AggExprTable* exprs = nullptr;
-    for (int32_t i = 0; i < n_aggs; i++) {
-      prog.aggs[i].op = aggs[i].op;
-      if (aggs[i].op == MI_AGG_SUM_EXPR) {
-        if (!exprs) {
-          std::memset(&exprs_table, 0, sizeof(exprs_table));
-          exprs = &exprs_table;
-        }
-        VectorExprOf("mi_aggregate_vectors", aggs[i], &prog.aggs[i], &exprs_table.exprs[i]);
-        continue;
-      }
-      prog.aggs[i].a = column(aggs[i].a);
-      prog.aggs[i].b = column(aggs[i].b);
-    }
+    const device::AggExprTable* exprs;
+    VectorProgramOf("mi_aggregate_vectors", aggs, n_aggs, &prog, &exprs_table, &exprs, nullptr);
     if (!device::AggProgramIsValid(prog, exprs))
       throw InvalidInputException("mi_aggregate_vectors: an operation, value class or width that does not fit (SUM takes integers of width 1 / 2 / 4 / 8 "
                                   "or floats of width 4 / 8, MIN / MAX also width 16, a product two integers or two floats)");
@@ -516,34 +527,11 @@ int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int
       prog.keys[k].cls = keys[k].key_class;
       r.kinds.push_back(groupkey::KindOfClass(keys[k].key_class));
     }
-    prog.aggs.n_aggs = n_aggs;
-    auto column = [](const mi_agg_column& c) {
-      device::AggColumnDev d;
-      d.data = c.data;
-      d.validity = static_cast<const uint64_t*>(c.validity);
-      d.width = c.width;
-      d.cls = c.value_class;
-      return d;
-    };
-    std::vector<int32_t> ops;
     device::AggExprTable exprs_table;
-    const device::AggExprTable* exprs = nullptr;
-    for (int32_t i = 0; i < n_aggs; i++) {
-      prog.aggs.aggs[i].op = aggs[i].op;
-      ops.push_back(aggs[i].op);
-      if (aggs[i].op == MI_AGG_SUM_EXPR) {
-        if (!exprs) {
-          std::memset(&exprs_table, 0, sizeof(exprs_table));
-          exprs = &exprs_table;
-        }
-        VectorExprOf("mi_group_aggregate_vectors", aggs[i], &prog.aggs.aggs[i], &exprs_table.exprs[i]);
-        r.classes.push_back(prog.aggs.aggs[i].a.cls);
-        continue;
-      }
-      prog.aggs.aggs[i].a = column(aggs[i].a);
-      prog.aggs.aggs[i].b = column(aggs[i].b);
-      r.classes.push_back(aggs[i].a.value_class);
-    }
+    const device::AggExprTable* exprs;
+    VectorProgramOf("mi_group_aggregate_vectors", aggs, n_aggs, &prog.aggs, &exprs_table, &exprs, &r.classes);
+    std::vector<int32_t> ops;
+    for (int32_t i = 0; i < n_aggs; i++) ops.push_back(aggs[i].op);
     if (!device::GroupProgramIsValid(prog, exprs))
       throw InvalidInputException("mi_group_aggregate_vectors: a key class, operation, value class or width that does not fit (keys: signed / unsigned of width "
                                   "1 / 2 / 4 / 8, wide or string of width 16; aggregates as mi_aggregate_vectors takes them)");
@@ -600,7 +588,7 @@ int mi_filter_pattern_launches(int64_t* n) {
 
 }  // extern "C"
 
-// scan operator + writer entry points live in scan_operator.cpp / writer.cpp (same extern "C" rules)
+// scan operator, aggregate + writer entry points live in scan_operator.cpp / scan_aggregate.cpp / writer.cpp (same extern "C" rules)
 namespace miarrow {
 int WrapC(const std::function<void()>& f) { return Wrap(f); }
 Context* ContextOf(mi_ctx* c) { return c ? c->ctx.get() : nullptr; }

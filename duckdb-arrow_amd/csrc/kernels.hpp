@@ -206,11 +206,15 @@ struct AggExprTable {
 //! integers or two floats; a kOpSumExpr needs `exprs`: 1 .. 4 factors, at least one column, every column factor with data,
 //! width 1 / 2 / 4 / 8 (integers) or 4 / 8 (floats), all integer-like or all floating point, none of 16 bytes
 bool AggProgramIsValid(const AggProgram& prog, const AggExprTable* exprs = nullptr);
+//! what agg_combine and group_combine take of a valid program: 4 bits per aggregate, the operation its partials merge by (a
+//! kOpSumExpr's merge as sums) and the class
+void PackOpsClasses(const AggProgram& prog, uint32_t* ops, uint32_t* classes);
 //! agg_windows: one partial per window and aggregate to d_partials[window * n_aggs + aggregate].  sel / sel_count in the
 //! filter's layout (2048 slots per window, the first sel_count[w] read), or both NULL = every row.  `exprs` is read only
 //! when the program holds a kOpSumExpr, and only then the expression instantiation is launched.
 hipError_t LaunchAggWindows(const AggProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
-                            aggmerge::Partial* d_partials, hipStream_t stream, const AggExprTable* exprs = nullptr);//! agg_combine: folds the partials of n_windows windows, in ascending order, into d_acc[0 .. n_aggs)
+                            aggmerge::Partial* d_partials, hipStream_t stream, const AggExprTable* exprs = nullptr);
+//! agg_combine: folds the partials of n_windows windows, in ascending order, into d_acc[0 .. n_aggs)
 hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_partials, int64_t n_windows, aggmerge::Partial* d_acc,
                             hipStream_t stream, const AggExprTable* exprs = nullptr);
 //! whether the program holds a kOpSumExpr (and its launches therefore need the table)

@@ -1,6 +1,7 @@
 // kernels_aggregate.hip -- K9: up to 8 aggregates (COUNT(*), COUNT, SUM, SUM of a product, MIN, MAX, SUM of a product of up
-// to 4 affine factors: kernels_agg_expr.inl) over decoded vectors,
-// under the selection vectors of the pushed-down filter (K6) or over every row (mi_scan_aggregate, mi_aggregate_vectors).
+// to 4 affine factors) over decoded vectors, under the selection vectors of the pushed-down filter (K6) or over every row
+// (mi_scan_aggregate, mi_aggregate_vectors).  How a row is read and folded into a lane's partial, and how a wave reduces its
+// lanes' partials, is kernels_agg_fold.inl, the one place for it: K10 (kernels_group.hip) includes the same text.
 //
 // agg_windows: one 256-thread workgroup per 2048-row window.  With a selection vector the lanes read sel[0 .. count)
 // coalesced and gather the rows it names (ascending inside the window, as kernels_gather.hip reads them); without one they
@@ -29,53 +30,7 @@ namespace {
 
 using aggmerge::Partial;
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-typedef u64x2 u64x2_a8 __attribute__((aligned(8)));   // a zero-copy alias of the Arrow body is 8-byte aligned only (leaf_wide)
-
-__device__ __forceinline__ bool row_is_valid(const uint64_t* validity, int64_t row) {
-  return validity == nullptr || ((GC<uint64_t>(validity)[row >> 6] >> (row & 63)) & 1ull) != 0;
-}
-
-// one integer of any class as a 128-bit two's-complement integer
-__device__ __forceinline__ void load_integer(const AggColumnDev& c, int64_t row, uint64_t* lo, uint64_t* hi) {
-  if (c.cls == aggmerge::kClassWide) {
-    const u64x2 v = GC<u64x2_a8>(c.data)[row];
-    *lo = v.x;
-    *hi = v.y;
-    return;
-  }
-  uint64_t u;
-  int64_t s;
-  switch (c.width) {
-    case 1: u = GC<uint8_t>(c.data)[row]; s = static_cast<int8_t>(u); break;
-    case 2: u = GC<uint16_t>(c.data)[row]; s = static_cast<int16_t>(u); break;
-    case 4: u = GC<uint32_t>(c.data)[row]; s = static_cast<int32_t>(u); break;
-    default: u = GC<uint64_t>(c.data)[row]; s = static_cast<int64_t>(u); break;
-  }
-  if (c.cls == aggmerge::kClassUnsigned) {
-    *lo = u;
-    *hi = 0;
-  } else {
-    *lo = static_cast<uint64_t>(s);
-    *hi = s < 0 ? ~0ull : 0ull;
-  }
-}
-
-__device__ __forceinline__ Partial load_partial(gptr<const Partial> p) {
-  const u64x2 x = ((gptr<const u64x2_a8>)p)[0], y = ((gptr<const u64x2_a8>)p)[1];
-  return Partial{x.x, x.y, y.x, y.y};
-}
-__device__ __forceinline__ void store_partial(gptr<Partial> p, const Partial& v) {
-  const u64x2 x = {v.lo, v.hi}, y = {v.count, v.flags};
-  ((gptr<u64x2_a8>)p)[0] = x;
-  ((gptr<u64x2_a8>)p)[1] = y;
-}
-
-__device__ __forceinline__ double load_double(const AggColumnDev& c, int64_t row) {
-  return c.width == 4 ? static_cast<double>(GC<float>(c.data)[row]) : GC<double>(c.data)[row];
-}
-
-#include "kernels_agg_expr.inl"
+#include "kernels_agg_fold.inl"
 
 // The kernel's text, once.  EXPR: the program may hold kOpSumExpr aggregates and `exprs` is their table; without it the
 // branch is not compiled and `exprs` not looked at, so agg_windows<HAS_SEL> below is the kernel it was before expressions.
@@ -99,7 +54,6 @@ __device__ __forceinline__ void agg_windows_body(const AggProgram& prog, const A
   for (int a = 0; a < prog.n_aggs; a++) {
     const AggDescDev& d = prog.aggs[a];
     const int op = d.op, cls = d.a.cls;
-    const bool is_sum = op == aggmerge::kOpSum || op == aggmerge::kOpSumProduct;
     Partial p = {0ull, 0ull, 0ull, 0ull};
     for (uint32_t i = threadIdx.x; i < cnt; i += kBlockThreads) {
       uint32_t r = i;
@@ -111,56 +65,12 @@ __device__ __forceinline__ void agg_windows_body(const AggProgram& prog, const A
         }
       }
       const int64_t row = row0 + r;
-      if (op == aggmerge::kOpCountStar) {
-        p.count++;
-        continue;
-      }
-      if (EXPR && op == aggmerge::kOpSumExpr) {   // validity, values and the sum: kernels_agg_expr.inl
-        fold_expr_row(exprs->exprs[a], cls, row, &p);
-        continue;
-      }
-      bool valid = row_is_valid(d.a.validity, row);
-      if (op == aggmerge::kOpSumProduct) valid = valid && row_is_valid(d.b.validity, row);
-      if (!valid) continue;
-      if (op == aggmerge::kOpCount) {
-        p.count++;
-      } else if (cls == aggmerge::kClassFloat) {
-        double v = load_double(d.a, row);
-        if (op == aggmerge::kOpSumProduct) v = __dmul_rn(v, load_double(d.b, row));   // rounded product, then the sum: no fma
-        if (is_sum) {
-          p.lo = aggmerge::BitsOf(p.count ? __dadd_rn(aggmerge::DoubleOf(p.lo), v) : v);
-          p.count++;
-        } else {
-          aggmerge::Fold<false>(op, cls, &p, aggmerge::CanonicalBits(v), 0ull);
-        }
-      } else {
-        uint64_t lo, hi;
-        load_integer(d.a, row, &lo, &hi);
-        if (op == aggmerge::kOpSumProduct) {
-          uint64_t blo, bhi;
-          load_integer(d.b, row, &blo, &bhi);
-          const unsigned __int128 x = (static_cast<unsigned __int128>(hi) << 64) | lo, y = (static_cast<unsigned __int128>(bhi) << 64) | blo;
-          const unsigned __int128 prod = x * y;   // modulo 2^128: the two's-complement product
-          lo = static_cast<uint64_t>(prod);
-          hi = static_cast<uint64_t>(prod >> 64);
-        }
-        if (is_sum) {
-          aggmerge::Add128(&p.lo, &p.hi, lo, hi);
-          p.count++;
-        } else {
-          aggmerge::Fold<false>(op, cls, &p, lo, hi);
-        }
-      }
+      if (EXPR && op == aggmerge::kOpSumExpr) fold_expr_row(exprs->exprs[a], cls, row, &p);
+      else fold_row(d, op, cls, row, &p);
     }
-    // wave reduction: lane l takes lane l + d while that lane exists (a lane whose partner would lie past the wave keeps its
-    // partial as it is: __shfl_down hands such a lane its own value back, which must not be folded in a second time)
 #pragma unroll
-    for (int dist = 32; dist >= 1; dist >>= 1) {
-      Partial o;
-      o.lo = __shfl_down(p.lo, dist, 64);
-      o.hi = __shfl_down(p.hi, dist, 64);
-      o.count = __shfl_down(p.count, dist, 64);
-      o.flags = __shfl_down(p.flags, dist, 64);
+    for (int dist = 32; dist >= 1; dist >>= 1) {   // wave reduction: lane l takes lane l + dist while that lane exists
+      const Partial o = shfl_down_partial(p, dist);
       if (lane + dist < 64) aggmerge::Merge<EXPR>(op, cls, &p, o);
     }
     if (lane == 0) wave_part[wave] = p;
@@ -273,6 +183,15 @@ bool AggProgramIsValid(const AggProgram& prog, const AggExprTable* exprs) {
   return true;
 }
 
+void PackOpsClasses(const AggProgram& prog, uint32_t* ops, uint32_t* classes) {
+  *ops = *classes = 0;
+  for (int a = 0; a < prog.n_aggs; a++) {
+    const int op = prog.aggs[a].op == aggmerge::kOpSumExpr ? aggmerge::kOpSum : prog.aggs[a].op;   // partials of either merge as sums
+    *ops |= static_cast<uint32_t>(op) << (4 * a);
+    *classes |= static_cast<uint32_t>(prog.aggs[a].a.cls) << (4 * a);
+  }
+}
+
 hipError_t LaunchAggWindows(const AggProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
                             aggmerge::Partial* d_partials, hipStream_t stream, const AggExprTable* exprs) {
   MI_DROP_STALE_ERROR();
@@ -295,12 +214,8 @@ hipError_t LaunchAggCombine(const AggProgram& prog, const aggmerge::Partial* d_p
   MI_DROP_STALE_ERROR();
   if (n_windows <= 0) return hipSuccess;
   if (!AggProgramIsValid(prog, exprs) || !d_partials || !d_acc) return hipErrorInvalidValue;
-  uint32_t ops = 0, classes = 0;
-  for (int a = 0; a < prog.n_aggs; a++) {
-    const int op = prog.aggs[a].op == aggmerge::kOpSumExpr ? aggmerge::kOpSum : prog.aggs[a].op;   // partials of either merge as sums
-    ops |= static_cast<uint32_t>(op) << (4 * a);
-    classes |= static_cast<uint32_t>(prog.aggs[a].a.cls) << (4 * a);
-  }
+  uint32_t ops, classes;
+  PackOpsClasses(prog, &ops, &classes);
   hipLaunchKernelGGL(agg_combine, dim3(1), dim3(64), 0, stream, ops, classes, prog.n_aggs, d_partials, n_windows, d_acc);
   g_agg_launches[1]++;
   return hipGetLastError();

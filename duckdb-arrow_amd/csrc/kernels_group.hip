@@ -1,8 +1,10 @@
 // kernels_group.hip -- K10: GROUP BY over decoded vectors (mi_scan_group_aggregate, mi_group_aggregate_vectors): up to 4
-// key columns, up to 8 aggregates of K9's kinds (the expression sum of kernels_agg_expr.inl included) per group, under the selection vectors of the pushed-down filter (K6) or
-// over every row.  Scope: few groups -- at most groupkey::kWindowLimit distinct keys among the selected rows of one
-// 2048-row window, groupkey::kMaxGroups in a scan; more raises MI_ST_GROUP_LIMIT.  The rules of a key are group_key.hpp,
-// the rules of a merge agg_merge.hpp, both shared with the host.
+// key columns, up to 8 aggregates of K9's kinds (the expression sum included) per group, under the selection vectors of the
+// pushed-down filter (K6) or over every row.  How a row is read and folded, and how a wave reduces its lanes' partials, is
+// kernels_agg_fold.inl, the one place for it, shared with K9; this file keeps the key table, the sort and the ranking.
+// Scope: few groups -- at most groupkey::kWindowLimit distinct keys among the selected rows of one 2048-row window,
+// groupkey::kMaxGroups in a scan; more raises MI_ST_GROUP_LIMIT.  The rules of a key are group_key.hpp, the rules of a
+// merge agg_merge.hpp, both shared with the host.
 //
 // group_windows: one 256-thread workgroup per 2048-row window, in three steps.
 //   1. keys     256 selected rows at a time: a lane normalises the key of its row and finds or inserts it in the window's
@@ -42,99 +44,12 @@ namespace {
 using aggmerge::Partial;
 using groupkey::Key;
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-typedef u64x2 u64x2_a8 __attribute__((aligned(8)));   // a zero-copy alias of the Arrow body is 8-byte aligned only
-
 constexpr int kWinSlots = 2 * groupkey::kWindowLimit;      // the window's table in LDS
 constexpr uint32_t kTableSlots = kGroupTableSlots;         // the scan-wide table in HBM
 constexpr uint32_t kSlotEmpty = 0xFFFFFFFFu, kSlotBusy = 0xFFFFFFFEu;
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
 
-__device__ __forceinline__ bool row_is_valid(const uint64_t* validity, int64_t row) {
-  return validity == nullptr || ((GC<uint64_t>(validity)[row >> 6] >> (row & 63)) & 1ull) != 0;
-}
-
-// ---- the aggregates' inputs, read as agg_windows reads them
-__device__ __forceinline__ void load_integer(const AggColumnDev& c, int64_t row, uint64_t* lo, uint64_t* hi) {
-  if (c.cls == aggmerge::kClassWide) {
-    const u64x2 v = GC<u64x2_a8>(c.data)[row];
-    *lo = v.x;
-    *hi = v.y;
-    return;
-  }
-  uint64_t u;
-  int64_t s;
-  switch (c.width) {
-    case 1: u = GC<uint8_t>(c.data)[row]; s = static_cast<int8_t>(u); break;
-    case 2: u = GC<uint16_t>(c.data)[row]; s = static_cast<int16_t>(u); break;
-    case 4: u = GC<uint32_t>(c.data)[row]; s = static_cast<int32_t>(u); break;
-    default: u = GC<uint64_t>(c.data)[row]; s = static_cast<int64_t>(u); break;
-  }
-  if (c.cls == aggmerge::kClassUnsigned) {
-    *lo = u;
-    *hi = 0;
-  } else {
-    *lo = static_cast<uint64_t>(s);
-    *hi = s < 0 ? ~0ull : 0ull;
-  }
-}
-
-__device__ __forceinline__ double load_double(const AggColumnDev& c, int64_t row) {
-  return c.width == 4 ? static_cast<double>(GC<float>(c.data)[row]) : GC<double>(c.data)[row];
-}
-
-__device__ __forceinline__ Partial load_partial(gptr<const Partial> p) {
-  const u64x2 x = ((gptr<const u64x2_a8>)p)[0], y = ((gptr<const u64x2_a8>)p)[1];
-  return Partial{x.x, x.y, y.x, y.y};
-}
-__device__ __forceinline__ void store_partial(gptr<Partial> p, const Partial& v) {
-  const u64x2 x = {v.lo, v.hi}, y = {v.count, v.flags};
-  ((gptr<u64x2_a8>)p)[0] = x;
-  ((gptr<u64x2_a8>)p)[1] = y;
-}
-
-// one selected row folded into a lane's partial: the arithmetic of agg_windows (128-bit wrapping sums, doubles without fma)
-__device__ __forceinline__ void fold_row(const AggDescDev& d, int op, int cls, int64_t row, Partial* p) {
-  if (op == aggmerge::kOpCountStar) {
-    p->count++;
-    return;
-  }
-  bool valid = row_is_valid(d.a.validity, row);
-  if (op == aggmerge::kOpSumProduct) valid = valid && row_is_valid(d.b.validity, row);
-  if (!valid) return;
-  const bool is_sum = op == aggmerge::kOpSum || op == aggmerge::kOpSumProduct;
-  if (op == aggmerge::kOpCount) {
-    p->count++;
-  } else if (cls == aggmerge::kClassFloat) {
-    double v = load_double(d.a, row);
-    if (op == aggmerge::kOpSumProduct) v = __dmul_rn(v, load_double(d.b, row));   // rounded product, then the sum: no fma
-    if (is_sum) {
-      p->lo = aggmerge::BitsOf(p->count ? __dadd_rn(aggmerge::DoubleOf(p->lo), v) : v);
-      p->count++;
-    } else {
-      aggmerge::Fold<false>(op, cls, p, aggmerge::CanonicalBits(v), 0ull);
-    }
-  } else {
-    uint64_t lo, hi;
-    load_integer(d.a, row, &lo, &hi);
-    if (op == aggmerge::kOpSumProduct) {
-      uint64_t blo, bhi;
-      load_integer(d.b, row, &blo, &bhi);
-      const unsigned __int128 x = (static_cast<unsigned __int128>(hi) << 64) | lo, y = (static_cast<unsigned __int128>(bhi) << 64) | blo;
-      const unsigned __int128 prod = x * y;   // modulo 2^128: the two's-complement product
-      lo = static_cast<uint64_t>(prod);
-      hi = static_cast<uint64_t>(prod >> 64);
-    }
-    if (is_sum) {
-      aggmerge::Add128(&p->lo, &p->hi, lo, hi);
-      p->count++;
-    } else {
-      aggmerge::Fold<false>(op, cls, p, lo, hi);
-    }
-  }
-}
-
-#include "kernels_agg_expr.inl"
+#include "kernels_agg_fold.inl"
 
 // one part of the key of `row`: 0, MI_ST_GROUP_KEY_LONG for a string that has no inline image, or kPartNull
 constexpr uint32_t kPartNull = 1u;
@@ -344,7 +259,7 @@ __device__ __forceinline__ void group_windows_body(const GroupProgram& prog, con
     for (uint32_t g = wave; g < n_local; g += kBlockThreads / 64) {
       const uint32_t begin = s_start[g], end = s_start[g + 1];
       Partial p = {0ull, 0ull, 0ull, 0ull};
-      if (EXPR && op == aggmerge::kOpSumExpr) {   // validity, values and the sum: kernels_agg_expr.inl
+      if (EXPR && op == aggmerge::kOpSumExpr) {   // validity, values and the sum: kernels_agg_fold.inl
         const AggExprDev& e = exprs->exprs[a];
         for (uint32_t j = begin + lane; j < end; j += 64) fold_expr_row(e, cls, row0 + (s_sort[j] & (kTileRows - 1)), &p);
       } else {
@@ -352,11 +267,7 @@ __device__ __forceinline__ void group_windows_body(const GroupProgram& prog, con
       }
 #pragma unroll
       for (int dist = 32; dist >= 1; dist >>= 1) {   // as agg_windows: lane l takes lane l + dist while that lane exists
-        Partial o;
-        o.lo = __shfl_down(p.lo, dist, 64);
-        o.hi = __shfl_down(p.hi, dist, 64);
-        o.count = __shfl_down(p.count, dist, 64);
-        o.flags = __shfl_down(p.flags, dist, 64);
+        const Partial o = shfl_down_partial(p, dist);
         if (lane + dist < 64) aggmerge::Merge<EXPR>(op, cls, &p, o);
       }
       if (lane == 0) store_partial(partials + (static_cast<size_t>(g) * n_aggs + a), p);
@@ -585,12 +496,8 @@ hipError_t LaunchGroupCombine(const GroupProgram& prog, const GroupWindowsOut& i
   MI_DROP_STALE_ERROR();
   if (n_windows <= 0) return hipSuccess;
   if (!GroupProgramIsValid(prog, exprs) || !in.heads || !table.head) return hipErrorInvalidValue;
-  uint32_t ops = 0, classes = 0;
-  for (int a = 0; a < prog.aggs.n_aggs; a++) {
-    const int op = prog.aggs.aggs[a].op == aggmerge::kOpSumExpr ? aggmerge::kOpSum : prog.aggs.aggs[a].op;   // partials of either merge as sums
-    ops |= static_cast<uint32_t>(op) << (4 * a);
-    classes |= static_cast<uint32_t>(prog.aggs.aggs[a].a.cls) << (4 * a);
-  }
+  uint32_t ops, classes;
+  PackOpsClasses(prog.aggs, &ops, &classes);
   hipLaunchKernelGGL(group_combine, dim3(1), dim3(kBlockThreads), 0, stream, prog.n_keys, prog.aggs.n_aggs, ops, classes, in, n_windows, table);
   g_group_launches[1]++;
   return hipGetLastError();

@@ -15,6 +15,8 @@
 //   scan_readahead.{hpp,cpp}   ReadAhead: producer threads, their queues and pinned staging buffers (host code only)
 //   scan_filter.cpp            pushed-down predicates: normalisation, binding to the scan's columns, constants in HBM,
 //                              the per-batch FilterProgram
+//   scan_aggregate.{hpp,cpp}   the fused aggregates (mi_scan_aggregate, mi_scan_group_aggregate): their types, the methods
+//                              below that bind, enqueue and drain them, their C ABI
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -31,8 +33,8 @@
 
 #include "batch_planner.hpp"
 #include "engine.hpp"
-#include "group_key.hpp"
 #include "ipc_stream_reader.hpp"
+#include "scan_aggregate.hpp"
 #include "scan_readahead.hpp"
 
 namespace miarrow {
@@ -188,71 +190,6 @@ struct DeviceColumnView {
   const uint8_t* h_validity = nullptr;
   int32_t offset_width = 0;
 };
-
-//! One aggregate of mi_scan_aggregate by column name, and what a draining call returns: the accumulators, the value class
-//! each is merged by (aggmerge::kClass*: what the host's merge of several devices needs), the rows seen
-struct AggFactorSpec {
-  bool has_column = false;   // false: the constant `add`
-  std::string column;
-  int64_t mul = 1, add = 0;  // MI_AGG_CONST_INT
-  double fmul = 1.0, fadd = 0.0;   // MI_AGG_CONST_DOUBLE
-  int32_t constants = MI_AGG_CONST_INT;
-};
-struct AggSpec {
-  int32_t op = 0;            // aggmerge::kOp*
-  std::string a, b;
-  std::vector<AggFactorSpec> factors;   // kOpSumExpr
-};
-//! the constants of one factor as the kernels take them: int64 two's complement for an integer expression, the bits of a
-//! double for a floating-point one.  Double constants on an integer expression are MI_ENOTSUP; integer constants a double
-//! does not hold exactly are MI_EINVAL.  `what` begins the message.
-void ExprFactorConstants(const std::string& what, bool is_float, int32_t constants, int64_t mul, int64_t add, double fmul, double fadd,
-                         uint64_t* mul_bits, uint64_t* add_bits);
-struct AggResult {
-  std::vector<aggmerge::Partial> values;
-  std::vector<int32_t> classes;
-  int64_t rows_scanned = 0, rows_selected = 0;
-};
-
-//! What mi_scan_group_aggregate returns: the groups' normalised keys (group_key.hpp) and one partial per group and
-//! aggregate, values[g * classes.size() + a]; kinds: groupkey::kKind* per key part.  In the result order once SortGroups ran.
-struct GroupResult {
-  std::vector<int32_t> kinds;
-  std::vector<int32_t> classes;
-  std::vector<groupkey::Key> keys;
-  std::vector<aggmerge::Partial> values;
-  int64_t rows_scanned = 0, rows_selected = 0;
-};
-//! copies the scan-wide table of K10 back (one copy: keys, accumulators, group count, flags), throws for the MI_ST_* bits it
-//! carries and appends its groups to out->keys / out->values
-void ReadGroupTable(const void* d_table, int n_keys, int n_aggs, hipStream_t stream, GroupResult* out);
-//! the result order: ascending by key, NULLS LAST (groupkey::KeyLess)
-void SortGroups(GroupResult* r);
-//! a sorted result as the C ABI returns it; more groups than `capacity` is MI_EINVAL with *n_groups set
-void FillGroupOutputs(const GroupResult& r, const std::vector<int32_t>& ops, mi_group_key_value* out_keys, mi_agg_value* out_values,
-                      int32_t capacity, int32_t* n_groups);
-//! MI_AGG_TIMING=1: device milliseconds of group_windows / group_combine summed over this process's calls of mi_scan_group_aggregate
-void GroupTimingTotals(double out_ms[2]);
-
-//! a finished accumulator as the C ABI returns it (mi_scan_aggregate, mi_aggregate_vectors)
-inline void FillAggValue(int32_t op, int32_t cls, const aggmerge::Partial& p, mi_agg_value* v) {
-  std::memset(v, 0, sizeof(*v));
-  v->count = static_cast<int64_t>(p.count);
-  if (op == aggmerge::kOpCountStar || op == aggmerge::kOpCount) {
-    v->kind = MI_AGG_VALUE_INT128;
-    v->lo = p.count;
-    return;
-  }
-  v->kind = cls == aggmerge::kClassFloat ? MI_AGG_VALUE_DOUBLE : MI_AGG_VALUE_INT128;
-  v->is_null = aggmerge::IsNull(op, p) ? 1 : 0;
-  if (v->is_null) return;
-  v->lo = p.lo;
-  v->hi = static_cast<int64_t>(p.hi);
-}
-//! "SUM", "MIN", ... for messages
-const char* AggOpName(int32_t op);
-//! MI_AGG_TIMING=1: device milliseconds of agg_windows / agg_combine summed over this process's calls of mi_scan_aggregate
-void AggTimingTotals(double out_ms[2]);
 
 class ScanBase {
  public:
@@ -457,11 +394,17 @@ class ArrowScan : public ScanBase {
     bool timed = false;                      // MI_AGG_TIMING=1: HIP events around every launch
     std::vector<HipEvent> events;            // timed: {before agg_windows, between, after agg_combine} per record batch
   } aggn;
+  // (the methods from here to DrainAggregates are scan_aggregate.cpp's)
   //! agg_windows + agg_combine (with keys: group_windows + group_combine) over the slot's decoded vectors and selection
   //! vectors, behind the filter on the compute stream
   void EnqueueAggregates(Slot& s);
+  //! aggn over the slot's decoded vectors as the launches take it: the aggregates, the keys when there are any, and -- the
+  //! return value tells -- the expressions of the kOpSumExpr aggregates
+  bool FillAggregatePrograms(const Slot& s, device::GroupProgram* gprog, device::AggExprTable* exprs) const;
   //! bind-time validation shared by Aggregate and GroupAggregate: a column an aggregate (or GROUP BY, `what`) may read
   const ScanColumn& AggregateColumn(const std::string& name, const std::string& what) const;
+  //! ... and a factor of SUM_PRODUCT / SUM_EXPR (`op`): such a column of a class a product takes, which goes to *cls
+  const ScanColumn& FactorColumn(const std::string& name, int32_t op, int32_t* cls) const;
   //! validates `specs` into aggn.aggs and adds the columns they read to `proj`
   void BindAggregateSpecs(const std::vector<AggSpec>& specs, const char* api, std::vector<std::string>* proj);
   //! runs the scan over `proj` with aggn.on: `begin` after Init (allocates the accumulators), then every record batch;

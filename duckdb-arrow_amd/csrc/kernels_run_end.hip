@@ -85,7 +85,11 @@ __device__ __forceinline__ void expand_tile(const mi_col_task& t, int64_t row0, 
     if (t.out_validity != nullptr) {
       const int j = wave + (kBlockThreads / 64) * k;  // the wave's 64 rows of this step are word j of the tile
       uint64_t word = __ballot(ok);
-      if (t.out_aux != nullptr && 64 * j < n) word &= GC<uint64_t>(t.out_aux)[(row0 >> 6) + j];  // struct parent, same rows
+      if (t.out_aux != nullptr && 64 * j < n) {
+        word &= GC<uint64_t>(t.out_aux)[(row0 >> 6) + j];  // struct parent, same rows
+        const int rem = n - 64 * j;
+        if (rem < 64) word |= ~0ull << rem;  // canonical pad bits, whatever the parent's are (as tile_valid_word)
+      }
       if (lane == 0 && 64 * j < n) GM<uint64_t>(t.out_validity)[(row0 >> 6) + j] = word;
     }
   }

@@ -1,26 +1,20 @@
 // scan_operator.cpp -- see scan_operator.hpp.
 #include "scan_operator.hpp"
-#include "io_pool.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <thread>
-#include <tuple>
 
 namespace miarrow {
 
 int WrapC(const std::function<void()>& f);  // c_api.cpp
 
 namespace {
-constexpr size_t kAlign = 256;
-size_t RoundUp(size_t v, size_t a = kAlign) { return (v + a - 1) / a * a; }
 // a buffer that lives as long as any of the shared pointers to its memory (dictionary versions keep them)
 template <typename Buffer>
 std::shared_ptr<void> Shared(size_t bytes) {
@@ -246,13 +240,6 @@ void ArrowScan::GrowSlots(size_t n) {
     for (auto& s : slots) InitSlot(s);   // (those that came along keep what they have)
 }
 
-void ArrowScan::EnsureHostOut(Slot& s, size_t bytes) {
-  if (opts.device_resident || bytes <= s.h_out.size()) return;
-  ctx->Bind();
-  Context::PreferNode near_the_gpu(ctx);   // (the caller's thread allocates: only its policy, for the length of this call)
-  Retire(Grow(s.h_out, bytes, GrownCapacity(bytes, s.h_out.size(), 1 << 16)));
-}
-
 ArrowScan::Slot* ArrowScan::FreeSlot() {
   for (auto& s : slots)
     if (!s.busy) return &s;
@@ -267,17 +254,9 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
   int64_t param;
   if (!f.Plan(&kind, &param, &w, /*value_only*/ true))
     throw NotImplementedException("Dictionary value type " + f.Format() + " is not decoded by the MI355X scan path");
-  // the values are decoded as ONE flat task below: value types that need more than {validity, buffer 1, buffer 2}
-  // (string views: a table of variadic buffers; lists / structs: child nodes) are refused instead of mis-wired
-  switch (kind) {
-    case MI_K_COPY: case MI_K_BOOL: case MI_K_DEC128: case MI_K_DATE64: case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64:
-    case MI_K_STR32: case MI_K_STR64: case MI_K_FIXED_BINARY: case MI_K_DURATION: case MI_K_INTERVAL_MONTHS: case MI_K_INTERVAL_MDN:
-    case MI_K_NARROW: case MI_K_HALF_FLOAT:
-      break;
-    default:
-      throw NotImplementedException("Dictionary of value type " + f.Format() + " (field '" + f.name +
-                                    "') is not decoded by the MI355X scan path: only flat value types are");
-  }
+  if (!DictionaryKindIsFlat(kind))
+    throw NotImplementedException("Dictionary of value type " + f.Format() + " (field '" + f.name +
+                                  "') is not decoded by the MI355X scan path: only flat value types are");
   // isDelta: the new values are appended to the existing dictionary (indices keep their meaning); otherwise the
   // dictionary is replaced.  Either way a NEW version is built; batches already in flight keep theirs.
   std::shared_ptr<DictState> old = dicts.count(b.dict_id) ? dicts[b.dict_id] : nullptr;
@@ -295,12 +274,11 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
     d->host_bodies = old->host_bodies;
   }
   if (b.owner) d->host_bodies.push_back(b.owner);
-  const size_t data_bytes = RoundUp(static_cast<size_t>(n + 1) * static_cast<size_t>(w));
-  const size_t valid_bytes = RoundUp(static_cast<size_t>((n + 1 + 63) / 64) * 8);
+  const size_t data_bytes = AlignUp(static_cast<size_t>(n + 1) * static_cast<size_t>(w));
+  const size_t valid_bytes = AlignUp(static_cast<size_t>((n + 1 + 63) / 64) * 8);
   // Nothing below waits for the device: the body goes up on the copy stream, the values are decoded on the compute stream
   // behind it (the record batches that use the dictionary follow on the same stream), the decode's status word comes back
-  // with the first such batch (DictState::h_status, checked in AcquireBatch).  The validity words are built on the host
-  // from the Arrow bitmap (the value types admitted above are flat: a value is NULL exactly when its bit says so).
+  // with the first such batch (DictState::h_status, checked in AcquireBatch).  The validity words are built on the host.
   d->d_data = DeviceBuffer(data_bytes);
   d->d_validity = DeviceBuffer(valid_bytes);
   d->h_words = PinnedBuffer(valid_bytes);
@@ -309,7 +287,7 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
   MI_HIP_CHECK(hipMemsetAsync(d->d_data.get(), 0, data_bytes, ctx->stream));
   uint8_t* heap = nullptr;
   if (b.body_size > 0) {
-    d->d_heaps.push_back(Shared<DeviceBuffer>(RoundUp(static_cast<size_t>(b.body_size) + 16)));
+    d->d_heaps.push_back(Shared<DeviceBuffer>(AlignUp(static_cast<size_t>(b.body_size) + 16)));
     heap = static_cast<uint8_t*>(d->d_heaps.back().get());
     // the body is pinned (the read-ahead's allocator for DICTIONARY_BATCH messages) and lives in host_bodies
     MI_HIP_CHECK(hipMemcpyAsync(heap, b.body, static_cast<size_t>(b.body_size), hipMemcpyHostToDevice, ctx->h2d_stream));
@@ -319,23 +297,10 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
   }
   if (n_old > 0)
     MI_HIP_CHECK(hipMemcpyAsync(d->d_data.get(), old->d_data.get(), static_cast<size_t>(n_old) * static_cast<size_t>(w), hipMemcpyDeviceToDevice, ctx->stream));
-  uint64_t* words = d->h_words.get<uint64_t>();
-  for (size_t i = 0; i < valid_bytes / 8; i++) words[i] = ~0ull;
-  auto set_bit = [&](int64_t i, bool v) {
-    if (v) words[static_cast<size_t>(i >> 6)] |= 1ull << (i & 63);
-    else words[static_cast<size_t>(i >> 6)] &= ~(1ull << (i & 63));
-  };
-  for (int64_t i = 0; i < n_old; i++) set_bit(i, old->host_valid[static_cast<size_t>(i)] != 0);
-  {
-    const mi_buffer_span* sp = &b.buffers[0];
-    const bool has_bitmap = sp[0].length > 0 && b.null_count[0] != 0;
-    if (has_bitmap && sp[0].length < (n_new + 7) / 8) throw InternalException("Arrow IPC validation failed: dictionary validity bitmap is too short");
-    for (int64_t i = 0; i < n_new; i++) set_bit(n_old + i, !has_bitmap || ((b.body[sp[0].offset + (i >> 3)] >> (i & 7)) & 1));
-  }
   if (n_new > 0) {
     // decode the new values into a tile-aligned scratch vector, then append (the scratch lives as long as the version:
     // freeing it here would wait for the device)
-    d->d_heaps.push_back(Shared<DeviceBuffer>(RoundUp(static_cast<size_t>(n_new) * static_cast<size_t>(w) + 16)));
+    d->d_heaps.push_back(Shared<DeviceBuffer>(AlignUp(static_cast<size_t>(n_new) * static_cast<size_t>(w) + 16)));
     void* scratch_data = d->d_heaps.back().get();
     mi_col_task t;
     std::memset(&t, 0, sizeof(t));
@@ -346,7 +311,7 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
     t.buf2 = payload ? heap + sp[2].offset : nullptr;
     t.buf2_len = payload ? sp[2].length : 0;
     t.out_data = scratch_data;
-    t.out_validity = nullptr;   // built on the host, above
+    t.out_validity = nullptr;   // built on the host, below
     const int64_t data_off = payload ? sp[2].offset : sp[1].offset;
     t.ptr_base = opts.device_resident ? reinterpret_cast<uint64_t>(heap + data_off) : reinterpret_cast<uint64_t>(b.body + data_off);
     t.nrows = n_new;
@@ -359,67 +324,11 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
                                 static_cast<size_t>(n_new) * static_cast<size_t>(w), hipMemcpyDeviceToDevice, ctx->stream));
     MI_HIP_CHECK(hipMemcpyAsync(d->h_status.get(), d->decode_plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   }
-  // string-valued dictionaries keep their values on the host too: pushed-down string predicates are matched against the
-  // dictionary once and against the rows by index (the offsets are validated here; the device validates them again)
-  d->host_valid.resize(static_cast<size_t>(n));
-  for (int64_t i = 0; i < n; i++) d->host_valid[static_cast<size_t>(i)] = (words[static_cast<size_t>(i >> 6)] >> (i & 63)) & 1;
-  if (IsStringKind(kind)) {
-    if (delta) d->host_strings = old->host_strings;
-    const mi_buffer_span* sp = &b.buffers[0];
-    for (int64_t i = 0; i < n_new; i++) {
-      const bool ok = d->host_valid[static_cast<size_t>(n_old + i)] != 0;
-      std::string v;
-      if (ok) {
-        if (kind == MI_K_FIXED_BINARY) {
-          v.assign(reinterpret_cast<const char*>(b.body + sp[1].offset + i * param), static_cast<size_t>(param));
-        } else {
-          int64_t o0, o1;
-          if (kind == MI_K_STR32) {
-            int32_t a, c;
-            std::memcpy(&a, b.body + sp[1].offset + 4 * i, 4);
-            std::memcpy(&c, b.body + sp[1].offset + 4 * (i + 1), 4);
-            o0 = a; o1 = c;
-          } else {
-            std::memcpy(&o0, b.body + sp[1].offset + 8 * i, 8);
-            std::memcpy(&o1, b.body + sp[1].offset + 8 * (i + 1), 8);
-          }
-          if (o0 < 0 || o1 < o0 || o1 > sp[2].length) throw InternalException("Arrow IPC validation failed: dictionary offsets");
-          v.assign(reinterpret_cast<const char*>(b.body + sp[2].offset + o0), static_cast<size_t>(o1 - o0));
-        }
-      }
-      d->host_strings.push_back(std::move(v));
-    }
-  } else if (FilterClassOf(f) != FilterValueClass::kOther) {
-    // FLOAT / DOUBLE / 128-bit dictionaries keep their decoded values on the host for the same reason.  The Arrow values are
-    // the decoded ones (float16 widened, exactly); the validity bitmap above says which of them count
-    const mi_buffer_span* sp = &b.buffers[0];
-    const size_t vw = static_cast<size_t>(w), sw = kind == MI_K_HALF_FLOAT ? 2 : vw;
-    if (sp[1].length < n_new * static_cast<int64_t>(sw)) throw InternalException("Arrow IPC validation failed: dictionary values buffer is too short");
-    if (delta) d->host_values = old->host_values;
-    d->host_values.resize(static_cast<size_t>(n) * vw, 0);
-    uint8_t* dst = d->host_values.data() + static_cast<size_t>(n_old) * vw;
-    const uint8_t* src = b.body + sp[1].offset;
-    if (kind != MI_K_HALF_FLOAT) {
-      std::memcpy(dst, src, static_cast<size_t>(n_new) * vw);
-    } else {
-      for (int64_t i = 0; i < n_new; i++) {
-        uint16_t h;
-        std::memcpy(&h, src + 2 * i, 2);
-        const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16, exp = (h >> 10) & 0x1Fu;
-        uint32_t man = h & 0x3FFu, bits;
-        if (exp == 0x1F) bits = sign | 0x7F800000u | (man << 13);
-        else if (exp != 0) bits = sign | ((exp + 112u) << 23) | (man << 13);
-        else if (man == 0) bits = sign;
-        else {   // subnormal half: normalise
-          uint32_t e = 113;
-          while (!(man & 0x400u)) { man <<= 1; e--; }
-          bits = sign | (e << 23) | ((man & 0x3FFu) << 13);
-        }
-        std::memcpy(dst + 4 * i, &bits, 4);
-      }
-    }
-  }
-  set_bit(n, false);  // the extra NULL entry at index dict_len (ColumnArrowToDuckDBDictionary)
+  // The host side (scan_dictionary.cpp): the validity words, and for string-valued and FLOAT / DOUBLE / 128-bit dictionaries
+  // the values themselves -- pushed-down predicates are matched against the dictionary once and against the rows by index
+  uint64_t* words = d->h_words.get<uint64_t>();
+  BuildDictionaryHost(b, kind, w, param, FilterClassOf(f) != FilterValueClass::kOther, delta ? old.get() : nullptr, words, valid_bytes / 8, d.get());
+  words[static_cast<size_t>(n >> 6)] &= ~(1ull << (n & 63));  // the extra NULL entry at index dict_len (ColumnArrowToDuckDBDictionary)
   MI_HIP_CHECK(hipMemcpyAsync(d->d_validity.get(), words, valid_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (!opts.device_resident) {
     // host consumers read the values from pinned memory: the copy rides the compute stream too, and every batch that uses
@@ -429,497 +338,6 @@ void ArrowScan::DecodeDictionary(const DecodedBatch& b) {
     d->h_validity = words;   // the same pinned words
   }
   dicts[b.dict_id] = d;
-}
-
-// Tables the tasks read from HBM (list windows, string-view buffers) travel in a pinned aux buffer beside the body.
-void ArrowScan::UploadAux(Slot& s, const std::vector<uint64_t>& aux) {
-  const size_t aux_bytes = aux.size() * 8;
-  if (!aux_bytes) return;
-  Retire(Grow(s.h_aux, aux_bytes, RoundUp(aux_bytes * 2, 4096)));   // the two grow together: twice the need
-  Retire(Grow(s.d_aux, aux_bytes, RoundUp(aux_bytes * 2, 4096)));
-  std::memcpy(s.h_aux.get(), aux.data(), aux_bytes);
-  MI_HIP_CHECK(hipMemcpyAsync(s.d_aux.get(), s.h_aux.get(), aux_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
-}
-
-// Where the planner finds the batch of a slot and where the consumer of its vectors will see the body.
-BatchPlacement ArrowScan::MakePlacement(const Slot& s) {
-  BatchPlacement where;
-  where.batch = &s.batch;
-  where.in_base = s.d_in.get();
-  // a host consumer of a body that only exists decompressed in HBM: string_t rows point into a pinned mirror of the body
-  where.consumer_base = opts.device_resident ? reinterpret_cast<uint64_t>(s.d_in.get())
-                                             : reinterpret_cast<uint64_t>(s.batch.deferred ? s.h_mirror.get() : s.batch.body);
-  where.dict_len = [this](int64_t id) -> int64_t {
-    auto it = dicts.find(id);
-    if (it == dicts.end()) throw IOException("RecordBatch uses dictionary id " + std::to_string(id) + " before its DictionaryBatch");
-    return it->second->dict_len;
-  };
-  return where;
-}
-
-void ArrowScan::CopyRanges(std::vector<std::pair<int64_t, int64_t>> ranges, const uint8_t* from, uint8_t* to, int64_t align_within) {
-  std::sort(ranges.begin(), ranges.end());
-  int64_t lo = -1, hi = -1;
-  auto flush = [&]() {
-    if (lo < 0) return;
-    if (align_within >= 0) hi = std::min<int64_t>((hi + 63) & ~int64_t(63), align_within);
-    MI_HIP_CHECK(hipMemcpyAsync(to + lo, from + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, ctx->h2d_stream));
-    stats.h2d_bytes += hi - lo;
-  };
-  for (const auto& r : ranges) {
-    if (lo >= 0 && r.first <= hi + (64 << 10)) {   // a gap this small is cheaper to copy than to split
-      hi = std::max(hi, r.first + r.second);
-      continue;
-    }
-    flush();
-    lo = align_within >= 0 ? r.first & ~int64_t(63) : r.first;
-    hi = r.first + r.second;
-  }
-  flush();
-}
-
-// A column absent from a file (union_by_name) is an all-NULL vector: reserved by the planner of the stage that lays the
-// projected columns out, zeroed (data 0, validity 0) on the compute stream, handed out by BuildChunk.
-void ArrowScan::PlanAbsentColumn(Slot& s, BatchPlanner& planner, size_t c, int64_t rows) {
-  Slot::Absent& a = s.absent[c];
-  int64_t param;
-  out_columns[c].field.Plan(&a.kind, &param, &a.width);
-  std::tie(a.data_off, a.valid_off) = planner.AddAbsentColumn(rows, a.width);
-}
-
-void ArrowScan::ZeroAbsentColumn(const Slot& s, size_t c, uint8_t* base, int64_t rows) {
-  const Slot::Absent& a = s.absent[c];
-  MI_HIP_CHECK(hipMemsetAsync(base + a.data_off, 0, static_cast<size_t>(rows) * static_cast<size_t>(std::max(a.width, 1)), ctx->stream));
-  MI_HIP_CHECK(hipMemsetAsync(base + a.valid_off, 0, static_cast<size_t>((rows + 63) / 64) * 8, ctx->stream));
-}
-
-// Stage A of a record batch: H2D of the body, the full-width decode tasks (every projected column; with compaction only
-// the filter columns), the filter, the fused aggregate and -- unless the batch is compacted, which needs the selected row
-// count on the host first (stage B) -- the copy back.
-void ArrowScan::EnqueueBatch(Slot& s) {
-  ctx->Bind();
-  const DecodedBatch& b = s.batch;
-  Source& src = sources[static_cast<size_t>(s.source)];
-  const int64_t n = b.length;
-  s.nrows = n;
-  s.compact = compact && n > 0;
-  s.needs_stage_b = false;
-  const int64_t n_windows = (n + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
-  // d_in must be final before tasks take addresses inside it
-  const size_t in_bytes = static_cast<size_t>(b.body_size) + 64;
-  Retire(Grow(s.d_in, in_bytes, GrownCapacity(in_bytes, s.d_in.size(), 1 << 16)));
-
-  PlannerOptions po;
-  po.array_align = kAlign;
-  // DirectConversion: a plain fixed-width column without NULLs needs no kernel at all -- its vector IS the
-  // Arrow buffer.  For a device-resident consumer that is the HBM copy of the body; for a HOST consumer it is the pinned host
-  // body itself, so the column crosses PCIe in neither direction (lineitem: 7 of 16 columns, 46 of 175 B/row in, 46 of 158
-  // B/row back).  On unless asked otherwise (-1) -- except while a consumer reads the vectors on the GPU (the fused COPY).
-  const bool zero_copy = opts.zero_copy_direct >= 0 && (opts.device_resident || !keep_on_device);
-  // a host consumer of a body that only exists decompressed in HBM: string_t rows point into a pinned mirror of the body
-  const bool mirror = b.deferred && !opts.device_resident;
-  // (mi_scan_aggregate reads the vectors in HBM: a host consumer's alias would be the pinned host body)
-  po.zero_copy_direct = zero_copy && !agg.on && !s.compact && !mirror && !(aggn.on && !opts.device_resident);
-  if (mirror) Retire(Grow(s.h_mirror, in_bytes, GrownCapacity(in_bytes, s.h_mirror.size(), 1 << 16)));
-  po.unset_all_valid = opts.unset_all_valid != 0;
-  s.planner.opts = po;
-  s.planner.Clear();
-  s.col_root.assign(out_columns.size(), -1);
-  s.absent.assign(out_columns.size(), {});
-  s.filter_root.assign(filter.columns.size(), -1);
-  s.node_dict.clear();
-
-  BatchPlacement where = MakePlacement(s);
-  // filter columns read their decoded vectors from HBM: never aliased into a body that may not even be uploaded
-  std::vector<char> no_alias(b.nodes.size(), 0);
-  if (has_filter) {
-    for (const int32_t wc : filter.columns) {
-      const int32_t fc = src.FileColumn(wc);
-      if (fc >= 0) no_alias[static_cast<size_t>(b.column_node[static_cast<size_t>(fc)])] = 1;
-    }
-    where.no_alias = &no_alias;
-  }
-  auto width_of = [](const ScanColumn& c) {
-    int32_t kind, w;
-    int64_t param;
-    c.field.Plan(&kind, &param, &w);
-    return w;
-  };
-  // ---- layout.  Full decode: [projected columns | sel | counts] travel back, then the filter-only columns.
-  //      Compaction (stage A): only the filter columns + sel + counts; the projected columns are planned in stage B.
-  if (!s.compact) {
-    for (size_t c = 0; c < out_columns.size(); c++) {
-      if (out_columns[c].is_constant()) continue;
-      const int32_t fc = src.out_to_file_column[c];
-      if (fc < 0) PlanAbsentColumn(s, s.planner, c, n);
-      else s.col_root[c] = s.planner.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
-    }
-  }
-  if (aggn.on) {   // refused before anything of this record batch is queued on the GPU
-    auto present = [&](int32_t c) {
-      if (c >= 0 && src.out_to_file_column[static_cast<size_t>(c)] < 0)
-        throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
-    };
-    for (const auto& a : aggn.aggs) {
-      present(a.col_a);
-      present(a.col_b);
-      for (const auto& f : a.factors) present(f.col);
-    }
-    for (const auto& k : aggn.keys)
-      if (src.out_to_file_column[static_cast<size_t>(k.col)] < 0)
-        throw InvalidInputException("GROUP BY column '" + out_columns[static_cast<size_t>(k.col)].name + "' is absent from a file of the scan");
-  }
-  if (has_filter) {
-    s.sel_off = s.planner.Reserve(static_cast<size_t>(n) * 4 + 16);
-    s.sel_count_off = s.planner.Reserve(static_cast<size_t>(n_windows) * 4 + 16);
-  }
-  s.d2h_bytes = (s.compact || aggn.on) ? 0 : s.planner.arena_bytes;   // (the aggregates' vectors never leave HBM)
-  if (has_filter) {
-    for (size_t k = 0; k < filter.columns.size(); k++) {
-      const int32_t wc = filter.columns[k];
-      if (wc >= 0 && !s.compact) {
-        s.filter_root[k] = s.col_root[static_cast<size_t>(wc)];
-        continue;
-      }
-      const int32_t fc = src.FileColumn(wc);
-      if (fc >= 0) s.filter_root[k] = s.planner.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
-    }
-  }
-  s.stage_a_bytes = s.planner.arena_bytes;
-  s.node_dict.resize(s.planner.nodes.size());
-  for (size_t i = 0; i < s.planner.nodes.size(); i++)
-    if (s.planner.nodes[i].dict_id >= 0) s.node_dict[i] = dicts[s.planner.nodes[i].dict_id];
-  // worst case for stage B: every row selected
-  size_t stage_b_worst = 0;
-  if (s.compact) {
-    stage_b_worst = 4096;
-    for (auto& c : out_columns)
-      if (!c.is_constant())
-        stage_b_worst += RoundUp(static_cast<size_t>(n) * static_cast<size_t>(std::max(width_of(c), 1)) + 16) + RoundUp(static_cast<size_t>((n + 63) / 64) * 8 + 8);
-  }
-  const size_t out_bytes = s.stage_a_bytes + stage_b_worst + 64;
-  Retire(Grow(s.d_out, out_bytes, GrownCapacity(out_bytes, s.d_out.size(), 1 << 16)));
-  EnsureHostOut(s, s.d2h_bytes + 64);
-  Retire(Grow(s.h_counts, static_cast<size_t>(n_windows + 1) * 4, RoundUp(static_cast<size_t>(n_windows + 1) * 8, 4096)));
-  UploadAux(s, s.planner.aux);
-  s.planner.Rebase(0, s.d_out.get(), s.d_aux.get());
-
-  stats.record_batches++;
-  s.h_status.get<uint32_t>()[2] = 0;
-  if (b.deferred) {
-    EnqueueLz4(s);   // compressed body -> HBM -> K8 kernels -> d_in; ctx->stream waits for them
-    if (mirror) {    // the payload of every string-like buffer goes back to the host as soon as it is decompressed
-      for (const DecodedNode& nd : b.nodes) {
-        if (!nd.field) continue;
-        size_t first = 0, last = 0;   // spans [first, last) hold bytes that string_t rows point at
-        switch (nd.field->type) {
-          case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY: first = 2; last = 3; break;
-          case MI_AT_FIXED_BINARY: first = 1; last = 2; break;
-          case MI_AT_UTF8_VIEW: case MI_AT_BINARY_VIEW: first = 2; last = nd.spans.size(); break;
-          default: break;
-        }
-        for (size_t k = first; k < last && k < nd.spans.size(); k++)
-          if (nd.spans[k].length > 0)
-          {
-            MI_HIP_CHECK(hipMemcpyAsync(s.h_mirror.get() + nd.spans[k].offset, s.d_in.get() + nd.spans[k].offset, static_cast<size_t>(nd.spans[k].length),
-                                        hipMemcpyDeviceToHost, ctx->d2h_stream));
-            stats.d2h_bytes += nd.spans[k].length;
-          }
-      }
-    }
-  } else {
-  // ---- H2D of the body on the copy stream: only what the kernels read (projected columns; with zero_copy_direct not even
-  // all of those): merge the buffer ranges, gaps below 64 KiB are cheaper to copy than to split.  A full scan is one copy.
-  std::vector<std::pair<int64_t, int64_t>> upload = s.planner.upload;
-  if (opts.device_resident)  // aliased vectors of a GPU consumer point into the HBM copy of the body
-    for (auto& nd : s.planner.nodes)
-      if (nd.alias_body_off >= 0) upload.emplace_back(nd.alias_body_off, nd.nrows * nd.width);
-  if (s.compact) {  // stage B reads every projected column
-    for (size_t c = 0; c < out_columns.size(); c++) {
-      const int32_t fc = out_columns[c].is_constant() ? -1 : src.out_to_file_column[c];
-      if (fc < 0) continue;
-      for (const auto& sp : b.nodes[static_cast<size_t>(b.column_node[static_cast<size_t>(fc)])].spans)
-        if (sp.length > 0) upload.emplace_back(sp.offset, sp.length);
-    }
-  }
-  if (b.body_size > 0) CopyRanges(std::move(upload), b.body, s.d_in.get(), /*align_within*/ b.body_size);
-  }
-  MI_HIP_CHECK(hipEventRecord(s.h2d_done, ctx->h2d_stream));
-  MI_HIP_CHECK(hipStreamWaitEvent(ctx->stream, s.h2d_done, 0));
-  if (!s.compact && n > 0)
-    for (size_t c = 0; c < out_columns.size(); c++)
-      if (!out_columns[c].is_constant() && src.out_to_file_column[c] < 0) ZeroAbsentColumn(s, c, s.d_out.get(), n);
-  s.plan->Set(s.planner.tasks.data(), static_cast<int32_t>(s.planner.tasks.size()), ctx->stream);
-  MI_HIP_CHECK(hipMemsetAsync(s.plan->d_status.get(), 0, sizeof(uint32_t), ctx->stream));
-  s.plan->Launch(ctx->stream);
-  if (has_filter && n > 0) {
-    const device::FilterProgram prog =
-        filter.Program(out_columns, {b, s.planner.nodes, s.filter_root, s.node_dict, s.d_in.get(), s.d_out.get(), s.d_out.get() + s.sel_off}, ctx->stream);
-    MI_HIP_CHECK(device::LaunchFilterProgram(prog, n, reinterpret_cast<mi_sel_t*>(s.d_out.get() + s.sel_off),
-                                             reinterpret_cast<uint32_t*>(s.d_out.get() + s.sel_count_off), ctx->stream));
-  }
-  if (agg.on && n > 0) {
-    // fused consumer: the decoded vectors are read once more by the aggregate kernel and never leave HBM
-    device::AggSumProductArgs a;
-    std::memset(&a, 0, sizeof(a));
-    auto column = [&](int32_t c, const void** data, const uint64_t** valid, int32_t* width) {
-      if (s.col_root[static_cast<size_t>(c)] < 0) throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
-      const PlannedNode& o = s.planner.nodes[static_cast<size_t>(s.col_root[static_cast<size_t>(c)])];
-      *data = s.d_out.get() + o.data_off;
-      *valid = o.valid_off >= 0 ? reinterpret_cast<const uint64_t*>(s.d_out.get() + o.valid_off) : nullptr;
-      *width = o.width;
-    };
-    a.n_filters = static_cast<int32_t>(agg.filter_cols.size());
-    for (int32_t k = 0; k < a.n_filters; k++) {
-      column(agg.filter_cols[static_cast<size_t>(k)], &a.fcol[k], &a.fvalid[k], &a.fwidth[k]);
-      a.lo[k] = agg.lo[static_cast<size_t>(k)];
-      a.hi[k] = agg.hi[static_cast<size_t>(k)];
-    }
-    column(agg.col_a, &a.a, &a.avalid, &a.awidth);
-    column(agg.col_b, &a.b, &a.bvalid, &a.bwidth);
-    a.nrows = n;
-    MI_HIP_CHECK(device::LaunchAggSumProduct(a, agg.d_acc.get<unsigned long long>(), ctx->num_cus, ctx->stream));
-    agg.rows_scanned += n;
-  }
-  if (aggn.on && n > 0) EnqueueAggregates(s);
-  MI_HIP_CHECK(hipEventRecord(s.compute_done, ctx->stream));
-  MI_HIP_CHECK(hipStreamWaitEvent(ctx->d2h_stream, s.compute_done, 0));
-  if (has_filter && n > 0)  // the per-window counts always come back (tiny): chunk sizes, Count(), the stage-B layout
-    MI_HIP_CHECK(hipMemcpyAsync(s.h_counts.get<uint32_t>(), s.d_out.get() + s.sel_count_off, static_cast<size_t>(n_windows) * 4, hipMemcpyDeviceToHost, ctx->d2h_stream));
-  if (s.compact) {
-    MI_HIP_CHECK(hipEventRecord(s.filter_done, ctx->d2h_stream));
-    s.needs_stage_b = true;
-    return;
-  }
-  s.host_vectors = !opts.device_resident && !agg.on && !aggn.on && s.d2h_bytes > 0 && !keep_on_device;
-  if (s.host_vectors) {
-    MI_HIP_CHECK(hipMemcpyAsync(s.h_out.get(), s.d_out.get(), s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
-    stats.d2h_bytes += static_cast<int64_t>(s.d2h_bytes);
-  }
-  for (const auto& nd : s.planner.nodes)
-    if (nd.alias_body_off >= 0) stats.aliased_bytes += nd.nrows * nd.width;
-  // the device status word travels with the results instead of costing a stream-wide synchronisation
-  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>(), s.plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
-  s.h_status.get<uint32_t>()[1] = 0;
-  MI_HIP_CHECK(hipEventRecord(s.d2h_done, ctx->d2h_stream));
-}
-
-// K8: the record batch arrived with its LZ4_FRAME buffers still compressed (DecodedBatch::deferred).  The compressed bytes
-// cross PCIe, the frames' blocks (tables built by the host reader from the block headers) are expanded into s.d_in at the
-// decompressed layout every span of the batch already refers to.
-void ArrowScan::EnqueueLz4(Slot& s) {
-  const int64_t t_k8 = trace ? TraceNow() : 0;
-  const DecodedBatch& b = s.batch;
-  const DeferredBody& d = *b.deferred;
-  if (!s.lz4_stream) {
-    // the slots share kLz4Streams streams (slot i uses stream i mod 3): the K8 kernels of neighbouring record batches overlap
-    // -- the token walk is latency-bound and leaves the chip idle -- without every slot holding a hardware queue of its own
-    // (one stream: 0.65 s for SF10, two 0.42, three 0.39, one per slot (8) 0.46)
-    // ZSTD: the entropy stage is one serial chain per block (milliseconds, a few lanes busy): more batches side by side
-    // With hardware queues to spare -- GPU_MAX_HW_QUEUES, which the HIP runtime reads at start-up (default 4), raised by
-    // the deployment to at least slots + 3 -- every slot gets a stream of its own: 0.24 s instead of 0.29 s at 8 slots
-    // and 20 queues (profiles/r02/lz4/streams_ab.txt); on the default 4 queues the same choice was the 0.46 s above.
-    int kLz4Streams = d.codec == 1 ? 16 : 3;
-    const int n_slots = static_cast<int>(slots.size());
-    if (HardwareQueues() >= n_slots + 3) kLz4Streams = n_slots;
-    const int idx = static_cast<int>(&s - slots.data());
-    if (idx >= kLz4Streams) {
-      Slot& owner = slots[static_cast<size_t>(idx % kLz4Streams)];
-      if (!owner.lz4_stream) owner.lz4_stream = owner.own_lz4_stream = HipStream::Create();
-      s.lz4_stream = owner.lz4_stream;
-    } else {
-      s.lz4_stream = s.own_lz4_stream = HipStream::Create();
-    }
-    s.lz4_done = HipEvent::Create();
-  }
-  const size_t out_size = static_cast<size_t>(b.body_size);
-  const size_t nb = d.blocks.size(), nf = d.buffers.size();
-  // scratch layout
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += RoundUp(bytes + 16, 256); return o; };
-  const size_t o_blocks = take(nb * sizeof(device::Lz4BlockDev)), o_buffers = take(nf * sizeof(device::Lz4BufferDev));
-  const bool is_zstd = d.codec == 1;
-  const size_t o_zblocks = take(is_zstd ? nb * sizeof(zstd::BlockInfo) : 0);
-  const size_t tables_bytes = at;
-  uint64_t total_seq = 0, max_len = 0;
-  uint32_t max_blocks = 0;
-  for (auto& blk : d.blocks) total_seq += is_zstd ? blk.seq_cap : device::Lz4SeqCapacity(blk.comp_size);
-  // ZSTD: the decoded literals of every block lie behind the compressed body, in the same allocation
-  const size_t lit_base = RoundUp(static_cast<size_t>(d.comp_size) + 64, 256);
-  const size_t comp_need = is_zstd ? lit_base + d.literal_scratch + 64 : static_cast<size_t>(d.comp_size) + 64;
-  const size_t o_bsize = take(nb * 4), o_bnseq = take(nb * 4), o_bbase = take(nb * 8), o_chunk = take((nb + 1) * 4), o_bufok = take(nf * 4), o_round = take(40 * 4),
-               o_status = take(4), o_mark = take(out_size + 16);
-  const size_t counters_end = at;
-  const size_t o_seq = take(static_cast<size_t>(total_seq) * 16), o_seqoff = take(static_cast<size_t>(total_seq) * 4);
-  const size_t o_lane_out = take(nb * 256 * 4), o_lane_n = take(nb * 256 * 4), o_rep = take(is_zstd ? nb * 256 * 16 : 0);
-  const size_t o_link = take(out_size * 4 + 16), o_skel = take(out_size * 4 + 16);
-  Retire(Grow(s.d_lz4, at, GrownCapacity(at, s.d_lz4.size(), 1 << 20)));
-  Retire(Grow(s.d_comp, comp_need, GrownCapacity(comp_need, s.d_comp.size(), 1 << 16)));
-  Retire(Grow(s.h_lz4, tables_bytes, RoundUp(std::max(tables_bytes, s.h_lz4.size() * 2), 1 << 16)));   // doubles
-  auto* hb = reinterpret_cast<device::Lz4BlockDev*>(s.h_lz4.get() + o_blocks);
-  auto* hf = reinterpret_cast<device::Lz4BufferDev*>(s.h_lz4.get() + o_buffers);
-  uint32_t seq_at = 0;
-  for (size_t i = 0; i < nb; i++) {
-    const auto& blk = d.blocks[i];
-    hb[i].comp_off = blk.comp_off;
-    hb[i].comp_size = blk.comp_size;
-    hb[i].buffer = blk.buffer;
-    hb[i].stored = blk.stored;
-    hb[i].seq_base = seq_at;
-    hb[i].seq_cap = is_zstd ? blk.seq_cap : device::Lz4SeqCapacity(blk.comp_size);
-    seq_at += hb[i].seq_cap;
-  }
-  if (is_zstd) {
-    auto* hz = reinterpret_cast<zstd::BlockInfo*>(s.h_lz4.get() + o_zblocks);
-    for (size_t i = 0; i < nb; i++) {
-      hz[i] = d.zblocks[i];
-      const bool in_scratch = hz[i].type == 1 || (hz[i].type == 2 && hz[i].lit_type != 0);
-      if (in_scratch) hz[i].lit_pos += static_cast<uint32_t>(lit_base);
-    }
-  }
-  for (size_t i = 0; i < nf; i++) {
-    const auto& f = d.buffers[i];
-    hf[i].out_off = static_cast<uint64_t>(f.out_off);
-    // a raw buffer (length prefix -1: Arrow C++ with min_space_savings, arrow-rs, Arrow Java) has no blocks: the layout
-    // kernels check "sum of the block sizes == out_len", which for it is 0 == 0; its bytes are copied below
-    hf[i].out_len = f.raw ? 0 : static_cast<uint64_t>(f.out_len);
-    hf[i].first_block = f.first_block;
-    hf[i].n_blocks = f.raw ? 0 : f.n_blocks;
-    hf[i].block_max = f.block_max;
-    hf[i].independent = f.independent ? 1u : 0u;
-    if (!f.raw) {
-      max_len = std::max<uint64_t>(max_len, static_cast<uint64_t>(f.out_len));
-      max_blocks = std::max<uint32_t>(max_blocks, f.n_blocks);
-    }
-  }
-  // H2D on the copy stream: the compressed bytes of the needed buffers (neighbours closer than 64 KiB travel as one copy)
-  std::vector<std::pair<int64_t, int64_t>> ranges;
-  for (auto& f : d.buffers) ranges.emplace_back(f.comp_off, f.comp_len);
-  if (is_zstd) stats.zstd_batches_on_device++;
-  else stats.lz4_batches_on_device++;
-  stats.decompressed_bytes += b.body_size;
-  CopyRanges(std::move(ranges), d.comp, s.d_comp.get(), /*align_within*/ -1);
-  MI_HIP_CHECK(hipMemcpyAsync(s.d_lz4.get(), s.h_lz4.get(), tables_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
-  MI_HIP_CHECK(hipEventRecord(s.h2d_done, ctx->h2d_stream));
-  hipStream_t q = s.lz4_stream;
-  MI_HIP_CHECK(hipStreamWaitEvent(q, s.h2d_done, 0));
-  // ONE memset per record batch: counters, status, marks.  The link words need none (every word a stage reads was written
-  // by the stage before it), nor does the body: the bytes between its buffers are padding nobody reads.
-  MI_HIP_CHECK(hipMemsetAsync(s.d_lz4.get() + tables_bytes, 0, counters_end - tables_bytes, q));
-  for (auto& f : d.buffers)
-    if (f.raw && f.out_len > 0)
-      MI_HIP_CHECK(hipMemcpyAsync(s.d_in.get() + f.out_off, s.d_comp.get() + f.comp_off, static_cast<size_t>(f.out_len), hipMemcpyDeviceToDevice, q));
-  device::Lz4Args a;
-  std::memset(&a, 0, sizeof(a));
-  a.comp = s.d_comp.get();
-  a.out = s.d_in.get();
-  a.out_size = out_size;
-  a.max_buffer_len = max_len;
-  a.max_buffer_blocks = max_blocks;
-  a.blocks = reinterpret_cast<const device::Lz4BlockDev*>(s.d_lz4.get() + o_blocks);
-  a.buffers = reinterpret_cast<const device::Lz4BufferDev*>(s.d_lz4.get() + o_buffers);
-  a.n_blocks = static_cast<uint32_t>(nb);
-  a.n_buffers = static_cast<uint32_t>(nf);
-  a.min_block_comp = 0xFFFFFFFFu;
-  for (auto& blk : d.blocks)
-    if (!blk.stored) {   // LZ4: which token walk fits; ZSTD: how much LDS the staged block takes
-      a.max_block_comp = std::max(a.max_block_comp, blk.comp_size);
-      a.min_block_comp = std::min(a.min_block_comp, blk.comp_size);
-    }
-  a.seq = s.d_lz4.get() + o_seq;
-  a.seq_off = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_seqoff);
-  a.lane_out = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_lane_out);
-  a.lane_nseq = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_lane_n);
-  a.link = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_link);
-  a.block_out_size = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_bsize);
-  a.block_nseq = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_bnseq);
-  a.block_out_base = reinterpret_cast<uint64_t*>(s.d_lz4.get() + o_bbase);
-  a.chunk_base = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_chunk);
-  a.buffer_ok = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_bufok);
-  a.round_left = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_round);
-  a.mark = s.d_lz4.get() + o_mark;
-  a.skel = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_skel);
-  a.status = reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_status);
-  a.zblocks = is_zstd ? s.d_lz4.get() + o_zblocks : nullptr;
-  a.literals = s.d_comp.get();
-  a.rep_state = is_zstd ? reinterpret_cast<uint32_t*>(s.d_lz4.get() + o_rep) : nullptr;
-  const int64_t t_launch = trace ? TraceNow() : 0;
-  MI_HIP_CHECK(device::LaunchLz4Decompress(a, ctx->num_cus, q));
-  if (trace) {
-    tr_k8_prep_ns += t_launch - t_k8;
-    tr_k8_launch_ns += TraceNow() - t_launch;
-  }
-  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>() + 2, a.status, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>() + 4, a.round_left + 37, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-  s.lz4_counted = false;
-  MI_HIP_CHECK(hipEventRecord(s.lz4_done, q));
-  MI_HIP_CHECK(hipStreamWaitEvent(ctx->stream, s.lz4_done, 0));
-  MI_HIP_CHECK(hipStreamWaitEvent(ctx->d2h_stream, s.lz4_done, 0));
-}
-
-// Stage B of a compacted batch: the filter's counts are on the host, so the projected columns get a dense layout sized
-// for the rows that survived; the gather kernel decodes exactly those and only they travel back.
-void ArrowScan::EnqueueStageB(Slot& s) {
-  ctx->Bind();
-  MI_HIP_CHECK(hipEventSynchronize(s.filter_done));
-  const DecodedBatch& b = s.batch;
-  Source& src = sources[static_cast<size_t>(s.source)];
-  const int64_t n = b.length;
-  const int64_t n_windows = (n + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
-  int64_t total = 0;
-  for (int64_t w = 0; w < n_windows; w++) total += s.h_counts.get<uint32_t>()[w];
-  s.needs_stage_b = false;
-  // a fresh planner pass for the projected columns: arena offsets relative to the compact region behind stage A's arrays
-  BatchPlanner cp(s.planner.opts);
-  cp.opts.zero_copy_direct = false;
-  BatchPlacement where = MakePlacement(s);
-  where.alloc_rows = total;
-  s.col_root.assign(out_columns.size(), -1);
-  for (size_t c = 0; c < out_columns.size(); c++) {
-    if (out_columns[c].is_constant()) continue;
-    const int32_t fc = src.out_to_file_column[c];
-    if (fc < 0) PlanAbsentColumn(s, cp, c, total);
-    else s.col_root[c] = cp.AddColumn(where, b.column_node[static_cast<size_t>(fc)]);
-  }
-  s.d2h_bytes = cp.arena_bytes;
-  const size_t region_off = RoundUp(s.stage_a_bytes, 4096);
-  if (region_off + cp.arena_bytes + 64 > s.d_out.size()) throw InternalException("compact region exceeds the slot");
-  uint8_t* region = s.d_out.get() + region_off;
-  EnsureHostOut(s, s.d2h_bytes + 64);
-  cp.Rebase(0, region, nullptr);
-  for (auto& t : cp.tasks) {
-    t.sel = s.d_out.get() + s.sel_off;
-    t.sel_count = s.d_out.get() + s.sel_count_off;
-  }
-  hipStream_t st = ctx->stream;
-  // validity words start as all ones (the gather kernel clears the NULLs); absent columns are all NULL
-  for (size_t c = 0; c < out_columns.size(); c++) {
-    if (out_columns[c].is_constant() || total == 0) continue;
-    if (s.col_root[c] < 0) {
-      ZeroAbsentColumn(s, c, region, total);
-      continue;
-    }
-    const PlannedNode& pn = cp.nodes[static_cast<size_t>(s.col_root[c])];
-    if (pn.valid_off >= 0) MI_HIP_CHECK(hipMemsetAsync(region + pn.valid_off, 0xFF, static_cast<size_t>((total + 63) / 64) * 8 + 8, st));
-  }
-  s.gather_plan->Set(cp.tasks.data(), static_cast<int32_t>(total > 0 ? cp.tasks.size() : 0), st);
-  MI_HIP_CHECK(hipMemsetAsync(s.gather_plan->d_status.get(), 0, sizeof(uint32_t), st));
-  if (total > 0) s.gather_plan->Launch(st);
-  MI_HIP_CHECK(hipEventRecord(s.compute_done, st));
-  MI_HIP_CHECK(hipStreamWaitEvent(ctx->d2h_stream, s.compute_done, 0));
-  if (!opts.device_resident && s.d2h_bytes > 0 && total > 0) {
-    MI_HIP_CHECK(hipMemcpyAsync(s.h_out.get(), region, s.d2h_bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
-    stats.d2h_bytes += static_cast<int64_t>(s.d2h_bytes);
-  }
-  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>(), s.plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
-  MI_HIP_CHECK(hipMemcpyAsync(s.h_status.get<uint32_t>() + 1, s.gather_plan->d_status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->d2h_stream));
-  MI_HIP_CHECK(hipEventRecord(s.d2h_done, ctx->d2h_stream));
-  // the chunk builder reads the compact layout from here on
-  s.node_dict.assign(cp.nodes.size(), nullptr);
-  for (size_t i = 0; i < cp.nodes.size(); i++)
-    if (cp.nodes[i].dict_id >= 0) s.node_dict[i] = dicts[cp.nodes[i].dict_id];
-  s.compact_region = region;
-  s.planner.nodes = std::move(cp.nodes);
 }
 
 // The vector of node `node` for chunk window `window`, children included.  Full layout: rows win[window] .. win[window + 1]
@@ -1324,112 +742,6 @@ void ArrowScan::SumProduct(const std::string& a, const std::string& b, const std
 
 double ArrowScan::Progress() { return readahead.Progress(); }
 
-// ------------------------------------------------------------------------------------------------ multi-device
-MultiDeviceScan::MultiDeviceScan(const std::vector<Context*>& ctxs, std::vector<std::string> paths, const mi_scan_options& o) {
-  if (ctxs.empty()) throw InvalidInputException("mi_scan_open_files_multi needs at least one context");
-  const int32_t n = static_cast<int32_t>(ctxs.size());
-  const int32_t outer_world = o.world > 1 ? o.world : 1, outer_rank = o.world > 1 ? o.rank : 0;
-  if (outer_rank < 0 || outer_rank >= outer_world) throw InvalidInputException("rank outside [0, world)");
-  for (int32_t i = 0; i < n; i++) {
-    if (!ctxs[static_cast<size_t>(i)]) throw InvalidInputException("mi_scan_open_files_multi: NULL context");
-    mi_scan_options so = o;
-    // batch k of the file list belongs to this scan when k mod world == rank; its j-th batch goes to context j mod n:
-    // k = rank + world * j  =>  sub-scan i takes the batches with k mod (world * n) == rank + world * i
-    so.world = outer_world * n;
-    so.rank = outer_rank + outer_world * i;
-    subs.push_back(std::make_unique<ArrowScan>(ctxs[static_cast<size_t>(i)], paths, so));
-  }
-  EnsureIoThreads(8 * n);  // every device reads its own record batches out of the page cache
-  pending.resize(subs.size());
-  have.assign(subs.size(), 0);
-  done.assign(subs.size(), 0);
-}
-
-const std::vector<ScanColumn>& MultiDeviceScan::Bind() {
-  for (size_t i = 1; i < subs.size(); i++) subs[i]->Bind();
-  return subs[0]->Bind();
-}
-
-void MultiDeviceScan::Init(const std::vector<std::string>& projected) {
-  for (auto& s : subs) s->Init(projected);
-}
-
-void MultiDeviceScan::SetFilter(FilterCnf cnf) {
-  for (auto& s : subs) s->SetFilter(cnf);
-}
-
-void MultiDeviceScan::ForEachParallel(const std::function<void(size_t)>& fn) {
-  std::vector<std::thread> threads;
-  std::vector<std::exception_ptr> errors(subs.size());
-  for (size_t i = 0; i < subs.size(); i++)
-    threads.emplace_back([&, i] {
-      try {
-        fn(i);
-      } catch (...) {
-        errors[i] = std::current_exception();
-      }
-    });
-  for (auto& t : threads) t.join();
-  for (auto& e : errors)
-    if (e) std::rethrow_exception(e);
-}
-
-// k-way merge on the record-batch ordinal: every sub-scan yields its own batches in ascending order, so the chunk to emit
-// is the pending one with the smallest batch_index.  A pending chunk stays valid until its sub-scan is pulled again, which
-// happens only after the consumer has come back for the next chunk.
-void MultiDeviceScan::Next(mi_data_chunk* out) {
-  if (last_emitted >= 0) {
-    have[static_cast<size_t>(last_emitted)] = 0;
-    last_emitted = -1;
-  }
-  int best = -1;
-  for (size_t i = 0; i < subs.size(); i++) {
-    if (!have[i] && !done[i]) {
-      subs[i]->Next(&pending[i]);
-      if (pending[i].size == 0) done[i] = 1;
-      else have[i] = 1;
-    }
-    if (have[i] && (best < 0 || pending[i].batch_index < pending[static_cast<size_t>(best)].batch_index)) best = static_cast<int>(i);
-  }
-  if (best < 0) {
-    std::memset(out, 0, sizeof(*out));
-    out->n_columns = static_cast<int32_t>(subs[0]->NumOutputColumns());
-    return;
-  }
-  *out = pending[static_cast<size_t>(best)];
-  last_emitted = best;
-}
-
-void MultiDeviceScan::Count(int64_t* rows, int64_t* selected, int64_t* chunks) {
-  std::vector<int64_t> r(subs.size(), 0), s(subs.size(), 0), c(subs.size(), 0);
-  ForEachParallel([&](size_t i) { subs[i]->Count(&r[i], &s[i], &c[i]); });
-  int64_t tr = 0, ts = 0, tc = 0;
-  for (size_t i = 0; i < subs.size(); i++) {
-    tr += r[i];
-    ts += s[i];
-    tc += c[i];
-  }
-  if (rows) *rows = tr;
-  if (selected) *selected = ts;
-  if (chunks) *chunks = tc;
-}
-
-void MultiDeviceScan::SumProduct(const std::string& a, const std::string& b, const std::vector<std::string>& filter_columns,
-                                 const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) {
-  std::vector<mi_sum_product_result> parts(subs.size());
-  for (auto& p : parts) std::memset(&p, 0, sizeof(p));
-  ForEachParallel([&](size_t i) { subs[i]->SumProduct(a, b, filter_columns, lo, hi, &parts[i]); });
-  unsigned __int128 sum = 0;
-  std::memset(out, 0, sizeof(*out));
-  for (auto& p : parts) {
-    sum += (static_cast<unsigned __int128>(static_cast<uint64_t>(p.sum_hi)) << 64) | p.sum_lo;  // two's complement: wraps like the device
-    out->rows_scanned += p.rows_scanned;
-    out->rows_selected += p.rows_selected;
-  }
-  out->sum_lo = static_cast<uint64_t>(sum);
-  out->sum_hi = static_cast<int64_t>(static_cast<uint64_t>(sum >> 64));
-}
-
 void ArrowScan::Stats(mi_scan_stats* out) {
   out->record_batches += stats.record_batches;
   out->lz4_batches_on_device += stats.lz4_batches_on_device;
@@ -1441,16 +753,6 @@ void ArrowScan::Stats(mi_scan_stats* out) {
   out->zstd_batches_on_device += stats.zstd_batches_on_device;
   out->d2h_bytes += stats.d2h_bytes;
   out->aliased_bytes += stats.aliased_bytes;
-}
-
-void MultiDeviceScan::Stats(mi_scan_stats* out) {
-  for (auto& s : subs) s->Stats(out);
-}
-
-double MultiDeviceScan::Progress() {
-  double p = 0;
-  for (auto& s : subs) p += s->Progress();
-  return p / static_cast<double>(subs.size());
 }
 
 }  // namespace miarrow

@@ -17,6 +17,11 @@
 //                              the per-batch FilterProgram
 //   scan_aggregate.{hpp,cpp}   the fused aggregates (mi_scan_aggregate, mi_scan_group_aggregate): their types, the methods
 //                              below that bind, enqueue and drain them, their C ABI
+//   scan_enqueue.cpp           what a record batch costs the GPU: stage A and stage B of ArrowScan as named steps, the K8
+//                              staging, the helpers both stages share
+//   scan_k8.{hpp,cpp}          the K8 scratch arena as data: layout, pinned tables, launch arguments (host code only)
+//   scan_dictionary.{hpp,cpp}  DictState and the host side of a dictionary version (host code only)
+//   scan_multi.cpp             MultiDeviceScan, over ArrowScan's public interface
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -35,6 +40,7 @@
 #include "engine.hpp"
 #include "ipc_stream_reader.hpp"
 #include "scan_aggregate.hpp"
+#include "scan_dictionary.hpp"
 #include "scan_readahead.hpp"
 
 namespace miarrow {
@@ -49,7 +55,6 @@ struct ScanColumn {
   bool is_constant() const { return is_filename || is_hive; }
 };
 
-inline bool IsStringKind(int32_t kind) { return kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY; }
 //! a run-end encoded column is filtered on its flat vector: what matters is the field of its values
 inline const ArrowField& ValueField(const ArrowField& f) { return f.type == MI_AT_RUN_END && f.children.size() == 2 ? f.children[1] : f; }
 //! Columns a range comparison / the fused aggregate reads as integers: integers, DATE, TIME / TIMESTAMP, DECIMAL(<= 18)
@@ -99,30 +104,6 @@ void CheckPattern(int compiled, int32_t op, const std::string& column);
 //! what a column's values are compared as by a pushed-down filter
 enum class FilterValueClass { kOther, kFloat32, kFloat64, kWide };
 FilterValueClass FilterClassOf(const ArrowField& field);
-
-//! One immutable version of a decoded dictionary (dict_len + 1 entries, the last one NULL).  Record batches keep the
-//! version they were enqueued with, so a later replacement / delta never changes what an in-flight batch sees.
-struct DictState {
-  DeviceBuffer d_data;           // decoded values on the device
-  DeviceBuffer d_validity;
-  PinnedBuffer h_data;           // pinned host copy (host consumers)
-  void* h_validity = nullptr;    // == h_words for host consumers
-  PinnedBuffer h_words;          // the validity words (uint64_t) as built on the host (uploaded from here)
-  PinnedBuffer h_status;         // status word (uint32_t) of the decode of the values, checked with the first batch that uses them
-  HipEvent uploaded;             // the dictionary body is in HBM
-  std::unique_ptr<Plan> decode_plan;   // kept until the version dies: its status word is read asynchronously
-  std::vector<std::shared_ptr<void>> d_heaps;      // device copies of the dictionary bodies (long string payload)
-  std::vector<std::shared_ptr<void>> host_bodies;  // host bodies: long dictionary strings point into them
-  int64_t dict_len = 0;
-  int32_t kind = 0, out_width = 0;
-  //! string-valued dictionaries: the values themselves (empty + not valid for NULL entries), for pushed-down string
-  //! predicates -- the dictionary is matched once, on the host, the rows by index (K6, kLeafDictMap)
-  std::vector<std::string> host_strings;
-  std::vector<char> host_valid;
-  //! FLOAT / DOUBLE / 128-bit dictionaries: the decoded values (out_width bytes each), for the same purpose
-  std::vector<uint8_t> host_values;
-  std::map<size_t, std::shared_ptr<void>> match_maps;   // filter leaf -> device byte per entry: 0 no, 1 yes, 2 NULL
-};
 
 //! A pushed-down filter bound to the columns of a scan (ArrowScan::Init)
 struct BoundFilter {
@@ -208,6 +189,9 @@ class ScanBase {
   virtual double Progress() = 0;
   virtual void Stats(mi_scan_stats* out) = 0;   // adds to *out
 };
+
+constexpr size_t kAlign = 256;   // arrays in HBM start on a multiple of this
+inline size_t AlignUp(size_t v, size_t a = kAlign) { return (v + a - 1) / a * a; }
 
 constexpr int kMaxDepth = 16;   // pipeline slots of a scan at most (24 and 32 were measured with 40 hardware queues: slower for both codecs of K8)
 
@@ -325,12 +309,35 @@ class ArrowScan : public ScanBase {
   std::vector<std::string> MapColumns(size_t si, const ArrowSchemaModel& schema);
   void GrowSlots(size_t n);
   void InitSlot(Slot& s);
-  void EnqueueBatch(Slot& s);
-  void EnqueueStageB(Slot& s);
-  void EnqueueLz4(Slot& s);
-  void UploadAux(Slot& s, const std::vector<uint64_t>& aux);
   void BuildVector(const Slot& s, int32_t node, size_t window, int64_t compact_rows, uint8_t* base, ChunkStorage* st, mi_vector* out);
   void DecodeDictionary(const DecodedBatch& b);
+  // ---- scan_enqueue.cpp: the GPU work of one record batch
+  //! stage A: body upload, full-width decode, filter, fused aggregates and -- unless the batch is compacted -- the copy back
+  void EnqueueBatch(Slot& s);
+  //! stage B of a compacted batch, once the filter's counts are on the host: gather of the selected rows, the copy back
+  void EnqueueStageB(Slot& s);
+  // the steps of stage A, in the order EnqueueBatch calls them
+  bool SetPlannerOptions(Slot& s, size_t in_bytes);
+  void LayOutStageA(Slot& s);
+  void RefuseAbsentAggregateColumns(const Source& src) const;
+  void SizeSlotBuffers(Slot& s);
+  void UploadBody(Slot& s, bool mirror);
+  void EnqueueLz4(Slot& s);
+  void ChooseLz4Stream(Slot& s, int32_t codec);
+  void MirrorStringPayload(Slot& s);
+  void LaunchStageA(Slot& s);
+  void EnqueueSumProduct(Slot& s);
+  void CopyBackStageA(Slot& s);
+  // what both stages do
+  //! every output column that is not a constant into `planner`: decoded from the file's column (its root goes to
+  //! s.col_root), or -- absent from this file -- an all-NULL vector of `rows` rows
+  void PlanOutputColumns(Slot& s, BatchPlanner& planner, const BatchPlacement& where, int64_t rows);
+  //! s.node_dict: the dictionary version every node of `nodes` uses as of now
+  void BindNodeDicts(Slot& s, const std::vector<PlannedNode>& nodes);
+  //! the status words of the slot's plans travel home behind the results (instead of costing a stream-wide synchronisation),
+  //! then d2h_done: stage A has one word (`with_gather` false: word 1 is zeroed), stage B two
+  void SendStatusHome(Slot& s, bool with_gather);
+  void UploadAux(Slot& s, const std::vector<uint64_t>& aux);
   BatchPlacement MakePlacement(const Slot& s);
   //! H2D on the copy stream: `ranges` ({offset, length}, the same in `from` and `to`) closer than 64 KiB travel as one copy.
   //! align_within >= 0: every copy starts and ends on a multiple of 64 bytes, or at that size.
@@ -340,6 +347,7 @@ class ArrowScan : public ScanBase {
   //! ... and zeroed on the compute stream
   void ZeroAbsentColumn(const Slot& s, size_t column, uint8_t* base, int64_t rows);
   void EnsureHostOut(Slot& s, size_t bytes);
+  // ----
   Slot* FreeSlot();
 
   Context* ctx;

@@ -329,6 +329,44 @@ def test_dictionary_encoded_double_equals_its_plain_twin(con, tmp_path):
         assert con.read_arrow(path, accept_dictionaries=True, filter_compact=True).project(["k"]).filter(expr).fetch_columns()[0] == want, expr
 
 
+def test_float16_dictionary_replaced_then_extended_by_a_delta(con, tmp_path):
+    """A float16 dictionary (widened to FLOAT on the host for the filter, on the device for the rows): 5 values, replaced by 65
+    -- the extra NULL entry then lands in a new validity word -- and extended by a delta of 2, a record batch after each; a
+    host consumer with a comparison pushed down on the column, against numpy over pyarrow's reading of the same file."""
+    rng = np.random.default_rng(23)
+    n = 2500
+    first = np.array([1.5, -0.0, 65504.0, -np.inf, 0.25], np.float16)
+    second = np.concatenate([np.array([0.0, -0.0, 6e-8, 6.104e-5, 65504.0, -65504.0, np.inf, -np.inf, 1.5], np.float16),
+                             (np.arange(56) / 4 - 5).astype(np.float16)])
+    third = np.concatenate([second, np.array([np.nan, 2.75], np.float16)])
+    assert len(second) == 65 and len(third) == 67
+    sch = pa.schema([("k", pa.int64()), ("d", pa.dictionary(pa.int16(), pa.float16()))])
+    path = str(tmp_path / "f16_dict.arrows")
+    with ipc.new_stream(path, sch, options=ipc.IpcWriteOptions(emit_dictionary_deltas=True)) as w:
+        for bi, values in enumerate((first, second, third)):
+            # the second entry of every dictionary is NULL, a tenth of the rows are NULL through their index
+            d = pa.DictionaryArray.from_arrays(pa.array(rng.integers(0, len(values), n).astype(np.int16), mask=rng.random(n) < 0.1),
+                                               pa.array(values, pa.float16(), mask=np.arange(len(values)) == 1))
+            w.write_batch(pa.record_batch([pa.array(np.arange(bi * n, (bi + 1) * n, dtype=np.int64)), d], schema=sch))
+    reader = ipc.open_stream(path)
+    plain = reader.read_all().column("d").cast(pa.float16())
+    assert reader.stats.num_dictionary_batches == 3 and reader.stats.num_replaced_dictionaries == 1 and reader.stats.num_dictionary_deltas == 1
+    null = np.asarray(plain.is_null())
+    vals = np.asarray(plain.fill_null(0)).astype(np.float32)
+    py = [None if m else float(v) for v, m in zip(vals, null)]
+    for expr in (("d", ">=", 1.5), ("d", "=", NAN), ("d", "<", 6.104e-5), ("d", "is null"), ("d", "in", [2.75, -0.0, 65504.0])):
+        if expr[1] == "is null":
+            mask = null
+        elif expr[1] == "in":
+            mask = np.logical_or.reduce([_compare_float(vals, "=", c, True) for c in expr[2]]) & ~null
+        else:
+            mask = _compare_float(vals, expr[1], expr[2], True) & ~null
+        want = np.flatnonzero(mask).tolist()
+        got_k, got_d = con.read_arrow(path, accept_dictionaries=True).project(["k", "d"]).filter(expr).fetch_columns()
+        assert got_k == want and len(want) > 0, expr
+        assert _same(got_d, [py[i] for i in want]), expr
+
+
 # ------------------------------------------------------------------------------------------------ 4. errors
 def _set_raw_filter(rel, column, value, value_kind):
     node = _ffi.FilterNode(op=_ffi.F_EQ, column=column.encode(), value=value, value_kind=value_kind)

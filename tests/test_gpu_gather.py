@@ -391,3 +391,76 @@ def test_compacted_scan_of_a_compressed_body(con, table_file, tmp_path, codec):
     """The gather kernel reads a body that was decompressed in HBM."""
     t, _ = table_file
     _scan_equals_pyarrow(con, t, _write_table(t, str(tmp_path / "z.arrows"), codec), "half")
+
+
+@pytest.mark.parametrize("device_resident", [False, True], ids=["host", "device_resident"])
+def test_compacted_scan_with_a_column_absent_from_the_second_file(con, tmp_path, device_resident):
+    """filter_compact with union_by_name over two files, the second without column `x`: both stages plan the output columns
+    (stage A when a batch is empty, stage B for the rows that survived) and zero the absent column's all-NULL vector.  Three
+    record batches of 5000 rows per file -- three windows, the last one ragged -- of which the first keeps every row, the
+    second none and the third about half; equal to pyarrow's reading of the two files, a host consumer and vectors in HBM."""
+    import ctypes as C
+    import pyarrow as pa
+    import pyarrow.ipc as ipc
+    from helpers import pyarrow_columns
+    from test_gpu_scan_operator import _mirror_device_vector
+    rng = np.random.default_rng(41)
+    rows, tables, paths = 5000, [], []
+    for fi in range(2):
+        n = 3 * rows
+        keep = np.concatenate([np.ones(rows, np.int8), np.zeros(rows, np.int8), (rng.random(rows) < 0.5).astype(np.int8)])
+        cols = {"k": pa.array(np.arange(n, dtype=np.int64) + fi * n), "keep": pa.array(keep),
+                "s": pa.array(["row %d %s" % (i, "long enough to leave the inline form" * (i % 3)) for i in range(n)], mask=rng.random(n) < 0.1),
+                "v": pa.array(rng.integers(-1000, 1000, n).astype(np.int32), mask=rng.random(n) < 0.2)}
+        if fi == 0:
+            cols["x"] = pa.array(rng.integers(0, 1 << 40, n), mask=rng.random(n) < 0.3)
+        t = pa.table(cols)
+        p = str(tmp_path / ("f%d.arrows" % fi))
+        with ipc.new_stream(p, t.schema) as w:
+            w.write_table(t, max_chunksize=rows)
+        tables.append(t)
+        paths.append(p)
+    names = ["k", "x", "s", "v"]
+    whole = pa.concat_tables([tables[0], tables[1].append_column("x", pa.nulls(3 * rows, pa.int64()))]).select(names + ["keep"])
+    want = pyarrow_columns(whole.filter(pa.array(np.asarray(whole.column("keep")) == 1)).select(names))
+    assert len(want[0]) > 2 * rows and want[1][-1] is None
+    rel = con.read_arrow(paths, union_by_name=True, filter_compact=True, device_resident=device_resident).project(names).filter(("keep", "=", 1))
+    if not device_resident:
+        assert canon_python(rel.fetch_columns()) == want
+        return
+    hip = C.CDLL("libamdhip64.so")
+    types = [da.parse_duck_type(x) for x in rel.types]
+    got = [[] for _ in types]
+    for ch in rel.chunks():
+        held = []
+        for ci, ty in enumerate(types):
+            got[ci].extend(da._vector_values(_mirror_device_vector(hip, ch.columns[ci], ty, ch.size, held), ty, ch.size))
+    assert canon_python(got) == want
+
+
+def test_compacted_scan_reports_what_the_gather_kernel_found(con, tmp_path):
+    """The status word of stage B's gather plan travels home beside stage A's: a string column with one decreasing offset,
+    projected but not filtered on, is decoded by the gather kernel alone when the scan compacts -- the scan fails as the
+    selection-vector scan of the same file does, and the undamaged twin reads."""
+    import pyarrow as pa
+    import pyarrow.ipc as ipc
+    n = 3000
+    t = pa.table({"k": pa.array(np.arange(n, dtype=np.int64)), "s": pa.array(["value %d of a string column" % i for i in range(n)])})
+    good = str(tmp_path / "good.arrows")
+    with ipc.new_stream(good, t.schema) as w:
+        w.write_table(t)
+    raw = bytearray(open(good, "rb").read())
+    offsets = np.asarray(t.column("s").chunk(0).buffers()[1]).view(np.int32)[: n + 1].copy()
+    at = bytes(raw).find(offsets.tobytes())
+    assert at > 0 and bytes(raw).find(offsets.tobytes(), at + 1) < 0
+    offsets[1500] = offsets[1501] + 7            # row 1499 ends behind the start of row 1501: row 1500 has a negative length
+    raw[at: at + 4 * (n + 1)] = offsets.tobytes()
+    bad = str(tmp_path / "bad.arrows")
+    open(bad, "wb").write(bytes(raw))
+    scan = lambda path, compact: con.read_arrow(path, filter_compact=compact).project(["k", "s"]).filter(("k", ">=", 1000)).fetch_columns()
+    assert scan(good, True) == scan(good, False) and len(scan(good, True)[0]) == 2000
+    with pytest.raises(da.MiError) as flat:
+        scan(bad, False)
+    with pytest.raises(da.MiError) as compact:
+        scan(bad, True)
+    assert str(compact.value) == str(flat.value) and compact.value.code == flat.value.code

@@ -314,7 +314,7 @@ def test_lz4_parse_kernel_variants(tmp_path, variant):
 @pytest.mark.gpu
 def test_lz4_one_stream_per_slot_with_hardware_queues_to_spare(tmp_path):
     """With GPU_MAX_HW_QUEUES >= slots + 3 in the process environment the K8 kernels of every slot run on a stream of their
-    own (scan_operator.cpp EnqueueLz4) instead of three shared ones: many small record batches in flight, the same vectors."""
+    own (scan_enqueue.cpp ChooseLz4Stream) instead of three shared ones: many small record batches in flight, the same vectors."""
     import subprocess, sys, textwrap
     code = textwrap.dedent("""
         import os, sys
@@ -340,3 +340,67 @@ def test_lz4_one_stream_per_slot_with_hardware_queues_to_spare(tmp_path):
     """) % (ROOT, str(tmp_path / "q.arrows"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, GPU_MAX_HW_QUEUES="20"), timeout=300)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
+
+
+def test_host_consumer_of_a_body_expanded_in_hbm_gets_every_kind_of_string_payload(con, tmp_path):
+    """A host consumer of LZ4 record batches that are expanded in HBM reads string_t rows that point into a pinned mirror of
+    the body, into which the payload buffers are copied back: buffer 2 of utf8 / large_binary, buffer 1 of fixed_size_binary,
+    every variadic buffer of a string view (here two).  Two record batches of 3000 rows, against pyarrow."""
+    rng = np.random.default_rng(61)
+    n = 6000
+    t = pa.table({
+        "u": pa.array(["utf8 %d %s" % (i, "past the inline twelve bytes" * (i % 3)) for i in range(n)], mask=rng.random(n) < 0.1),
+        "lb": pa.array([b"\x00large %d" % i + b"\xff" * (i % 23) for i in range(n)], pa.large_binary(), mask=rng.random(n) < 0.1),
+        "fb": pa.array([b"%013d" % i for i in range(n)], pa.binary(13), mask=rng.random(n) < 0.1),
+        # 16 bytes each, an array per record batch: 48000 bytes of payload, which pyarrow keeps in two data buffers
+        "sv": pa.chunked_array([pa.array(["view %011d" % i for i in range(lo, lo + 3000)], pa.string_view()) for lo in (0, 3000)]),
+        "k": pa.array(np.arange(n, dtype=np.int64)),
+    })
+    path = str(tmp_path / "strings.arrows")
+    _write(path, t, 3000)
+    batches = list(ipc.open_stream(path))
+    assert [b.num_rows for b in batches] == [3000, 3000] and all(len(b.column("sv").buffers()) == 4 for b in batches)
+    rel = con.read_arrow(path, host_decompress="gpu")
+    assert [canon_python(c) for c in rel.fetch_columns()] == pyarrow_columns(t)
+    assert rel.stats()["lz4_batches_on_device"] == 2
+
+
+def _messages(stream_bytes):
+    out = []
+    with pa.BufferReader(stream_bytes) as br:
+        reader = ipc.MessageReader.open_stream(br)
+        while True:
+            try:
+                out.append(reader.read_next_message().serialize().to_pybytes())
+            except StopIteration:
+                return out
+
+
+def test_plain_and_lz4_batches_with_raw_buffers_in_one_scan_that_grows_its_slots(con, tmp_path):
+    """One stream whose record batches are plain, plain, LZ4, LZ4, plain, LZ4, LZ4, plain (compression is a property of the
+    message), the LZ4 ones with their second buffer stored raw.  With pipeline_depth left to the scan it starts with three
+    slots and grows to eight at the first compressed body, while the plain batches in front of it are in flight; a GPU and a
+    host consumer, against pyarrow."""
+    rng = np.random.default_rng(67)
+    n = 8 * 3000
+    t = pa.table({"k": pa.array(np.arange(n, dtype=np.int64)), "r": pa.array(rng.integers(0, 1 << 62, n)),
+                  "s": pa.array(["row %d %s" % (i % 101, "x" * (i % 17)) for i in range(n)], mask=rng.random(n) < 0.1)})
+
+    def stream(codec):
+        sink = pa.BufferOutputStream()
+        with ipc.new_stream(sink, t.schema, options=ipc.IpcWriteOptions(compression=codec)) as w:
+            w.write_table(t, max_chunksize=3000)
+        return sink.getvalue().to_pybytes()
+
+    plain, packed = _messages(stream(None)), _messages(rewrite_buffers_raw(stream("lz4"), lambda bi, k, ln: k == 1))
+    assert len(plain) == len(packed) == 9       # the schema and eight record batches
+    mixed = plain[0] + b"".join((plain if i in (1, 2, 5, 8) else packed)[i] for i in range(1, 9)) + b"\xff\xff\xff\xff\x00\x00\x00\x00"
+    assert ipc.open_stream(pa.py_buffer(mixed)).read_all().equals(t)
+    path = str(tmp_path / "mixed.arrows")
+    open(path, "wb").write(mixed)
+    want = pyarrow_columns(t)
+    got, st = _device_scan(con, path, pipeline_depth=0)
+    assert got == want and st["record_batches"] == 8 and st["lz4_batches_on_device"] == 4, st
+    rel = con.read_arrow(path, host_decompress="gpu", pipeline_depth=0)
+    assert [canon_python(c) for c in rel.fetch_columns()] == want
+    assert rel.stats()["lz4_batches_on_device"] == 4

@@ -210,3 +210,44 @@ def test_io_pool_under_tsan_and_asan_ubsan(tmp_path):
             assert run.returncode == 0, (name, case, run.stdout[-1000:], run.stderr[-3000:])
             assert re.search(r"^\d+ checks, 0 failed$", run.stdout, re.M), (name, case, run.stdout, run.stderr[-3000:])
             assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, (name, case, run.stderr[-3000:])
+
+
+def _build_and_run_check(tmp_path, name, sources):
+    """g++ -fsanitize=address,undefined over tests/sanitize/<name>.cpp and `sources` (of csrc); the headers name HIP types,
+    so the ROCm include directory is on the path, but nothing of HIP is called or linked."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    csrc = os.path.join(ROOT, "duckdb-arrow_amd", "csrc")
+    exe = str(tmp_path / name)
+    build = subprocess.run(
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
+         "-I", os.path.join(ROOT, "include"), "-I", csrc, "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"),
+         os.path.join(ROOT, "tests", "sanitize", name + ".cpp")] + [os.path.join(csrc, s) for s in sources] + ["-o", exe],
+        capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr.lower() and "cannot find" in build.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
+    assert run.returncode == 0, (run.stdout[-1000:], run.stderr[-3000:])
+    assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr and "FAILED" not in run.stderr, run.stderr[-3000:]
+    m = re.search(r"^(\d+) checks, 0 failed$", run.stdout, re.M)
+    assert m, run.stdout
+    return int(m.group(1))
+
+
+def test_k8_scratch_arena_under_asan_and_ubsan(tmp_path):
+    """The K8 staging's arithmetic (duckdb-arrow_amd/csrc/scan_k8.cpp: where every table, counter and scratch array of a
+    compressed record batch lies, the pinned tables, the launch arguments) is host code without a HIP call;
+    tests/sanitize/k8_scratch_check.cpp runs it over hand-built LZ4 and ZSTD bodies -- empty, 0 / 1 / 300 blocks, a raw buffer
+    between compressed ones, stored blocks, a 1-byte and a 4 MiB block -- against offsets written out from the rule
+    round_up(bytes + 16, 256), and fills the tables into an allocation of exactly the reported size."""
+    assert _build_and_run_check(tmp_path, "k8_scratch_check", ["scan_k8.cpp"]) > 3000
+
+
+def test_dictionary_host_side_under_asan_and_ubsan(tmp_path):
+    """The host side of a dictionary version (duckdb-arrow_amd/csrc/scan_dictionary.cpp: validity words, host_valid,
+    host_strings with their offset checks, host_values with the float16 widening) reads bytes that come from a file;
+    tests/sanitize/dictionary_host_check.cpp runs it over hand-built DictionaryBatch bodies whose buffer under test ends the
+    allocation: replace and delta, bitmaps, the word edges 0 / 1 / 63 / 64 / 65, STR32 / STR64 / FIXED_BINARY, float16 against
+    numpy's bit patterns, float64, 128-bit values, and damaged inputs beside clean twins, each of which must raise."""
+    assert _build_and_run_check(tmp_path, "dictionary_host_check", ["scan_dictionary.cpp"]) > 60000

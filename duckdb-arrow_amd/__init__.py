@@ -668,6 +668,16 @@ def parse_duck_type(text):
                 name, _, rest = part.partition(" ")
             kids.append((name, parse_duck_type(rest)))
         return ("struct", kids)
+    if text.startswith("UNION(") and text.endswith(")"):
+        kids = []
+        for part in _split_top(text[6:-1]):
+            if part.startswith('"'):
+                j = part.index('"', 1)
+                name, rest = part[1:j], part[j + 1:]
+            else:
+                name, _, rest = part.partition(" ")
+            kids.append((name, parse_duck_type(rest)))
+        return ("union", kids)
     if text.startswith("MAP(") and text.endswith(")"):
         k, v = _split_top(text[4:-1])
         return ("map", parse_duck_type(k), parse_duck_type(v))
@@ -703,6 +713,13 @@ def _vector_values(v, ty, n):
         child = v.children[0]
         cvals = _vector_values(child, ty[1], child.count)
         return [cvals[r * ty[2]: (r + 1) * ty[2]] if ok[r] else None for r in range(n)]
+    if ty[0] == "union":
+        if v.n_children == 0:      # a column absent from this file (union_by_name): an all-NULL vector without a tree
+            return [None] * n
+        # children: the tag vector (UTINYINT member index), then one vector per member; a row is its selected member's value
+        tags = _flat_values("UTINYINT", 1, v.children[0].data, None, n)
+        kids = [_vector_values(v.children[1 + i], kt, n) for i, (_, kt) in enumerate(ty[1])]
+        return [kids[tags[r]][r] if ok[r] else None for r in range(n)]
     kids = [_vector_values(v.children[i], kt, n) for i, (_, kt) in enumerate(ty[1])]
     return [{nm: kid[r] for (nm, _), kid in zip(ty[1], kids)} if ok[r] else None for r in range(n)]
 

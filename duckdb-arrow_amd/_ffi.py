@@ -18,6 +18,8 @@ K_COPY, K_BOOL, K_DEC128, K_DATE64, K_MUL_I32, K_MUL_I64, K_DIV_I64, K_STR32, K_
     K_DURATION, K_INTERVAL_MONTHS, K_INTERVAL_MDN, K_NARROW, K_HALF_FLOAT, K_NULL, K_STRVIEW, K_LIST32, K_LIST64, \
     K_STRUCT = range(1, 22)
 K_RUN_END = 22
+K_UNION, K_UNION_DENSE = 23, 24
+MAX_UNION_MEMBERS = 32
 K_ENC_COPY, K_ENC_DEC128, K_ENC_BOOL, K_ENC_STR32, K_ENC_VALIDITY, K_ENC_LIST32, K_ENC_STRVIEW = 32, 33, 34, 35, 36, 37, 38
 
 ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL_RANGE, ST_OFFSET_OVERFLOW, ST_DICT_INDEX, ST_INTERNAL = \
@@ -25,6 +27,7 @@ ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL
 ST_BAD_RUN_ENDS = 512
 ST_SEL_RANGE = 1024
 ST_GROUP_LIMIT, ST_GROUP_KEY_LONG = 2048, 4096
+ST_BAD_UNION_TAG, ST_BAD_UNION_OFFSET = 8192, 16384
 
 
 class Field(C.Structure):

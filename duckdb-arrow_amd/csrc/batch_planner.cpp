@@ -4,6 +4,8 @@
 #include <algorithm>
 #include <cstring>
 
+#include "union_format.hpp"
+
 namespace miarrow {
 
 namespace {
@@ -80,8 +82,19 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
     }
     if (nd.children.size() != 2) throw InternalException("run-end encoded field without exactly two children");
   }
+  if (kind == MI_K_UNION) {
+    // the members take their NULLs from masks in the union's row numbering (Supported() refuses these at bind already)
+    for (int32_t a = parent; a >= 0; a = nodes[static_cast<size_t>(a)].parent) {
+      const int32_t at = nodes[static_cast<size_t>(a)].arrow_type;
+      if (at == MI_AT_LIST || at == MI_AT_LARGE_LIST || at == MI_AT_MAP || at == MI_AT_FIXED_LIST || at == MI_AT_RUN_END)
+        throw NotImplementedException("Column '" + nd.field->name + "': unions inside a list / map / fixed_size_list / run-end encoded array are not decoded by the MI355X scan path");
+    }
+    if (nd.children.size() != nd.field->children.size() || nd.children.empty() || nd.children.size() > MI_MAX_UNION_MEMBERS)
+      throw InternalException("union field whose nodes do not match its members");
+  }
   const DecodedNode* ree_values = kind == MI_K_RUN_END ? &b.nodes[static_cast<size_t>(nd.children[1])] : nullptr;
-  const bool scratch = parent >= 0 && nodes[static_cast<size_t>(parent)].kind == MI_K_RUN_END;  // values of a run-end array
+  // values of a run-end array, member array of a dense union: decoded in their own row space, expanded by index afterwards
+  const bool scratch = parent >= 0 && (nodes[static_cast<size_t>(parent)].kind == MI_K_RUN_END || nodes[static_cast<size_t>(parent)].kind == MI_K_UNION_DENSE);
   const int32_t idx = static_cast<int32_t>(nodes.size());
   nodes.emplace_back();
   auto span = [&](size_t k) { return k < nd.spans.size() ? nd.spans[k] : mi_buffer_span{0, 0}; };
@@ -105,7 +118,15 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
       return idx;
     }
     // a run-end array's NULLs are its values' NULLs
-    const int64_t nulls = ree_values ? ree_values->null_count : nd.null_count;
+    int64_t nulls = ree_values ? ree_values->null_count : nd.null_count;
+    if (kind == MI_K_UNION) {  // ... and a union's are its members': without a bitmap that can clear a bit every row is valid
+      nulls = 0;
+      for (int32_t cn : nd.children) {
+        const DecodedNode& m = b.nodes[static_cast<size_t>(cn)];
+        if (m.null_count != 0 || m.field->type == MI_AT_NULL) nulls = -1;
+      }
+      o.null_count = nulls;
+    }
     const bool all_valid = opts.unset_all_valid && nulls == 0 && parent_valid_off < 0 && extra_rows == 0 && kind != MI_K_NULL;
     Alloc((where.alloc_rows >= 0 && nd.depth == 0 ? where.alloc_rows : n) + extra_rows, w, !all_valid, &o.data_off, &o.valid_off);
   }
@@ -182,6 +203,38 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
       o.heap_size = v.heap_size;
       break;
     }
+    case MI_K_UNION: {
+      // tags in the node's data array; behind it one mask per member, each followed by a spare word
+      const size_t m = nd.children.size();
+      const bool dense = nd.field->unit == 1;
+      const size_t stride = static_cast<size_t>((n + 63) / 64) * 8 + 8;
+      const size_t mask_off = Reserve(m * stride);
+      nodes[static_cast<size_t>(idx)].mask_off = static_cast<int64_t>(mask_off);
+      nodes[static_cast<size_t>(idx)].mask_stride = static_cast<int64_t>(stride);
+      t.validity = nullptr;
+      t.null_count = 0;
+      t.buf1 = where.in_base + span(0).offset;
+      t.ptr_base = dense ? reinterpret_cast<uint64_t>(where.in_base + span(1).offset) : 0;
+      t.param2 = static_cast<int64_t>(mask_off) - static_cast<int64_t>(data_off);
+      t.buf2_len = static_cast<int64_t>(stride);
+      // the union table (mi_arrow_ipc.h: MI_K_UNION)
+      int8_t table[unionfmt::kTableEntries];
+      const ArrowField& uf = *nd.field;
+      unionfmt::BuildTable(uf.type_ids.data(), uf.has_type_ids ? static_cast<int>(uf.type_ids.size()) : -1, static_cast<int>(m), table);
+      aux_at = static_cast<int64_t>(aux.size());
+      aux.resize(aux.size() + unionfmt::kTableWords);
+      std::memcpy(&aux[static_cast<size_t>(aux_at)], table, sizeof(table));
+      for (int32_t cn : nd.children) {
+        const DecodedNode& mn = b.nodes[static_cast<size_t>(cn)];
+        const bool null_type = mn.field->type == MI_AT_NULL;
+        const bool bitmap = !null_type && !mn.spans.empty() && mn.spans[0].length > 0;
+        aux.push_back(bitmap ? reinterpret_cast<uint64_t>(where.in_base + mn.spans[0].offset) : 0);
+        aux.push_back(static_cast<uint64_t>(mn.length));
+        aux.push_back(static_cast<uint64_t>(bitmap ? mn.null_count : 0));
+        aux.push_back(null_type ? unionfmt::kMemberNullType : 0);
+      }
+      break;
+    }
     case MI_K_LIST32: case MI_K_LIST64: {
       if (nd.children.size() != 1) throw InternalException("list field without exactly one child");
       t.param = b.nodes[static_cast<size_t>(nd.children[0])].length;
@@ -212,19 +265,21 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
     }
     default: break;
   }
-  nodes[static_cast<size_t>(idx)].ptr_base = t.ptr_base;
-  if (kind != MI_K_RUN_END) nodes[static_cast<size_t>(idx)].heap_size = kind == MI_K_FIXED_BINARY ? span(1).length : t.buf2_len;
+  nodes[static_cast<size_t>(idx)].ptr_base = kind == MI_K_UNION ? 0 : t.ptr_base;
+  if (kind != MI_K_RUN_END && kind != MI_K_UNION) nodes[static_cast<size_t>(idx)].heap_size = kind == MI_K_FIXED_BINARY ? span(1).length : t.buf2_len;
   // a struct without NULLs of its own or of a parent has nothing to compute when its validity stays unset
   const bool has_work = n > 0 && !(kind == MI_K_STRUCT && valid_off < 0);
   if (has_work) {
     if (aux_at >= 0) aux_fixups.emplace_back(tasks.size(), static_cast<size_t>(aux_at));
-    if (kind == MI_K_RUN_END) value_fixups.push_back(tasks.size());
+    if (kind == MI_K_RUN_END) value_fixups.push_back(tasks.size());  // (dense union members: AddUnionChildren)
     nodes[static_cast<size_t>(idx)].task = static_cast<int32_t>(tasks.size());
     tasks.push_back(t);
   }
   if (kind == MI_K_LIST32 || kind == MI_K_LIST64) {
     const int32_t c = AddNode(where, nd.children[0], child_win, false, -1, 0, idx, 0);
     nodes[static_cast<size_t>(idx)].children.push_back(c);
+  } else if (kind == MI_K_UNION) {
+    AddUnionChildren(where, ni, idx, win, win_is_tiles);
   } else if (kind == MI_K_STRUCT && !nd.children.empty()) {
     const bool fixed = nd.field->type == MI_AT_FIXED_LIST;
     const int64_t size = fixed ? param : 1;
@@ -236,6 +291,97 @@ int32_t BatchPlanner::AddNode(const BatchPlacement& where, int32_t ni, std::vect
     }
   }
   return idx;
+}
+
+// The children of a planned union node, as DuckDB's UNION vector lists them: the tag vector (the union's own data array), then
+// one vector per member.  Sparse: the member array itself, a struct child whose parent words are the member's mask.  Dense:
+// a vector of the union's length that an MI_K_UNION_DENSE task fills from the member array, which is decoded by its usual
+// task into a scratch vector of its own row space (never aliased), as a run-end array's values are.
+void BatchPlanner::AddUnionChildren(const BatchPlacement& where, int32_t ni, int32_t idx, const std::vector<int64_t>& win, bool win_is_tiles) {
+  const DecodedBatch& b = *where.batch;
+  const DecodedNode& nd = b.nodes[static_cast<size_t>(ni)];
+  const bool dense = nd.field->unit == 1;
+  const int64_t n = nd.length;
+  const PlannedNode u = nodes[static_cast<size_t>(idx)];  // (a copy: `nodes` grows below)
+  {
+    const int32_t ti = static_cast<int32_t>(nodes.size());
+    nodes.emplace_back();
+    PlannedNode& tag = nodes.back();
+    tag.synth = 1;
+    tag.kind = MI_K_COPY;
+    tag.width = 1;
+    tag.param = 1;
+    tag.arrow_type = MI_AT_INT;
+    tag.nrows = n;
+    tag.depth = u.depth + 1;
+    tag.parent = idx;
+    tag.win = win;
+    tag.source_node = ni;
+    tag.data_off = u.data_off;
+    nodes[static_cast<size_t>(idx)].children.push_back(ti);
+  }
+  for (size_t k = 0; k < nd.children.size(); k++) {
+    const int64_t mask = u.mask_off + static_cast<int64_t>(k) * u.mask_stride;
+    if (!dense) {
+      const int32_t c = AddNode(where, nd.children[k], win, win_is_tiles, mask, 1, idx, 0);
+      nodes[static_cast<size_t>(idx)].children.push_back(c);
+      continue;
+    }
+    const DecodedNode& mn = b.nodes[static_cast<size_t>(nd.children[k])];
+    int32_t mk, mw;
+    int64_t mp;
+    if (!mn.field->Plan(&mk, &mp, &mw)) throw InternalException("dense union member without a decode kind");
+    const int32_t di = static_cast<int32_t>(nodes.size());
+    nodes.emplace_back();
+    {
+      PlannedNode& d = nodes.back();
+      d.synth = 2;
+      d.kind = MI_K_UNION_DENSE;
+      d.value_kind = mk;
+      d.width = mw;
+      d.param = mw;
+      d.arrow_type = mn.field->type;
+      d.nrows = n;
+      d.null_count = -1;
+      d.depth = u.depth + 1;
+      d.parent = idx;
+      d.win = win;
+      d.source_node = nd.children[k];
+      Alloc(n, mw, true, &d.data_off, &d.valid_off);
+    }
+    nodes[static_cast<size_t>(idx)].children.push_back(di);
+    std::vector<int64_t> vwin;
+    for (int64_t r = 0; r < mn.length; r += MI_VECTOR_SIZE) vwin.push_back(r);
+    vwin.push_back(mn.length);
+    if (mn.length == 0) vwin.push_back(0);
+    const int32_t vi = AddNode(where, nd.children[k], std::move(vwin), true, -1, 0, di, 0);
+    const PlannedNode& v = nodes[static_cast<size_t>(vi)];
+    PlannedNode& d = nodes[static_cast<size_t>(di)];
+    d.ptr_base = v.ptr_base;
+    d.heap_size = v.heap_size;
+    if (n == 0) continue;
+    mi_col_task t;
+    std::memset(&t, 0, sizeof(t));
+    t.kind = MI_K_UNION_DENSE;
+    t.nrows = n;
+    t.depth = d.depth;
+    t.param = mw;
+    t.flags = 1;
+    t.buf1 = where.in_base + nd.spans[1].offset;
+    t.buf2 = OffsetHandle(static_cast<int64_t>(v.data_off));
+    t.buf2_len = v.nrows;
+    if (v.valid_off >= 0 && v.null_count != 0) {
+      t.validity = OffsetHandle(v.valid_off);
+      t.null_count = v.null_count;
+    }
+    t.ptr_base = v.ptr_base;
+    t.out_data = OffsetHandle(static_cast<int64_t>(d.data_off));
+    t.out_validity = OffsetHandle(d.valid_off);
+    t.out_aux = OffsetHandle(mask);
+    value_fixups.push_back(tasks.size());
+    d.task = static_cast<int32_t>(tasks.size());
+    tasks.push_back(t);
+  }
 }
 
 void BatchPlanner::Rebase(size_t first_task, uint8_t* arena_base, const uint8_t* aux_base) {

@@ -35,7 +35,12 @@ struct PlannedNode {
   int64_t heap_size = 0;               //               bytes of that data buffer
   int32_t source_node = -1;            // index into DecodedBatch::nodes
   int32_t task = -1;                   // index into BatchPlanner::tasks (-1: no task -- empty, aliased or nothing to do)
-  int32_t value_kind = 0;              // MI_K_RUN_END: kind of the values child (decoded as scratch, not one of `children`)
+  int32_t value_kind = 0;              // MI_K_RUN_END / MI_K_UNION_DENSE: kind of the values child / the member array (decoded
+                                       // as scratch, not one of `children`)
+  int64_t mask_off = -1, mask_stride = 0;  // MI_K_UNION: arena offset of member 0's mask, bytes from one mask to the next
+  int32_t synth = 0;                   // a child the planner made, not a field node of the batch: 1 = the tag vector of a union
+                                       // (its data array IS the union's), 2 = a dense union member, expanded from its scratch
+                                       // vector (source_node = the member's node, which the scratch vector shares)
 };
 
 struct PlannerOptions {
@@ -84,7 +89,8 @@ class BatchPlanner {
   int32_t AddNode(const BatchPlacement& where, int32_t ni, std::vector<int64_t> win, bool win_is_tiles, int64_t parent_valid_off,
                   int32_t parent_div, int32_t parent, int64_t extra_rows);
   std::vector<std::pair<size_t, size_t>> aux_fixups;      // (task index, first aux word)
-  std::vector<size_t> value_fixups;                       // MI_K_RUN_END tasks: buf2 / validity are arena offsets too
+  void AddUnionChildren(const BatchPlacement& where, int32_t ni, int32_t idx, const std::vector<int64_t>& win, bool win_is_tiles);
+  std::vector<size_t> value_fixups;                       // MI_K_RUN_END / MI_K_UNION_DENSE tasks: buf2 / validity are arena offsets too
   friend class HbmStream;
 };
 

@@ -354,6 +354,8 @@ void SliceBatch(const ArrowSchemaModel& schema, const std::vector<int32_t>& proj
       const int32_t pt = pn.field->type;
       if (pt == MI_AT_STRUCT && n != pn.length)
         throw InternalException("Struct child " + f.name + " has length " + std::to_string(n) + ", its parent " + std::to_string(pn.length));
+      if (pt == MI_AT_UNION && pn.field->unit == 0 && !pn.field->has_dictionary && n != pn.length)
+        throw InternalException("Sparse union member " + f.name + " has length " + std::to_string(n) + ", its parent " + std::to_string(pn.length));
       if (pt == MI_AT_FIXED_LIST) {
         int64_t expect = 0;  // length <= 2^40 and listSize < 2^31: checked anyway, the product sizes buffers
         if (__builtin_mul_overflow(pn.length, static_cast<int64_t>(pn.field->byte_width), &expect) || n != expect)
@@ -383,6 +385,7 @@ void SliceBatch(const ArrowSchemaModel& schema, const std::vector<int32_t>& proj
       const mi_buffer_span none{0, 0};
       const mi_buffer_span& s0 = own > 0 ? nd.spans[0] : none;
       const mi_buffer_span& s1 = own > 1 ? nd.spans[1] : none;
+      if (kind == MI_K_UNION && s0.length < n) throw InternalException(BufferSizeError(f.name, 0, n, s0.length));  // type ids, no validity
       if (s0.length != 0 && s0.length < (n + 7) / 8) throw InternalException(BufferSizeError(f.name, 0, (n + 7) / 8, s0.length));
       if (kind != MI_K_NULL && s0.length == 0 && n > 0 && nulls > 0)
         throw InternalException("Column " + f.name + " has null_count " + std::to_string(nulls) + " but no validity buffer");

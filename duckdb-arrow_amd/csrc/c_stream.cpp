@@ -146,7 +146,7 @@ void CheckOffsets(const DecodedBatch& b, const DecodedNode& nd, int64_t limit, c
 void ValidateNodeFull(const DecodedBatch& b, const DecodedNode& nd, const std::map<int64_t, std::shared_ptr<DictValues>>& dicts) {
   int32_t kind, w;
   int64_t param;
-  if (!nd.field->Plan(&kind, &param, &w, nd.value_only))
+  if (!nd.field->Plan(&kind, &param, &w, nd.value_only) || kind == MI_K_UNION)   // unions are decoded by the scan, not exported
     throw NotImplementedException("Arrow type " + nd.field->Format() + " of field '" + nd.field->name + "' is not exported by this reader");
   switch (kind) {
     case MI_K_STR32: CheckOffsets<int32_t>(b, nd, nd.spans[2].length, "string"); break;

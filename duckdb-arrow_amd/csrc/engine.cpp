@@ -104,6 +104,8 @@ int OutWidth(int32_t kind, int64_t param) {
     case MI_K_STRUCT: return 0;
     case MI_K_DICT: return 4;
     case MI_K_RUN_END: return static_cast<int>((param >> 8) & 0xFF);
+    case MI_K_UNION: return 1;
+    case MI_K_UNION_DENSE: return static_cast<int>(param);
     default: return 0;
   }
 }
@@ -112,7 +114,8 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
   auto fail = [&](const std::string& what) {
     throw InvalidInputException("task " + std::to_string(i) + ": " + what);
   };
-  if (t.kind != MI_K_RUN_END && t.kind != MI_K_ENC_STRVIEW && device::ClassOfKind(t.kind) < 0) fail("unknown kind " + std::to_string(t.kind));
+  const bool own_kernel = t.kind == MI_K_RUN_END || t.kind == MI_K_ENC_STRVIEW || t.kind == MI_K_UNION || t.kind == MI_K_UNION_DENSE;
+  if (!own_kernel && device::ClassOfKind(t.kind) < 0) fail("unknown kind " + std::to_string(t.kind));
   if (t.sel != nullptr) {  // gather mode: decode only the rows a selection vector names, compacted per 2048-row window
     if (!device::KindCanGather(t.kind)) fail("kind " + std::to_string(t.kind) + " cannot be decoded through a selection vector");
     if (t.sel_count == nullptr) fail("gather tasks need sel_count (rows selected per 2048-row window)");
@@ -191,6 +194,26 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
       if (t.flags > 1) fail("RUN_END parents are structs (flags 0 or 1)");
       break;
     }
+    case MI_K_UNION: {
+      const int64_t words = (t.nrows + 63) / 64;
+      if (t.param < 1 || t.param > MI_MAX_UNION_MEMBERS) fail("UNION needs param = number of members, 1 .. " + std::to_string(MI_MAX_UNION_MEMBERS));
+      if (t.buf2 == nullptr || reinterpret_cast<uintptr_t>(t.buf2) % 8 != 0) fail("UNION needs the union table (8-byte aligned) in buf2");
+      if (t.ptr_base % 4 != 0) fail("UNION dense offsets misaligned");
+      if (t.param2 <= 0 || t.param2 % 8 != 0 || t.param2 < t.nrows) fail("UNION needs param2 = distance from out_data to mask 0: a multiple of 8 behind the tags");
+      if (t.buf2_len % 8 != 0 || t.buf2_len < 8 * words) fail("UNION needs buf2_len = distance between masks: a multiple of 8, at least 8 ceil(nrows / 64)");
+      if (t.flags > 1) fail("UNION parents are structs (flags 0 or 1)");
+      if (t.sel != nullptr) fail("UNION tasks cannot be decoded through a selection vector");
+      break;
+    }
+    case MI_K_UNION_DENSE:
+      if (t.param != 1 && t.param != 2 && t.param != 4 && t.param != 8 && t.param != 16) fail("UNION_DENSE width must be 1,2,4,8,16");
+      if (reinterpret_cast<uintptr_t>(t.buf1) % 4 != 0) fail("UNION_DENSE offsets misaligned");
+      if (t.buf2 == nullptr || reinterpret_cast<uintptr_t>(t.buf2) % 16 != 0) fail("UNION_DENSE needs the member's decoded vector (16-byte aligned) in buf2");
+      if (t.buf2_len < 0) fail("UNION_DENSE needs buf2_len = rows of the member's vector");
+      if (t.out_aux == nullptr || reinterpret_cast<uintptr_t>(t.out_aux) % 8 != 0) fail("UNION_DENSE needs the member's mask (8-byte aligned) in out_aux");
+      if (t.flags > 1) fail("UNION_DENSE masks have the union's row numbering (flags 0 or 1)");
+      if (t.sel != nullptr) fail("UNION_DENSE tasks cannot be decoded through a selection vector");
+      break;
     case MI_K_ENC_COPY:
       if (t.param != 1 && t.param != 2 && t.param != 4 && t.param != 8 && t.param != 16) fail("ENC_COPY width must be 1,2,4,8,16");
       break;
@@ -215,6 +238,10 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
 constexpr int kRunEndSlot = device::kNumClasses;
 // ... and of string-view encode tasks (encode_string_view, kernels_encode_view.hip); their bytes count under kClassEncString
 constexpr int kEncViewSlot = device::kNumClasses + 1;
+// ... of union tag passes (transcode_union, kernels_union.hip: with the other slices of their depth, so before anything
+// deeper) and of dense union expansions (transcode_union_dense: with the run-end slices); both count under kClassMisc
+constexpr int kUnionSlot = device::kNumClasses + 2;
+constexpr int kUnionDenseSlot = device::kNumClasses + 3;
 
 static int64_t TaskBytesRead(const mi_col_task& t) {
   const int64_t n = t.nrows;
@@ -223,6 +250,10 @@ static int64_t TaskBytesRead(const mi_col_task& t) {
     b = t.param2 * ((t.param & 0xFF) + ((t.param >> 8) & 0xFF)) + (t.validity ? ((t.param2 + 63) / 64) * 8 : 0);
     return b + (t.out_aux ? ((n + 63) / 64) * 8 : 0);
   }
+  if (t.kind == MI_K_UNION)   // type ids, dense offsets, the parent's words (member bitmaps: a bit per row at most, not counted)
+    return n * (t.ptr_base ? 5 : 1) + (t.out_aux ? ((n + 63) / 64) * 8 : 0);
+  if (t.kind == MI_K_UNION_DENSE)   // offsets, the mask, and every value of the member once at most
+    return n * 4 + ((n + 63) / 64) * 8 + std::min(n, t.buf2_len) * t.param;
   if (t.kind < MI_K_ENC_COPY) {
     if (t.validity && t.null_count != 0) b += (n + 7) / 8;
     switch (t.kind) {
@@ -260,7 +291,7 @@ static int64_t TaskBytesRead(const mi_col_task& t) {
 static int64_t TaskBytesWritten(const mi_col_task& t) {
   const int64_t n = t.nrows;
   if (t.kind < MI_K_ENC_COPY) {
-    return n * OutWidth(t.kind, t.param) + (t.out_validity ? ((n + 63) / 64) * 8 : 0);
+    return n * OutWidth(t.kind, t.param) + ((t.out_validity ? 1 : 0) + (t.kind == MI_K_UNION ? t.param : 0)) * ((n + 63) / 64) * 8;
   }
   int64_t b = t.out_validity ? (n + 7) / 8 : 0;  // bitmap
   switch (t.kind) {
@@ -321,7 +352,8 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
     mi_col_task t = in_tasks[i];
     // run-end expansion lives outside kernels_decode.hip: its bytes count under the misc class, its slices go last
     const bool run_end = t.kind == MI_K_RUN_END, enc_view = t.kind == MI_K_ENC_STRVIEW;
-    const int cls = run_end ? static_cast<int>(device::kClassMisc) : enc_view ? static_cast<int>(device::kClassEncString) : device::ClassOfTask(t);
+    const int own_slot = run_end ? kRunEndSlot : enc_view ? kEncViewSlot : t.kind == MI_K_UNION ? kUnionSlot : t.kind == MI_K_UNION_DENSE ? kUnionDenseSlot : -1;
+    const int cls = own_slot >= 0 && !enc_view ? static_cast<int>(device::kClassMisc) : enc_view ? static_cast<int>(device::kClassEncString) : device::ClassOfTask(t);
     if (t.kind >= MI_K_ENC_COPY) {
       is_encode = true;
       t.depth = 0;
@@ -335,23 +367,27 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
     class_rows[cls] += t.nrows;
     max_depth = std::max(max_depth, t.depth);
     staged.push_back(t);
-    staged_cls.push_back(run_end ? kRunEndSlot : enc_view ? kEncViewSlot : cls);
+    staged_cls.push_back(own_slot >= 0 ? own_slot : cls);
   }
   n_null_counts = null_counter;
   order.assign(static_cast<size_t>(n_tasks), {0, 0});
   // depth-major, shallow first (a child sees its parent's finished validity); then, in a slice of their own per depth after
   // every other slice, the run-end expansions: they read the decoded vector of their values child, which is deeper than they are;
   // last, the string-view encode tasks (a kernel of their own, launched only by plans that have such tasks)
+  // A union's tag pass runs in pass 0 behind the class slices of its own depth: its masks are the parent words of its members,
+  // which are one level deeper.  The dense union expansions run with the run-end slices: they read scratch vectors too.
   for (int pass = 0; pass < 3; pass++)
   for (int depth = 0; depth <= max_depth; depth++) {
-    for (int c = 0; c < device::kNumClasses; c++) {
-      if (pass == 1 && c != device::kClassMisc) continue;
-      if (pass == 2 && c != device::kClassEncString) continue;
-      const int want = pass == 0 ? c : pass == 1 ? kRunEndSlot : kEncViewSlot;
+    const int n_slots = pass == 0 ? device::kNumClasses + 1 : pass == 1 ? 2 : 1;
+    for (int k = 0; k < n_slots; k++) {
+      const int want = pass == 0 ? (k < device::kNumClasses ? k : kUnionSlot) : pass == 1 ? (k == 0 ? kRunEndSlot : kUnionDenseSlot) : kEncViewSlot;
+      const int c = want < device::kNumClasses ? want : want == kEncViewSlot ? static_cast<int>(device::kClassEncString) : static_cast<int>(device::kClassMisc);
       ClassSlice sl;
       sl.cls = c;
-      sl.run_end = pass == 1;
-      sl.enc_view = pass == 2;
+      sl.run_end = want == kRunEndSlot;
+      sl.enc_view = want == kEncViewSlot;
+      sl.union_tags = want == kUnionSlot;
+      sl.union_dense = want == kUnionDenseSlot;
       sl.depth = depth;
       sl.first_task = static_cast<int32_t>(tasks.size());
       sl.tile_begin_at = static_cast<int32_t>(tile_begin.size());
@@ -367,7 +403,7 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
         tiles += nt;
         if (tiles > 0xFFFFFFF0ull) throw InvalidInputException("plan has too many tiles");
         tile_task.insert(tile_task.end(), static_cast<size_t>(nt), local_task);
-        if (c == device::kClassMisc && !sl.run_end) sl.misc_groups |= 1u << device::MiscGroupOfKind(t.kind);
+        if (want == device::kClassMisc) sl.misc_groups |= 1u << device::MiscGroupOfKind(t.kind);
         if (c == device::kClassDec128 || c == device::kClassString)   // which of the two kernel instances has tiles (device: tile_needs_mask)
           sl.misc_groups |= ((t.validity != nullptr && t.null_count != 0) || t.out_aux != nullptr) ? 2u : 1u;
         if (c == device::kClassEncString && t.kind == MI_K_ENC_LIST32) sl.misc_groups |= 2u;
@@ -435,6 +471,10 @@ void Plan::LaunchSlice(const ClassSlice& cs, hipStream_t s) {
   int64_t* null_counts = d_null_counts.get<int64_t>();
   if (cs.run_end) {
     MI_HIP_CHECK(device::LaunchRunEnd(t, tb, tt, cs.n_tasks, cs.total_tiles, status, s));
+    return;
+  }
+  if (cs.union_tags || cs.union_dense) {
+    MI_HIP_CHECK(device::LaunchUnion(cs.union_dense, t, tb, tt, cs.n_tasks, cs.total_tiles, status, s));
     return;
   }
   if (cs.enc_view) {   // the look-back words are those of encode_string_1p's slice, which has run by now (same stream)
@@ -542,6 +582,8 @@ void ThrowForStatus(uint32_t bits) {
   if (bits & MI_ST_DECIMAL_RANGE) throw ConversionException("Decimal value does not fit the physical type of its declared precision");
   if (bits & MI_ST_BAD_RUN_ENDS)
     throw InternalException("Arrow IPC validation failed: run ends are not positive and strictly increasing or end before the array does");
+  if (bits & MI_ST_BAD_UNION_TAG) throw InvalidInputException("Arrow union tag out of range");
+  if (bits & MI_ST_BAD_UNION_OFFSET) throw InternalException("Arrow IPC validation failed: union offsets are negative or exceed the member array");
   if (bits & MI_ST_DECOMPRESS)
     throw IOException("LZ4_FRAME compressed buffer is malformed or does not decompress to its declared size (Expected decompressed size mismatch)");
   if (bits & MI_ST_INTERNAL) throw InternalException("a kernel gave up waiting for another workgroup (bounded spin exceeded)");

@@ -54,6 +54,8 @@ struct ClassSlice {
   int32_t tile_begin_at = 0;  // index into Plan::tile_begin / d_tile_begin (n_tasks + 1 entries)
   uint32_t total_tiles = 0;
   bool run_end = false;       // MI_K_RUN_END tasks: launched by LaunchRunEnd (accounted under the misc class)
+  bool union_tags = false;    // MI_K_UNION tasks: transcode_union (kernels_union.hip), in pass 0 behind the class slices of their depth
+  bool union_dense = false;   // MI_K_UNION_DENSE tasks: transcode_union_dense, with the run-end slices (both under the misc class)
   bool enc_view = false;      // MI_K_ENC_STRVIEW tasks: launched by LaunchEncodeStringView (accounted under the encode-string class:
                               // class_bytes_*, class_tiles and LaunchTimed add encode_string_view to encode_string_1p's line when a plan
                               // has both -- time a kernel alone with a plan of its tasks alone, as tools/encode_bench.py does)

@@ -100,7 +100,7 @@ class HbmStream {
         const DecodedNode& dn = b.nodes[static_cast<size_t>(p.source_node)];
         mi_hbm_node c;
         std::memset(&c, 0, sizeof(c));
-        std::snprintf(c.name, sizeof(c.name), "%s", dn.field->name.c_str());
+        std::snprintf(c.name, sizeof(c.name), "%s", p.synth == 1 ? "" : dn.field->name.c_str());   // (a union's tag vector has no name)
         c.kind = p.kind;
         c.out_width = p.width;
         c.arrow_type = p.arrow_type;
@@ -116,8 +116,10 @@ class HbmStream {
         c.alias_off = p.alias_body_off >= 0 ? b.body_file_offset + p.alias_body_off : -1;
         c.ptr_base = p.ptr_base;
         c.first_span = static_cast<int32_t>(c_spans.size());
-        c.n_spans = static_cast<int32_t>(dn.spans.size());
-        for (const auto& sp : dn.spans) c_spans.push_back(mi_buffer_span{b.body_file_offset + sp.offset, sp.length});
+        // (the planner's own nodes -- a union's tag vector, a dense member's expanded vector -- own no Arrow buffers)
+        c.n_spans = p.synth ? 0 : static_cast<int32_t>(dn.spans.size());
+        for (int32_t k2 = 0; k2 < c.n_spans; k2++)
+          c_spans.push_back(mi_buffer_span{b.body_file_offset + dn.spans[static_cast<size_t>(k2)].offset, dn.spans[static_cast<size_t>(k2)].length});
         c.first_window = static_cast<int32_t>(c_windows.size());
         c.n_windows = static_cast<int32_t>(p.win.size());
         c_windows.insert(c_windows.end(), p.win.begin(), p.win.end());

@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "flatbuf.hpp"
+#include "union_format.hpp"
 
 namespace miarrow {
 
@@ -59,6 +60,12 @@ std::string ArrowField::Format() const {
     case MI_AT_MAP: return "+m";
     case MI_AT_FIXED_LIST: std::snprintf(tmp, sizeof(tmp), "+w:%d", byte_width); return tmp;
     case MI_AT_RUN_END: return "+r";
+    case MI_AT_UNION: {  // "+us:<ids>" / "+ud:<ids>": the type ids as the schema lists them (absent: the child indices)
+      std::string s = unit == 1 ? "+ud:" : "+us:";
+      for (size_t i = 0; i < children.size(); i++)
+        s += (i ? "," : "") + std::to_string(has_type_ids && i < type_ids.size() ? type_ids[i] : static_cast<int32_t>(i));
+      return s;
+    }
     default: return "?";
   }
 }
@@ -101,8 +108,36 @@ std::string ArrowField::DuckType() const {
       return "MAP(?, ?)";
     }
     case MI_AT_RUN_END: return children.size() == 2 ? children[1].DuckType() : "?";  // flattened, as DuckDB's Arrow scan reads it
+    case MI_AT_UNION: {
+      std::string s = "UNION(";
+      for (size_t i = 0; i < children.size(); i++) {
+        if (i) s += ", ";
+        s += children[i].name + " " + children[i].DuckType();
+      }
+      return s + ")";
+    }
     default: return "?";
   }
+}
+
+// Why this union is not decoded ("" = it is): the checks that need the field alone (where it stands is Supported()'s part).
+std::string ArrowField::UnionRefusal() const {
+  if (unit != 0 && unit != 1) return "union mode " + std::to_string(unit);
+  const int defect = unionfmt::CheckTypeIds(type_ids.data(), has_type_ids ? static_cast<int>(type_ids.size()) : -1, static_cast<int>(children.size()));
+  if (defect != unionfmt::kIdsOk) return unionfmt::DefectText(defect);
+  for (auto& c : children) {
+    if (c.has_dictionary) return "dictionary-encoded union member '" + c.name + "'";
+    if (c.type == MI_AT_RUN_END) return "run-end encoded union member '" + c.name + "'";
+    if (unit == 1) {  // a dense member decodes into a scratch vector that is expanded by index, as a run-end array's values are
+      int32_t ck, cw;
+      int64_t cp;
+      if (c.type == MI_AT_UNION || !c.Plan(&ck, &cp, &cw) || ck == MI_K_NULL || ck == MI_K_LIST32 || ck == MI_K_LIST64 || ck == MI_K_STRUCT)
+        return "dense union member '" + c.name + "' of type " + c.DuckType() + " (null type, lists, structs and unions are not expanded by offset)";
+    } else if (c.type == MI_AT_UNION && c.unit != 0) {
+      return "dense union '" + c.name + "' as a member of a sparse union";
+    }
+  }
+  return "";
 }
 
 bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, bool value_only) const {
@@ -173,9 +208,12 @@ bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, bool va
       int32_t vk, vw;
       int64_t vp;
       if (v.has_dictionary || !v.Plan(&vk, &vp, &vw)) return false;
-      if (vk == MI_K_NULL || vk == MI_K_LIST32 || vk == MI_K_LIST64 || vk == MI_K_STRUCT || vk == MI_K_RUN_END) return false;
+      if (vk == MI_K_NULL || vk == MI_K_LIST32 || vk == MI_K_LIST64 || vk == MI_K_STRUCT || vk == MI_K_RUN_END || vk == MI_K_UNION) return false;
       return set(MI_K_RUN_END, (re.bit_width / 8) | (static_cast<int64_t>(vw) << 8), vw);
     }
+    case MI_AT_UNION:  // the tag pass: uint8 member index per row; the members are tasks of their own
+      if (!UnionRefusal().empty()) return false;
+      return set(MI_K_UNION, static_cast<int64_t>(children.size()), 1);
     default: return false;
   }
 }
@@ -224,10 +262,28 @@ bool ArrowField::Supported(std::string* why) const {
   int32_t kind, w;
   int64_t param;
   if (!Plan(&kind, &param, &w)) {
-    if (why) *why = "Arrow type " + Format() + " of field '" + name + "'";
+    if (why) {
+      *why = "Arrow type " + Format() + " of field '" + name + "'";
+      if (type == MI_AT_UNION && !has_dictionary) *why += " (" + UnionRefusal() + ")";
+    }
     return false;
   }
   if (has_dictionary) return true;
+  if (type == MI_AT_LIST || type == MI_AT_LARGE_LIST || type == MI_AT_MAP || type == MI_AT_FIXED_LIST || type == MI_AT_RUN_END) {
+    // a union's members take their NULLs from masks in the union's own row numbering, tile by tile: the windows of a list's
+    // child vector and the runs of a run-end array have another
+    std::function<const ArrowField*(const ArrowField&)> find_union = [&](const ArrowField& f) -> const ArrowField* {
+      if (f.type == MI_AT_UNION && !f.has_dictionary) return &f;
+      for (auto& c : f.children)
+        if (const ArrowField* hit = find_union(c)) return hit;
+      return nullptr;
+    };
+    for (auto& c : children)
+      if (const ArrowField* hit = find_union(c)) {
+        if (why) *why = "union field '" + hit->name + "' inside the list / map / fixed_size_list / run-end encoded '" + name + "'";
+        return false;
+      }
+  }
   if (type == MI_AT_LIST || type == MI_AT_LARGE_LIST || type == MI_AT_MAP || type == MI_AT_FIXED_LIST) {
     // DuckDB's list vectors are windows of one child vector: a run-end encoded child would need its runs split per window
     std::function<const ArrowField*(const ArrowField&)> find_ree = [&](const ArrowField& f) -> const ArrowField* {
@@ -369,7 +425,17 @@ static ArrowField DecodeField(const fb::Table& f, int depth) {
       o.byte_width = t.scalar<int32_t>(0, 0);
       if (o.byte_width < 0) throw IOException("Expected FixedSizeList listSize >= 0 but got " + std::to_string(o.byte_width));
       break;
-    case MI_AT_UNION: o.unit = t.scalar<int16_t>(0, 0); break;  // UnionMode: 0 sparse, 1 dense
+    case MI_AT_UNION: {  // Union { mode:UnionMode [0] (0 sparse, 1 dense); typeIds:[int] [1] }
+      o.unit = t.scalar<int16_t>(0, 0);
+      uint32_t n_ids;
+      const int64_t iv = t.vector(1, &n_ids);
+      if (iv >= 0) {
+        if (n_ids > 4096 || !t.b->in(iv, 4 * static_cast<int64_t>(n_ids))) throw IOException("Union typeIds out of bounds");
+        o.has_type_ids = true;
+        for (uint32_t i = 0; i < n_ids; i++) o.type_ids.push_back(fb::load<int32_t>(t.b->base + iv + 4 * static_cast<int64_t>(i)));
+      }
+      break;
+    }
     default: break;
   }
   fb::Table d = f.table(4);
@@ -524,6 +590,8 @@ static fb::Builder::Offset BuildField(fb::Builder& fbb, const ArrowField& f) {
     fbb.AddScalar<uint8_t>(2, f.dict_ordered ? 1 : 0, 0);
     dict = fbb.EndTable();
   }
+  fb::Builder::Offset union_ids = 0;
+  if (f.type == MI_AT_UNION && f.has_type_ids) union_ids = fbb.CreateStructVector(f.type_ids.data(), f.type_ids.size(), 4, 4);
   // the type table (tables without fields still need an (empty) table object)
   fb::Builder::Offset type;
   fbb.StartTable();
@@ -550,6 +618,10 @@ static fb::Builder::Offset BuildField(fb::Builder& fbb, const ArrowField& f) {
     case MI_AT_DURATION: fbb.AddScalar<int16_t>(0, static_cast<int16_t>(f.unit), 1); break;
     case MI_AT_INTERVAL: fbb.AddScalar<int16_t>(0, static_cast<int16_t>(f.unit), 0); break;
     case MI_AT_FIXED_BINARY: case MI_AT_FIXED_LIST: fbb.AddScalar<int32_t>(0, f.byte_width, 0); break;
+    case MI_AT_UNION:
+      fbb.AddScalar<int16_t>(0, static_cast<int16_t>(f.unit), 0);
+      fbb.AddOffset(1, union_ids);
+      break;
     default: break;
   }
   type = fbb.EndTable();

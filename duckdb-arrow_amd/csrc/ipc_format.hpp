@@ -100,6 +100,8 @@ struct ArrowField {
   int32_t dict_index_bit_width = 32;
   bool dict_index_signed = true;
   bool dict_ordered = false;
+  bool has_type_ids = false;           // union: Union.typeIds is present (absent: type id = child index)
+  std::vector<int32_t> type_ids;       // union: as the schema lists them, unchecked (union_format.hpp: CheckTypeIds)
   std::vector<ArrowField> children;
   std::vector<std::pair<std::string, std::string>> metadata;
 
@@ -110,6 +112,7 @@ struct ArrowField {
   bool Plan(int32_t* kind, int64_t* param, int32_t* out_width, bool value_only = false) const;
   // Buffers of this node (the dictionary's values when value_only, else its indices): the one place that knows them
   FieldLayout Layout(bool value_only = false) const;
+  std::string UnionRefusal() const;  // a union field: why Plan() refuses it, "" when it does not
   bool Supported(std::string* why) const;  // this field and all its descendants can be decoded by the path
   int64_t CountFields() const;   // IPCStreamReader::CountFields (base_stream_reader.cpp:271-277)
   int64_t CountBuffers() const;  // buffers this field and its children own in a RecordBatch body (no variadic ones)

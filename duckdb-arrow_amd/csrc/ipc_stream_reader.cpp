@@ -121,6 +121,8 @@ MessageType IPCStreamReader::ReadNextMessage(std::vector<MessageType> expected_t
   throw IOException("Expected " + wanted + " Arrow IPC message but got " + (at_end ? "end of stream" : MessageTypeString(got)));
 }
 
+static bool HasUnionField(const ArrowField& f);
+
 bool IPCStreamReader::GetNextBatch(DecodedBatch* out, bool accept_dictionaries, bool skip_body) {
   GetBaseSchema();
   std::vector<MessageType> expected = {MessageType::RECORD_BATCH};
@@ -143,6 +145,10 @@ bool IPCStreamReader::GetNextBatch(DecodedBatch* out, bool accept_dictionaries, 
     out->compression = meta.compression;
     return true;
   }
+  // before V5 a union owned a validity buffer of its own: the buffer walk (ArrowField::Layout) knows the V5 layout only
+  if (message.version < 4 && !meta.is_dictionary)
+    if (const ArrowField* u = WantedFieldWith(HasUnionField))
+      throw NotImplementedException("Column '" + u->name + "': union arrays of a stream whose metadata version is below V5 carry a validity buffer and are not read");
   std::shared_ptr<const DeferredBody> deferred;
   if (meta.compression != -1 && cur_size > 0) deferred = DecompressBody(&meta);
   if (base_schema.endianness == 1) SwapBodyEndianness(meta);
@@ -237,6 +243,19 @@ static bool HasRunEndField(const ArrowField& f) {
   return f.type == MI_AT_RUN_END || std::any_of(f.children.begin(), f.children.end(), HasRunEndField);
 }
 
+static bool HasUnionField(const ArrowField& f) {
+  return (f.type == MI_AT_UNION && !f.has_dictionary) || std::any_of(f.children.begin(), f.children.end(), HasUnionField);
+}
+
+// the first projected (or any, without a projection) top-level field that `has` something, or nullptr
+const ArrowField* IPCStreamReader::WantedFieldWith(bool (*has)(const ArrowField&)) const {
+  for (size_t i = 0; i < base_schema.fields.size(); i++) {
+    const bool wanted = !HasProjection() || std::find(projected_columns.begin(), projected_columns.end(), static_cast<int32_t>(i)) != projected_columns.end();
+    if (wanted && has(base_schema.fields[i])) return &base_schema.fields[i];
+  }
+  return nullptr;
+}
+
 void IPCStreamReader::SwapBodyEndianness(const RecordBatchMeta& meta) {
   // the swap itself would be right (run_ends is an int child), but no test pins big-endian run-end encoded columns yet
   for (size_t i = 0; i < base_schema.fields.size(); i++) {
@@ -244,6 +263,10 @@ void IPCStreamReader::SwapBodyEndianness(const RecordBatchMeta& meta) {
     if (wanted && !meta.is_dictionary && HasRunEndField(base_schema.fields[i]))
       throw NotImplementedException("Column '" + base_schema.fields[i].name + "': run-end encoded arrays in a big-endian stream are not read");
   }
+  // ... and the same goes for unions (the offsets of a dense union are int32 and would be swapped)
+  if (!meta.is_dictionary)
+    if (const ArrowField* u = WantedFieldWith(HasUnionField))
+      throw NotImplementedException("Column '" + u->name + "': union arrays in a big-endian stream are not read");
   if (cur_size <= 0) return;
   // the body must be ours to rewrite: caller-owned buffers (scan_arrow_ipc) are copied first
   if (!cur_owner) {

@@ -103,6 +103,8 @@ class IPCStreamReader {
   //! Big-endian stream: refuses run-end encoded columns, then swaps the body in place (after decompression); a
   //! caller-owned body is copied first
   void SwapBodyEndianness(const RecordBatchMeta& meta);
+  //! The first projected top-level field (any, without a projection) for which `has` holds, or nullptr
+  const ArrowField* WantedFieldWith(bool (*has)(const ArrowField&)) const;
   bool defer_lz4 = false, defer_zstd = false;
   std::shared_ptr<void> compressed_owner;
 

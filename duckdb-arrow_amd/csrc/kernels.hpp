@@ -46,6 +46,12 @@ int MiscGroupOfKind(int32_t kind);
 hipError_t LaunchRunEnd(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task, int32_t n_tasks,
                         uint32_t total_tiles, uint32_t* d_status, hipStream_t stream);
 
+// Union columns (kernels_union.hip), one workgroup per 2048-row tile.  dense = false: MI_K_UNION tasks (transcode_union, the
+// tag pass: tags, the union's validity, one mask per member), launched before anything deeper than they are.  dense = true:
+// MI_K_UNION_DENSE tasks (transcode_union_dense), launched with the run-end slices: their members' scratch vectors first.
+hipError_t LaunchUnion(bool dense, const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task, int32_t n_tasks,
+                       uint32_t total_tiles, uint32_t* d_status, hipStream_t stream);
+
 //! Fused consumer: sum(a * b) over the rows that pass up to 4 conjunctive range filters, straight
 //! from the decoded vectors in HBM.  acc = {sum low 64 bits, sum high 64 bits (two's complement), rows selected}.
 struct AggSumProductArgs {

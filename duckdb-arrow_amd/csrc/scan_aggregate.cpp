@@ -110,6 +110,9 @@ const ScanColumn& ArrowScan::AggregateColumn(const std::string& name, const std:
   if (!it->field.Supported(&why)) throw NotImplementedException("Column '" + name + "': " + why + " is not decoded by the MI355X scan path yet");
   if (it->field.has_dictionary || ValueField(it->field).has_dictionary)
     throw NotImplementedException(what + " on the dictionary-encoded column '" + name + "' is not computed in the scan");
+  // a union's vector is a tag vector over member vectors: no aggregate (COUNT included) and no GROUP BY key reads that tree
+  if (it->field.type == MI_AT_UNION)
+    throw NotImplementedException(what + " on the union column '" + name + "' (" + it->field.DuckType() + ") is not computed in the scan");
   return *it;
 }
 

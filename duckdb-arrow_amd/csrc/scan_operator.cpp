@@ -361,7 +361,7 @@ void ArrowScan::BuildVector(const Slot& s, int32_t node, size_t window, int64_t 
   v->kind = o.kind;
   v->out_width = o.width;
   v->count = r1 - r0;
-  const int32_t vk = o.kind == MI_K_RUN_END ? o.value_kind : o.kind;  // run-end encoded: the values' string heap
+  const int32_t vk = o.kind == MI_K_RUN_END || o.kind == MI_K_UNION_DENSE ? o.value_kind : o.kind;  // run-end encoded, dense union member: the values' string heap
   if (IsStringKind(vk)) {
     v->heap = reinterpret_cast<const void*>(o.ptr_base);
     v->heap_size = o.heap_size;

@@ -103,6 +103,30 @@ enum mi_kind {
   MI_K_RUN_END = 22,      /* run_end_encoded -> flat vector of the values' type; buf1 = run ends, param = run-end width (2,4,8) |
                              out width << 8, param2 = number of runs; buf2 / validity = the values child's decoded vector and
                              validity words (NULL: all valid), null_count != 0 when those words exist.  Runs after its values */
+  MI_K_UNION = 23,        /* sparse / dense union, the tag pass -> DuckDB UNION tag vector + the masks its member vectors AND in.
+                             buf1 = type ids (int8, row_offset applies); ptr_base = device address of the dense int32 offsets
+                             (row_offset applies), 0 = sparse; param = m, the number of members (1 .. MI_MAX_UNION_MEMBERS);
+                             buf2 = the union table, 16 + 4 m words of 8 bytes, 8-byte aligned: words 0..15 are the id -> member
+                             table (128 int8 entries, entry i = member index of type id i, -1 = no member; union_format.hpp
+                             builds it), then per member {address of its Arrow validity bitmap or 0, its length in rows (dense:
+                             offsets are checked against it), its null_count (0: the bitmap is ignored), flags (bit 0: null type,
+                             every row NULL)}.  A sparse member's bitmap is read at bit row_offset + r, a dense member's at bit
+                             offsets[r].  out_data = the tags, uint8 per row (the member index; 0 for a NULL row); out_validity =
+                             the union's validity words or NULL; out_aux = a struct parent's words (flags 0 or 1); param2 = byte
+                             distance from out_data to mask 0 and buf2_len = byte distance from one mask to the next (multiples
+                             of 8, buf2_len >= 8 ceil(nrows / 64)): mask k holds ceil(nrows / 64) words, bit r = row r selects
+                             member k and is not NULL, pad bits ones -- the out_aux of member k's own task, which is one level
+                             deeper and so runs later.  validity, null_count are not read.  A type id that is negative or no
+                             member raises MI_ST_BAD_UNION_TAG, a dense offset outside [0, member length) MI_ST_BAD_UNION_OFFSET:
+                             the row is NULL, its offset is never used */
+  MI_K_UNION_DENSE = 24,  /* one member of a dense union, expanded from its scratch vector (the member array decoded by its usual
+                             task in its own row space, any depth-first position in the plan: these tasks run after every other
+                             slice).  buf1 = the union's int32 offsets (row_offset applies); buf2 = the scratch vector (16-byte
+                             aligned), buf2_len = its rows; validity = the scratch vector's validity WORDS or NULL (all valid),
+                             null_count != 0 when they exist; out_aux = the member's mask from the MI_K_UNION task (required,
+                             flags 0 or 1); param = bytes per value (1, 2, 4, 8, 16).  Row r with its mask bit set and
+                             0 <= offsets[r] < buf2_len takes value and validity bit of scratch row offsets[r]; every other
+                             row is zero and NULL (an offset out of range under a set bit raises MI_ST_BAD_UNION_OFFSET) */
   /* encode direction (K7), used by mi_encode_* plans */
   MI_K_ENC_COPY = 32,     /* K7b fixed-width copy; param = width */
   MI_K_ENC_DEC128 = 33,   /* K7b int16/32/64 -> decimal128 sign extension; param = in width */
@@ -121,8 +145,10 @@ typedef struct mi_field {
   char name[128];
   char timezone[64];
   char duck_type[1024];   /* DuckDB logical type as `typeof` prints it: BIGINT, DECIMAL(15,2), TIMESTAMP WITH TIME ZONE,
-                           * STRUCT(a INTEGER, b VARCHAR[])[] ... (nested types need the room; longer ones are refused) */
-  char format[32];        /* Arrow C data interface format string: "l", "u", "d:15,2", "tdD", "tsu:UTC" */
+                           * STRUCT(a INTEGER, b VARCHAR[])[], UNION(i INTEGER, s VARCHAR) ... (nested types need the room; longer ones are
+                           * refused) */
+  char format[32];        /* Arrow C data interface format string: "l", "u", "d:15,2", "tdD", "tsu:UTC"; a union is "+us:<ids>" /
+                           * "+ud:<ids>" with its type ids as the schema lists them, cut to the 31 characters there are */
   int32_t arrow_type;     /* enum mi_arrow_type */
   int32_t bit_width, is_signed, precision, scale, unit, byte_width, nullable;
   int32_t has_dictionary, dict_index_bit_width, dict_index_signed;
@@ -130,7 +156,7 @@ typedef struct mi_field {
   int32_t kind;           /* enum mi_kind that decodes this column, 0 when unsupported on the path */
   int32_t out_width;      /* bytes per row of the DuckDB vector */
   int64_t param;          /* kind parameter */
-  int32_t n_buffers;      /* buffers this field owns in a RecordBatch */
+  int32_t n_buffers;      /* buffers this field owns in a RecordBatch (a union itself counts 2, dense or sparse) */
   int32_t flat_index;     /* depth-first flattened field index (IPCStreamReader::CountFields, base_stream_reader.cpp:271-277) */
 } mi_field;
 
@@ -328,6 +354,9 @@ typedef struct mi_col_task {
 #define MI_ST_SEL_RANGE 1024u     /* aggregates: a selection index names no row of its 2048-row window (skipped, never read) */
 #define MI_ST_GROUP_LIMIT 2048u   /* GROUP BY: more than MI_GROUP_WINDOW_LIMIT distinct keys in a window or MI_MAX_GROUPS in a scan */
 #define MI_ST_GROUP_KEY_LONG 4096u /* GROUP BY: a selected row's VARCHAR / BLOB key is longer than 12 bytes */
+#define MI_ST_BAD_UNION_TAG 8192u  /* union: a type id is negative or names no member ("Arrow union tag out of range") */
+#define MI_ST_BAD_UNION_OFFSET 16384u /* dense union: an offset is negative or past its member array (FULL validation) */
+#define MI_MAX_UNION_MEMBERS 32    /* members of a union column: one ballot per member and 64-row group, 8 KiB of masks per tile */
 
 /* Uploads the task table to HBM (descriptor table + tile index) and returns a reusable plan.  One plan =
  * any number of (batch, column) tasks = ONE fused kernel launch per mi_plan_launch. */
@@ -532,7 +561,10 @@ typedef struct mi_vector {
   const void* dictionary;   /* MI_K_DICT: decoded dictionary values (dict_len + 1 entries, last = NULL) */
   const mi_validity_t* dictionary_validity;
   int64_t dict_len;
-  /* nested vectors (list / map / struct / fixed_size_list): children of this chunk's vector.  A list's child covers the
+  /* nested vectors (list / map / struct / fixed_size_list / union): children of this chunk's vector.  A union (kind
+   * MI_K_UNION) has n_children = members + 1, chunked like a struct's: child 0 is the tag vector (UTINYINT, the member index of
+   * every row, 0 for a NULL row; its data is this vector's data), children 1..m are the member vectors, one slot per union row,
+   * NULL wherever another member is selected (kind MI_K_UNION_DENSE for the members of a dense union).  A list's child covers the
    * child rows [child_offset, child_offset + child_count) of the record batch; its data pointer is already advanced, its
    * validity pointer addresses the word that holds its first row and `validity_shift` = first row mod 64 (child windows
    * are not word aligned; 0 for top-level vectors and struct children of them). */

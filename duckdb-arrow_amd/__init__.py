@@ -566,6 +566,28 @@ def filter_pattern_launches():
     return n.value
 
 
+_FILTER_LEAF_FIELDS = ("data", "validity", "in_values", "lo", "hi", "op", "width", "flags", "n_in")
+
+
+def filter_program(ctx, leaves, nrows, sel_ptr, count_ptr, stream=0):
+    """A hand-built program of the filter kernel's own leaves over resident vectors (mi_filter_program_vectors): `leaves` are
+    dicts (missing fields are 0) or tuples in the order data, validity, in_values, lo, hi, op, width, flags, n_in, every
+    address a device address.  Nothing is normalised, uploaded or waited for; _ffi.FL_* / FLF_* name the ops and flag bits."""
+    arr = (_ffi.FilterVectorLeaf * max(len(leaves), 1))()
+    for slot, leaf in zip(arr, leaves):
+        if not isinstance(leaf, dict):
+            leaf = dict(zip(_FILTER_LEAF_FIELDS, leaf))
+        unknown = set(leaf) - set(_FILTER_LEAF_FIELDS)
+        if unknown:
+            raise ValueError("filter_program: unknown leaf field %s" % sorted(unknown))
+        for name in _FILTER_LEAF_FIELDS:
+            v = int(leaf.get(name, 0) or 0)
+            if name in ("lo", "hi") and v >= 1 << 63:   # an address above 2^63 in a signed field
+                v -= 1 << 64
+            setattr(slot, name, v or None if name in ("data", "validity", "in_values") else v)
+    _ffi.check(_ffi.lib().mi_filter_program_vectors(ctx._h, arr, len(leaves), nrows, sel_ptr or None, count_ptr or None, C.c_void_p(stream or None)))
+
+
 def writer_fused_counts():
     """(row groups the fused COPY pump encoded where the scan decoded them, string-view columns among them) by this process."""
     groups, views = C.c_int64(), C.c_int64()

@@ -100,6 +100,16 @@ FV_INT64, FV_DOUBLE, FV_INT128 = 0, 1, 2
 F_EQ, F_NE, F_LT, F_LE, F_GT, F_GE, F_IS_NULL, F_IS_NOT_NULL, F_IN, F_STARTS_WITH, F_AND, F_OR = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 16, 17
 F_CONTAINS, F_ENDS_WITH, F_LIKE, F_NOT_LIKE = 11, 12, 13, 14
 
+# enum mi_filter_leaf_op / mi_filter_leaf_flag: the kernel's own leaves (mi_filter_program_vectors)
+FL_RANGE, FL_IS_NULL, FL_IS_NOT_NULL, FL_IN, FL_STR_IN, FL_DICT_MAP, FL_STR_RANGE, FL_WIDE_RANGE, FL_WIDE_IN, FL_STR_MATCH = range(1, 11)
+FLF_UNSIGNED, FLF_NEGATE, FLF_ENDS_CLAUSE, FLF_BIAS, FLF_FLOAT = 1, 2, 4, 8, 16
+MAX_FILTER_LEAVES = 24
+
+
+class FilterVectorLeaf(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("validity", C.c_void_p), ("in_values", C.c_void_p), ("lo", C.c_int64), ("hi", C.c_int64),
+                ("op", C.c_int32), ("width", C.c_int32), ("flags", C.c_int32), ("n_in", C.c_int32)]
+
 
 class HbmOptions(C.Structure):
     _fields_ = [("columns", C.POINTER(C.c_char_p)), ("n_columns", C.c_int32), ("accept_dictionaries", C.c_int32),
@@ -285,6 +295,7 @@ SIGNATURES = {
     "mi_filter_string": (C.c_int, [P, P, P, C.c_int64, P, C.c_uint64, C.c_int32, C.c_char_p, C.c_int32, P, P, C.c_int32, C.POINTER(C.c_float)]),
     "mi_filter_like_match": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     "mi_filter_pattern_launches": (C.c_int, [C.POINTER(C.c_int64)]),
+    "mi_filter_program_vectors": (C.c_int, [P, C.POINTER(FilterVectorLeaf), C.c_int32, C.c_int64, P, P, P]),
     "mi_writer_fused_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mi_scan_set_filter_range": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64]),
     "mi_scan_set_filter": (C.c_int, [P, C.POINTER(FilterNode), C.c_int32, C.c_int32]),

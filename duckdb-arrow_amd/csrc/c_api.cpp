@@ -3,6 +3,7 @@
 // boundary (src/include/ipc/array_stream.hpp:29-48).
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -583,6 +584,85 @@ int mi_filter_pattern_launches(int64_t* n) {
   return Wrap([&] {
     if (!n) throw InvalidInputException("mi_filter_pattern_launches: NULL argument");
     *n = device::FilterPatternLaunches();
+  });
+}
+
+// the header restates the kernel's leaf forms and flag bits, and the leaf itself
+static_assert(MI_FL_RANGE == device::kLeafRange && MI_FL_IS_NULL == device::kLeafIsNull && MI_FL_IS_NOT_NULL == device::kLeafIsNotNull &&
+              MI_FL_IN == device::kLeafIn && MI_FL_STR_IN == device::kLeafStrIn && MI_FL_DICT_MAP == device::kLeafDictMap &&
+              MI_FL_STR_RANGE == device::kLeafStrRange && MI_FL_WIDE_RANGE == device::kLeafWideRange && MI_FL_WIDE_IN == device::kLeafWideIn &&
+              MI_FL_STR_MATCH == device::kLeafStrMatch, "mi_filter_leaf_op restates kLeaf*");
+static_assert(MI_FLF_UNSIGNED == device::kLeafUnsigned && MI_FLF_NEGATE == device::kLeafNegate && MI_FLF_ENDS_CLAUSE == device::kLeafEndsClause &&
+              MI_FLF_BIAS == device::kLeafBias && MI_FLF_FLOAT == device::kLeafFloat, "mi_filter_leaf_flag restates the flag bits");
+static_assert(MI_MAX_FILTER_LEAVES == device::kMaxFilterLeaves, "MI_MAX_FILTER_LEAVES restates kMaxFilterLeaves");
+static_assert(sizeof(mi_filter_vector_leaf) == sizeof(device::FilterLeafDev) &&
+              offsetof(mi_filter_vector_leaf, data) == offsetof(device::FilterLeafDev, data) &&
+              offsetof(mi_filter_vector_leaf, validity) == offsetof(device::FilterLeafDev, validity) &&
+              offsetof(mi_filter_vector_leaf, in_values) == offsetof(device::FilterLeafDev, in_values) &&
+              offsetof(mi_filter_vector_leaf, lo) == offsetof(device::FilterLeafDev, lo) &&
+              offsetof(mi_filter_vector_leaf, hi) == offsetof(device::FilterLeafDev, hi) &&
+              offsetof(mi_filter_vector_leaf, op) == offsetof(device::FilterLeafDev, op) &&
+              offsetof(mi_filter_vector_leaf, width) == offsetof(device::FilterLeafDev, width) &&
+              offsetof(mi_filter_vector_leaf, flags) == offsetof(device::FilterLeafDev, flags) &&
+              offsetof(mi_filter_vector_leaf, n_in) == offsetof(device::FilterLeafDev, n_in), "mi_filter_vector_leaf is FilterLeafDev, field for field");
+
+int mi_filter_program_vectors(mi_ctx* ctx, const mi_filter_vector_leaf* leaves, int32_t n_leaves, int64_t nrows, mi_sel_t* sel_out,
+                              uint32_t* count_out, void* stream) {
+  return Wrap([&] {
+    if (!ctx || !sel_out || !count_out) throw InvalidInputException("mi_filter_program_vectors: NULL argument");
+    if (n_leaves < 0 || n_leaves > MI_MAX_FILTER_LEAVES)
+      throw InvalidInputException("mi_filter_program_vectors takes 0 to " + std::to_string(MI_MAX_FILTER_LEAVES) + " leaves, not " + std::to_string(n_leaves));
+    if (n_leaves > 0 && !leaves) throw InvalidInputException("mi_filter_program_vectors: NULL leaves");
+    if (nrows < 0) throw InvalidInputException("mi_filter_program_vectors: negative row count");
+    device::FilterProgram prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_leaves = n_leaves;
+    for (int32_t l = 0; l < n_leaves; l++) {
+      const mi_filter_vector_leaf& in = leaves[l];
+      auto refuse = [&](const std::string& what) { throw InvalidInputException("mi_filter_program_vectors: leaf " + std::to_string(l) + ": " + what); };
+      const bool is_null_op = in.op == MI_FL_IS_NULL || in.op == MI_FL_IS_NOT_NULL;
+      const bool is_int_op = in.op == MI_FL_RANGE || in.op == MI_FL_IN;
+      const bool is_str_op = in.op == MI_FL_STR_IN || in.op == MI_FL_STR_RANGE || in.op == MI_FL_STR_MATCH;
+      const bool is_wide_op = in.op == MI_FL_WIDE_RANGE || in.op == MI_FL_WIDE_IN;
+      if (!is_null_op && !is_int_op && !is_str_op && !is_wide_op && in.op != MI_FL_DICT_MAP) refuse("unknown op " + std::to_string(in.op));
+      if (!is_null_op) {
+        if (!in.data) refuse("NULL data");
+        bool fits;
+        if (is_int_op) fits = (in.flags & MI_FLF_FLOAT) ? (in.width == 4 || in.width == 8) : (in.width == 1 || in.width == 2 || in.width == 4 || in.width == 8);
+        else fits = in.width == (in.op == MI_FL_DICT_MAP ? 4 : 16);
+        if (!fits) refuse("width " + std::to_string(in.width) + " does not fit the op (integers 1 / 2 / 4 / 8, floats 4 / 8, wide and string rows 16, dictionary indices 4)");
+      }
+      if (in.n_in < 0) refuse("negative n_in");
+      if ((in.op == MI_FL_IN || in.op == MI_FL_WIDE_IN || in.op == MI_FL_STR_IN) && in.n_in > 256) refuse("more than 256 constants");
+      // the bounds of a string or wide range, the segments and a wide list are read whatever n_in says; the other tables entry by entry
+      const bool reads_table = in.op == MI_FL_STR_RANGE || in.op == MI_FL_STR_MATCH || is_wide_op ||
+                               ((in.op == MI_FL_IN || in.op == MI_FL_STR_IN || in.op == MI_FL_DICT_MAP) && in.n_in > 0);
+      if (reads_table && !in.in_values) refuse("NULL in_values");
+      if (in.op == MI_FL_STR_RANGE && (in.n_in & ~0xF)) refuse("a string range's n_in holds four bits");
+      if (in.op == MI_FL_STR_MATCH && ((in.n_in & 0xFF) < 1 || (in.n_in & 0xFF) > likematch::kMaxSegments || (in.n_in & ~0x3FF)))
+        refuse("a pattern leaf takes 1 to 8 segments and two anchor bits");
+      if (in.op == MI_FL_DICT_MAP && (in.lo < 0 || in.lo > 3)) refuse("dictionary map mode " + std::to_string(in.lo) + " outside 0 .. 3");
+      if ((in.flags & MI_FLF_NEGATE) && (is_null_op || in.op == MI_FL_DICT_MAP)) refuse("MI_FLF_NEGATE on IS [NOT] NULL or a dictionary map");
+      if (reinterpret_cast<uintptr_t>(in.data) & 7u) refuse("data is not 8-byte aligned");
+      if (reinterpret_cast<uintptr_t>(in.validity) & 7u) refuse("validity is not 8-byte aligned");
+      if (l == n_leaves - 1 && !(in.flags & MI_FLF_ENDS_CLAUSE)) refuse("the last leaf does not end its clause");
+      device::FilterLeafDev& L = prog.leaves[l];
+      L.data = in.data;
+      L.validity = static_cast<const uint64_t*>(in.validity);
+      L.in_values = in.in_values;
+      L.lo = in.lo;
+      L.hi = in.hi;
+      L.op = in.op;
+      L.width = in.width;
+      L.flags = in.flags;
+      L.n_in = in.n_in;
+    }
+    if (nrows == 0) return;
+    ctx->ctx->Bind();
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
+    const hipError_t e = device::LaunchFilterProgram(prog, nrows, sel_out, count_out, s);
+    if (e == hipErrorInvalidValue) throw InvalidInputException("mi_filter_program_vectors: the launcher refuses the program (a pattern leaf takes 1 to 8 segments and no other bit in n_in)");
+    MI_HIP_CHECK(e);
   });
 }
 

@@ -149,6 +149,12 @@ constexpr int kLeafBias = 8;        //        uint64 column: values and constant
 constexpr int kLeafFloat = 16;      //        FLOAT / DOUBLE column (width 4 / 8): every value goes through filterkey::FloatKey
                                     //        (filter_key.hpp) before the range / IN comparison, whose constants are keys
 constexpr int kMaxFilterLeaves = 24;
+// The contract of a leaf, held by the program-level suite (mi_filter_program_vectors, tests/test_gpu_filter_programs.py):
+//   * data and validity are 8-byte aligned (what the planner hands over for an aliased Arrow buffer), whatever the width;
+//   * a NULL row of a string_t vector is sixteen zero bytes: the string leaves may look at any row, valid or not;
+//   * kLeafDictMap ignores `validity` (the map knows its NULLs) and takes no kLeafNegate (lo = 1 is its negation);
+//   * a program of no leaves keeps every row;
+//   * the last leaf of a program carries kLeafEndsClause: a clause left open is dropped.
 struct FilterLeafDev {
   const void* data;                 // decoded fixed-width vector (device), NULL for IS [NOT] NULL
   const uint64_t* validity;         // validity words (device) or NULL = all valid

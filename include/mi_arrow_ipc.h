@@ -829,6 +829,42 @@ int mi_filter_like_match(int32_t op, const char* pattern, int32_t pattern_len, c
 /* Debug getter: launches by this process so far of the filter kernel's third instance, the one run for programs that hold a
  * contains / ends_with / LIKE leaf which did not fold into another form.  mi_filter_launch_counts does not count them. */
 int mi_filter_pattern_launches(int64_t* n);
+/* Test and verification hook: the program-level entry of the filter kernel (K6), as mi_aggregate_vectors is K9's.  The leaves
+ * are the kernel's own (csrc/kernels.hpp, FilterLeafDev, field for field) in conjunctive normal form: leaves in clause order,
+ * MI_FLF_ENDS_CLAUSE on the last leaf of every clause.  Nothing of mi_scan_set_filter's front end runs: no range is merged,
+ * no constant converted or uploaded.  data, validity and in_values -- and every address a constant table holds -- are DEVICE
+ * addresses the caller keeps alive until the kernel has run; the call launches on `stream` (NULL: the context's) and does not
+ * wait.  sel_out holds 2048 entries and count_out one per window of 2048 rows.
+ *   MI_FL_RANGE        lo <= v <= hi on integers of width 1 / 2 / 4 / 8 (MI_FLF_UNSIGNED: zero-extended; MI_FLF_BIAS: v ^ 2^63 first);
+ *                      with MI_FLF_FLOAT on IEEE floats of width 4 / 8, lo and hi being keys (mi_filter_float_key)
+ *   MI_FL_IN           v is one of in_values[0 .. n_in) (int64, or keys), n_in <= 256
+ *   MI_FL_IS_NULL / MI_FL_IS_NOT_NULL   validity alone (data may be NULL; a NULL validity = every row valid)
+ *   MI_FL_STR_IN       string_t rows (width 16); lo = the heap's device address, hi = the pointer value of its byte 0; in_values = 3
+ *                      words per constant: {length | dword1 << 32, dword2 | dword3 << 32, device address of the bytes}
+ *   MI_FL_STR_RANGE    in_values = two such constants (lower, upper); n_in = 1 has lower | 2 inclusive | 4 has upper | 8 inclusive
+ *   MI_FL_STR_MATCH    in_values = 1 .. 8 such constants, the segments; n_in = their number | head anchor << 8 | tail anchor << 9
+ *   MI_FL_DICT_MAP     uint32 indices (width 4); in_values = n_in bytes (0 no, 1 yes, 2 NULL entry; an index >= n_in counts as 2);
+ *                      lo = 0 match, 1 no match, 2 IS NULL, 3 IS NOT NULL.  The validity pointer is not read.
+ *   MI_FL_WIDE_RANGE   hugeint rows (width 16); in_values = {lo.lower, lo.upper, hi.lower, hi.upper}
+ *   MI_FL_WIDE_IN      in_values = n_in {lower, upper} pairs, n_in <= 256
+ * MI_FLF_NEGATE keeps the valid rows the comparison fails (not on MI_FL_DICT_MAP, MI_FL_IS_NULL, MI_FL_IS_NOT_NULL).  data and
+ * validity are 8-byte aligned; a NULL string_t row is sixteen zero bytes.  An empty program keeps every row; nrows == 0 launches
+ * nothing.  MI_EINVAL, with the leaf's index in the message, for whatever does not fit the above. */
+enum mi_filter_leaf_op {
+  MI_FL_RANGE = 1, MI_FL_IS_NULL = 2, MI_FL_IS_NOT_NULL = 3, MI_FL_IN = 4, MI_FL_STR_IN = 5, MI_FL_DICT_MAP = 6, MI_FL_STR_RANGE = 7,
+  MI_FL_WIDE_RANGE = 8, MI_FL_WIDE_IN = 9, MI_FL_STR_MATCH = 10
+};
+enum mi_filter_leaf_flag { MI_FLF_UNSIGNED = 1, MI_FLF_NEGATE = 2, MI_FLF_ENDS_CLAUSE = 4, MI_FLF_BIAS = 8, MI_FLF_FLOAT = 16 };
+#define MI_MAX_FILTER_LEAVES 24
+typedef struct mi_filter_vector_leaf {
+  const void* data;
+  const void* validity;
+  const int64_t* in_values;
+  int64_t lo, hi;
+  int32_t op, width, flags, n_in;
+} mi_filter_vector_leaf;
+int mi_filter_program_vectors(mi_ctx* ctx, const mi_filter_vector_leaf* leaves, int32_t n_leaves, int64_t nrows, mi_sel_t* sel_out,
+                              uint32_t* count_out, void* stream);
 /* Debug getter: row groups mi_writer_sink_scan's fused pump has encoded where the scan decoded them (no host staging) in this
  * process so far, and how many string-view columns (produce_arrow_string_view) they held, summed over those row groups. */
 int mi_writer_fused_counts(int64_t* row_groups, int64_t* view_columns);

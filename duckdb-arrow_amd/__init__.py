@@ -18,6 +18,7 @@ import decimal
 import os
 import re
 import struct
+import uuid
 
 import numpy as np
 
@@ -604,6 +605,19 @@ def _valid_bits(validity_ptr, n, shift=0):
     return np.unpackbits(words.view(np.uint8), bitorder="little")[shift: shift + n].astype(bool)
 
 
+def uuid_to_hugeint(u):
+    """uuid.UUID (or its text) -> the signed 128-bit integer DuckDB stores for it: the UUID's bits with the top bit flipped, so
+    that signed order is the order of the canonical text (extension_format.hpp: UuidFromArrow)."""
+    u = u if isinstance(u, uuid.UUID) else uuid.UUID(str(u))
+    v = u.int ^ (1 << 127)
+    return v - (1 << 128) if v >= (1 << 127) else v
+
+
+def uuid_from_hugeint(v):
+    """the inverse of uuid_to_hugeint"""
+    return uuid.UUID(int=(int(v) & ((1 << 128) - 1)) ^ (1 << 127))
+
+
 def _string_values(data_ptr, n, ok, as_bytes):
     raw = np.ctypeslib.as_array(C.cast(data_ptr, C.POINTER(C.c_uint8)), shape=(n * 16,)).reshape(n, 16)
     lens = raw[:, 0:4].copy().view(np.uint32).reshape(-1)
@@ -630,7 +644,7 @@ def _flat_values(duck_type, width, data_ptr, validity_ptr, n, shift=0):
     ok = _valid_bits(validity_ptr, n, shift)
     if n == 0:
         return []
-    if duck_type in ("VARCHAR", "BLOB"):
+    if duck_type in ("VARCHAR", "BLOB", "JSON"):
         return _string_values(data_ptr, n, ok, as_bytes=(duck_type == "BLOB"))
     raw = np.ctypeslib.as_array(C.cast(data_ptr, C.POINTER(C.c_uint8)), shape=(n * width,))
     if duck_type == "BOOLEAN":
@@ -643,6 +657,9 @@ def _flat_values(duck_type, width, data_ptr, validity_ptr, n, shift=0):
     if duck_type == "INTERVAL":
         md, us = raw.view(np.int32), raw.view(np.int64)
         return [(int(md[4 * i]), int(md[4 * i + 1]), int(us[2 * i + 1])) if ok[i] else None for i in range(n)]
+    if duck_type == "UUID":
+        lo, hi = raw.view(np.uint64)[0::2], raw.view(np.int64)[1::2]
+        return [uuid_from_hugeint((int(hi[i]) << 64) + int(lo[i])) if ok[i] else None for i in range(n)]
     if duck_type.startswith("DECIMAL") and width == 16:
         lo, hi = raw.view(np.uint64)[0::2], raw.view(np.int64)[1::2]
         return [(int(hi[i]) << 64) + int(lo[i]) if ok[i] else None for i in range(n)]
@@ -711,7 +728,7 @@ def _vector_values(v, ty, n):
     shift = v.validity_shift
     if v.kind == _ffi.K_DICT:
         dt = ty[1]
-        base = _flat_values(dt, {"VARCHAR": 16, "BLOB": 16}.get(dt, _dict_width(dt)), v.dictionary, v.dictionary_validity,
+        base = _flat_values(dt, {"VARCHAR": 16, "BLOB": 16, "JSON": 16}.get(dt, _dict_width(dt)), v.dictionary, v.dictionary_validity,
                             v.dict_len + 1)
         sel = np.ctypeslib.as_array(C.cast(v.data, C.POINTER(C.c_uint32)), shape=(max(n, 1),))[:n]
         return [base[int(x)] for x in sel]
@@ -755,7 +772,7 @@ def chunk_to_columns(chunk, fields):
 def _dict_width(duck_type):
     if duck_type in _INT_TYPES:
         return np.dtype(_INT_TYPES[duck_type]).itemsize
-    return {"BOOLEAN": 1, "FLOAT": 4, "DOUBLE": 8, "INTERVAL": 16}.get(duck_type, 8)
+    return {"BOOLEAN": 1, "FLOAT": 4, "DOUBLE": 8, "INTERVAL": 16, "UUID": 16}.get(duck_type, 8)
 
 
 # ---------------------------------------------------------------------------------------------------- scan operator
@@ -808,7 +825,8 @@ class Relation:
         Constants are the stored integers, or str / bytes for VARCHAR / BLOB columns (byte-wise order).  The column's DuckDB
         type picks what a number is sent as: FLOAT / DOUBLE columns take Python floats (float('nan'), inf; ints are converted)
         in DuckDB's total order -- NaN = NaN, NaN greatest, -0.0 = +0.0; HUGEINT / DECIMAL(19..38) columns take ints of up to
-        128 bits; a decimal.Decimal on any DECIMAL column is scaled to the stored integer.  A float against an integer column
+        128 bits; UUID columns take uuid.UUID values or their text; a decimal.Decimal on any DECIMAL column is scaled to the
+        stored integer.  A float against an integer column
         is refused.  NULL semantics are SQL's: a comparison with NULL is not true.  Needles and suffixes are literal bytes; in a
         LIKE pattern `%` is the only wildcard (`_` and more than 8 literal segments are refused with MI_ENOTSUP, there is no
         escape character), and a NULL row passes neither "like" nor "not like"."""
@@ -822,6 +840,11 @@ class Relation:
         def numbers(col, vals):
             """-> (value_kind, low words, high words or None) of the constants of one leaf"""
             ty = duck.get(col, "")
+            if ty == "UUID" and vals and all(isinstance(v, (uuid.UUID, str, bytes)) for v in vals):
+                # the hugeint_t image, always as 128 bits: an image that happens to fit 64 bits is still no int64 constant
+                stored = [uuid_to_hugeint(v.decode() if isinstance(v, bytes) else v) for v in vals]
+                signed = lambda w: w - (1 << 64) if w >= (1 << 63) else w
+                return _ffi.FV_INT128, [signed(v & ((1 << 64) - 1)) for v in stored], [signed((v >> 64) & ((1 << 64) - 1)) for v in stored]
             if ty in ("FLOAT", "DOUBLE") and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in vals):
                 return _ffi.FV_DOUBLE, [struct.unpack("<q", struct.pack("<d", float(v)))[0] for v in vals], None
             m = re.match(r"DECIMAL\((\d+),(\d+)\)$", ty)
@@ -857,7 +880,8 @@ class Relation:
             col, op = e[0], e[1].lower()
             n = _ffi.FilterNode(op=ops[op], column=col.encode())
             as_bytes = lambda v: v.encode() if isinstance(v, str) else bytes(v)
-            if op == "in" and len(e[2]) > 0 and isinstance(e[2][0], (str, bytes)):
+            is_uuid = duck.get(col) == "UUID"   # its text is a 128-bit constant, not a byte string
+            if op == "in" and len(e[2]) > 0 and isinstance(e[2][0], (str, bytes)) and not is_uuid:
                 vals = [as_bytes(v) for v in e[2]]
                 ptrs = (C.c_char_p * len(vals))(*vals)
                 lens = (C.c_int32 * len(vals))(*[len(v) for v in vals])
@@ -872,7 +896,7 @@ class Relation:
                     arr_hi = (C.c_int64 * max(len(highs), 1))(*highs)
                     keep.append(arr_hi)
                     n.values_hi = arr_hi
-            elif op not in ("is null", "is not null") and isinstance(e[2], (str, bytes)):
+            elif op not in ("is null", "is not null") and isinstance(e[2], (str, bytes)) and not is_uuid:
                 v = as_bytes(e[2])
                 keep.append(v)
                 n.str_value, n.str_len = v, len(v)
@@ -955,15 +979,21 @@ class Relation:
         scanned, selected = C.c_int64(), C.c_int64()
         _ffi.check(_ffi.lib().mi_scan_aggregate(self._h, arr, len(checked), out, C.byref(scanned), C.byref(selected)))
         self._initialised = True
-        values = [_agg_value(v) for v in out]
+        values = self._typed_aggregates(checked, [_agg_value(v) for v in out])
         return (values, scanned.value, selected.value) if detail else values
+
+    def _typed_aggregates(self, checked, values):
+        """MIN / MAX of a UUID column come back as uuid.UUID, not as the stored 128-bit integer"""
+        types = {f["name"]: f["duck_type"] for f in self.fields}
+        as_uuid = [name in ("min", "max") and types.get(cols[0] if isinstance(cols[0], str) else cols[0].decode()) == "UUID" for name, cols in checked]
+        return [uuid_from_hugeint(v) if u and v is not None else v for u, v in zip(as_uuid, values)]
 
     def group_aggregate(self, keys, specs, detail=False, capacity=_ffi.MAX_GROUPS):
         """SELECT k_1 .. k_m, agg_1 .. agg_n ... GROUP BY k_1 .. k_m (m <= 4, n <= 8) over the rows the pushed-down filter
         keeps, on the GPU (mi_scan_group_aggregate), for few groups: at most 256 distinct keys per 2048-row window and 4096
         in the scan.  `keys`: column names; `specs` as aggregate() takes them.  Returns [(key_tuple, [values...]), ...]
-        sorted ascending by key, NULLS LAST; a key comes back as an int (the stored integer), a str (VARCHAR), bytes (BLOB)
-        or None.  With `detail`: (rows, rows_scanned, rows_selected)."""
+        sorted ascending by key, NULLS LAST; a key comes back as an int (the stored integer), a str (VARCHAR / JSON), bytes (BLOB),
+        a uuid.UUID, a bool or None.  With `detail`: (rows, rows_scanned, rows_selected)."""
         keys = _group_check_keys(keys)
         checked = _agg_check_specs(specs)
         arr, _keep = _agg_scan_specs(checked)
@@ -976,8 +1006,14 @@ class Relation:
                                                       C.byref(n_groups), C.byref(scanned), C.byref(selected)))
         self._initialised = True
         types = {f["name"]: f["duck_type"] for f in self.fields}
-        text = [str(types.get(k if isinstance(k, str) else k.decode(), "")).upper().startswith("VARCHAR") for k in keys]
+        text = [str(types.get(k if isinstance(k, str) else k.decode(), "")).upper().startswith(("VARCHAR", "JSON")) for k in keys]
         rows = _group_rows(out_keys, out_values, n_groups.value, len(keys), len(checked), text, False)
+        # UUID keys as uuid.UUID, BOOLEAN keys as bool (the stored integers otherwise); the order is the stored one either way
+        key_types = [str(types.get(k if isinstance(k, str) else k.decode(), "")).upper() for k in keys]
+        typed = {"UUID": uuid_from_hugeint, "BOOLEAN": bool}
+        if any(t in typed for t in key_types):
+            rows = [(tuple(typed[t](v) if t in typed and v is not None else v for t, v in zip(key_types, key)), vals) for key, vals in rows]
+        rows = [(key, self._typed_aggregates(checked, vals)) for key, vals in rows]
         return (rows, scanned.value, selected.value) if detail else rows
 
     def progress(self):
@@ -1020,7 +1056,7 @@ def _vector_from_python(values, duck_type, keep):
     if not ok.all():
         validity = np.packbits(np.concatenate([ok, np.ones((-n) % 64, bool)]), bitorder="little").view(np.uint64).copy()
     t = duck_type.upper()
-    if t in ("VARCHAR", "BLOB"):
+    if t in ("VARCHAR", "BLOB", "JSON"):
         data = np.zeros((n, 16), np.uint8)
         for i, v in enumerate(values):
             if v is None:
@@ -1050,6 +1086,14 @@ def _vector_from_python(values, duck_type, keep):
             return data.reshape(-1), validity
         dt = np.int16 if p <= 4 else np.int32 if p <= 9 else np.int64
         return np.array([0 if v is None else v for v in values], dt), validity
+    if t == "UUID":   # uuid.UUID values (or their text) as DuckDB stores them
+        data = np.zeros((n, 2), np.uint64)
+        for i, v in enumerate(values):
+            if v is not None:
+                h = uuid_to_hugeint(v)
+                data[i, 0] = h & 0xFFFFFFFFFFFFFFFF
+                data[i, 1] = (h >> 64) & 0xFFFFFFFFFFFFFFFF
+        return data.reshape(-1), validity
     if t == "HUGEINT":
         data = np.zeros((n, 2), np.uint64)
         for i, v in enumerate(values):

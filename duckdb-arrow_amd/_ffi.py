@@ -19,8 +19,10 @@ K_COPY, K_BOOL, K_DEC128, K_DATE64, K_MUL_I32, K_MUL_I64, K_DIV_I64, K_STR32, K_
     K_STRUCT = range(1, 22)
 K_RUN_END = 22
 K_UNION, K_UNION_DENSE = 23, 24
+K_UUID, K_BOOL8 = 25, 26
 MAX_UNION_MEMBERS = 32
 K_ENC_COPY, K_ENC_DEC128, K_ENC_BOOL, K_ENC_STR32, K_ENC_VALIDITY, K_ENC_LIST32, K_ENC_STRVIEW = 32, 33, 34, 35, 36, 37, 38
+K_ENC_UUID_TEXT = 39
 
 ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL_RANGE, ST_OFFSET_OVERFLOW, ST_DICT_INDEX, ST_INTERNAL = \
     1, 2, 4, 8, 16, 32, 64, 128

@@ -15,6 +15,7 @@
 
 #include "scan_operator.hpp"
 #include "writer_internal.hpp"
+#include "extension_format.hpp"
 #include "writer_plan.hpp"
 
 namespace miarrow {
@@ -236,7 +237,7 @@ bool FusedSinkPossible(mi_writer* w, ArrowScan* scan) {
     const auto& wc = w->buffer->columns[static_cast<size_t>(w->buffer->roots[c])];
     if (!wc.children.empty()) return false;
     if (wc.enc_kind != MI_K_ENC_COPY && wc.enc_kind != MI_K_ENC_DEC128 && wc.enc_kind != MI_K_ENC_BOOL && wc.enc_kind != MI_K_ENC_STR32 &&
-        wc.enc_kind != MI_K_ENC_STRVIEW)
+        wc.enc_kind != MI_K_ENC_STRVIEW && wc.enc_kind != MI_K_ENC_UUID_TEXT)
       return false;
   }
   return true;
@@ -364,6 +365,14 @@ int64_t PayloadOf(const DeviceColumnView& v, int64_t r0, int64_t m) {
   return total;
 }
 
+// text bytes of a UUID column's rows [r0, r0 + m): 36 per valid row
+int64_t UuidTextPayloadOf(const DeviceColumnView& v, int64_t r0, int64_t m) {
+  int64_t valid = m;
+  if (v.null_count != 0 && v.h_validity)
+    for (int64_t i = r0; i < r0 + m; i++) valid -= ((v.h_validity[i >> 3] >> (i & 7)) & 1) ? 0 : 1;
+  return valid * extfmt::kUuidTextBytes;
+}
+
 // row groups the fused pump has encoded where they lay in HBM, and string-view columns among them (mi_writer_fused_counts)
 std::atomic<int64_t> g_fused_row_groups{0}, g_fused_view_columns{0};
 
@@ -404,7 +413,9 @@ bool FusedPump::ViewsOf(const BatchRef& ref, std::vector<DeviceColumnView>* view
     if (!v.flat) return false;
     const auto& wc = WriterColumn(c);
     const bool is_string = v.kind == MI_K_STR32 || v.kind == MI_K_STR64;
-    if (wc.enc_kind == MI_K_ENC_STR32 || wc.enc_kind == MI_K_ENC_STRVIEW) {
+    if (wc.enc_kind == MI_K_ENC_UUID_TEXT) {   // the decoded hugeint_t rows, NULLs by the Arrow bitmap on the host
+      if (v.kind != MI_K_UUID || (v.null_count != 0 && !v.h_validity)) return false;
+    } else if (wc.enc_kind == MI_K_ENC_STR32 || wc.enc_kind == MI_K_ENC_STRVIEW) {
       if (!is_string) return false;
     } else if (is_string || v.width != wc.width || v.kind == MI_K_STRVIEW || v.kind == MI_K_FIXED_BINARY) {
       return false;
@@ -436,7 +447,8 @@ void FusedPump::EncodeOnGpu(int tok, const std::vector<DeviceColumnView>& views,
   std::vector<EncodeNode> nodes(n_cols);
   for (size_t c = 0; c < n_cols; c++) {
     const auto& wc = WriterColumn(c);
-    const int64_t payload = wc.enc_kind == MI_K_ENC_STR32 ? PayloadOf(views[c], r0, m) : wc.enc_kind == MI_K_ENC_STRVIEW ? LongPayloadOf(views[c], r0, m) : 0;
+    const int64_t payload = wc.enc_kind == MI_K_ENC_STR32 ? PayloadOf(views[c], r0, m) : wc.enc_kind == MI_K_ENC_STRVIEW ? LongPayloadOf(views[c], r0, m)
+                            : wc.enc_kind == MI_K_ENC_UUID_TEXT ? UuidTextPayloadOf(views[c], r0, m) : 0;
     nodes[c] = EncodeNode{wc.enc_kind, wc.param, wc.large_offsets, m, payload};
   }
   g_fused_row_groups++;

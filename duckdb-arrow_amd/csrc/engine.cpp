@@ -91,7 +91,8 @@ void Context::Bind() const { MI_HIP_CHECK(hipSetDevice(device)); }
 int OutWidth(int32_t kind, int64_t param) {
   switch (kind) {
     case MI_K_COPY: return static_cast<int>(param);
-    case MI_K_BOOL: return 1;
+    case MI_K_BOOL: case MI_K_BOOL8: return 1;
+    case MI_K_UUID: return 16;
     case MI_K_DEC128: return static_cast<int>(param);
     case MI_K_DATE64: return 4;
     case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: return 8;
@@ -184,6 +185,9 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
     case MI_K_DURATION:
       if (t.param == 0) fail("duration factor must be non-zero");
       break;
+    case MI_K_UUID:
+      if (reinterpret_cast<uintptr_t>(t.buf1) % 4 != 0) fail("uuid buffer must be 4-byte aligned");
+      break;
     case MI_K_RUN_END: {
       const int64_t rw = t.param & 0xFF, w = (t.param >> 8) & 0xFF;
       if (rw != 2 && rw != 4 && rw != 8) fail("RUN_END run-end width must be 2,4,8");
@@ -228,6 +232,13 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
     case MI_K_ENC_LIST32:
       if (reinterpret_cast<uintptr_t>(t.buf1) % 16 != 0) fail("list_entry_t vector must be 16-byte aligned");
       break;
+    case MI_K_ENC_UUID_TEXT:
+      if (t.out_aux == nullptr) fail("out_aux (string data) is NULL");
+      if (reinterpret_cast<uintptr_t>(t.buf1) % 16 != 0) fail("UUID vector must be 16-byte aligned");
+      if (reinterpret_cast<uintptr_t>(t.out_aux) % 16 != 0) fail("string data buffer must be 16-byte aligned");
+      if (reinterpret_cast<uintptr_t>(t.out_data) % 8 != 0) fail("offsets buffer misaligned");
+      if (t.nrows > 0x7FFFFFFFll) fail("more than INT32_MAX rows");
+      break;
     default: break;
   }
   if (t.kind >= MI_K_ENC_COPY && t.kind != MI_K_ENC_COPY && t.out_validity == nullptr)
@@ -266,7 +277,8 @@ static int64_t TaskBytesRead(const mi_col_task& t) {
       case MI_K_STR64: b += (n ? (n + 1) * 8 : 0) + t.buf2_len; break;
       case MI_K_DICT: b += n * (t.param & 0xFF); break;
       case MI_K_INTERVAL_MONTHS: b += n * 4; break;
-      case MI_K_INTERVAL_MDN: b += n * 16; break;
+      case MI_K_INTERVAL_MDN: case MI_K_UUID: b += n * 16; break;
+      case MI_K_BOOL8: b += n; break;
       case MI_K_NARROW: b += n * (t.param & 0xFF); break;
       case MI_K_HALF_FLOAT: b += n * 2; break;
       case MI_K_LIST32: b += n ? (n + 1) * 4 : 0; break;
@@ -280,7 +292,7 @@ static int64_t TaskBytesRead(const mi_col_task& t) {
     switch (t.kind) {
       case MI_K_ENC_COPY: case MI_K_ENC_DEC128: b += n * t.param; break;
       case MI_K_ENC_BOOL: b += n; break;
-      case MI_K_ENC_STR32: case MI_K_ENC_LIST32: case MI_K_ENC_STRVIEW: b += n * 16; break;  // + payload, known only after the scan (reported via buf2_len if given)
+      case MI_K_ENC_STR32: case MI_K_ENC_LIST32: case MI_K_ENC_STRVIEW: case MI_K_ENC_UUID_TEXT: b += n * 16; break;  // + payload, known only after the scan (reported via buf2_len if given)
       default: break;
     }
     if (t.kind == MI_K_ENC_STR32 || t.kind == MI_K_ENC_STRVIEW) b += t.buf2_len;   // (views: the long strings alone)
@@ -298,7 +310,7 @@ static int64_t TaskBytesWritten(const mi_col_task& t) {
     case MI_K_ENC_COPY: b += n * t.param; break;
     case MI_K_ENC_DEC128: b += n * 16; break;
     case MI_K_ENC_BOOL: b += (n + 7) / 8; break;
-    case MI_K_ENC_STR32: b += (n + 1) * ((t.flags & 1) ? 8 : 4) + t.buf2_len; break;
+    case MI_K_ENC_STR32: case MI_K_ENC_UUID_TEXT: b += (n + 1) * ((t.flags & 1) ? 8 : 4) + t.buf2_len; break;   // (buf2_len: the text bytes)
     case MI_K_ENC_LIST32: b += (n + 1) * ((t.flags & 1) ? 8 : 4); break;
     case MI_K_ENC_STRVIEW: b += n * 16 + t.buf2_len; break;
     default: break;
@@ -407,6 +419,7 @@ void Plan::Set(const mi_col_task* in_tasks, int32_t n_tasks, hipStream_t upload_
         if (c == device::kClassDec128 || c == device::kClassString)   // which of the two kernel instances has tiles (device: tile_needs_mask)
           sl.misc_groups |= ((t.validity != nullptr && t.null_count != 0) || t.out_aux != nullptr) ? 2u : 1u;
         if (c == device::kClassEncString && t.kind == MI_K_ENC_LIST32) sl.misc_groups |= 2u;
+        if (c == device::kClassEncFixed) sl.misc_groups |= t.kind == MI_K_ENC_UUID_TEXT ? 2u : 1u;   // which of its two kernels has tiles
         order[i] = {static_cast<int>(slices.size()), static_cast<int32_t>(local_task)};
         local_task++;
         tasks.push_back(t);
@@ -483,7 +496,7 @@ void Plan::LaunchSlice(const ClassSlice& cs, hipStream_t s) {
   }
   switch (cs.cls) {
     case device::kClassEncFixed:
-      MI_HIP_CHECK(device::LaunchEncodeFixed(t, tb, tt, cs.n_tasks, cs.total_tiles, null_counts, s));
+      MI_HIP_CHECK(device::LaunchEncodeFixed(t, tb, tt, cs.n_tasks, cs.total_tiles, null_counts, status, cs.misc_groups, s));
       break;
     case device::kClassEncString:
       MI_HIP_CHECK(device::LaunchEncodeString(t, tb, tt, cs.n_tasks, cs.total_tiles, d_tile_sums.get<int64_t>(), null_counts, status, (cs.misc_groups & 2u) != 0, s));

@@ -9,6 +9,7 @@
 #include <functional>
 #include <unordered_map>
 
+#include "extension_format.hpp"
 #include "flatbuf.hpp"
 #include "union_format.hpp"
 
@@ -72,6 +73,12 @@ std::string ArrowField::Format() const {
 
 std::string ArrowField::DuckType() const {
   char tmp[64];
+  switch (extension) {
+    case extfmt::kUuid: return "UUID";
+    case extfmt::kBool8: return "BOOLEAN";
+    case extfmt::kJson: return "JSON";
+    default: break;
+  }
   switch (type) {
     case MI_AT_NULL: return "\"NULL\"";
     case MI_AT_INT: {
@@ -151,6 +158,8 @@ bool ArrowField::Plan(int32_t* kind, int64_t* param, int32_t* out_width, bool va
     return true;
   }
   auto set = [&](int32_t k, int64_t p, int32_t w) { *kind = k; *param = p; *out_width = w; return true; };
+  if (extension == extfmt::kUuid) return set(MI_K_UUID, 16, 16);
+  if (extension == extfmt::kBool8) return set(MI_K_BOOL8, 1, 1);
   switch (type) {
     case MI_AT_INT: return set(MI_K_COPY, bit_width / 8, bit_width / 8);
     case MI_AT_NULL: return set(MI_K_NULL, 0, 1);
@@ -381,6 +390,21 @@ static void DecodeKeyValues(const fb::Table& t, int id, std::vector<std::pair<st
   }
 }
 
+// The canonical extension type a field's metadata names, honoured only on the storage type it is defined for (the
+// dictionary's value type when the field is dictionary-encoded); any other name, and a name on another storage type, reads
+// as the storage type.
+static int32_t ExtensionOf(const ArrowField& f) {
+  for (auto& kv : f.metadata) {
+    if (kv.first != "ARROW:extension:name") continue;
+    if (kv.second == "arrow.uuid") return f.type == MI_AT_FIXED_BINARY && f.byte_width == extfmt::kUuidBytes ? extfmt::kUuid : extfmt::kNone;
+    if (kv.second == "arrow.bool8") return f.type == MI_AT_INT && f.bit_width == 8 && f.is_signed ? extfmt::kBool8 : extfmt::kNone;
+    if (kv.second == "arrow.json")
+      return f.type == MI_AT_UTF8 || f.type == MI_AT_LARGE_UTF8 || f.type == MI_AT_UTF8_VIEW ? extfmt::kJson : extfmt::kNone;
+    return extfmt::kNone;
+  }
+  return extfmt::kNone;
+}
+
 static ArrowField DecodeField(const fb::Table& f, int depth) {
   // Field { name [0]; nullable [1]; type_type [2]; type [3]; dictionary [4]; children [5]; custom_metadata [6] }
   if (depth > 64) throw IOException("Schema nesting too deep");
@@ -458,6 +482,7 @@ static ArrowField DecodeField(const fb::Table& f, int depth) {
     o.children.push_back(DecodeField(c, depth + 1));
   }
   DecodeKeyValues(f, 6, &o.metadata);
+  o.extension = ExtensionOf(o);
   return o;
 }
 
@@ -823,6 +848,15 @@ ArrowField FieldFromDuckType(const std::string& name, const std::string& duck_ty
   if (t == "FLOAT") { f.type = MI_AT_FLOAT; f.precision = 1; return f; }
   if (t == "DOUBLE") { f.type = MI_AT_FLOAT; f.precision = 2; return f; }
   if (t == "VARCHAR") { f.type = MI_AT_UTF8; return f; }
+  // UUID, arrow_lossless_conversion = false: utf8 of the canonical text, no extension metadata.  `extension` tells the writer that
+  // the vector it reads holds hugeint_t rows (MI_K_ENC_UUID_TEXT); it is not part of the encoded schema
+  if (t == "UUID") { f.type = MI_AT_UTF8; f.extension = extfmt::kUuid; return f; }
+  if (t == "JSON") {  // ArrowConverter with arrow_lossless_conversion = false: utf8 that carries the canonical extension name
+    f.type = MI_AT_UTF8;
+    f.extension = extfmt::kJson;
+    f.metadata = {{"ARROW:extension:name", "arrow.json"}, {"ARROW:extension:metadata", ""}};
+    return f;
+  }
   if (t == "BLOB") { f.type = MI_AT_BINARY; return f; }
   if (t == "DATE") { f.type = MI_AT_DATE; f.unit = 0; return f; }
   if (t == "TIME") { f.type = MI_AT_TIME; f.unit = 2; f.bit_width = 64; return f; }

@@ -104,6 +104,10 @@ struct ArrowField {
   std::vector<int32_t> type_ids;       // union: as the schema lists them, unchecked (union_format.hpp: CheckTypeIds)
   std::vector<ArrowField> children;
   std::vector<std::pair<std::string, std::string>> metadata;
+  //! derived from `metadata` by the schema decode: the canonical extension type (extfmt::Extension) that ARROW:extension:name
+  //! names, when this field's storage type (its dictionary's values, when dictionary-encoded) is the one it needs; else kNone.
+  //! On a field made by FieldFromDuckType: the DuckDB type was UUID / JSON (the writer reads hugeint_t rows for kUuid)
+  int32_t extension = 0;
 
   // derived
   std::string Format() const;    // Arrow C data interface format string

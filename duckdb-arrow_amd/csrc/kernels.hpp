@@ -286,8 +286,10 @@ void GroupLaunchCounts(int64_t out[2]);
 
 // K7 launches.  The string / list kernel is a single pass (decoupled look-back across the tiles of a column); it needs
 // 2 * total_tiles + 1 state words (zeroed by the launch).
+// LaunchEncodeFixed: groups bit 0 = the slice has tiles of encode_fixed, bit 1 = of encode_uuid_text (MI_K_ENC_UUID_TEXT).
 hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
-                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, hipStream_t stream);
+                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t groups,
+                             hipStream_t stream);
 hipError_t LaunchEncodeString(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
                               int32_t n_tasks, uint32_t total_tiles, int64_t* d_tile_state, int64_t* d_null_counts,
                               uint32_t* d_status, bool has_lists, hipStream_t stream);

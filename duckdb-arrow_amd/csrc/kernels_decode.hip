@@ -7,6 +7,7 @@
 // src/scanner/scan_arrow_ipc.cpp:56, src/file_scanner/arrow_file_scan.cpp:68-72); canonical values for slots upstream
 // leaves undefined: NULL rows of converted columns = 0, validity pad bits = 1.
 #include "device_common.hpp"
+#include "extension_format.hpp"
 
 #include <algorithm>
 
@@ -339,6 +340,36 @@ __device__ __forceinline__ void tile_half_float(const mi_col_task& t, int64_t ro
   }
 }
 
+// arrow.uuid: the 16 bytes of a row in text order -> hugeint_t{lower, upper} (extension_format.hpp); one 16-byte load and one
+// 16-byte store per row.  Every row is converted, the rows under a NULL too: source-derived, as MI_K_COPY leaves them.
+__device__ __forceinline__ void tile_uuid(const mi_col_task& t, int64_t row0, int n) {
+  gptr<const uint8_t> src = GC<uint8_t>(t.buf1) + (t.row_offset + row0) * 16;
+  gptr<u32x4> out = GM<u32x4>(t.out_data) + row0;
+#pragma unroll 4
+  for (int r = threadIdx.x; r < n; r += kBlockThreads) {
+    const u32x4 v = ld16((gptr<const u32x4_a4>)(src + 16 * static_cast<int64_t>(r)));
+    const extfmt::UuidValue u = extfmt::UuidFromHalves(static_cast<uint64_t>(v.x) | (static_cast<uint64_t>(v.y) << 32),
+                                                       static_cast<uint64_t>(v.z) | (static_cast<uint64_t>(v.w) << 32));
+    const uint64_t upper = static_cast<uint64_t>(u.upper);
+    st16(out + r, u32x4{static_cast<uint32_t>(u.lower), static_cast<uint32_t>(u.lower >> 32), static_cast<uint32_t>(upper), static_cast<uint32_t>(upper >> 32)});
+  }
+}
+
+// arrow.bool8: int8 -> BOOLEAN byte (v != 0), four rows per lane as one dword (the source sits on any byte: row_offset); every
+// row is converted, as above
+__device__ __forceinline__ void tile_bool8(const mi_col_task& t, int64_t row0, int n) {
+  typedef uint32_t u32_a1 __attribute__((aligned(1)));
+  gptr<const uint8_t> src = GC<uint8_t>(t.buf1) + t.row_offset + row0;
+  gptr<uint8_t> out = GM<uint8_t>(t.out_data) + row0;   // tiles start 16-byte aligned
+  for (int base = 4 * static_cast<int>(threadIdx.x); base < n; base += 4 * kBlockThreads) {
+    if (base + 4 <= n) {
+      *(gptr<uint32_t>)(out + base) = extfmt::Bool8x4(*(gptr<const u32_a1>)(src + base));
+    } else {
+      for (int k = 0; base + k < n; k++) out[base + k] = extfmt::Bool8(static_cast<int8_t>(src[base + k]));
+    }
+  }
+}
+
 // arrow null type: every row NULL
 __device__ __forceinline__ void tile_null(const mi_col_task& t, int64_t row0, int n) {
   gptr<uint8_t> out = GM<uint8_t>(t.out_data) + row0;
@@ -641,7 +672,7 @@ __global__ __launch_bounds__(kLightThreads) void transcode_misc_light(const mi_c
 }
 
 // The kinds that keep 256-thread workgroups.  GROUP 1: list entries, string views, struct validity; GROUP 2: the rare
-// flat kinds (intervals, durations, decimal32/64, half floats, null); the common flat kinds are transcode_misc_light's.
+// flat kinds (intervals, durations, decimal32/64, half floats, null, uuid, bool8); the common flat kinds are transcode_misc_light's.
 // Each group is its own kernel (own register budget) and a plan launches only the groups its tasks use.
 template <int GROUP>
 __global__ __launch_bounds__(kBlockThreads) void transcode_misc(const mi_col_task* __restrict__ tasks,
@@ -676,6 +707,8 @@ __global__ __launch_bounds__(kBlockThreads) void transcode_misc(const mi_col_tas
           break;
         }
         case MI_K_DURATION: tile_duration(t, row0, n, status, s_valid); break;
+        case MI_K_UUID: tile_uuid(t, row0, n); break;
+        case MI_K_BOOL8: tile_bool8(t, row0, n); break;
         default: break;
       }
     }
@@ -699,8 +732,8 @@ int ClassOfKind(int32_t kind) {
     case MI_K_STR32: case MI_K_STR64: case MI_K_FIXED_BINARY: return kClassString;
     case MI_K_BOOL: case MI_K_DATE64: case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DURATION:
     case MI_K_DICT: case MI_K_INTERVAL_MONTHS: case MI_K_INTERVAL_MDN: case MI_K_NARROW: case MI_K_HALF_FLOAT:
-    case MI_K_NULL: case MI_K_STRVIEW: case MI_K_LIST32: case MI_K_LIST64: case MI_K_STRUCT: return kClassMisc;
-    case MI_K_ENC_COPY: case MI_K_ENC_DEC128: case MI_K_ENC_BOOL: case MI_K_ENC_VALIDITY: return kClassEncFixed;
+    case MI_K_NULL: case MI_K_STRVIEW: case MI_K_LIST32: case MI_K_LIST64: case MI_K_STRUCT: case MI_K_UUID: case MI_K_BOOL8: return kClassMisc;
+    case MI_K_ENC_COPY: case MI_K_ENC_DEC128: case MI_K_ENC_BOOL: case MI_K_ENC_VALIDITY: case MI_K_ENC_UUID_TEXT: return kClassEncFixed;
     case MI_K_ENC_STR32: case MI_K_ENC_LIST32: return kClassEncString;
     default: return -1;
   }

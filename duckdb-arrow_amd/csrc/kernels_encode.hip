@@ -2,6 +2,7 @@
 // (call site in the reference: src/writer/column_data_collection_serializer.cpp:85).
 #include "device_common.hpp"
 #include "encode_common.hpp"
+#include "extension_format.hpp"
 
 #include <algorithm>
 
@@ -57,6 +58,7 @@ __global__ __launch_bounds__(kBlockThreads) void encode_fixed(const mi_col_task*
                                                               uint32_t total_tiles, int64_t* __restrict__ null_counts) {
   for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
     MI_TILE_PROLOGUE();
+    if (t.kind == MI_K_ENC_UUID_TEXT) continue;  // uniform: encode_uuid_text owns this tile
     // wave 0 asks for the tile's validity words, moves its share of the data, and only then turns the words into bitmap
     // bytes and a NULL count: one round trip for the wave instead of two
     const EncValidity tv = enc_tile_validity_load(t, row0, n);
@@ -304,6 +306,117 @@ __device__ __forceinline__ void stage_to_data(const uint8_t* st, uint32_t shiftw
     const bool last_partial = (end & 15u) != 0 && lastlo != 0;
     const bool mine = threadIdx.x < 16 ? first_partial : last_partial;
     if (mine && idx >= shiftw && idx < end) gbase[idx] = st[idx];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- K7f, UUID -> text
+// hugeint_t UUID rows -> utf8 / large_utf8, DuckDB's Arrow export of a UUID column (ArrowVarcharData over UUID::ToString): a
+// valid row is 36 bytes of text, a NULL row none (its offset repeats).  So a tile's first byte is 36 x the valid rows in front
+// of it, and the tile counts those itself from the validity words [0, row0 / 64) -- at most 15 KiB of reads for the last tile
+// of a 122 880-row row group; there is no look-back and no wait for another workgroup.  Inside the tile a row's slot is the
+// rank of its valid bit (the words in LDS, a 33-entry prefix of their popcounts).  256-row sub-blocks: every lane loads its
+// row (16 bytes), puts the text together in registers (extension_format.hpp: UuidTextWords) and stores it to LDS as nine
+// dwords -- 36 x slot keeps them 4-byte aligned --, and the sub-block leaves as 16-byte stores (stage_to_data) from two
+// alternating stage buffers, one barrier per sub-block.  Bitmap and NULL count: enc_tile_validity_load / _finish.
+constexpr int kUuidStage = kBlockThreads * extfmt::kUuidTextBytes;   // bytes of a sub-block without NULLs
+constexpr int kUuidStageBuf = kUuidStage + 32;                       // + the phase of its first byte (< 16), whole 16-byte rows
+
+__global__ __launch_bounds__(kBlockThreads) void encode_uuid_text(const mi_col_task* __restrict__ tasks,
+                                                                  const uint32_t* __restrict__ tile_begin, const uint32_t* __restrict__ tile_task, int n_tasks,
+                                                                  uint32_t total_tiles, int64_t* __restrict__ null_counts, uint32_t* __restrict__ status) {
+  constexpr int kWords = kTileRows / 64, kWaves = kBlockThreads / 64;
+  static_assert(kUuidStageBuf % 16 == 0, "both stage buffers start 16-byte aligned");
+  __shared__ uint64_t s_valid[kWords];
+  __shared__ uint32_t s_pref[kWords + 1];           // valid rows of the tile in front of word j; [kWords]: in the tile
+  __shared__ unsigned long long s_before[kWaves];
+  __shared__ __attribute__((aligned(16))) uint8_t stage[2 * kUuidStageBuf];
+  (void)n_tasks;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+    MI_TILE_PROLOGUE();
+    if (t.kind != MI_K_ENC_UUID_TEXT) continue;  // uniform: encode_fixed owns this tile
+    __syncthreads();  // the tile before this one is done with the shared words
+    const EncValidity tv = enc_tile_validity_load(t, row0, n, s_valid);
+    const bool has = t.validity != nullptr;
+    if (has) {  // valid rows in front of the tile: row0 is a multiple of 2048, so whole words
+      gptr<const uint64_t> W = GC<uint64_t>(t.validity);
+      const int nw = static_cast<int>(row0 >> 6);
+      unsigned long long c = 0;
+      for (int i = threadIdx.x; i < nw; i += kBlockThreads) c += static_cast<unsigned long long>(__builtin_popcountll(W[i]));
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
+      if (lane == 0) s_before[wave] = c;
+    }
+    enc_tile_validity_finish(t, row0, n, null_counts, tv, s_valid);
+    __syncthreads();  // s_valid, s_before
+    const int nwords = (n + 63) >> 6;
+    if (wave == 0) {
+      uint32_t v = 0;
+      if (lane < nwords) {
+        uint64_t w = s_valid[lane];
+        const int rem = n - 64 * lane;
+        if (rem < 64) w &= (1ull << rem) - 1ull;   // the pad bits are no rows
+        v = static_cast<uint32_t>(__builtin_popcountll(w));
+      }
+      const uint32_t inc = wave_inclusive_scan_u32(v);
+      if (lane < kWords) s_pref[lane] = inc - v;
+      if (lane == kWords - 1) s_pref[kWords] = inc;
+    }
+    __syncthreads();  // s_pref
+    unsigned long long before = static_cast<unsigned long long>(row0);
+    if (has) {
+      before = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; w++) before += s_before[w];
+    }
+    const bool large = (t.flags & 1) != 0;  // LargeUtf8: int64 offsets (arrow_large_buffer_size)
+    gptr<const u32x4> src = GC<u32x4>(t.buf1) + row0;
+    gptr<int32_t> offp = GM<int32_t>(t.out_data) + row0 + 1;
+    gptr<int64_t> offp64 = GM<int64_t>(t.out_data) + row0 + 1;
+    gptr<uint8_t> data = GM<uint8_t>(t.out_aux);
+    if (threadIdx.x == 0) {
+      if (row0 == 0) {
+        if (large) offp64[-1] = 0;
+        else offp[-1] = 0;
+      }
+      // the column's last tile knows the size of its data buffer: int32 offsets must fit (ArrowAppender's check)
+      if (tile + 1 == tile_begin[ti + 1] && !large && static_cast<int64_t>(before + s_pref[kWords]) * extfmt::kUuidTextBytes > 0x7FFFFFFFll)
+        atomicOr(status, MI_ST_OFFSET_OVERFLOW);
+    }
+    const int nsub = (n + kBlockThreads - 1) / kBlockThreads;
+    uint32_t buf = 0;
+#pragma clang loop unroll(disable)
+    for (int k = 0; k < nsub; k++) {
+      const int r = static_cast<int>(threadIdx.x) + k * kBlockThreads;
+      const int j = k * kWaves + wave;   // the word of this wave's 64 rows
+      const bool active = r < n;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (active) v = __builtin_nontemporal_load(src + r);
+      const uint64_t word = j < nwords ? s_valid[j] : 0ull;
+      const bool ok = active && ((word >> lane) & 1ull);
+      const uint32_t slot = s_pref[j] + static_cast<uint32_t>(__builtin_popcountll(word & ((1ull << lane) - 1ull)));   // rank in the tile
+      const uint32_t sub0 = s_pref[k * kWaves], sub1 = s_pref[k * kWaves + kWaves];
+      if (active) {
+        const int64_t end = static_cast<int64_t>(before + slot + (ok ? 1u : 0u)) * extfmt::kUuidTextBytes;
+        if (large) offp64[r] = end;
+        else offp[r] = static_cast<int32_t>(end);
+      }
+      const int64_t base = static_cast<int64_t>(before + sub0) * extfmt::kUuidTextBytes;   // first byte of the sub-block
+      const uint32_t bytes = (sub1 - sub0) * extfmt::kUuidTextBytes;
+      const uint32_t shiftw = static_cast<uint32_t>(base & 15);   // a multiple of 4
+      uint8_t* st = stage + buf * kUuidStageBuf;
+      if (ok) {
+        uint32_t w[9];
+        extfmt::UuidTextWords(static_cast<uint64_t>(v.x) | (static_cast<uint64_t>(v.y) << 32),
+                              static_cast<int64_t>(static_cast<uint64_t>(v.z) | (static_cast<uint64_t>(v.w) << 32)), w);
+        uint32_t* d = reinterpret_cast<uint32_t*>(st + shiftw + (slot - sub0) * extfmt::kUuidTextBytes);
+#pragma unroll
+        for (int i = 0; i < 9; i++) d[i] = w[i];
+      }
+      __syncthreads();
+      if (bytes != 0) stage_to_data(st, shiftw, shiftw + bytes, data + base - shiftw);
+      buf ^= 1u;   // the buffer is written again two sub-blocks on, behind the next barrier
+    }
   }
 }
 
@@ -616,11 +729,17 @@ __global__ __launch_bounds__(kBlockThreads) void encode_string_slow(const mi_col
 // Encode launches follow the decode rule: one workgroup per tile (the dispatcher balances them), owner of a tile from
 // the tile -> task table.
 hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
-                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, hipStream_t stream) {
+                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t groups,
+                             hipStream_t stream) {
   MI_DROP_STALE_ERROR();
   if (total_tiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(encode_fixed, dim3(total_tiles), dim3(kBlockThreads), 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks,
-                     total_tiles, d_null_counts);
+  // groups: bit 0 = tiles of encode_fixed, bit 1 = MI_K_ENC_UUID_TEXT tiles; a tile of the other kernel returns at once
+  if (groups & 1u)
+    hipLaunchKernelGGL(encode_fixed, dim3(total_tiles), dim3(kBlockThreads), 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks,
+                       total_tiles, d_null_counts);
+  if (groups & 2u)
+    hipLaunchKernelGGL(encode_uuid_text, dim3(total_tiles), dim3(kBlockThreads), 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks,
+                       total_tiles, d_null_counts, d_status);
   return hipGetLastError();
 }
 

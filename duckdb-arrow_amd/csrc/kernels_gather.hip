@@ -15,6 +15,7 @@
 // stores are coalesced.  Validity: the host presets the output words to all ones; a column with NULLs clears bits with one
 // wave ballot + at most two atomicAnd per 64 rows (a window's output range is not word aligned).
 #include "device_common.hpp"
+#include "extension_format.hpp"
 
 namespace miarrow {
 namespace device {
@@ -199,6 +200,24 @@ __global__ __launch_bounds__(kBlockThreads) void transcode_gather(const mi_col_t
         });
         break;
       }
+      case MI_K_UUID: {   // every selected row is converted, as the flat tile does
+        gptr<const uint8_t> src = GC<uint8_t>(t.buf1) + t.row_offset * 16;
+        gptr<u32x4> out = GM<u32x4>(t.out_data);
+        gather_rows(t, row0, out0, sel, cnt, [&](int64_t r, int64_t s, bool) {
+          const u32x4 v = *(gptr<const u32x4_a4>)(src + 16 * s);
+          const extfmt::UuidValue u = extfmt::UuidFromHalves(static_cast<uint64_t>(v.x) | (static_cast<uint64_t>(v.y) << 32),
+                                                             static_cast<uint64_t>(v.z) | (static_cast<uint64_t>(v.w) << 32));
+          const uint64_t upper = static_cast<uint64_t>(u.upper);
+          out[r] = u32x4{static_cast<uint32_t>(u.lower), static_cast<uint32_t>(u.lower >> 32), static_cast<uint32_t>(upper), static_cast<uint32_t>(upper >> 32)};
+        });
+        break;
+      }
+      case MI_K_BOOL8: {
+        gptr<const int8_t> src = GC<int8_t>(t.buf1) + t.row_offset;
+        gptr<uint8_t> out = GM<uint8_t>(t.out_data);
+        gather_rows(t, row0, out0, sel, cnt, [&](int64_t r, int64_t s, bool) { out[r] = extfmt::Bool8(src[s]); });
+        break;
+      }
       case MI_K_DATE64: {
         gptr<const int64_t> src = GC<int64_t>(t.buf1) + t.row_offset;
         gptr<int32_t> out = GM<int32_t>(t.out_data);
@@ -269,7 +288,7 @@ __global__ __launch_bounds__(kBlockThreads) void transcode_gather(const mi_col_t
 bool KindCanGather(int32_t kind) {
   switch (kind) {
     case MI_K_COPY: case MI_K_DEC128: case MI_K_STR32: case MI_K_STR64: case MI_K_FIXED_BINARY: case MI_K_BOOL: case MI_K_DATE64:
-    case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DICT:
+    case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DICT: case MI_K_UUID: case MI_K_BOOL8:
       return true;
     default:
       return false;

@@ -277,7 +277,7 @@ int32_t GroupKeyClassOf(const ScanColumn& c) {
     default: break;
   }
   if (IsStringKind(kind)) return groupkey::kKeyString;
-  if (kind == MI_K_BOOL) return groupkey::kKeyUnsigned;
+  if (kind == MI_K_BOOL || kind == MI_K_BOOL8) return groupkey::kKeyUnsigned;
   if (IsIntegerLike(kind, w, vf, /*allow_bool*/ false)) return vf.type == MI_AT_INT && !vf.is_signed ? groupkey::kKeyUnsigned : groupkey::kKeySigned;
   return 0;
 }

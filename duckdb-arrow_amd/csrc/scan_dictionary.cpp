@@ -3,13 +3,15 @@
 
 #include <cstring>
 
+#include "extension_format.hpp"
+
 namespace miarrow {
 
 bool DictionaryKindIsFlat(int32_t kind) {
   switch (kind) {
     case MI_K_COPY: case MI_K_BOOL: case MI_K_DEC128: case MI_K_DATE64: case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64:
     case MI_K_STR32: case MI_K_STR64: case MI_K_FIXED_BINARY: case MI_K_DURATION: case MI_K_INTERVAL_MONTHS: case MI_K_INTERVAL_MDN:
-    case MI_K_NARROW: case MI_K_HALF_FLOAT:
+    case MI_K_NARROW: case MI_K_HALF_FLOAT: case MI_K_UUID: case MI_K_BOOL8:
       return true;
     default:
       return false;
@@ -65,7 +67,8 @@ void AppendHostStrings(const DecodedBatch& b, int32_t kind, int64_t param, int64
   }
 }
 
-// the new fixed-width values as the decode leaves them (float16 widened, exactly; every other admitted type as it is stored)
+// the new fixed-width values as the decode leaves them (float16 widened, exactly; arrow.uuid as hugeint_t, arrow.bool8 as 0 / 1;
+// every other admitted type as it is stored)
 void AppendHostValues(const DecodedBatch& b, int32_t kind, int32_t width, int64_t n_old, int64_t n_new, DictHostValues* out) {
   const mi_buffer_span* sp = &b.buffers[0];
   const size_t vw = static_cast<size_t>(width), sw = kind == MI_K_HALF_FLOAT ? 2 : vw;
@@ -73,6 +76,18 @@ void AppendHostValues(const DecodedBatch& b, int32_t kind, int32_t width, int64_
   out->host_values.resize(static_cast<size_t>(n_old + n_new) * vw, 0);
   uint8_t* dst = out->host_values.data() + static_cast<size_t>(n_old) * vw;
   const uint8_t* src = b.body + sp[1].offset;
+  if (kind == MI_K_UUID) {
+    for (int64_t i = 0; i < n_new; i++) {
+      const extfmt::UuidValue u = extfmt::UuidFromArrow(src + 16 * i);
+      std::memcpy(dst + 16 * i, &u.lower, 8);
+      std::memcpy(dst + 16 * i + 8, &u.upper, 8);
+    }
+    return;
+  }
+  if (kind == MI_K_BOOL8) {
+    for (int64_t i = 0; i < n_new; i++) dst[i] = extfmt::Bool8(static_cast<int8_t>(src[i]));
+    return;
+  }
   if (kind != MI_K_HALF_FLOAT) {
     if (n_new > 0) std::memcpy(dst, src, static_cast<size_t>(n_new) * vw);
     return;

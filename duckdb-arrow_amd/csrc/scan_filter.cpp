@@ -17,6 +17,7 @@
 #include <cstring>
 #include <limits>
 
+#include "extension_format.hpp"
 #include "filter_key.hpp"
 #include "like_match.hpp"
 #include "scan_operator.hpp"
@@ -30,6 +31,7 @@ FilterValueClass FilterClassOf(const ArrowField& field) {
   if (!vf.Plan(&kind, &param, &w, /*value_only*/ true)) return FilterValueClass::kOther;
   if (vf.type == MI_AT_FLOAT && (w == 4 || w == 8)) return w == 4 ? FilterValueClass::kFloat32 : FilterValueClass::kFloat64;
   if (vf.type == MI_AT_DECIMAL && kind == MI_K_COPY && w == 16) return FilterValueClass::kWide;
+  if (kind == MI_K_UUID) return FilterValueClass::kWide;   // hugeint_t whose signed order is the order of the text
   return FilterValueClass::kOther;
 }
 
@@ -118,7 +120,10 @@ FilterLeaf LeafOf(const mi_filter_node& n, const std::vector<ScanColumn>* column
       if (n.value_kind == MI_FV_DOUBLE && !is_float) throw InvalidInputException(what + "a double constant (MI_FV_DOUBLE) needs a FLOAT / DOUBLE column");
       if (n.value_kind != MI_FV_DOUBLE && is_float) throw InvalidInputException(what + "a FLOAT / DOUBLE column needs double constants (MI_FV_DOUBLE)");
       if (n.value_kind == MI_FV_INT128 && cls != FilterValueClass::kWide)
-        throw InvalidInputException(what + "a 128-bit constant (MI_FV_INT128) needs a HUGEINT / DECIMAL(19..38) column");
+        throw InvalidInputException(what + "a 128-bit constant (MI_FV_INT128) needs a HUGEINT / DECIMAL(19..38) / UUID column");
+      // an int64 is no UUID: sign-extended, as on HUGEINT, it would name a value no text maps to
+      if (n.value_kind == MI_FV_INT64 && ValueField(sc->field).extension == extfmt::kUuid)
+        throw InvalidInputException(what + "a UUID column needs 128-bit constants (MI_FV_INT128): the hugeint_t image of the UUID");
     } else {
       cls = n.value_kind == MI_FV_DOUBLE ? FilterValueClass::kFloat64 : n.value_kind == MI_FV_INT128 ? FilterValueClass::kWide : FilterValueClass::kOther;
     }

@@ -582,6 +582,7 @@ void ArrowScan::DeviceColumn(const BatchRef& ref, size_t c, DeviceColumnView* ou
     out->h_offsets = s.batch.body + dn.spans[1].offset;
     out->h_validity = dn.spans[0].length > 0 ? s.batch.body + dn.spans[0].offset : nullptr;
   }
+  if (pn.kind == MI_K_UUID) out->h_validity = dn.spans[0].length > 0 ? s.batch.body + dn.spans[0].offset : nullptr;   // (sizes its text)
   out->flat = true;
 }
 

@@ -61,7 +61,7 @@ inline const ArrowField& ValueField(const ArrowField& f) { return f.type == MI_A
 //! -- and booleans where `allow_bool` -- by their transcode plan
 inline bool IsIntegerLike(int32_t kind, int32_t width, const ArrowField& f, bool allow_bool) {
   return (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
-          kind == MI_K_DIV_I64 || kind == MI_K_NARROW || (allow_bool && kind == MI_K_BOOL)) &&
+          kind == MI_K_DIV_I64 || kind == MI_K_NARROW || (allow_bool && (kind == MI_K_BOOL || kind == MI_K_BOOL8))) &&
          (width == 1 || width == 2 || width == 4 || width == 8) && f.type != MI_AT_FLOAT;
 }
 

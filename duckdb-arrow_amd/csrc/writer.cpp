@@ -1,6 +1,7 @@
 // writer.cpp -- see writer.hpp.
 #include "writer.hpp"
 #include "writer_internal.hpp"
+#include "extension_format.hpp"
 #include "writer_plan.hpp"
 
 #include <fcntl.h>
@@ -53,6 +54,7 @@ void EncodePlanFor(const ArrowField& f, int32_t* enc_kind, int64_t* param, int32
       else { *enc_kind = MI_K_ENC_COPY; *param = 16; *width = 16; }
       return;
     case MI_AT_UTF8: case MI_AT_BINARY: case MI_AT_LARGE_UTF8: case MI_AT_LARGE_BINARY:
+      if (f.extension == extfmt::kUuid) { *enc_kind = MI_K_ENC_UUID_TEXT; *param = 16; *width = 16; return; }   // hugeint_t rows -> their text
       *enc_kind = MI_K_ENC_STR32; *param = 0; *width = 16; return;
     case MI_AT_UTF8_VIEW: *enc_kind = MI_K_ENC_STRVIEW; *param = 0; *width = 16; return;   // produce_arrow_string_view
     default: throw NotImplementedException("Arrow type " + f.Format() + " is not encoded by the MI355X writer path");
@@ -217,6 +219,12 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
   std::memcpy(c.data.get() + static_cast<size_t>(c.count) * static_cast<size_t>(c.width),
               static_cast<const uint8_t*>(v.data) + static_cast<size_t>(start) * static_cast<size_t>(c.width),
               static_cast<size_t>(n) * static_cast<size_t>(c.width));
+  if (c.enc_kind == MI_K_ENC_UUID_TEXT) {   // 36 bytes of text per valid row, none per NULL row
+    int64_t valid = n;
+    if (v.validity)
+      for (int64_t i = 0; i < n; i++) valid -= BitAt(v.validity, vbit + i) ? 0 : 1;
+    c.payload_bytes += valid * extfmt::kUuidTextBytes;
+  }
   if (c.enc_kind == MI_K_ENC_STR32 || c.enc_kind == MI_K_ENC_STRVIEW) {
     c.payload_bytes += payload;
     if (extra_heap > 0) {
@@ -602,7 +610,8 @@ void MakeLarge(ArrowField& f) {
 // produce_arrow_string_view: VARCHAR at any depth exports as Utf8View, whatever arrow_large_buffer_size says (ArrowConverter::
 // ToArrowSchema asks for the view property first); BLOB is not touched (DuckDB writes no binary views)
 void MakeView(ArrowField& f) {
-  if (f.type == MI_AT_UTF8) f.type = MI_AT_UTF8_VIEW;
+  // (a UUID column stays utf8 / large_utf8: DuckDB's switch for UUID looks at the offset size alone)
+  if (f.type == MI_AT_UTF8 && f.extension != extfmt::kUuid) f.type = MI_AT_UTF8_VIEW;
   for (auto& c : f.children) MakeView(c);
 }
 

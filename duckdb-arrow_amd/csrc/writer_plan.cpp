@@ -26,7 +26,7 @@ void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out) {
       case MI_K_ENC_COPY: add_span(n * c.param); break;
       case MI_K_ENC_DEC128: add_span(n * 16); break;
       case MI_K_ENC_BOOL: add_span((n + 7) / 8); break;
-      case MI_K_ENC_STR32:
+      case MI_K_ENC_STR32: case MI_K_ENC_UUID_TEXT:
         if (c.payload_bytes > 0x7FFFFFFFll && !c.large_offsets) {
           throw InvalidInputException(
               "Arrow Appender: The maximum total string size for regular string buffers is 2147483647 but the offset of " +
@@ -67,6 +67,10 @@ mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, cons
   t.out_data = body + spans[1].offset;
   if (node.kind == MI_K_ENC_LIST32) return t;   // bitmap + int32 (or int64) offsets from the staged list_entry_t rows
   t.param = node.param;
+  if (node.kind == MI_K_ENC_UUID_TEXT) {   // no heap: the text is made from the rows
+    t.buf2_len = node.payload_bytes;
+    t.out_aux = body + spans[2].offset;
+  }
   if (node.kind == MI_K_ENC_STR32 || node.kind == MI_K_ENC_STRVIEW) {
     t.buf2 = in.heap;
     t.buf2_len = node.payload_bytes;

@@ -29,7 +29,7 @@ struct EncodeNode {
   bool large_offsets = false;   // int64 Arrow offsets
   int64_t rows = 0;
   int64_t payload_bytes = 0;    // size of the Arrow data buffer: MI_K_ENC_STR32 the bytes of the valid rows, MI_K_ENC_STRVIEW of
-                                // those among them that are longer than 12 bytes
+                                // those among them that are longer than 12 bytes, MI_K_ENC_UUID_TEXT 36 per valid row
 };
 struct BodyLayout {
   std::vector<mi_buffer_span> spans;   // RecordBatch.buffers

@@ -90,7 +90,10 @@ inline void MiSchemaToDuck(mi_reader* reader, vector<mi_field>& fields, vector<s
       throw NotImplementedException("Column '%s' (%s) is not decoded by the MI355X scan path", f.name, f.format);
     }
     names.emplace_back(f.name);
-    types.push_back(TransformStringToLogicalType(f.duck_type));
+    // UUID parses as DuckDB's own type (its hugeint_t image is what the scan hands over).  JSON is VARCHAR under the alias
+    // "JSON", which the parser only knows once the json extension is loaded: a top-level JSON column is mapped by hand
+    // (arrow.json inside a nested type still needs that extension).
+    types.push_back(string(f.duck_type) == "JSON" ? LogicalType::JSON() : TransformStringToLogicalType(f.duck_type));
   }
 }
 

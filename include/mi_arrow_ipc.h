@@ -127,6 +127,10 @@ enum mi_kind {
                              flags 0 or 1); param = bytes per value (1, 2, 4, 8, 16).  Row r with its mask bit set and
                              0 <= offsets[r] < buf2_len takes value and validity bit of scratch row offsets[r]; every other
                              row is zero and NULL (an offset out of range under a set bit raises MI_ST_BAD_UNION_OFFSET) */
+  MI_K_UUID = 25,         /* arrow.uuid on fixed_size_binary(16) -> DuckDB UUID, hugeint_t{u64 lower, i64 upper}: upper = bytes 0..7
+                             big-endian with bit 63 flipped, lower = bytes 8..15 big-endian (extension_format.hpp); every row is
+                             converted, NULL rows too; buf1 4-byte aligned */
+  MI_K_BOOL8 = 26,        /* arrow.bool8 on int8 -> DuckDB BOOLEAN, one byte per row: v != 0; every row is converted */
   /* encode direction (K7), used by mi_encode_* plans */
   MI_K_ENC_COPY = 32,     /* K7b fixed-width copy; param = width */
   MI_K_ENC_DEC128 = 33,   /* K7b int16/32/64 -> decimal128 sign extension; param = in width */
@@ -136,9 +140,12 @@ enum mi_kind {
   MI_K_ENC_LIST32 = 37,   /* list_entry_t{u64 offset, u64 length} rows -> bitmap + int32 Arrow offsets (running sum of the
                            * lengths of the valid rows, NULL rows repeat the offset: ArrowListData::AppendOffsets); the
                            * child rows are a node of their own, gathered in list order */
-  MI_K_ENC_STRVIEW = 38   /* K7e string_t -> Arrow string views (Utf8View, produce_arrow_string_view): out_data = 16 bytes per row,
+  MI_K_ENC_STRVIEW = 38,  /* K7e string_t -> Arrow string views (Utf8View, produce_arrow_string_view): out_data = 16 bytes per row,
                            * out_aux = the ONE data buffer (the strings of more than 12 bytes of the valid rows, back to back in
                            * row order; int32 offsets, no large variant) */
+  MI_K_ENC_UUID_TEXT = 39 /* DuckDB UUID (hugeint_t) rows -> utf8 of their canonical text, as DuckDB exports UUID columns: out_data =
+                           * int32 offsets (flags bit 0: int64, LargeUtf8), out_aux = the text, 36 bytes per valid row and none per
+                           * NULL row (16-byte aligned); buf2_len = the bytes out_aux holds (statistics only) */
 };
 
 typedef struct mi_field {

@@ -66,13 +66,6 @@ struct mi_plan {
   std::unique_ptr<Plan> plan;
 };
 
-// the dominant kernel of every class, as rocprofv3 prints it
-extern "C" const char* KernelNameOfClass(int32_t cls) {
-  static const char* names[device::kNumClasses] = {"transcode_copy", "transcode_dec128", "transcode_string", "transcode_misc_light",
-                                                  "encode_fixed", "encode_string_1p", "transcode_gather"};
-  return (cls >= 0 && cls < device::kNumClasses) ? names[cls] : "";
-}
-
 extern "C" {
 
 const char* mi_last_error(void) { return g_last_error.c_str(); }
@@ -294,7 +287,7 @@ int mi_plan_class_stats(const mi_plan* plan, int32_t cls, int64_t* bytes_read, i
     if (bytes_written) *bytes_written = plan->plan->class_bytes_written[cls];
     if (rows) *rows = plan->plan->class_rows[cls];
     if (tiles) *tiles = plan->plan->class_tiles[cls];
-    if (kernel_name) *kernel_name = KernelNameOfClass(cls);
+    if (kernel_name) *kernel_name = device::KernelNameOfClass(cls);
   });
 }
 

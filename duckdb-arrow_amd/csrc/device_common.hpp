@@ -65,9 +65,7 @@ __device__ __forceinline__ void raise(uint32_t* status, uint32_t bits) {
 // With a parent (out_aux = validity words of the struct / fixed_size_list vector that owns this column) the parent's
 // NULLs propagate into the child (ArrowToDuckDBStruct / ArrowToDuckDBArray).  `s_valid` (LDS, 32 words) receives the
 // combined words so the data lanes canonicalise NULL rows with the same mask; returns whether any row can be NULL.
-__device__ __forceinline__ bool tile_needs_mask(const mi_col_task& t) {
-  return (t.validity != nullptr && t.null_count != 0) || t.out_aux != nullptr;
-}
+__device__ __forceinline__ bool tile_needs_mask(const mi_col_task& t) { return TaskNeedsMask(t); }
 
 template <int T = kBlockThreads>  // threads of the workgroup that owns the tile
 __device__ __forceinline__ void tile_validity(const mi_col_task& t, int64_t row0, int n, uint64_t* s_valid = nullptr) {

@@ -295,8 +295,6 @@ int mi_hbm_stats(mi_hbm* h, int64_t* bytes_read, int64_t* bytes_written, int64_t
   });
 }
 
-const char* KernelNameOfClass(int32_t cls);  // c_api.cpp
-
 int mi_hbm_class_stats(mi_hbm* h, int32_t kernel_class, int64_t* bytes_read, int64_t* bytes_written, int64_t* rows,
                        int64_t* tiles, const char** kernel_name) {
   return WrapC([&] {
@@ -306,7 +304,7 @@ int mi_hbm_class_stats(mi_hbm* h, int32_t kernel_class, int64_t* bytes_read, int
     if (bytes_written) *bytes_written = p.class_bytes_written[kernel_class];
     if (rows) *rows = p.class_rows[kernel_class];
     if (tiles) *tiles = p.class_tiles[kernel_class];
-    if (kernel_name) *kernel_name = KernelNameOfClass(kernel_class);
+    if (kernel_name) *kernel_name = device::KernelNameOfClass(kernel_class);
   });
 }
 

@@ -8,38 +8,21 @@
 #include "../../include/mi_arrow_ipc.h"
 #include "agg_merge.hpp"
 #include "lz4_encode_format.hpp"
+#include "task_kind.hpp"
 
 namespace miarrow {
 namespace device {
 
 constexpr int kBlockThreads = 256;   // 4 waves of 64
 constexpr int kTileRows = 2048;      // rows per tile == DuckDB STANDARD_VECTOR_SIZE: one tile is one output vector
-#ifndef MI_COPY_TILE_ROWS
-#define MI_COPY_TILE_ROWS 2048
-#endif
-#ifndef MI_DEC_TILE_ROWS
-#define MI_DEC_TILE_ROWS 2048
-#endif
-constexpr int kCopyTileRows = MI_COPY_TILE_ROWS;  // copy / dec128 tiles may span several vectors (multiples of 2048)
-constexpr int kDecTileRows = MI_DEC_TILE_ROWS;
-int TileRowsOfClass(int cls);
-
-// Kernel classes: a plan groups its tasks by class and launches one kernel per non-empty class.
-enum KernelClass { kClassCopy = 0, kClassDec128 = 1, kClassString = 2, kClassMisc = 3, kClassEncFixed = 4, kClassEncString = 5, kClassGather = 6,
-                   kNumClasses = 7 };
-int ClassOfKind(int32_t kind);  // -1 for an unknown kind
-//! class of a task: gather mode (mi_col_task.sel) has its own kernel; -1 when the kind is unknown or cannot be gathered
-int ClassOfTask(const mi_col_task& t);
-bool KindCanGather(int32_t kind);
+static_assert(kTileRows == kVectorRows, "the plan layout (task_kind.hpp) counts tiles of kVectorRows rows");
 
 // One launch over a device-resident task table slice.  `tile_begin[i]` = first tile of task i within the slice,
 // tile_begin[n_tasks] = total_tiles.  `status` accumulates MI_ST_* bits.
 // `tile_task[tile]` = task index (within the slice) of every tile of the slice.  One workgroup per tile.
+// `kernel_mask`: which kernels of the class have tiles (KernelMaskOfTask, task_kind.hpp).
 hipError_t LaunchTranscode(int cls, const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
-                           int32_t n_tasks, uint32_t total_tiles, uint32_t* d_status, uint32_t misc_groups, hipStream_t stream);
-// which transcode_misc kernel owns a kind of the misc class: 0 / 3 common flat kinds (one wave per tile; 3 = 8-byte inputs),
-// 1 nested, 2 rare flat
-int MiscGroupOfKind(int32_t kind);
+                           int32_t n_tasks, uint32_t total_tiles, uint32_t* d_status, uint32_t kernel_mask, hipStream_t stream);
 
 // Run-end encoded columns (kernels_run_end.hip): MI_K_RUN_END tasks only, one workgroup per 2048-row tile.  Launched after
 // every other slice of the plan: the values child must be decoded first.
@@ -286,9 +269,9 @@ void GroupLaunchCounts(int64_t out[2]);
 
 // K7 launches.  The string / list kernel is a single pass (decoupled look-back across the tiles of a column); it needs
 // 2 * total_tiles + 1 state words (zeroed by the launch).
-// LaunchEncodeFixed: groups bit 0 = the slice has tiles of encode_fixed, bit 1 = of encode_uuid_text (MI_K_ENC_UUID_TEXT).
+// LaunchEncodeFixed: kernel_mask bit 0 = the slice has tiles of encode_fixed, bit 1 = of encode_uuid_text (MI_K_ENC_UUID_TEXT).
 hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
-                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t groups,
+                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t kernel_mask,
                              hipStream_t stream);
 hipError_t LaunchEncodeString(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
                               int32_t n_tasks, uint32_t total_tiles, int64_t* d_tile_state, int64_t* d_null_counts,

@@ -1,7 +1,7 @@
 // kernels_decode.hip -- Arrow IPC buffers -> DuckDB vectors (K1-K5 + nested types), one kernel per class.
 //
 // Kernel classes: each class is its own kernel so that it gets the register budget of its own inner loop (a single
-// switch over all kinds needed 154 VGPRs = 3 waves/SIMD).  A plan groups its tasks by class (engine.cpp).
+// switch over all kinds needed 154 VGPRs = 3 waves/SIMD).  A plan groups its tasks by class (plan_layout.cpp).
 //
 // Semantics restated per kernel from DuckDB's ArrowToDuckDB (call sites in the reference:
 // src/scanner/scan_arrow_ipc.cpp:56, src/file_scanner/arrow_file_scan.cpp:68-72); canonical values for slots upstream
@@ -451,15 +451,6 @@ __device__ __forceinline__ void tile_strview(const mi_col_task& t, int64_t row0,
   raise(status, err);
 }
 
-__device__ __forceinline__ int misc_group_of(int32_t kind) {
-  switch (kind) {
-    case MI_K_BOOL: case MI_K_DICT: case MI_K_MUL_I32: return 0;
-    case MI_K_DATE64: case MI_K_MUL_I64: case MI_K_DIV_I64: return 3;
-    case MI_K_STRUCT: case MI_K_LIST32: case MI_K_LIST64: case MI_K_STRVIEW: return 1;
-    default: return 2;
-  }
-}
-
 // The common flat kinds (group 0) move 2-16 KB per tile: with 256-thread workgroups a CU holds 8 such tiles and each is
 // one chain of dependent round trips (task lookup, bitmap, data), which left the kernel latency bound (1.8-2.3 TB/s).
 // Here ONE WAVE owns a tile -- 32 independent tiles per CU, no workgroup barriers -- and a lane moves 4 consecutive rows
@@ -557,7 +548,7 @@ __global__ __launch_bounds__(kLightThreads) void transcode_misc_light(const mi_c
   __shared__ uint64_t s_valid[kTileRows / 64];
   for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
     MI_TILE_PROLOGUE();
-    if (misc_group_of(t.kind) != (WIDE ? 3 : 0)) continue;  // uniform: another group's launch owns this tile
+    if (MiscGroupOfKind(t.kind) != (WIDE ? 3 : 0)) continue;  // uniform: another group's launch owns this tile
     // NULLs of the column itself: lane L asks for dword L of the tile's 2048 validity bits BEFORE the data loads leave; a data
     // lane gets the bits of its 4 rows from the lane that holds them (one ds_bpermute, no memory access), and the same dwords
     // are the tile's validity words, stored behind the data -- the tile stays ONE round trip.  Children of structs /
@@ -683,7 +674,7 @@ __global__ __launch_bounds__(kBlockThreads) void transcode_misc(const mi_col_tas
   for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
     MI_TILE_PROLOGUE();
     __shared__ uint64_t s_valid[kTileRows / 64];
-    if (misc_group_of(t.kind) != GROUP) continue;  // uniform: another group's launch owns this tile
+    if (MiscGroupOfKind(t.kind) != GROUP) continue;  // uniform: another group's launch owns this tile
     if (tile_needs_mask(t)) __syncthreads();
     if (t.kind != MI_K_NULL) tile_validity(t, row0, n, s_valid);
     if (GROUP == 1) {
@@ -717,44 +708,8 @@ __global__ __launch_bounds__(kBlockThreads) void transcode_misc(const mi_col_tas
 
 }  // namespace
 
-int TileRowsOfClass(int cls) {
-  switch (cls) {
-    case kClassCopy: return kCopyTileRows;
-    case kClassDec128: return kDecTileRows;
-    default: return kTileRows;
-  }
-}
-
-int ClassOfKind(int32_t kind) {
-  switch (kind) {
-    case MI_K_COPY: return kClassCopy;
-    case MI_K_DEC128: return kClassDec128;
-    case MI_K_STR32: case MI_K_STR64: case MI_K_FIXED_BINARY: return kClassString;
-    case MI_K_BOOL: case MI_K_DATE64: case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DURATION:
-    case MI_K_DICT: case MI_K_INTERVAL_MONTHS: case MI_K_INTERVAL_MDN: case MI_K_NARROW: case MI_K_HALF_FLOAT:
-    case MI_K_NULL: case MI_K_STRVIEW: case MI_K_LIST32: case MI_K_LIST64: case MI_K_STRUCT: case MI_K_UUID: case MI_K_BOOL8: return kClassMisc;
-    case MI_K_ENC_COPY: case MI_K_ENC_DEC128: case MI_K_ENC_BOOL: case MI_K_ENC_VALIDITY: case MI_K_ENC_UUID_TEXT: return kClassEncFixed;
-    case MI_K_ENC_STR32: case MI_K_ENC_LIST32: return kClassEncString;
-    default: return -1;
-  }
-}
-
-int ClassOfTask(const mi_col_task& t) {
-  if (t.sel != nullptr) return KindCanGather(t.kind) ? kClassGather : -1;
-  return ClassOfKind(t.kind);
-}
-
-int MiscGroupOfKind(int32_t kind) {
-  switch (kind) {
-    case MI_K_BOOL: case MI_K_DICT: case MI_K_MUL_I32: return 0;
-    case MI_K_DATE64: case MI_K_MUL_I64: case MI_K_DIV_I64: return 3;
-    case MI_K_STRUCT: case MI_K_LIST32: case MI_K_LIST64: case MI_K_STRVIEW: return 1;
-    default: return 2;
-  }
-}
-
 hipError_t LaunchTranscode(int cls, const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
-                           int32_t n_tasks, uint32_t total_tiles, uint32_t* d_status, uint32_t misc_groups, hipStream_t stream) {
+                           int32_t n_tasks, uint32_t total_tiles, uint32_t* d_status, uint32_t kernel_mask, hipStream_t stream) {
   MI_DROP_STALE_ERROR();
   if (total_tiles == 0) return hipSuccess;
   if (d_tile_task == nullptr) return hipErrorInvalidValue;
@@ -763,19 +718,19 @@ hipError_t LaunchTranscode(int cls, const mi_col_task* d_tasks, const uint32_t* 
   hipLaunchKernelGGL(KERNEL, grid, BLOCK, 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks, total_tiles, d_status)
   switch (cls) {
     case kClassCopy: MI_LAUNCH(transcode_copy, block); break;
-    case kClassDec128:   // misc_groups: bit 0 = tiles without NULLs, bit 1 = tiles that need a mask
-      if (misc_groups & 1u) MI_LAUNCH(transcode_dec128<false>, block);
-      if (misc_groups & 2u) MI_LAUNCH(transcode_dec128<true>, block);
+    case kClassDec128:   // kernel_mask: bit 0 = tiles without NULLs, bit 1 = tiles that need a mask
+      if (kernel_mask & 1u) MI_LAUNCH(transcode_dec128<false>, block);
+      if (kernel_mask & 2u) MI_LAUNCH(transcode_dec128<true>, block);
       break;
     case kClassString:
-      if (misc_groups & 1u) MI_LAUNCH(transcode_string<false>, block);
-      if (misc_groups & 2u) MI_LAUNCH(transcode_string<true>, block);
+      if (kernel_mask & 1u) MI_LAUNCH(transcode_string<false>, block);
+      if (kernel_mask & 2u) MI_LAUNCH(transcode_string<true>, block);
       break;
     case kClassMisc:
-      if (misc_groups & 1u) MI_LAUNCH(transcode_misc_light<false>, dim3(kLightThreads));
-      if (misc_groups & 8u) MI_LAUNCH(transcode_misc_light<true>, dim3(kLightThreads));
-      if (misc_groups & 2u) MI_LAUNCH(transcode_misc<1>, block);
-      if (misc_groups & 4u) MI_LAUNCH(transcode_misc<2>, block);
+      if (kernel_mask & 1u) MI_LAUNCH(transcode_misc_light<false>, dim3(kLightThreads));
+      if (kernel_mask & 8u) MI_LAUNCH(transcode_misc_light<true>, dim3(kLightThreads));
+      if (kernel_mask & 2u) MI_LAUNCH(transcode_misc<1>, block);
+      if (kernel_mask & 4u) MI_LAUNCH(transcode_misc<2>, block);
       break;
     default:
       return hipErrorInvalidValue;

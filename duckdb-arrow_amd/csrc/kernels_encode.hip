@@ -729,15 +729,15 @@ __global__ __launch_bounds__(kBlockThreads) void encode_string_slow(const mi_col
 // Encode launches follow the decode rule: one workgroup per tile (the dispatcher balances them), owner of a tile from
 // the tile -> task table.
 hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
-                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t groups,
+                             int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t kernel_mask,
                              hipStream_t stream) {
   MI_DROP_STALE_ERROR();
   if (total_tiles == 0) return hipSuccess;
-  // groups: bit 0 = tiles of encode_fixed, bit 1 = MI_K_ENC_UUID_TEXT tiles; a tile of the other kernel returns at once
-  if (groups & 1u)
+  // kernel_mask: bit 0 = tiles of encode_fixed, bit 1 = MI_K_ENC_UUID_TEXT tiles; a tile of the other kernel returns at once
+  if (kernel_mask & 1u)
     hipLaunchKernelGGL(encode_fixed, dim3(total_tiles), dim3(kBlockThreads), 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks,
                        total_tiles, d_null_counts);
-  if (groups & 2u)
+  if (kernel_mask & 2u)
     hipLaunchKernelGGL(encode_uuid_text, dim3(total_tiles), dim3(kBlockThreads), 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks,
                        total_tiles, d_null_counts, d_status);
   return hipGetLastError();

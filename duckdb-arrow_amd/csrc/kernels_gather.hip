@@ -285,16 +285,6 @@ __global__ __launch_bounds__(kBlockThreads) void transcode_gather(const mi_col_t
 
 }  // namespace
 
-bool KindCanGather(int32_t kind) {
-  switch (kind) {
-    case MI_K_COPY: case MI_K_DEC128: case MI_K_STR32: case MI_K_STR64: case MI_K_FIXED_BINARY: case MI_K_BOOL: case MI_K_DATE64:
-    case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DICT: case MI_K_UUID: case MI_K_BOOL8:
-      return true;
-    default:
-      return false;
-  }
-}
-
 hipError_t LaunchGather(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task, int32_t n_tasks,
                         uint32_t total_tiles, int64_t* d_window_base, uint32_t* d_status, hipStream_t stream) {
   MI_DROP_STALE_ERROR();

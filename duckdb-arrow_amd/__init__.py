@@ -25,7 +25,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import MiError, VECTOR_SIZE  # noqa: F401
 
-__all__ = ["Connection", "Reader", "Context", "Plan", "Table", "MiError", "nanoarrow_version", "version", "build",
+__all__ = ["Connection", "Reader", "Context", "Plan", "Table", "UnionValue", "MiError", "nanoarrow_version", "version", "build",
            "synth_lineitem_stream", "VECTOR_SIZE"]
 
 
@@ -1101,7 +1101,67 @@ def _vector_from_python(values, duck_type, keep):
                 data[i, 0] = v & 0xFFFFFFFFFFFFFFFF
                 data[i, 1] = (v >> 64) & 0xFFFFFFFFFFFFFFFF
         return data.reshape(-1), validity
+    if t == "INTERVAL":   # (months, days, micros), as fetch_columns returns them -> interval_t rows
+        data = np.zeros(n, np.dtype([("months", np.int32), ("days", np.int32), ("micros", np.int64)]))
+        for i, v in enumerate(values):
+            if v is not None:
+                data[i] = tuple(int(x) for x in v)
+        return data.view(np.uint8).reshape(-1), validity
+    if t in ('"NULL"', "NULL"):   # every value must be None; one byte per row, as the scan's vector of this type has
+        if ok.any():
+            raise MiError(_ffi.MI_EINVAL, 'a "NULL" column holds only None')
+        return np.zeros(max(n, 1), np.uint8), validity
     return np.array([0 if v is None else v for v in values], _INT_TYPES[t]), validity
+
+
+class UnionValue:
+    """A value of a UNION column with its member named: UnionValue("s", "text").  A bare python value goes to the first
+    member whose type takes it (what fetch_columns returns for a union column is bare values)."""
+
+    def __init__(self, member, value):
+        self.member, self.value = member, value
+
+    def __repr__(self):
+        return "UnionValue(%r, %r)" % (self.member, self.value)
+
+
+def _python_value_fits(v, ty):
+    if ty[0] == "leaf":
+        t = ty[1].upper()
+        if t in ("VARCHAR", "JSON"):
+            return isinstance(v, str)
+        if t == "BLOB":
+            return isinstance(v, (bytes, bytearray))
+        if t == "BOOLEAN":
+            return isinstance(v, (bool, np.bool_))
+        if t in ("FLOAT", "DOUBLE"):
+            return isinstance(v, (float, np.floating))
+        if t == "INTERVAL":
+            return isinstance(v, tuple) and len(v) == 3
+        if t in ('"NULL"', "NULL"):
+            return False
+        if t == "UUID":
+            import uuid as _uuid
+            return isinstance(v, _uuid.UUID)
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if ty[0] == "struct":
+        return isinstance(v, dict)
+    if ty[0] == "map":
+        return isinstance(v, dict) or (isinstance(v, list) and all(isinstance(e, tuple) and len(e) == 2 for e in v))
+    return isinstance(v, list)   # list / array
+
+
+def _union_member(v, members):
+    """-> (member index, the member's value) of one non-None python value of a UNION(members) column."""
+    if isinstance(v, UnionValue):
+        for k, (nm, _) in enumerate(members):
+            if nm == v.member:
+                return k, v.value
+        raise MiError(_ffi.MI_EINVAL, "UNION has no member '%s'" % v.member)
+    for k, (_, kt) in enumerate(members):
+        if _python_value_fits(v, kt):
+            return k, v
+    raise MiError(_ffi.MI_EINVAL, "no member of the UNION takes the value %r" % (v,))
 
 
 def _fill_vector(vec, values, ty, keep):
@@ -1141,6 +1201,28 @@ def _fill_vector(vec, values, ty, keep):
                 flat.extend([None] * ty[2] if v is None else list(v))
             kids = (_ffi.Vector * 1)()
             _fill_vector(kids[0], flat, ty[1], keep)
+        elif ty[0] == "union":
+            # child 0 the tags (UTINYINT member index, 0 for a NULL row; also this vector's data), then one vector per member
+            # with a slot per row, NULL wherever another member is selected
+            members = ty[1]
+            tags = np.zeros(max(n, 1), np.uint8)
+            per_member = [[None] * n for _ in members]
+            for i, v in enumerate(values):
+                if v is None:
+                    continue
+                k, inner = _union_member(v, members)
+                tags[i] = k
+                per_member[k][i] = inner
+                if inner is None:   # a NULL of member k is a NULL union row in DuckDB's vector (the tag is kept)
+                    ok[i] = False
+            if not ok.all():
+                validity = np.packbits(np.concatenate([ok, np.ones((-n) % 64, bool)]), bitorder="little").view(np.uint64).copy()
+            keep.append(tags)
+            vec.data = tags.ctypes.data
+            kids = (_ffi.Vector * (len(members) + 1))()
+            kids[0].data, kids[0].count = tags.ctypes.data, n
+            for k, (_, kt) in enumerate(members):
+                _fill_vector(kids[1 + k], per_member[k], kt, keep)
         else:  # struct
             kids = (_ffi.Vector * len(ty[1]))()
             for k, (nm, kt) in enumerate(ty[1]):

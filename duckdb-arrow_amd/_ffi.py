@@ -23,6 +23,7 @@ K_UUID, K_BOOL8 = 25, 26
 MAX_UNION_MEMBERS = 32
 K_ENC_COPY, K_ENC_DEC128, K_ENC_BOOL, K_ENC_STR32, K_ENC_VALIDITY, K_ENC_LIST32, K_ENC_STRVIEW = 32, 33, 34, 35, 36, 37, 38
 K_ENC_UUID_TEXT = 39
+K_ENC_INTERVAL, K_ENC_UNION = 41, 42   # (40 is not a kind)
 
 ST_BAD_OFFSETS, ST_STRING_TOO_LARGE, ST_MUL_OVERFLOW, ST_INDEX_RANGE, ST_DECIMAL_RANGE, ST_OFFSET_OVERFLOW, ST_DICT_INDEX, ST_INTERNAL = \
     1, 2, 4, 8, 16, 32, 64, 128

@@ -763,6 +763,14 @@ static std::vector<std::string> SplitTopLevel(const std::string& text) {
   return parts;
 }
 
+// A union anywhere inside a list, map or fixed-size list is not written (nor read: ArrowField::Supported): its member vectors
+// would have to be gathered in list order under masks the GPU makes.
+static void RefuseUnionBelow(const std::string& column, const ArrowField& f, const char* container) {
+  if (f.type == MI_AT_UNION)
+    throw NotImplementedException("Column '" + column + "': a UNION inside a " + container + " is not encoded by the MI355X writer path");
+  for (auto& c : f.children) RefuseUnionBelow(column, c, container);
+}
+
 // Nested DuckDB types the way ArrowConverter::ToArrowSchema exports them: LIST -> list<l: T>, ARRAY -> fixed_size_list
 // <l: T>[N], STRUCT -> struct with the field names, MAP -> map<entries: struct<key: K not null, value: V> not null>.
 static bool NestedFieldFromDuckType(const std::string& name, const std::string& duck_type, ArrowField* out) {
@@ -777,6 +785,7 @@ static bool NestedFieldFromDuckType(const std::string& name, const std::string& 
     if (open == std::string::npos) throw InvalidInputException("Malformed type '" + duck_type + "'");
     const std::string size = t.substr(open + 1, t.size() - open - 2);
     f.children.push_back(FieldFromDuckType("l", t.substr(0, open)));
+    RefuseUnionBelow(name, f.children.back(), "list");
     if (size.empty()) {
       f.type = MI_AT_LIST;
     } else {
@@ -788,24 +797,43 @@ static bool NestedFieldFromDuckType(const std::string& name, const std::string& 
     return true;
   }
   const std::string up = Upper(t);
-  if (up.rfind("STRUCT(", 0) == 0 && t.back() == ')') {
-    f.type = MI_AT_STRUCT;
-    for (auto& part : SplitTopLevel(t.substr(7, t.size() - 8))) {
+  const bool is_union = up.rfind("UNION(", 0) == 0;
+  if (is_union && t.back() != ')') throw InvalidInputException("Column '" + name + "': malformed type '" + duck_type + "'");
+  if ((up.rfind("STRUCT(", 0) == 0 || is_union) && t.back() == ')') {
+    const std::string what = is_union ? "Column '" + name + "': malformed union member" : std::string("Malformed struct field");
+    const size_t open = is_union ? 6 : 7;
+    f.type = is_union ? MI_AT_UNION : MI_AT_STRUCT;
+    for (auto& part : SplitTopLevel(t.substr(open, t.size() - open - 1))) {
       std::string child_name, rest;
       if (!part.empty() && part[0] == '"') {
         const size_t q = part.find('"', 1);
-        if (q == std::string::npos) throw InvalidInputException("Malformed struct field in '" + duck_type + "'");
+        if (q == std::string::npos) throw InvalidInputException(what + " in '" + duck_type + "'");
         child_name = part.substr(1, q - 1);
         rest = part.substr(q + 1);
       } else {
         const size_t sp = part.find(' ');
-        if (sp == std::string::npos) throw InvalidInputException("Malformed struct field in '" + duck_type + "'");
+        if (sp == std::string::npos) throw InvalidInputException(what + " in '" + duck_type + "'");
         child_name = part.substr(0, sp);
         rest = part.substr(sp + 1);
       }
       f.children.push_back(FieldFromDuckType(child_name, rest));
     }
-    if (f.children.empty()) throw InvalidInputException("STRUCT without fields: '" + duck_type + "'");
+    if (!is_union) {
+      if (f.children.empty()) throw InvalidInputException("STRUCT without fields: '" + duck_type + "'");
+      *out = f;
+      return true;
+    }
+    // DuckDB's export (ArrowConverter::ToArrowSchema, ArrowUnionData): a SPARSE union, the type ids 0 .. m - 1, one nullable
+    // child per member.  A dense union the scan read comes back as this one.
+    f.unit = 0;
+    const int defect = unionfmt::CheckTypeIds(nullptr, -1, static_cast<int>(f.children.size()));
+    if (defect != unionfmt::kIdsOk) throw NotImplementedException("Column '" + name + "': " + unionfmt::DefectText(defect) + " in '" + duck_type + "'");
+    f.has_type_ids = true;
+    for (size_t k = 0; k < f.children.size(); k++) {
+      f.type_ids.push_back(static_cast<int32_t>(k));
+      if (f.children[k].type == MI_AT_UNION)
+        throw NotImplementedException("Column '" + name + "': union member '" + f.children[k].name + "' is itself a UNION, which the writer does not encode");
+    }
     *out = f;
     return true;
   }
@@ -820,6 +848,7 @@ static bool NestedFieldFromDuckType(const std::string& name, const std::string& 
     entries.children.push_back(FieldFromDuckType("key", kv[0]));
     entries.children[0].nullable = false;
     entries.children.push_back(FieldFromDuckType("value", kv[1]));
+    RefuseUnionBelow(name, entries, "map");
     f.children.push_back(entries);
     *out = f;
     return true;
@@ -865,6 +894,8 @@ ArrowField FieldFromDuckType(const std::string& name, const std::string& duck_ty
   if (t == "TIMESTAMP_MS") { f.type = MI_AT_TIMESTAMP; f.unit = 1; return f; }
   if (t == "TIMESTAMP_NS") { f.type = MI_AT_TIMESTAMP; f.unit = 3; return f; }
   if (t == "TIMESTAMP WITH TIME ZONE" || t == "TIMESTAMPTZ") { f.type = MI_AT_TIMESTAMP; f.unit = 2; f.timezone = "UTC"; return f; }
+  if (t == "INTERVAL") { f.type = MI_AT_INTERVAL; f.unit = 2; return f; }   // month_day_nano, whatever interval or duration the scan read
+  if (t == "\"NULL\"" || t == "NULL") { f.type = MI_AT_NULL; return f; }
   if (t == "HUGEINT") { f.type = MI_AT_DECIMAL; f.precision = 38; f.scale = 0; f.bit_width = 128; return f; }
   int p = 0, s = 0;
   if (std::sscanf(t.c_str(), "DECIMAL(%d,%d)", &p, &s) == 2 || std::sscanf(t.c_str(), "DECIMAL(%d, %d)", &p, &s) == 2) {

@@ -269,10 +269,13 @@ void GroupLaunchCounts(int64_t out[2]);
 
 // K7 launches.  The string / list kernel is a single pass (decoupled look-back across the tiles of a column); it needs
 // 2 * total_tiles + 1 state words (zeroed by the launch).
-// LaunchEncodeFixed: kernel_mask bit 0 = the slice has tiles of encode_fixed, bit 1 = of encode_uuid_text (MI_K_ENC_UUID_TEXT).
+// LaunchEncodeFixed: kernel_mask bit 0 = the slice has tiles of encode_fixed, bit 1 = of encode_uuid_text (MI_K_ENC_UUID_TEXT),
+// bit 2 = of encode_union (MI_K_ENC_UNION, kernels_encode_union.hip: LaunchEncodeUnion, which it starts before the other two).
 hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
                              int32_t n_tasks, uint32_t total_tiles, int64_t* d_null_counts, uint32_t* d_status, uint32_t kernel_mask,
                              hipStream_t stream);
+hipError_t LaunchEncodeUnion(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task, int32_t n_tasks,
+                             uint32_t total_tiles, uint32_t* d_status, hipStream_t stream);
 hipError_t LaunchEncodeString(const mi_col_task* d_tasks, const uint32_t* d_tile_begin, const uint32_t* d_tile_task,
                               int32_t n_tasks, uint32_t total_tiles, int64_t* d_tile_state, int64_t* d_null_counts,
                               uint32_t* d_status, bool has_lists, hipStream_t stream);

@@ -53,12 +53,35 @@ __device__ __forceinline__ void enc_tile_bool(const mi_col_task& t, int64_t row0
   out[threadIdx.x] = static_cast<uint8_t>(b);
 }
 
+// K7h: interval_t{int32 months, int32 days, int64 micros} -> month_day_nano {int32 months, int32 days, int64 nanoseconds}, one
+// 16-byte load and store per row.  nanoseconds = micros * 1000 in two's complement, unchecked (ArrowIntervalConverter): the
+// product is taken unsigned, which has the same low 64 bits and no overflow to be undefined.  A NULL row is 16 zero bytes.
+__device__ __forceinline__ void enc_tile_interval(const mi_col_task& t, int64_t row0, int n) {
+  gptr<const u32x4> src = GC<u32x4>(t.buf1) + row0;
+  gptr<const uint64_t> valid = GC<uint64_t>(t.validity);
+  const bool has = t.validity != nullptr;
+  gptr<u32x4> out = GM<u32x4>(t.out_data) + row0;
+#pragma unroll 4
+  for (int r = threadIdx.x; r < n; r += kBlockThreads) {
+    const u32x4 v = __builtin_nontemporal_load(src + r);
+    const uint64_t nanos = (static_cast<uint64_t>(v.z) | (static_cast<uint64_t>(v.w) << 32)) * 1000ull;
+    u32x4 o = {0u, 0u, 0u, 0u};
+    if (enc_row_valid(valid, has, row0 + r)) {
+      o.x = v.x;
+      o.y = v.y;
+      o.z = static_cast<uint32_t>(nanos);
+      o.w = static_cast<uint32_t>(nanos >> 32);
+    }
+    __builtin_nontemporal_store(o, out + r);
+  }
+}
+
 __global__ __launch_bounds__(kBlockThreads) void encode_fixed(const mi_col_task* __restrict__ tasks,
                                                               const uint32_t* __restrict__ tile_begin, const uint32_t* __restrict__ tile_task, int n_tasks,
                                                               uint32_t total_tiles, int64_t* __restrict__ null_counts) {
   for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
     MI_TILE_PROLOGUE();
-    if (t.kind == MI_K_ENC_UUID_TEXT) continue;  // uniform: encode_uuid_text owns this tile
+    if (t.kind == MI_K_ENC_UUID_TEXT || t.kind == MI_K_ENC_UNION) continue;  // uniform: encode_uuid_text / encode_union own this tile
     // wave 0 asks for the tile's validity words, moves its share of the data, and only then turns the words into bitmap
     // bytes and a NULL count: one round trip for the wave instead of two
     const EncValidity tv = enc_tile_validity_load(t, row0, n);
@@ -74,6 +97,7 @@ __global__ __launch_bounds__(kBlockThreads) void encode_fixed(const mi_col_task*
         else enc_tile_dec128<int16_t>(t, row0, n);
         break;
       case MI_K_ENC_BOOL: enc_tile_bool(t, row0, n); break;
+      case MI_K_ENC_INTERVAL: enc_tile_interval(t, row0, n); break;
       default: break;
     }
     enc_tile_validity_finish(t, row0, n, null_counts, tv);
@@ -733,7 +757,13 @@ hipError_t LaunchEncodeFixed(const mi_col_task* d_tasks, const uint32_t* d_tile_
                              hipStream_t stream) {
   MI_DROP_STALE_ERROR();
   if (total_tiles == 0) return hipSuccess;
-  // kernel_mask: bit 0 = tiles of encode_fixed, bit 1 = MI_K_ENC_UUID_TEXT tiles; a tile of the other kernel returns at once
+  // kernel_mask: bit 0 = tiles of encode_fixed, bit 1 = MI_K_ENC_UUID_TEXT tiles, bit 2 = MI_K_ENC_UNION tiles; a tile of another
+  // kernel returns at once.  The union pass goes first: its masks are the validity words of its members' tasks, which the
+  // kernels below and the later slices of the plan read (same stream).
+  if (kernel_mask & 4u) {
+    const hipError_t e = LaunchEncodeUnion(d_tasks, d_tile_begin, d_tile_task, n_tasks, total_tiles, d_status, stream);
+    if (e != hipSuccess) return e;
+  }
   if (kernel_mask & 1u)
     hipLaunchKernelGGL(encode_fixed, dim3(total_tiles), dim3(kBlockThreads), 0, stream, d_tasks, d_tile_begin, d_tile_task, n_tasks,
                        total_tiles, d_null_counts);

@@ -135,9 +135,21 @@ static void ValidateTask(const mi_col_task& t, size_t i) {
       if (reinterpret_cast<uintptr_t>(t.out_data) % 8 != 0) fail("offsets buffer misaligned");
       if (t.nrows > 0x7FFFFFFFll) fail("more than INT32_MAX rows");
       break;
+    case MI_K_ENC_INTERVAL:
+      if (reinterpret_cast<uintptr_t>(t.buf1) % 16 != 0) fail("interval_t vector must be 16-byte aligned");
+      break;
+    case MI_K_ENC_UNION: {
+      const int64_t words = (t.nrows + 63) / 64;
+      if (t.param < 1 || t.param > MI_MAX_UNION_MEMBERS) fail("ENC_UNION needs param = number of members, 1 .. " + std::to_string(MI_MAX_UNION_MEMBERS));
+      if (t.buf2 == nullptr || reinterpret_cast<uintptr_t>(t.buf2) % 8 != 0) fail("ENC_UNION needs the members' validity addresses (8-byte aligned) in buf2");
+      if (t.out_aux == nullptr || reinterpret_cast<uintptr_t>(t.out_aux) % 8 != 0) fail("ENC_UNION needs the masks (8-byte aligned) in out_aux");
+      if (t.buf2_len % 8 != 0 || t.buf2_len < 8 * words) fail("ENC_UNION needs buf2_len = distance between masks: a multiple of 8, at least 8 ceil(nrows / 64)");
+      if (t.ptr_base % 8 != 0) fail("ENC_UNION parent words misaligned");
+      break;
+    }
     default: break;
   }
-  if (t.kind >= MI_K_ENC_COPY && t.kind != MI_K_ENC_COPY && t.out_validity == nullptr)
+  if (t.kind >= MI_K_ENC_COPY && t.kind != MI_K_ENC_COPY && t.kind != MI_K_ENC_UNION && t.out_validity == nullptr)
     fail("encode tasks need out_validity (the bitmap is always emitted; only a bare ENC_COPY of list offsets has none)");
 }
 
@@ -179,7 +191,8 @@ static int64_t TaskBytesRead(const mi_col_task& t) {
     switch (t.kind) {
       case MI_K_ENC_COPY: case MI_K_ENC_DEC128: b += n * t.param; break;
       case MI_K_ENC_BOOL: b += n; break;
-      case MI_K_ENC_STR32: case MI_K_ENC_LIST32: case MI_K_ENC_STRVIEW: case MI_K_ENC_UUID_TEXT: b += n * 16; break;  // + payload, known only after the scan (reported via buf2_len if given)
+      case MI_K_ENC_UNION: b += n + (t.param + (t.ptr_base ? 1 : 0)) * ((n + 63) / 64) * 8; break;   // tags; member (at most) and parent words
+      case MI_K_ENC_STR32: case MI_K_ENC_LIST32: case MI_K_ENC_STRVIEW: case MI_K_ENC_UUID_TEXT: case MI_K_ENC_INTERVAL: b += n * 16; break;  // + payload, known only after the scan (reported via buf2_len if given)
       default: break;
     }
     if (t.kind == MI_K_ENC_STR32 || t.kind == MI_K_ENC_STRVIEW) b += t.buf2_len;   // (views: the long strings alone)
@@ -192,10 +205,11 @@ static int64_t TaskBytesWritten(const mi_col_task& t) {
   if (t.kind < MI_K_ENC_COPY) {
     return n * device::OutWidth(t.kind, t.param) + ((t.out_validity ? 1 : 0) + (t.kind == MI_K_UNION ? t.param : 0)) * ((n + 63) / 64) * 8;
   }
+  if (t.kind == MI_K_ENC_UNION) return n + t.param * ((n + 63) / 64) * 8;   // type ids and the masks; no bitmap
   int64_t b = t.out_validity ? (n + 7) / 8 : 0;  // bitmap
   switch (t.kind) {
     case MI_K_ENC_COPY: b += n * t.param; break;
-    case MI_K_ENC_DEC128: b += n * 16; break;
+    case MI_K_ENC_DEC128: case MI_K_ENC_INTERVAL: b += n * 16; break;
     case MI_K_ENC_BOOL: b += (n + 7) / 8; break;
     case MI_K_ENC_STR32: case MI_K_ENC_UUID_TEXT: b += (n + 1) * ((t.flags & 1) ? 8 : 4) + t.buf2_len; break;   // (buf2_len: the text bytes)
     case MI_K_ENC_LIST32: b += (n + 1) * ((t.flags & 1) ? 8 : 4); break;

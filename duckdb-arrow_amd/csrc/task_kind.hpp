@@ -95,7 +95,8 @@ MI_HD constexpr int SlotOfKind(int32_t kind) {
     case MI_K_BOOL: case MI_K_DATE64: case MI_K_MUL_I32: case MI_K_MUL_I64: case MI_K_DIV_I64: case MI_K_DURATION:
     case MI_K_DICT: case MI_K_INTERVAL_MONTHS: case MI_K_INTERVAL_MDN: case MI_K_NARROW: case MI_K_HALF_FLOAT:
     case MI_K_NULL: case MI_K_STRVIEW: case MI_K_LIST32: case MI_K_LIST64: case MI_K_STRUCT: case MI_K_UUID: case MI_K_BOOL8: return kClassMisc;
-    case MI_K_ENC_COPY: case MI_K_ENC_DEC128: case MI_K_ENC_BOOL: case MI_K_ENC_VALIDITY: case MI_K_ENC_UUID_TEXT: return kClassEncFixed;
+    case MI_K_ENC_COPY: case MI_K_ENC_DEC128: case MI_K_ENC_BOOL: case MI_K_ENC_VALIDITY: case MI_K_ENC_UUID_TEXT:
+    case MI_K_ENC_INTERVAL: case MI_K_ENC_UNION: return kClassEncFixed;
     case MI_K_ENC_STR32: case MI_K_ENC_LIST32: return kClassEncString;
     case MI_K_RUN_END: return kSlotRunEnd;
     case MI_K_ENC_STRVIEW: return kSlotEncView;
@@ -159,14 +160,15 @@ MI_HD constexpr bool TaskNeedsMask(const mi_col_task& t) {
 //   misc:              1 << MiscGroupOfKind -- bit 0 transcode_misc_light<false>, bit 1 transcode_misc<1> (nested), bit 2
 //                      transcode_misc<2> (rare flat), bit 3 transcode_misc_light<true> (8-byte inputs)
 //   dec128, string:    bit 0 the instance for tiles without NULLs, bit 1 the one for tiles that need a mask (TaskNeedsMask)
-//   enc_fixed:         bit 0 encode_fixed, bit 1 encode_uuid_text
+//   enc_fixed:         bit 0 encode_fixed, bit 1 encode_uuid_text, bit 2 encode_union (launched first: its masks are the validity of
+//                      its members' tasks, which are tasks of this slice or of a later one)
 //   enc_string:        bit 1 the slice has lists (strings set nothing)
 //   every other slot:  one kernel, 0
 MI_HD constexpr uint32_t KernelMaskOfTask(int slot, const mi_col_task& t) {
   switch (slot) {
     case kClassMisc: return 1u << MiscGroupOfKind(t.kind);
     case kClassDec128: case kClassString: return TaskNeedsMask(t) ? 2u : 1u;
-    case kClassEncFixed: return t.kind == MI_K_ENC_UUID_TEXT ? 2u : 1u;
+    case kClassEncFixed: return t.kind == MI_K_ENC_UUID_TEXT ? 2u : t.kind == MI_K_ENC_UNION ? 4u : 1u;
     case kClassEncString: return t.kind == MI_K_ENC_LIST32 ? 2u : 0u;
     default: return 0u;
   }

@@ -91,5 +91,32 @@ MI_UNION_FN Row RowRule(int member, bool dense, int64_t offset, int64_t member_l
   return Row{member, true, 0u};
 }
 
+// ---------------------------------------------------------------------------------------------------- the way back
+// A DuckDB UNION vector -> an Arrow SPARSE union with the type ids 0 .. m - 1 (MI_K_ENC_UNION, kernels_encode_union.hip; the
+// writer's staging in writer.cpp and tests/union_encode_cases.py restate it).  The union has no bitmap of its own: a row's
+// NULL lives in its member.  So the pass writes the type id of every row and, per member, an EFFECTIVE validity mask that the
+// member's own encode task takes for its validity.
+
+struct EncodedRow {
+  int type_id;      // == the tag; 0 for a NULL union row (ArrowUnionData::Append) and for a tag that names no member
+  int member;       // whose mask may hold the row's bit: the tag clamped into 0 .. m - 1 (0 for a tag >= m)
+  bool selects;     // the union row is valid and its tag names a member: bit r of mask `member` = selects && the member's own bit
+  uint32_t status;  // kStBadTag / 0
+};
+
+//! The rule for one row.  `tag` as loaded (uint8); union_valid = the union's validity bit ANDed with a struct parent's.
+//! A tag >= m under a valid row is reported and the row goes to member 0 as NULL; under a NULL row the tag is not looked at.
+MI_UNION_FN EncodedRow EncodeRow(int tag, int m, bool union_valid) {
+  if (!union_valid) return EncodedRow{0, 0, false, 0u};
+  if (tag < 0 || tag >= m) return EncodedRow{0, 0, false, kStBadTag};
+  return EncodedRow{tag, tag, true, 0u};
+}
+
+//! Word j of a mask over n rows: `bits` with the pad bits (rows >= n) set
+MI_UNION_FN uint64_t WithPadBits(uint64_t bits, int64_t n, int64_t j) {
+  const int64_t rem = n - 64 * j;
+  return rem >= 64 ? bits : rem <= 0 ? ~0ull : bits | (~0ull << rem);
+}
+
 }  // namespace unionfmt
 }  // namespace miarrow

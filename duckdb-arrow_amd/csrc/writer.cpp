@@ -2,6 +2,7 @@
 #include "writer.hpp"
 #include "writer_internal.hpp"
 #include "extension_format.hpp"
+#include "union_format.hpp"
 #include "writer_plan.hpp"
 
 #include <fcntl.h>
@@ -57,8 +58,12 @@ void EncodePlanFor(const ArrowField& f, int32_t* enc_kind, int64_t* param, int32
       if (f.extension == extfmt::kUuid) { *enc_kind = MI_K_ENC_UUID_TEXT; *param = 16; *width = 16; return; }   // hugeint_t rows -> their text
       *enc_kind = MI_K_ENC_STR32; *param = 0; *width = 16; return;
     case MI_AT_UTF8_VIEW: *enc_kind = MI_K_ENC_STRVIEW; *param = 0; *width = 16; return;   // produce_arrow_string_view
-    default: throw NotImplementedException("Arrow type " + f.Format() + " is not encoded by the MI355X writer path");
+    case MI_AT_INTERVAL:   // interval_t rows -> month_day_nano, the one interval DuckDB exports
+      if (f.unit != 2) break;
+      *enc_kind = MI_K_ENC_INTERVAL; *param = 16; *width = 16; return;
+    default: break;
   }
+  throw NotImplementedException("Arrow type " + f.Format() + " is not encoded by the MI355X writer path");
 }
 
 // append `n` bits of `src` starting at bit `spos` (src NULL = all ones) to `dst` at bit position `pos`
@@ -97,8 +102,15 @@ int32_t ChunkCollection::AddField(const ArrowField& f, int32_t depth) {
     c.arrow_type = f.type;
     c.depth = depth;
     switch (f.type) {
-      case MI_AT_STRUCT: break;
+      case MI_AT_STRUCT: case MI_AT_NULL: break;   // (a null node stages its count alone)
       case MI_AT_FIXED_LIST: c.param = f.byte_width; break;
+      case MI_AT_UNION:   // the tag bytes; the members are nodes of their own, appended row for row like a struct's children
+        if (f.unit != 0 || f.children.empty() || f.children.size() > static_cast<size_t>(unionfmt::kMaxMembers))
+          throw NotImplementedException("Column '" + f.name + "': only sparse unions of 1 .. 32 members are encoded by the MI355X writer path");
+        c.enc_kind = MI_K_ENC_UNION;
+        c.param = static_cast<int64_t>(f.children.size());
+        c.width = 1;
+        break;
       case MI_AT_LIST: case MI_AT_LARGE_LIST: case MI_AT_MAP: c.enc_kind = MI_K_ENC_LIST32; c.param = 0; c.width = 16; break;
       default: EncodePlanFor(f, &c.enc_kind, &c.param, &c.width); break;
     }
@@ -139,6 +151,14 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
   const int64_t vbit = static_cast<int64_t>(v.validity_shift) + start;  // bit of v.validity that belongs to row `start`
   {
     Column& c = columns[static_cast<size_t>(ni)];
+    if (c.IsNull()) {   // nothing to stage: every row is NULL
+      c.count += n;
+      return;
+    }
+    if (c.IsUnion()) {
+      AppendUnion(ni, v, start, n);
+      return;
+    }
     if (!c.IsGroup() && !v.data) throw InvalidInputException("DataChunk column " + std::to_string(ni) + " has no data");
     if ((c.IsList() || c.IsGroup()) && (v.n_children < (c.arrow_type == MI_AT_STRUCT ? static_cast<int32_t>(c.children.size()) : 1) || !v.children))
       throw InvalidInputException("nested vector without child vectors");
@@ -252,6 +272,47 @@ void ChunkCollection::AppendNode(int32_t ni, const mi_vector& v, int64_t start, 
   c.count += n;
 }
 
+// A union node: its tag bytes and validity words as they are, and under them the member vectors row for row, each with the
+// EFFECTIVE validity the union's pass will give it on the GPU (union_format.hpp: EncodeRow) -- the row is valid, its tag names
+// the member, the member's own bit is set -- so that what is staged for a member (the bytes of its valid strings, the child
+// rows of its valid lists) is what its encode task will write.
+void ChunkCollection::AppendUnion(int32_t ni, const mi_vector& v, int64_t start, int64_t n) {
+  const int32_t m = static_cast<int32_t>(columns[static_cast<size_t>(ni)].children.size());
+  if (v.n_children != m + 1 || !v.children)
+    throw InvalidInputException("union vector with " + std::to_string(v.n_children) + " child vectors, the writer expects the tags and " +
+                                std::to_string(m) + " members");
+  const uint8_t* tags = static_cast<const uint8_t*>(v.data ? v.data : v.children[0].data);
+  if (!tags) throw InvalidInputException("union vector without tags");
+  const int64_t vbit = static_cast<int64_t>(v.validity_shift) + start;
+  Reserve(columns[static_cast<size_t>(ni)], columns[static_cast<size_t>(ni)].count + n, 0);
+  {
+    Column& c = columns[static_cast<size_t>(ni)];
+    AppendBits(c.validity.get<uint64_t>(), c.count, v.validity, vbit, n);
+    if (v.validity && !c.has_nulls) {
+      for (int64_t i = 0; i < n; i++)
+        if (!BitAt(v.validity, vbit + i)) { c.has_nulls = true; break; }
+    }
+    std::memcpy(c.data.get() + c.count, tags + start, static_cast<size_t>(n));
+    c.count += n;
+    size_in_bytes += n;
+  }
+  // bit start + i of a member's mask = row i of the slice
+  std::vector<uint64_t> mask(static_cast<size_t>((start + n + 63) / 64));
+  for (int32_t k = 0; k < m; k++) {
+    const mi_vector& mv = v.children[1 + k];
+    const int64_t mbit = static_cast<int64_t>(mv.validity_shift) + start;
+    std::fill(mask.begin(), mask.end(), 0ull);
+    for (int64_t i = 0; i < n; i++) {
+      const unionfmt::EncodedRow row = unionfmt::EncodeRow(tags[start + i], m, BitAt(v.validity, vbit + i));
+      if (row.selects && row.member == k && BitAt(mv.validity, mbit + i)) mask[static_cast<size_t>((start + i) >> 6)] |= 1ull << ((start + i) & 63);
+    }
+    mi_vector masked = mv;
+    masked.validity = mask.data();
+    masked.validity_shift = 0;
+    AppendNode(columns[static_cast<size_t>(ni)].children[static_cast<size_t>(k)], masked, start, n);
+  }
+}
+
 void ChunkCollection::Reset() {
   for (auto& c : columns) {
     c.count = 0;
@@ -296,18 +357,26 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   // the body layout, and the device staging layout beside it
   const size_t n_nodes = buffer.columns.size();
   std::vector<EncodeNode> nodes(n_nodes);
-  struct InOff { size_t data, validity, heap; };
+  struct InOff { size_t data, validity, heap, members, masks, mask_stride; };   // members, masks: union nodes
   std::vector<InOff> in_off(n_nodes);
-  size_t in_bytes = 0;
+  size_t in_bytes = 0, n_unions = 0;
   for (size_t ci = 0; ci < n_nodes; ci++) {
     auto& c = buffer.columns[ci];
-    nodes[ci] = EncodeNode{c.IsGroup() ? MI_K_ENC_VALIDITY : c.enc_kind, c.param, c.large_offsets, c.count, c.payload_bytes};
+    nodes[ci] = EncodeNode{c.IsGroup() ? MI_K_ENC_VALIDITY : c.IsNull() ? kEncNodeNull : c.enc_kind, c.param, c.large_offsets, c.count, c.payload_bytes};
     in_off[ci].data = in_bytes;
     in_bytes += RoundUp(static_cast<size_t>(c.count) * static_cast<size_t>(c.width) + 16, 256);
     in_off[ci].validity = in_bytes;
     in_bytes += RoundUp(static_cast<size_t>((c.count + 63) / 64) * 8 + 8, 256);
     in_off[ci].heap = in_bytes;
     in_bytes += RoundUp(static_cast<size_t>(c.heap_used) + 16, 256);
+    if (c.IsUnion()) {   // the addresses of its members' validity words, and the scratch its pass leaves their masks in
+      in_off[ci].members = in_bytes;
+      in_bytes += RoundUp(static_cast<size_t>(unionfmt::kMaxMembers) * 8, 256);
+      in_off[ci].mask_stride = RoundUp(static_cast<size_t>((c.count + 63) / 64) * 8 + 8, 256);
+      in_off[ci].masks = in_bytes;
+      in_bytes += in_off[ci].mask_stride * c.children.size();
+      n_unions++;
+    }
   }
   BodyLayout layout;
   LayOutBody(nodes, &layout);
@@ -320,10 +389,15 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   MI_HIP_CHECK(hipMemsetAsync(d_body.get(), 0, body_bytes, s));  // the padding bytes of every buffer are zero
   std::vector<mi_col_task> tasks;
   std::vector<int32_t> validity_task(n_nodes, -1);  // task whose NULL counter belongs to node ci
+  // a union member's task reads the mask the union's pass makes for it in place of its staged validity words (the same bits)
+  std::vector<const uint8_t*> member_mask(n_nodes, nullptr);
+  if (n_unions) Fit(h_union, n_unions * static_cast<size_t>(unionfmt::kMaxMembers) * 8);
+  size_t unions_done = 0;
   for (size_t ci = 0; ci < n_nodes; ci++) {
     auto& c = buffer.columns[ci];
     const int64_t n = c.count;
     if (n == 0) continue;  // zero-length buffers, no work
+    if (c.IsNull()) continue;  // no buffers either
     const uint8_t* d_data = d_in.get() + in_off[ci].data;
     const uint8_t* d_validity = d_in.get() + in_off[ci].validity;
     const uint8_t* d_heap = d_in.get() + in_off[ci].heap;
@@ -334,7 +408,23 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
     if (c.heap_used)
       MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].heap, c.heap.get(), static_cast<size_t>(c.heap_used), hipMemcpyHostToDevice, s));
     // a struct / fixed-size list reads its own validity words; the staged string_t rows point at heap offsets (ptr_base 0)
-    const EncodeInput in{c.IsGroup() ? d_validity : d_data, c.has_nulls ? d_validity : nullptr, d_heap, 0};
+    EncodeInput in{c.IsGroup() ? d_validity : d_data, c.has_nulls ? d_validity : nullptr, d_heap, 0};
+    if (member_mask[ci]) {
+      in.validity = member_mask[ci];
+      if (c.IsGroup()) in.data = member_mask[ci];
+    }
+    if (c.IsUnion()) {
+      uint64_t* table = h_union.get<uint64_t>() + unions_done++ * static_cast<size_t>(unionfmt::kMaxMembers);
+      for (size_t k = 0; k < c.children.size(); k++) {
+        const size_t child = static_cast<size_t>(c.children[k]);
+        table[k] = buffer.columns[child].has_nulls ? reinterpret_cast<uint64_t>(d_in.get() + in_off[child].validity) : 0;
+        member_mask[child] = d_in.get() + in_off[ci].masks + k * in_off[ci].mask_stride;
+      }
+      MI_HIP_CHECK(hipMemcpyAsync(d_in.get() + in_off[ci].members, table, c.children.size() * 8, hipMemcpyHostToDevice, s));
+      in.member_validity = d_in.get() + in_off[ci].members;
+      in.masks = d_in.get() + in_off[ci].masks;
+      in.mask_stride = static_cast<int64_t>(in_off[ci].mask_stride);
+    }
     validity_task[ci] = static_cast<int32_t>(tasks.size());
     tasks.push_back(EncodeTask(nodes[ci], &layout.spans[static_cast<size_t>(layout.first_span[ci])], in, d_body.get()));
   }
@@ -355,8 +445,10 @@ idx_t ColumnDataCollectionSerializer::Serialize(ChunkCollection& buffer) {
   ThrowForStatus(plan->Status());  // synchronises the stream
   std::vector<int64_t> null_counts = plan->NullCounts(/*reset*/ true);
   std::vector<std::pair<int64_t, int64_t>> node_counts;
-  for (size_t ci = 0; ci < n_nodes; ci++)
-    node_counts.emplace_back(buffer.columns[ci].count, validity_task[ci] >= 0 ? null_counts[static_cast<size_t>(validity_task[ci])] : 0);
+  for (size_t ci = 0; ci < n_nodes; ci++) {   // (a union's counter stays 0: it has no bitmap; every row of a null node is NULL)
+    const auto& c = buffer.columns[ci];
+    node_counts.emplace_back(c.count, c.IsNull() ? c.count : validity_task[ci] >= 0 ? null_counts[static_cast<size_t>(validity_task[ci])] : 0);
+  }
   int64_t n_view_fields = 0;   // RecordBatch.variadicBufferCounts: one data buffer per view field, rows or not
   for (auto& c : buffer.columns) n_view_fields += c.enc_kind == MI_K_ENC_STRVIEW;
   header = EncodeRecordBatchMessage(n_top, node_counts, *spans, body_size, compression == MI_WRITE_COMPRESSION_LZ4_FRAME ? 0 : -1, n_view_fields);

@@ -93,6 +93,8 @@ class ChunkCollection {
     std::vector<int32_t> children;
     bool IsList() const { return arrow_type == MI_AT_LIST || arrow_type == MI_AT_LARGE_LIST || arrow_type == MI_AT_MAP; }
     bool IsGroup() const { return arrow_type == MI_AT_STRUCT || arrow_type == MI_AT_FIXED_LIST; }
+    bool IsUnion() const { return arrow_type == MI_AT_UNION; }   // stages its tags (width 1); children = the members
+    bool IsNull() const { return arrow_type == MI_AT_NULL; }     // stages nothing but `count`
   };
   std::vector<Column> columns;     // every field node, depth first
   std::vector<int32_t> roots;      // node of top-level column c
@@ -100,6 +102,7 @@ class ChunkCollection {
  private:
   int32_t AddField(const ArrowField& f, int32_t depth);
   void AppendNode(int32_t ni, const mi_vector& v, int64_t start, int64_t n);
+  void AppendUnion(int32_t ni, const mi_vector& v, int64_t start, int64_t n);
   void Reserve(Column& c, int64_t rows, int64_t extra_heap);
   Context* ctx;
   int64_t count = 0;
@@ -138,6 +141,7 @@ class ColumnDataCollectionSerializer {
   PinnedBuffer bodies[2];         // the current one is bodies[cur_body]
   int cur_body = 0;
   DeviceBuffer d_body, d_in;
+  PinnedBuffer h_union;   // per union node of the batch: the device addresses of its members' validity words
   int64_t body_size = 0;
   std::unique_ptr<Plan> plan;
 };

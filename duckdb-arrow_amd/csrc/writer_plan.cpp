@@ -19,12 +19,17 @@ void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out) {
     const int64_t n = c.rows;
     if (n > 0x7FFFFFFFll) throw InvalidInputException("record batch too large");
     out->first_span[i] = static_cast<int32_t>(out->spans.size());
+    if (c.kind == kEncNodeNull) continue;   // no buffers
+    if (c.kind == MI_K_ENC_UNION) {         // type ids alone
+      add_span(n);
+      continue;
+    }
     add_span((n + 7) / 8);
     const int64_t off_width = c.large_offsets ? 8 : 4;
     switch (c.kind) {
       case MI_K_ENC_LIST32: add_span((n + 1) * off_width); break;
       case MI_K_ENC_COPY: add_span(n * c.param); break;
-      case MI_K_ENC_DEC128: add_span(n * 16); break;
+      case MI_K_ENC_DEC128: case MI_K_ENC_INTERVAL: add_span(n * 16); break;
       case MI_K_ENC_BOOL: add_span((n + 7) / 8); break;
       case MI_K_ENC_STR32: case MI_K_ENC_UUID_TEXT:
         if (c.payload_bytes > 0x7FFFFFFFll && !c.large_offsets) {
@@ -58,6 +63,15 @@ mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, cons
   t.kind = node.kind;
   t.validity = in.validity;
   t.buf1 = in.data;
+  if (node.kind == MI_K_ENC_UNION) {   // type ids into the body, the members' masks into scratch; no bitmap
+    t.param = node.param;
+    t.buf2 = in.member_validity;
+    t.buf2_len = in.mask_stride;
+    t.ptr_base = reinterpret_cast<uint64_t>(in.parent_validity);
+    t.out_data = body + spans[0].offset;
+    t.out_aux = in.masks;
+    return t;
+  }
   t.out_validity = body + spans[0].offset;
   if (node.kind == MI_K_ENC_VALIDITY) {   // the node's own bitmap + NULL count
     t.out_data = body + spans[0].offset;

@@ -22,9 +22,12 @@ constexpr size_t kBufferAlign = 64;  // Arrow's recommended buffer alignment; an
 inline size_t RoundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ------------------------------------------------------------------------------------------------ body layout
+//! EncodeNode::kind of an Arrow null node: no buffers, no task; its field node is {length = rows, null_count = rows}
+constexpr int32_t kEncNodeNull = -1;
 //! One field node of a record batch to encode
 struct EncodeNode {
-  int32_t kind = 0;             // MI_K_ENC_* of a leaf; MI_K_ENC_LIST32: list / map; MI_K_ENC_VALIDITY: struct / fixed-size list
+  int32_t kind = 0;             // MI_K_ENC_* of a leaf; MI_K_ENC_LIST32: list / map; MI_K_ENC_VALIDITY: struct / fixed-size list;
+                                // MI_K_ENC_UNION: a union (its members are nodes of their own); kEncNodeNull
   int64_t param = 0;            // leaf: vector element width (or decimal physical width)
   bool large_offsets = false;   // int64 Arrow offsets
   int64_t rows = 0;
@@ -33,12 +36,15 @@ struct EncodeNode {
 };
 struct BodyLayout {
   std::vector<mi_buffer_span> spans;   // RecordBatch.buffers
-  std::vector<int32_t> first_span;     // per node: its validity span; offsets / data and string data follow it
+  std::vector<int32_t> first_span;     // per node: its validity span; offsets / data and string data follow it.  A union's one
+                                       // span is its type ids (it has no validity), a null node has none
   int64_t body_size = 0;
 };
 //! Field nodes depth first, per node validity (always emitted, ArrowAppender::FinalizeChild), then offsets / data -- the
 //! order ArrowIpcEncoderEncodeSimpleRecordBatch walks the ArrowArray tree; every buffer starts on a multiple of
 //! kBufferAlign.  A string-view node (MI_K_ENC_STRVIEW) has three: bitmap, 16 bytes of view per row, one data buffer.
+//! A union node (MI_K_ENC_UNION) has ONE, its int8 type ids (sparse: no offsets, and a union never has a bitmap); an
+//! interval node (MI_K_ENC_INTERVAL) bitmap + 16 bytes per row; a null node (kEncNodeNull) none at all.
 //! Throws when a node has more than INT32_MAX rows or int32 offsets cannot address its string bytes.
 void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out);
 
@@ -48,8 +54,13 @@ struct EncodeInput {
   const void* validity = nullptr;   // validity words, NULL when every row is valid
   const void* heap = nullptr;       // MI_K_ENC_STR32 / MI_K_ENC_STRVIEW: the bytes long string_t rows point into ...
   uint64_t ptr_base = 0;            // ... and the pointer value its byte 0 has inside them
+  // MI_K_ENC_UNION (data = the tags, validity = the union's words):
+  const void* member_validity = nullptr;   // m words: the address of every member's own validity words, 0 = all valid
+  void* masks = nullptr;                   // where the pass leaves the members' effective masks, mask k at k * mask_stride
+  int64_t mask_stride = 0;                 // bytes, a multiple of 8
+  const void* parent_validity = nullptr;   // a struct parent's words, NULL = none
 };
-//! The encode task of `node`: `spans` are the node's own (BodyLayout::first_span), `body` is where the body starts in HBM
+//! The encode task of `node` (not a kEncNodeNull one: it has none): `spans` are the node's own (BodyLayout::first_span), `body` is where the body starts in HBM
 mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, const EncodeInput& in, uint8_t* body);
 
 // ------------------------------------------------------------------------------------------------ compressed body

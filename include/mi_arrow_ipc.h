@@ -143,9 +143,27 @@ enum mi_kind {
   MI_K_ENC_STRVIEW = 38,  /* K7e string_t -> Arrow string views (Utf8View, produce_arrow_string_view): out_data = 16 bytes per row,
                            * out_aux = the ONE data buffer (the strings of more than 12 bytes of the valid rows, back to back in
                            * row order; int32 offsets, no large variant) */
-  MI_K_ENC_UUID_TEXT = 39 /* DuckDB UUID (hugeint_t) rows -> utf8 of their canonical text, as DuckDB exports UUID columns: out_data =
+  MI_K_ENC_UUID_TEXT = 39,/* DuckDB UUID (hugeint_t) rows -> utf8 of their canonical text, as DuckDB exports UUID columns: out_data =
                            * int32 offsets (flags bit 0: int64, LargeUtf8), out_aux = the text, 36 bytes per valid row and none per
                            * NULL row (16-byte aligned); buf2_len = the bytes out_aux holds (statistics only) */
+  /* (40 is not a kind: plans refuse it as unknown) */
+  MI_K_ENC_INTERVAL = 41, /* DuckDB interval_t{int32 months, int32 days, int64 micros} rows (buf1, 16-byte aligned) -> Arrow
+                           * interval[month_day_nano] {int32 months, int32 days, int64 nanoseconds}, 16 bytes per row in out_data:
+                           * nanoseconds = micros * 1000 in int64 two's complement, UNCHECKED -- a product past 63 bits wraps, as in
+                           * DuckDB's ArrowIntervalConverter; a NULL row is 16 zero bytes; bitmap and NULL count as every kind */
+  MI_K_ENC_UNION = 42     /* the union's own pass of a DuckDB UNION vector -> Arrow sparse union: buf1 = the tag vector (uint8 member
+                           * index per row), validity = the union's validity words (NULL: every row valid), ptr_base = device
+                           * address of a struct parent's validity words (0: none), param = m, the number of members (1 ..
+                           * MI_MAX_UNION_MEMBERS), buf2 = m words of 8 bytes (8-byte aligned): the device address of member k's own
+                           * validity words, 0 = every row valid.  out_data = the int8 type ids, one per row: the tag, 0 for a NULL
+                           * union row.  out_aux = the members' effective validity masks (8-byte aligned), mask k at byte k *
+                           * buf2_len (buf2_len a multiple of 8, >= 8 ceil(nrows / 64)): ceil(nrows / 64) words, bit r = the
+                           * union row r is valid (and its struct parent's) AND tag[r] == k AND member k's own bit r is set; pad
+                           * bits ones.  Mask k is the `validity` of member k's own encode task, whatever its kind: those tasks may
+                           * stand anywhere in the same plan, the union pass is launched ahead of every other encode kernel.  A
+                           * union has no bitmap (out_validity is not read) and its NULL counter stays 0.  A tag >= m under a valid
+                           * row raises MI_ST_BAD_UNION_TAG: the row takes type id 0 and is NULL in every mask; no tag is used
+                           * unclamped as an index (union_format.hpp: EncodeRow) */
 };
 
 typedef struct mi_field {

@@ -661,7 +661,7 @@ int mi_filter_program_vectors(mi_ctx* ctx, const mi_filter_vector_leaf* leaves, 
 
 }  // extern "C"
 
-// scan operator, aggregate + writer entry points live in scan_operator.cpp / scan_aggregate.cpp / writer.cpp (same extern "C" rules)
+// scan operator, aggregate + writer entry points live in scan_operator.cpp / scan_aggregate.cpp / writer_api.cpp (same extern "C" rules)
 namespace miarrow {
 int WrapC(const std::function<void()>& f) { return Wrap(f); }
 Context* ContextOf(mi_ctx* c) { return c ? c->ctx.get() : nullptr; }

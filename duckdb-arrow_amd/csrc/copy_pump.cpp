@@ -87,7 +87,7 @@ void ParallelPump::AppendPieces(mi_writer_local* sink, const std::vector<Piece>&
     const BatchRef ref = ledger.RefOf(pc.batch);
     for (int32_t wi = pc.w0; wi < pc.w1; wi++) {
       scan->BuildChunk(ref, wi, storage, chunk);
-      sink->buffer->Append(*chunk);
+      TimedAppend(*sink->buffer, *chunk);
     }
     ledger.ClosePiece(pc.batch);
   }
@@ -538,7 +538,7 @@ void FusedPump::Pump(const BatchRef& first) {
       scan->EnsureHostVectors(ref);
       for (int32_t wi = pc.window0; wi < pc.window1; wi++) {
         scan->BuildChunk(ref, wi, &storage, &chunk);
-        local->buffer->Append(chunk);
+        TimedAppend(*local->buffer, chunk);
       }
       if (pc.closes_group) FlushHost();
     }

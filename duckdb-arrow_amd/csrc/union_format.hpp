@@ -93,7 +93,7 @@ MI_UNION_FN Row RowRule(int member, bool dense, int64_t offset, int64_t member_l
 
 // ---------------------------------------------------------------------------------------------------- the way back
 // A DuckDB UNION vector -> an Arrow SPARSE union with the type ids 0 .. m - 1 (MI_K_ENC_UNION, kernels_encode_union.hip; the
-// writer's staging in writer.cpp and tests/union_encode_cases.py restate it).  The union has no bitmap of its own: a row's
+// writer's staging in chunk_staging.cpp and tests/union_encode_cases.py restate it).  The union has no bitmap of its own: a row's
 // NULL lives in its member.  So the pass writes the type id of every row and, per member, an EFFECTIVE validity mask that the
 // member's own encode task takes for its validity.
 

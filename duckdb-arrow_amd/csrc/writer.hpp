@@ -11,12 +11,14 @@
 // straight into the IPC body layout (every buffer padded to 8 bytes, column_data_collection_serializer.cpp:86-92 ->
 // ArrowIpcEncoderEncodeSimpleRecordBatch) and DMA'd back as one body.
 // The units of this direction:
-//   writer.{hpp,cpp}        chunk staging, the serializer, the stream writer, the C API with its option parser
-//   writer_plan.{hpp,cpp}   body layout, compressed body layout, encode tasks, the pumps' cut rule and batch ledger (host
-//                           code only)
+//   chunk_staging.{hpp,cpp} ChunkCollection: the buffered rows of a row group in DuckDB layout (host code only)
+//   writer.{hpp,cpp}        the serializer, the stream writer
+//   writer_api.cpp          the C API with its option parser
+//   writer_plan.{hpp,cpp}   body layout, device staging layout, compressed body layout, encode tasks, the pumps' cut rule
+//                           and batch ledger (host code only)
 //   writer_compress.cpp     BodyCompressor: the encoded body in HBM -> the LZ4_FRAME body in HBM (COMPRESSION lz4)
 //   copy_pump.cpp           mi_writer_sink_scan: the sink-thread pump and the fused pump of COPY (FROM read_arrow(..))
-//   writer_internal.hpp     struct mi_writer / mi_writer_local, shared by writer.cpp and copy_pump.cpp
+//   writer_internal.hpp     struct mi_writer / mi_writer_local, shared by writer.cpp, writer_api.cpp and copy_pump.cpp
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -30,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "chunk_staging.hpp"
 #include "engine.hpp"
 #include "ipc_format.hpp"
 #include "writer_plan.hpp"
@@ -56,57 +59,6 @@ class BodyCompressor {
   std::vector<DeviceBuffer> retired_device;
   std::vector<PinnedBuffer> retired_pinned;
   CompressedBodyLayout layout;
-};
-
-//! The buffered rows of one future record batch (the reference's local ColumnDataCollection,
-//! write_arrow_stream.cpp:43-52): per FIELD NODE (depth first; a flat column is one node) a pinned staging array in
-//! DuckDB layout.  Nested vectors are flattened while they are appended, the way ArrowAppender walks them: struct and
-//! fixed-size-list children take every parent row, a list's child rows are gathered in list order (NULL lists add none)
-//! and the list node itself stages its list_entry_t rows (the GPU turns their lengths into the int32 Arrow offsets).
-class ChunkCollection {
- public:
-  //! fields as exported (LargeUtf8 / LargeBinary / LargeList nodes get int64 offsets)
-  ChunkCollection(Context* ctx, const std::vector<ArrowField>& fields);
-  void Append(const mi_data_chunk& chunk);
-  void Reset();
-  int64_t Count() const { return count; }
-  int64_t SizeInBytes() const { return size_in_bytes; }
-
-  struct Column {
-    int32_t enc_kind = 0;    // MI_K_ENC_* of a leaf; MI_K_ENC_LIST32 for a list / map; 0 for struct / fixed-size list
-    int32_t arrow_type = 0;  // MI_AT_*
-    int64_t param = 0;       // vector element width (or decimal physical width); fixed_size_list: list size
-    int32_t width = 0;       // bytes per staged row (list: 16 = one list_entry_t)
-    int32_t depth = 0;
-    int64_t count = 0;       // rows buffered in this node
-    PinnedBuffer data;
-    PinnedBuffer validity;        // uint64_t words
-    PinnedBuffer heap;            // payload of long strings (pointer = heap offset)
-    int64_t heap_used = 0;
-    int64_t payload_bytes = 0;    // sum of valid string lengths = size of the Arrow data buffer (list: child rows gathered)
-    bool has_nulls = false;
-    bool large_offsets = false;   // int64 Arrow offsets (arrow_large_buffer_size)
-    // long-string payloads are staged in `heap` and the staged string_t rows point at heap offsets.  When the
-    // source vector declares the allocation its long strings live in (mi_vector.heap: the Arrow data buffer of a scanned
-    // record batch) and they ascend inside it, the bytes from the first to the last long string of an appended slice are
-    // staged with ONE copy; otherwise string by string.  Nothing outside a declared allocation or a string is ever read.
-    std::vector<int32_t> children;
-    bool IsList() const { return arrow_type == MI_AT_LIST || arrow_type == MI_AT_LARGE_LIST || arrow_type == MI_AT_MAP; }
-    bool IsGroup() const { return arrow_type == MI_AT_STRUCT || arrow_type == MI_AT_FIXED_LIST; }
-    bool IsUnion() const { return arrow_type == MI_AT_UNION; }   // stages its tags (width 1); children = the members
-    bool IsNull() const { return arrow_type == MI_AT_NULL; }     // stages nothing but `count`
-  };
-  std::vector<Column> columns;     // every field node, depth first
-  std::vector<int32_t> roots;      // node of top-level column c
-
- private:
-  int32_t AddField(const ArrowField& f, int32_t depth);
-  void AppendNode(int32_t ni, const mi_vector& v, int64_t start, int64_t n);
-  void AppendUnion(int32_t ni, const mi_vector& v, int64_t start, int64_t n);
-  void Reserve(Column& c, int64_t rows, int64_t extra_heap);
-  Context* ctx;
-  int64_t count = 0;
-  int64_t size_in_bytes = 0;
 };
 
 class ColumnDataCollectionSerializer {

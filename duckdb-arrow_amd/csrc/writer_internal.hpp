@@ -1,4 +1,5 @@
-// writer_internal.hpp -- what writer.cpp (C API) and copy_pump.cpp (COPY pumps) share behind include/mi_arrow_ipc.h.
+// writer_internal.hpp -- what writer.cpp, writer_api.cpp (C API) and copy_pump.cpp (COPY pumps) share behind
+// include/mi_arrow_ipc.h.
 #pragma once
 
 #include <functional>
@@ -17,6 +18,10 @@ struct SinkTimers {
   std::mutex mu;  // several sink threads add their stage times
 };
 SinkTimers& Timers();  // writer.cpp
+//! buffer.Append(chunk) under the `append` timer
+void TimedAppend(ChunkCollection& buffer, const mi_data_chunk& chunk);   // writer.cpp
+//! Staging memory of a writer: pinned memory allocated with `ctx`'s device bound
+StagingAllocator PinnedStaging(Context* ctx);   // writer.cpp
 
 // The sink's buffers grow by GrownCapacity -- a quarter of headroom: row groups of one table differ by a few percent, and
 // the outgrown buffer is freed at once, which waits for the device to go idle (with the other sink threads' row groups in

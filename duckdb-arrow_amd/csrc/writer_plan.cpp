@@ -4,6 +4,8 @@
 #include <algorithm>
 #include <cstring>
 
+#include "union_format.hpp"
+
 namespace miarrow {
 
 void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out) {
@@ -54,6 +56,30 @@ void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out) {
     }
   }
   out->body_size = static_cast<int64_t>(body_off);
+}
+
+void LayOutStaging(const std::vector<StagingNode>& nodes, StagingLayout* out) {
+  out->nodes.assign(nodes.size(), StagingLayout::Node{0, 0, 0, 0, 0, 0});
+  size_t at = 0;
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const StagingNode& c = nodes[i];
+    StagingLayout::Node& o = out->nodes[i];
+    const size_t validity_bytes = static_cast<size_t>((c.rows + 63) / 64) * 8;
+    o.data = at;
+    at += RoundUp(static_cast<size_t>(c.rows) * static_cast<size_t>(c.width) + 16, 256);
+    o.validity = at;
+    at += RoundUp(validity_bytes + 8, 256);
+    o.heap = at;
+    at += RoundUp(static_cast<size_t>(c.heap_used) + 16, 256);
+    if (c.is_union) {
+      o.members = at;
+      at += RoundUp(static_cast<size_t>(unionfmt::kMaxMembers) * 8, 256);
+      o.mask_stride = RoundUp(validity_bytes + 8, 256);
+      o.masks = at;
+      at += o.mask_stride * static_cast<size_t>(c.n_members);
+    }
+  }
+  out->total = at;
 }
 
 mi_col_task EncodeTask(const EncodeNode& node, const mi_buffer_span* spans, const EncodeInput& in, uint8_t* body) {

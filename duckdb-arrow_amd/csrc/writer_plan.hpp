@@ -1,7 +1,8 @@
 // writer_plan.hpp -- what the encode direction decides without a GPU, one definition each: where the buffers of a record
-// batch lie in its IPC body, the encode task of a field node, where the COPY pumps end a row group, and which record
-// batches of the scan a pump still holds.  Host code only (no HIP header), so tests/sanitize/writer_plan_check.cpp runs it
-// under AddressSanitizer and ThreadSanitizer.  writer.cpp (serializer) and copy_pump.cpp (both pumps) call it.
+// batch lie in its IPC body, where its staged arrays lie in the device buffer the kernels read, the encode task of a field
+// node, where the COPY pumps end a row group, and which record batches of the scan a pump still holds.  Host code only (no
+// HIP header), so tests/sanitize/writer_plan_check.cpp runs it under AddressSanitizer and ThreadSanitizer.  writer.cpp
+// (serializer) and copy_pump.cpp (both pumps) call it.
 #pragma once
 
 #include <algorithm>
@@ -47,6 +48,28 @@ struct BodyLayout {
 //! interval node (MI_K_ENC_INTERVAL) bitmap + 16 bytes per row; a null node (kEncNodeNull) none at all.
 //! Throws when a node has more than INT32_MAX rows or int32 offsets cannot address its string bytes.
 void LayOutBody(const std::vector<EncodeNode>& nodes, BodyLayout* out);
+
+//! What one field node has staged for the device
+struct StagingNode {
+  int64_t rows = 0;
+  int32_t width = 0;        // bytes per staged row
+  int64_t heap_used = 0;    // bytes of long strings
+  bool is_union = false;
+  int32_t n_members = 0;    // union: its members
+};
+struct StagingLayout {
+  struct Node {
+    size_t data, validity, heap;
+    size_t members, masks, mask_stride;   // union nodes: the addresses of its members' validity words (kMaxMembers of them),
+                                          // and the scratch its pass leaves their masks in, mask k at masks + k * mask_stride
+  };
+  std::vector<Node> nodes;
+  size_t total = 0;
+};
+//! Where the staged arrays of every node lie in the one device buffer the serializer copies them into: nodes depth first,
+//! per node data, validity, heap, then a union's two extras; every array starts on a multiple of 256 and has a few bytes
+//! of slack behind it (the kernels load whole words)
+void LayOutStaging(const std::vector<StagingNode>& nodes, StagingLayout* out);
 
 //! Where the K7 kernels read one node (device addresses)
 struct EncodeInput {

@@ -522,6 +522,54 @@ def group_aggregate_counters():
     return a.value, b.value, c.value, d.value
 
 
+def _hash_check_args(key, max_groups, capacity):
+    """What needs no library: ONE key, 1 <= max_groups <= 2^24 -> (key, max_groups, capacity); capacity None = max_groups"""
+    if isinstance(key, list) or (isinstance(key, tuple) and all(isinstance(k, (str, bytes, tuple, list)) for k in key)):
+        if len(key) != 1:
+            raise MiError(_ffi.MI_ENOTSUP, "hash_aggregate takes ONE key column, not %d: a key of several columns is not one 64-bit word; "
+                                           "group_aggregate takes up to %d key columns for few groups" % (len(key), _ffi.MAX_GROUP_KEYS))
+        key = key[0]
+    if isinstance(max_groups, bool) or not isinstance(max_groups, int) or not 1 <= max_groups <= _ffi.MAX_HASH_GROUPS:
+        raise MiError(_ffi.MI_EINVAL, "hash_aggregate: max_groups must be an int of 1 to %d (MI_MAX_HASH_GROUPS), not %r" % (_ffi.MAX_HASH_GROUPS, max_groups))
+    capacity = max_groups if capacity is None else max(int(capacity), 0)
+    return key, max_groups, capacity
+
+
+def hash_aggregate_vectors(ctx, key, specs, nrows, max_groups, sel_ptr=0, count_ptr=0, capacity=None, stream=0, detail=False):
+    """Hash GROUP BY over resident vectors for many groups (mi_hash_aggregate_vectors).  `key`: ONE column (data_ptr,
+    validity_ptr or 0, width, key_class) with key_class "signed" or "unsigned" ("wide" and "string" are MI_ENOTSUP:
+    group_aggregate_vectors takes them for few groups); `specs`, sel_ptr / count_ptr as aggregate_vectors takes them, without
+    floating-point sums and 16-byte MIN / MAX; `max_groups`: 1 .. 2^24 distinct keys, more is MI_ENOTSUP.  Returns
+    [((key,), [values...]), ...] sorted ascending by key, NULLS LAST; with `detail` every value is a (value, contributing
+    rows) pair.  `capacity` (default max_groups): the groups the result arrays hold."""
+    classes = {"signed": _ffi.GROUP_KEY_CLASS_SIGNED, "unsigned": _ffi.GROUP_KEY_CLASS_UNSIGNED, "wide": _ffi.GROUP_KEY_CLASS_WIDE,
+               "string": _ffi.GROUP_KEY_CLASS_STRING}
+    agg_classes = {"any": _ffi.AGG_CLASS_ANY, "signed": _ffi.AGG_CLASS_SIGNED, "unsigned": _ffi.AGG_CLASS_UNSIGNED,
+                   "float": _ffi.AGG_CLASS_FLOAT, "wide": _ffi.AGG_CLASS_WIDE}
+    key, max_groups, capacity = _hash_check_args(key, max_groups, capacity)
+    checked = _agg_check_specs(specs)
+    data, validity, width, cls = key
+    if cls not in classes:
+        raise MiError(_ffi.MI_EINVAL, "hash_aggregate_vectors: unknown key class %r (one of %s)" % (cls, ", ".join(sorted(classes))))
+    kcol = _ffi.GroupKeyColumn()
+    kcol.data, kcol.validity, kcol.width, kcol.key_class = data or None, validity or None, width, classes[cls]
+    arr, _keep = _agg_vector_specs(checked, agg_classes)
+    out_keys = (_ffi.GroupKeyValue * max(capacity, 1))()
+    out_values = (_ffi.AggValue * max(capacity * len(checked), 1))()
+    n_groups = C.c_int32()
+    _ffi.check(_ffi.lib().mi_hash_aggregate_vectors(ctx._h, C.byref(kcol), arr, len(checked), sel_ptr or None, count_ptr or None, nrows, max_groups,
+                                                    out_keys, out_values, capacity, C.byref(n_groups), C.c_void_p(stream or None)))
+    return _group_rows(out_keys, out_values, n_groups.value, 1, len(checked), [False], detail)
+
+
+def hash_aggregate_counters():
+    """(hash_group_rows launches, hash_group_collect launches, hash_group_rows ms, hash_group_collect ms) of this process; the
+    times are summed over the mi_scan_hash_aggregate / mi_hash_aggregate_vectors calls that ran with MI_AGG_TIMING=1."""
+    a, b, c, d = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    _ffi.check(_ffi.lib().mi_hash_aggregate_counters(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
 def filter_float_key(value, width):
     """The order-preserving integer key the filter kernel compares a FLOAT (width 4) / DOUBLE (width 8) value by."""
     key = C.c_int64()
@@ -1014,6 +1062,29 @@ class Relation:
         if any(t in typed for t in key_types):
             rows = [(tuple(typed[t](v) if t in typed and v is not None else v for t, v in zip(key_types, key)), vals) for key, vals in rows]
         rows = [(key, self._typed_aggregates(checked, vals)) for key, vals in rows]
+        return (rows, scanned.value, selected.value) if detail else rows
+
+    def hash_aggregate(self, key, specs, max_groups, detail=False, capacity=None):
+        """SELECT k, agg_1 .. agg_n ... GROUP BY k over the rows the pushed-down filter keeps, on the GPU, for MANY groups
+        (mi_scan_hash_aggregate): ONE integer-like key column (integers, BOOLEAN, DATE, TIME / TIMESTAMP, DECIMAL(<=18)) and up
+        to `max_groups` (1 .. 2^24) distinct keys; more is MI_ENOTSUP, naming max_groups.  `specs` as aggregate() takes them,
+        without floating-point sums and MIN / MAX of 16-byte columns (MI_ENOTSUP: group_aggregate takes those, several keys,
+        16-byte and string keys, for few groups).  Returns [((key,), [values...]), ...] sorted ascending by key, NULLS LAST.
+        With `detail`: (rows, rows_scanned, rows_selected).  `capacity` (default max_groups): the groups the result arrays hold."""
+        key, max_groups, capacity = _hash_check_args(key, max_groups, capacity)
+        checked = _agg_check_specs(specs)
+        arr, _keep = _agg_scan_specs(checked)
+        out_keys = (_ffi.GroupKeyValue * max(capacity, 1))()
+        out_values = (_ffi.AggValue * max(capacity * len(checked), 1))()
+        n_groups, scanned, selected = C.c_int32(), C.c_int64(), C.c_int64()
+        _ffi.check(_ffi.lib().mi_scan_hash_aggregate(self._h, key.encode() if isinstance(key, str) else key, arr, len(checked), max_groups, out_keys,
+                                                     out_values, capacity, C.byref(n_groups), C.byref(scanned), C.byref(selected)))
+        self._initialised = True
+        rows = _group_rows(out_keys, out_values, n_groups.value, 1, len(checked), [False], False)
+        types = {f["name"]: f["duck_type"] for f in self.fields}
+        if str(types.get(key if isinstance(key, str) else key.decode(), "")).upper() == "BOOLEAN":
+            rows = [(tuple(bool(v) if v is not None else v for v in k), vals) for k, vals in rows]
+        rows = [(k, self._typed_aggregates(checked, vals)) for k, vals in rows]
         return (rows, scanned.value, selected.value) if detail else rows
 
     def progress(self):

@@ -195,6 +195,7 @@ class AggVectorSpec(C.Structure):
 
 
 MAX_GROUP_KEYS, GROUP_WINDOW_LIMIT, MAX_GROUPS = 4, 256, 4096
+MAX_HASH_GROUPS = 1 << 24
 GROUP_KEY_INT128, GROUP_KEY_STRING = 0, 1
 GROUP_KEY_CLASS_SIGNED, GROUP_KEY_CLASS_UNSIGNED, GROUP_KEY_CLASS_WIDE, GROUP_KEY_CLASS_STRING = 1, 2, 3, 4
 
@@ -326,6 +327,11 @@ SIGNATURES = {
     "mi_group_aggregate_vectors": (C.c_int, [P, C.POINTER(GroupKeyColumn), C.c_int32, C.POINTER(AggVectorSpec), C.c_int32, P, P, C.c_int64,
                                              C.POINTER(GroupKeyValue), C.POINTER(AggValue), C.c_int32, C.POINTER(C.c_int32), P]),
     "mi_group_aggregate_counters": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mi_scan_hash_aggregate": (C.c_int, [P, C.c_char_p, C.POINTER(AggSpec), C.c_int32, C.c_int32, C.POINTER(GroupKeyValue), C.POINTER(AggValue),
+                                         C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mi_hash_aggregate_vectors": (C.c_int, [P, C.POINTER(GroupKeyColumn), C.POINTER(AggVectorSpec), C.c_int32, P, P, C.c_int64, C.c_int32,
+                                            C.POINTER(GroupKeyValue), C.POINTER(AggValue), C.c_int32, C.POINTER(C.c_int32), P]),
+    "mi_hash_aggregate_counters": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mi_scan_progress": (C.c_double, [P]),
     "mi_scan_get_stats": (C.c_int, [P, P]),
     "mi_write_options_init": (C.c_int, [C.POINTER(WriteOptions)]),

@@ -545,6 +545,65 @@ int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int
   });
 }
 
+int mi_hash_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* key, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel,
+                              const uint32_t* sel_count, int64_t nrows, int32_t max_groups, mi_group_key_value* out_keys,
+                              mi_agg_value* out_values, int32_t capacity, int32_t* n_groups, void* stream) {
+  return Wrap([&] {
+    if (n_groups) *n_groups = 0;
+    if (!ctx || !key || !aggs || !out_keys || !out_values || !n_groups) throw InvalidInputException("mi_hash_aggregate_vectors: NULL argument");
+    if (n_aggs < 1 || n_aggs > MI_MAX_AGGREGATES)
+      throw InvalidInputException("mi_hash_aggregate_vectors takes 1 to " + std::to_string(MI_MAX_AGGREGATES) + " aggregates, not " + std::to_string(n_aggs));
+    if ((sel == nullptr) != (sel_count == nullptr)) throw InvalidInputException("mi_hash_aggregate_vectors: sel and sel_count go together");
+    if (nrows < 0 || capacity < 0) throw InvalidInputException("mi_hash_aggregate_vectors: negative row count or capacity");
+    CheckHashMaxGroups("mi_hash_aggregate_vectors", max_groups);
+    device::GroupProgram prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_keys = 1;
+    prog.keys[0].data = key->data;
+    prog.keys[0].validity = static_cast<const uint64_t*>(key->validity);
+    prog.keys[0].width = key->width;
+    prog.keys[0].cls = key->key_class;
+    if (key->key_class == MI_GROUP_KEY_CLASS_WIDE || key->key_class == MI_GROUP_KEY_CLASS_STRING) RefuseHashKeyClass("the key column", key->key_class);
+    GroupResult r;
+    r.kinds.push_back(groupkey::kKindInt128);
+    r.key_cls = key->key_class;
+    device::AggExprTable exprs_table;
+    const device::AggExprTable* exprs;
+    VectorProgramOf("mi_hash_aggregate_vectors", aggs, n_aggs, &prog.aggs, &exprs_table, &exprs, &r.classes);
+    std::vector<int32_t> ops;
+    for (int32_t i = 0; i < n_aggs; i++) {
+      ops.push_back(aggs[i].op);
+      RefuseHashAggregate("aggregate " + std::to_string(i), aggs[i].op, r.classes[static_cast<size_t>(i)]);
+    }
+    if (!device::HashGroupProgramIsValid(prog, exprs))
+      throw InvalidInputException("mi_hash_aggregate_vectors: a key class, operation, value class or width that does not fit (key: signed / unsigned of width "
+                                  "1 / 2 / 4 / 8; aggregates as mi_aggregate_vectors takes them, without floating-point sums and 16-byte MIN / MAX)");
+    ctx->ctx->Bind();
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
+    const uint32_t mg = static_cast<uint32_t>(max_groups);
+    DeviceBuffer d_all(HashBufferBytes(mg, n_aggs));
+    ClearHashBuffer(prog, d_all.get(), mg, s);
+    const char* timing = std::getenv("MI_AGG_TIMING");
+    const bool timed = timing && timing[0] == '1';
+    HipEvent begin, end;
+    if (timed) {
+      begin = HipEvent::CreateTimed();
+      end = HipEvent::CreateTimed();
+      MI_HIP_CHECK(hipEventRecord(begin, s));
+    }
+    MI_HIP_CHECK(device::LaunchHashGroupRows(prog, sel, sel_count, nrows, device::HashTableAt(d_all.get(), mg, n_aggs), s, exprs));
+    if (timed) MI_HIP_CHECK(hipEventRecord(end, s));
+    CollectHashGroups(prog, d_all.get(), mg, s, &r);   // (waits for the stream)
+    if (timed && nrows > 0) {
+      float ms = 0;
+      MI_HIP_CHECK(hipEventElapsedTime(&ms, begin, end));
+      AddHashTiming(0, ms);
+    }
+    SortGroups(&r);
+    FillGroupOutputs(r, ops, out_keys, out_values, capacity, n_groups);
+  });
+}
+
 int mi_filter_float_key(double v, int32_t width, int64_t* key) {
   return Wrap([&] {
     if (!key || (width != 4 && width != 8)) throw InvalidInputException("mi_filter_float_key: width must be 4 or 8");

@@ -267,6 +267,39 @@ hipError_t LaunchGroupCombine(const GroupProgram& prog, const GroupWindowsOut& i
 //! launches by this process so far: [0] group_windows, [1] group_combine
 void GroupLaunchCounts(int64_t out[2]);
 
+// K11: hash GROUP BY over decoded vectors for many groups (kernels_hash_group.hip; the rules of the table are
+// hash_group.hpp).  ONE key column of an integer class in prog.keys[0], up to `max_groups` (1 .. hashgroup::kMaxHashGroups)
+// distinct keys in a call, and the aggregates whose merge is exact in any order.
+//! the table in HBM for the whole call (hashgroup::TableBytes bytes): head words, `slots` key words, the records
+struct HashTableDev {
+  uint32_t* head;
+  uint64_t* keys;
+  uint64_t* records;
+  uint32_t slots;       // hashgroup::SlotsFor(max_groups)
+  uint32_t max_groups;
+};
+HashTableDev HashTableAt(void* base, uint32_t max_groups, int n_aggs);
+//! what hash_group_collect writes: the first head[kHeadCollected] (<= max_groups) entries of keys / nulls / partials (n_aggs each)
+struct HashCollectOut {
+  uint64_t* keys;
+  aggmerge::Partial* partials;
+  uint32_t* nulls;
+};
+size_t HashCollectBytes(uint32_t max_groups, int n_aggs);
+HashCollectOut HashCollectAt(void* base, uint32_t max_groups, int n_aggs);
+//! one key column that hashgroup::HashProgramIsValid takes, and a valid aggregate program of the operations it takes
+bool HashGroupProgramIsValid(const GroupProgram& prog, const AggExprTable* exprs = nullptr);
+//! hash_group_clear: every slot free, every record the identity of its operation, the head zero (asynchronous)
+hipError_t LaunchHashGroupClear(const GroupProgram& prog, const HashTableDev& table, hipStream_t stream);
+//! hash_group_rows: every selected row of `nrows` rows finds or claims its key's slot and applies its aggregates to the
+//! slot's records by atomics; sel / sel_count / exprs as LaunchAggWindows takes them
+hipError_t LaunchHashGroupRows(const GroupProgram& prog, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows,
+                               const HashTableDev& table, hipStream_t stream, const AggExprTable* exprs = nullptr);
+//! hash_group_collect: the records in use as dense arrays, in no particular order
+hipError_t LaunchHashGroupCollect(const GroupProgram& prog, const HashTableDev& table, const HashCollectOut& out, hipStream_t stream);
+//! launches by this process so far: [0] hash_group_rows, [1] hash_group_collect
+void HashGroupLaunchCounts(int64_t out[2]);
+
 // K7 launches.  The string / list kernel is a single pass (decoupled look-back across the tiles of a column); it needs
 // 2 * total_tiles + 1 state words (zeroed by the launch).
 // LaunchEncodeFixed: kernel_mask bit 0 = the slice has tiles of encode_fixed, bit 1 = of encode_uuid_text (MI_K_ENC_UUID_TEXT),

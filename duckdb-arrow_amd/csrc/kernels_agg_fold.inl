@@ -1,7 +1,8 @@
 // kernels_agg_fold.inl -- the one place where K9 (kernels_aggregate.hip) and K10 (kernels_group.hip) read a row and fold it:
 // how a validity bit, an integer of any class, a float and a Partial are loaded, the fold of one selected row into a lane's
-// partial (fold_row; fold_expr_row for kOpSumExpr) and the shuffle of a partial for the reduction over a wave.  Included by both
-// files inside their unnamed namespace, behind device_common.hpp, agg_merge.hpp and `using aggmerge::Partial`.  The
+// partial (fold_row; fold_expr_row for kOpSumExpr) and the shuffle of a partial for the reduction over a wave.  K11
+// (kernels_hash_group.hip) reads a row through the same text: it folds the row into an empty partial and sends that to its
+// table by atomics.  Included by these files inside their unnamed namespace, behind device_common.hpp, agg_merge.hpp and `using aggmerge::Partial`.  The
 // arithmetic of a merge, of a factor and of the product is agg_merge.hpp, shared with the host.
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));

@@ -1,7 +1,7 @@
 // scan_aggregate.cpp -- see scan_aggregate.hpp: the fused aggregates of a scan.  The ArrowScan methods here validate the
 // aggregates at bind time (messages name the column and the operation), project exactly the columns they read, give every
-// record batch its two launches behind the filter on the compute stream and read the result back once at the end; the
-// MultiDeviceScan methods merge the devices' results; the C ABI of both calls closes the file.
+// record batch its launches behind the filter on the compute stream and read the result back once at the end; the
+// MultiDeviceScan methods merge the devices' results; the C ABI of the three calls closes the file.
 #include "scan_operator.hpp"
 
 #include <hip/hip_runtime.h>
@@ -383,6 +383,166 @@ void ArrowScan::GroupAggregate(const std::vector<std::string>& keys, const std::
   aggn.keys.clear();
 }
 
+// ------------------------------------------------------------------------------------------------ hash GROUP BY
+// mi_scan_hash_aggregate: the aggregates whose merge is exact in any order per group of ONE integer key, for many groups
+// (K11, kernels_hash_group.hip; the rules are hash_group.hpp).  The table is cleared on the scan's stream in the setup hook,
+// every record batch gets one hash_group_rows behind its filter, and hash_group_collect runs once at the end: the head and
+// exactly the records in use come back, and the host sorts them.
+namespace {
+std::atomic<int64_t> g_hash_events_ns[2];   // MI_AGG_TIMING=1: device time of hash_group_rows / hash_group_collect, nanoseconds
+size_t HashTableBytesAligned(uint32_t max_groups, int n_aggs) { return AlignUp(hashgroup::TableBytes(max_groups, n_aggs)); }
+bool AggTimingOn() {
+  const char* timing = std::getenv("MI_AGG_TIMING");
+  return timing && timing[0] == '1';
+}
+}  // namespace
+
+void HashTimingTotals(double out_ms[2]) {
+  out_ms[0] = static_cast<double>(g_hash_events_ns[0].load()) * 1e-6;
+  out_ms[1] = static_cast<double>(g_hash_events_ns[1].load()) * 1e-6;
+}
+
+void AddHashTiming(int which, double ms) { g_hash_events_ns[which] += static_cast<int64_t>(ms * 1e6); }
+
+void RefuseHashKeyClass(const std::string& who, int32_t key_cls) {
+  if (key_cls == groupkey::kKeySigned || key_cls == groupkey::kKeyUnsigned) return;
+  if (key_cls != groupkey::kKeyWide && key_cls != groupkey::kKeyString)   // FLOAT / DOUBLE, INTERVAL, nested ...: no grouped call takes these
+    throw NotImplementedException("hash GROUP BY on " + who + " stays above the scan: the key is one integer, BOOLEAN, DATE, TIME / TIMESTAMP or DECIMAL(<=18) column");
+  const char* what = key_cls == groupkey::kKeyWide ? "a 16-byte key" : "a VARCHAR / BLOB key";
+  throw NotImplementedException("hash GROUP BY on " + who + ": " + what + " is not one 64-bit word -- the key is one integer, BOOLEAN, DATE, TIME / TIMESTAMP or "
+                                "DECIMAL(<=18) column; mi_scan_group_aggregate takes " + what + " for few groups");
+}
+
+void RefuseHashAggregate(const std::string& who, int32_t op, int32_t cls) {
+  const bool sums = op == aggmerge::kOpSum || op == aggmerge::kOpSumProduct || op == aggmerge::kOpSumExpr;
+  if (sums && cls == aggmerge::kClassFloat)
+    throw NotImplementedException(std::string(AggOpName(op)) + " on " + who + ": the hash GROUP BY adds in arrival order, so a floating-point sum would differ from run "
+                                  "to run; mi_scan_group_aggregate keeps it bit-reproducible for few groups");
+  if ((op == aggmerge::kOpMin || op == aggmerge::kOpMax) && cls == aggmerge::kClassWide)
+    throw NotImplementedException(std::string(AggOpName(op)) + " on " + who + ": there is no 128-bit atomic, so MIN / MAX of a 16-byte column is not taken by the hash "
+                                  "GROUP BY; mi_scan_group_aggregate takes it for few groups");
+}
+
+void CheckHashMaxGroups(const char* api, int64_t max_groups) {
+  if (max_groups < 1 || max_groups > static_cast<int64_t>(hashgroup::kMaxHashGroups))
+    throw InvalidInputException(std::string(api) + ": max_groups must be 1 to " + std::to_string(hashgroup::kMaxHashGroups) + " (MI_MAX_HASH_GROUPS), not " + std::to_string(max_groups));
+}
+
+size_t HashBufferBytes(uint32_t max_groups, int n_aggs) { return HashTableBytesAligned(max_groups, n_aggs) + device::HashCollectBytes(max_groups, n_aggs); }
+
+void ClearHashBuffer(const device::GroupProgram& prog, void* d_buf, uint32_t max_groups, hipStream_t stream) {
+  MI_HIP_CHECK(device::LaunchHashGroupClear(prog, device::HashTableAt(d_buf, max_groups, prog.aggs.n_aggs), stream));
+}
+
+void CollectHashGroups(const device::GroupProgram& prog, void* d_buf, uint32_t max_groups, hipStream_t stream, GroupResult* out) {
+  const int n_aggs = prog.aggs.n_aggs;
+  const device::HashTableDev table = device::HashTableAt(d_buf, max_groups, n_aggs);
+  const device::HashCollectOut rec = device::HashCollectAt(static_cast<uint8_t*>(d_buf) + HashTableBytesAligned(max_groups, n_aggs), max_groups, n_aggs);
+  const bool timed = AggTimingOn();
+  HipEvent begin, end;
+  if (timed) {
+    begin = HipEvent::CreateTimed();
+    end = HipEvent::CreateTimed();
+    MI_HIP_CHECK(hipEventRecord(begin, stream));
+  }
+  MI_HIP_CHECK(device::LaunchHashGroupCollect(prog, table, rec, stream));
+  if (timed) MI_HIP_CHECK(hipEventRecord(end, stream));
+  uint32_t head[hashgroup::kHeadWords];
+  MI_HIP_CHECK(hipMemcpyAsync(head, table.head, sizeof(head), hipMemcpyDeviceToHost, stream));
+  MI_HIP_CHECK(hipStreamSynchronize(stream));
+  if (timed) {
+    float ms = 0;
+    MI_HIP_CHECK(hipEventElapsedTime(&ms, begin, end));
+    AddHashTiming(1, ms);
+  }
+  const uint32_t status = head[hashgroup::kHeadStatus];
+  if (status & MI_ST_GROUP_LIMIT)
+    throw NotImplementedException("hash GROUP BY found more than max_groups = " + std::to_string(max_groups) + " distinct keys among the selected rows: call again with a larger "
+                                  "max_groups (at most " + std::to_string(hashgroup::kMaxHashGroups) + ")");
+  ThrowForStatus(status);
+  const size_t n = std::min<size_t>(head[hashgroup::kHeadCollected], max_groups);
+  if (n == 0) return;
+  std::vector<uint64_t> keys(n);
+  std::vector<uint32_t> nulls(n);
+  const size_t v0 = out->values.size();
+  out->values.resize(v0 + n * static_cast<size_t>(n_aggs));
+  MI_HIP_CHECK(hipMemcpyAsync(keys.data(), rec.keys, n * 8, hipMemcpyDeviceToHost, stream));
+  MI_HIP_CHECK(hipMemcpyAsync(nulls.data(), rec.nulls, n * 4, hipMemcpyDeviceToHost, stream));
+  MI_HIP_CHECK(hipMemcpyAsync(out->values.data() + v0, rec.partials, n * static_cast<size_t>(n_aggs) * sizeof(aggmerge::Partial), hipMemcpyDeviceToHost, stream));
+  MI_HIP_CHECK(hipStreamSynchronize(stream));
+  const int key_cls = prog.keys[0].cls;
+  out->keys.reserve(out->keys.size() + n);
+  for (size_t g = 0; g < n; g++) {
+    groupkey::Key k;
+    std::memset(&k, 0, sizeof(k));
+    k.nulls = nulls[g] ? 1u : 0u;
+    if (!k.nulls) {
+      k.lo[0] = keys[g];
+      k.hi[0] = hashgroup::KeyHigh(key_cls, keys[g]);
+    }
+    out->keys.push_back(k);
+  }
+}
+
+void ArrowScan::HashAggregate(const std::string& key, const std::vector<AggSpec>& specs, uint32_t max_groups, GroupResult* out) {
+  if (initialized) throw InvalidInputException("mi_scan_hash_aggregate replaces mi_scan_init / mi_scan_next: call it right after bind");
+  CheckHashMaxGroups("mi_scan_hash_aggregate", max_groups);
+  Bind();
+  std::vector<std::string> proj;
+  aggn.keys.clear();
+  *out = GroupResult();
+  const ScanColumn& c = AggregateColumn(key, "GROUP BY");
+  AggregateState::KeyBound kb;
+  kb.cls = GroupKeyClassOf(c);
+  RefuseHashKeyClass("column '" + key + "' (" + c.field.DuckType() + ")", kb.cls);
+  kb.col = SlotOf(&proj, key);
+  out->kinds.push_back(groupkey::kKindInt128);
+  out->key_cls = kb.cls;
+  try {
+    BindAggregateSpecs(specs, "mi_scan_hash_aggregate", &proj);
+    for (size_t a = 0; a < aggn.aggs.size(); a++) {
+      const AggregateState::Bound& b = aggn.aggs[a];
+      if (b.col_a < 0) continue;   // COUNT(*)
+      const std::string& name = proj[static_cast<size_t>(b.col_a)];
+      const ScanColumn& ac = AggregateColumn(name, AggOpName(b.op));
+      RefuseHashAggregate("column '" + name + "' (" + ac.field.DuckType() + ")", b.op, b.cls);
+    }
+    aggn.keys.push_back(kb);
+    aggn.hash_max_groups = max_groups;
+    const int n_aggs = static_cast<int>(aggn.aggs.size());
+    device::GroupProgram shape;   // what the clear and the collect read of a program: the operations and classes
+    std::memset(&shape, 0, sizeof(shape));
+    shape.n_keys = 1;
+    shape.keys[0].cls = kb.cls;
+    shape.aggs.n_aggs = n_aggs;
+    for (int a = 0; a < n_aggs; a++) {
+      shape.aggs.aggs[a].op = aggn.aggs[static_cast<size_t>(a)].op;
+      shape.aggs.aggs[a].a.cls = aggn.aggs[static_cast<size_t>(a)].cls;
+    }
+    std::atomic<int64_t> batch_ns[2];   // [0] hash_group_rows; [1] the empty interval behind it, which is nobody's time
+    batch_ns[0] = 0;
+    batch_ns[1] = 0;
+    const int64_t selected = DrainAggregates(proj, [&] {
+      aggn.d_hash = DeviceBuffer(HashBufferBytes(max_groups, n_aggs));
+      ClearHashBuffer(shape, aggn.d_hash.get(), max_groups, ctx->stream);   // on the scan's own stream, never the null stream
+    }, batch_ns);
+    g_hash_events_ns[0] += batch_ns[0].load();
+    for (auto& b : aggn.aggs) out->classes.push_back(b.cls);
+    CollectHashGroups(shape, aggn.d_hash.get(), max_groups, ctx->stream, out);
+    SortGroups(out);
+    out->rows_scanned = aggn.rows_scanned;
+    out->rows_selected = selected;
+  } catch (...) {
+    aggn.keys.clear();
+    aggn.hash_max_groups = 0;
+    aggn.d_hash = DeviceBuffer();
+    throw;
+  }
+  aggn.keys.clear();
+  aggn.hash_max_groups = 0;
+  aggn.d_hash = DeviceBuffer();
+}
+
 // ---- per record batch: the programs over the slot's decoded vectors, then the two launches
 bool ArrowScan::FillAggregatePrograms(const Slot& s, device::GroupProgram* gprog, device::AggExprTable* exprs) const {
   auto column = [&](int32_t c, const void** data, const uint64_t** validity, int32_t* width) {
@@ -440,6 +600,14 @@ void ArrowScan::EnqueueAggregates(Slot& s) {
     aggn.events.push_back(HipEvent::CreateTimed());
     MI_HIP_CHECK(hipEventRecord(aggn.events.back(), ctx->stream));
   };
+  if (aggn.hash_max_groups != 0) {   // K11: one launch; the stamps keep DrainAggregates' three-per-batch shape
+    stamp();
+    MI_HIP_CHECK(device::LaunchHashGroupRows(gprog, sel, sel_count, n, device::HashTableAt(aggn.d_hash.get(), aggn.hash_max_groups, prog.n_aggs), ctx->stream, exprs));
+    stamp();
+    stamp();
+    aggn.rows_scanned += n;
+    return;
+  }
   if (!aggn.keys.empty()) {
     const size_t bytes = device::GroupWindowsBytes(n_windows, gprog.n_keys, prog.n_aggs);
     Retire(Grow(aggn.d_windows, bytes, GrownCapacity(bytes, aggn.d_windows.size(), 1 << 16)));
@@ -497,6 +665,42 @@ void MultiDeviceScan::GroupAggregate(const std::vector<std::string>& keys, const
   }
   for (size_t g = 0; g < table.size(); g++) {
     out->keys.push_back(table.key(g));
+    out->values.insert(out->values.end(), table.partials(g), table.partials(g) + n_aggs);
+  }
+  SortGroups(out);
+}
+
+void MultiDeviceScan::HashAggregate(const std::string& key, const std::vector<AggSpec>& specs, uint32_t max_groups, GroupResult* out) {
+  CheckHashMaxGroups("mi_scan_hash_aggregate", max_groups);
+  std::vector<GroupResult> parts(subs.size());
+  ForEachParallel([&](size_t i) { subs[i]->HashAggregate(key, specs, max_groups, &parts[i]); });
+  // sub-scan order, group by group, through the serial model of the device's table (hashgroup::SerialTable)
+  *out = GroupResult();
+  out->kinds = parts[0].kinds;
+  out->classes = parts[0].classes;
+  std::vector<int> ops, classes(out->classes.begin(), out->classes.end());
+  for (const AggSpec& sp : specs) ops.push_back(sp.op);
+  hashgroup::SerialTable table(max_groups, ops, classes);
+  const size_t n_aggs = specs.size();
+  for (auto& p : parts) {
+    for (size_t g = 0; g < p.keys.size(); g++)
+      if (!table.Merge(p.keys[g].lo[0], (p.keys[g].nulls & 1u) != 0, &p.values[g * n_aggs]))
+        throw NotImplementedException("hash GROUP BY found more than max_groups = " + std::to_string(max_groups) + " distinct keys among the selected rows of the "
+                                      "devices together: call again with a larger max_groups");
+    out->rows_scanned += p.rows_scanned;
+    out->rows_selected += p.rows_selected;
+  }
+  const int key_cls = parts[0].key_cls;   // (one column, one class: every sub-scan bound the same)
+  out->key_cls = key_cls;
+  for (size_t g = 0; g < table.size(); g++) {
+    groupkey::Key k;
+    std::memset(&k, 0, sizeof(k));
+    k.nulls = table.is_null(g) ? 1u : 0u;
+    if (!k.nulls) {
+      k.lo[0] = table.key(g);
+      k.hi[0] = hashgroup::KeyHigh(key_cls, k.lo[0]);
+    }
+    out->keys.push_back(k);
     out->values.insert(out->values.end(), table.partials(g), table.partials(g) + n_aggs);
   }
   SortGroups(out);
@@ -607,6 +811,29 @@ int mi_scan_group_aggregate(mi_scan* s, const char* const* key_columns, int32_t 
 
 int mi_group_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, double* windows_ms, double* combine_ms) {
   return Counters(device::GroupLaunchCounts, GroupTimingTotals, window_launches, combine_launches, windows_ms, combine_ms);
+}
+
+int mi_scan_hash_aggregate(mi_scan* s, const char* key_column, const mi_agg_spec* aggs, int32_t n_aggs, int32_t max_groups,
+                           mi_group_key_value* out_keys, mi_agg_value* out_values, int32_t capacity, int32_t* n_groups, int64_t* rows_scanned,
+                           int64_t* rows_selected) {
+  return WrapC([&] {
+    if (n_groups) *n_groups = 0;
+    if (!s || !key_column || !aggs || !out_keys || !out_values || !n_groups) throw InvalidInputException("mi_scan_hash_aggregate: NULL argument");
+    if (capacity < 0) throw InvalidInputException("mi_scan_hash_aggregate: negative capacity");
+    CheckHashMaxGroups("mi_scan_hash_aggregate", max_groups);
+    const std::vector<AggSpec> specs = SpecsOf("mi_scan_hash_aggregate", aggs, n_aggs);
+    GroupResult r;
+    ScanOf(s)->HashAggregate(key_column, specs, static_cast<uint32_t>(max_groups), &r);
+    std::vector<int32_t> ops;
+    for (const AggSpec& sp : specs) ops.push_back(sp.op);
+    FillGroupOutputs(r, ops, out_keys, out_values, capacity, n_groups);
+    if (rows_scanned) *rows_scanned = r.rows_scanned;
+    if (rows_selected) *rows_selected = r.rows_selected;
+  });
+}
+
+int mi_hash_aggregate_counters(int64_t* rows_launches, int64_t* collect_launches, double* rows_ms, double* collect_ms) {
+  return Counters(device::HashGroupLaunchCounts, HashTimingTotals, rows_launches, collect_launches, rows_ms, collect_ms);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// scan_aggregate.hpp -- the host side of the fused aggregates (mi_scan_aggregate, mi_scan_group_aggregate; K9 and K10):
+// scan_aggregate.hpp -- the host side of the fused aggregates (mi_scan_aggregate, mi_scan_group_aggregate,
+// mi_scan_hash_aggregate; K9, K10 and K11):
 // what a call is given by column name, what it returns, and the helpers the vector calls of c_api.cpp share with it.
 // scan_aggregate.cpp holds the ArrowScan / MultiDeviceScan methods that bind, enqueue and drain them, and their C ABI.
 #pragma once
@@ -12,8 +13,13 @@
 #include "../../include/mi_arrow_ipc.h"
 #include "agg_merge.hpp"
 #include "group_key.hpp"
+#include "hash_group.hpp"
 
 namespace miarrow {
+
+namespace device {
+struct GroupProgram;   // kernels.hpp
+}
 
 //! One aggregate of mi_scan_aggregate by column name, and what a draining call returns: the accumulators, the value class
 //! each is merged by (aggmerge::kClass*: what the host's merge of several devices needs), the rows seen
@@ -45,6 +51,7 @@ struct AggResult {
 struct GroupResult {
   std::vector<int32_t> kinds;
   std::vector<int32_t> classes;
+  int32_t key_cls = 0;       // mi_scan_hash_aggregate alone: groupkey::kKey* of its one key column
   std::vector<groupkey::Key> keys;
   std::vector<aggmerge::Partial> values;
   int64_t rows_scanned = 0, rows_selected = 0;
@@ -57,6 +64,23 @@ void SortGroups(GroupResult* r);
 //! a sorted result as the C ABI returns it; more groups than `capacity` is MI_EINVAL with *n_groups set
 void FillGroupOutputs(const GroupResult& r, const std::vector<int32_t>& ops, mi_group_key_value* out_keys, mi_agg_value* out_values,
                       int32_t capacity, int32_t* n_groups);
+
+// ---- K11, the hash GROUP BY for many groups (mi_scan_hash_aggregate, mi_hash_aggregate_vectors; hash_group.hpp).  Its result
+// is a GroupResult with one INT128 key part.
+//! MI_ENOTSUP for a key class the hash table does not take (16-byte and string keys: K10 takes them for few groups), and
+//! for an aggregate whose merge is not exact in any order (a floating-point sum) or has no atomic (a 16-byte MIN / MAX);
+//! `who` names the column
+void RefuseHashKeyClass(const std::string& who, int32_t key_cls);
+void RefuseHashAggregate(const std::string& who, int32_t op, int32_t cls);
+//! MI_EINVAL unless 1 <= max_groups <= MI_MAX_HASH_GROUPS
+void CheckHashMaxGroups(const char* api, int64_t max_groups);
+//! the bytes of one call's device buffer: the table (hashgroup::TableBytes), then what hash_group_collect writes
+size_t HashBufferBytes(uint32_t max_groups, int n_aggs);
+//! hash_group_clear over such a buffer (asynchronous)
+void ClearHashBuffer(const device::GroupProgram& prog, void* d_buf, uint32_t max_groups, hipStream_t stream);
+//! hash_group_collect, then the head and exactly the records in use copied back: throws for the MI_ST_* bits the head carries
+//! (MI_ST_GROUP_LIMIT with a message that names max_groups) and appends the groups to out->keys / out->values, unsorted
+void CollectHashGroups(const device::GroupProgram& prog, void* d_buf, uint32_t max_groups, hipStream_t stream, GroupResult* out);
 
 //! a finished accumulator as the C ABI returns it (mi_scan_aggregate, mi_aggregate_vectors)
 inline void FillAggValue(int32_t op, int32_t cls, const aggmerge::Partial& p, mi_agg_value* v) {
@@ -79,5 +103,9 @@ const char* AggOpName(int32_t op);
 //! and of group_windows / group_combine over its calls of mi_scan_group_aggregate
 void AggTimingTotals(double out_ms[2]);
 void GroupTimingTotals(double out_ms[2]);
+//! ... and of hash_group_rows / hash_group_collect over its calls of mi_scan_hash_aggregate and mi_hash_aggregate_vectors
+void HashTimingTotals(double out_ms[2]);
+//! adds one timed launch to those totals: which = 0 hash_group_rows, 1 hash_group_collect
+void AddHashTiming(int which, double ms);
 
 }  // namespace miarrow

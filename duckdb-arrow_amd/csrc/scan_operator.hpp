@@ -186,6 +186,8 @@ class ScanBase {
   virtual void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) = 0;
   //! mi_scan_group_aggregate: the groups of this scan, sorted
   virtual void GroupAggregate(const std::vector<std::string>& keys, const std::vector<AggSpec>& specs, GroupResult* out) = 0;
+  //! mi_scan_hash_aggregate: the groups of this scan by one integer key, up to `max_groups` of them, sorted
+  virtual void HashAggregate(const std::string& key, const std::vector<AggSpec>& specs, uint32_t max_groups, GroupResult* out) = 0;
   virtual double Progress() = 0;
   virtual void Stats(mi_scan_stats* out) = 0;   // adds to *out
 };
@@ -220,6 +222,8 @@ class ArrowScan : public ScanBase {
   void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) override;
   //! the same aggregates per group of up to 4 key columns, for few groups (mi_scan_group_aggregate)
   void GroupAggregate(const std::vector<std::string>& keys, const std::vector<AggSpec>& specs, GroupResult* out) override;
+  //! the aggregates whose merge is exact in any order per group of ONE integer key, for many groups (mi_scan_hash_aggregate)
+  void HashAggregate(const std::string& key, const std::vector<AggSpec>& specs, uint32_t max_groups, GroupResult* out) override;
 
   // ---- batch-level pull (what Next() is built on; the COPY pump and the multi-device scan use it directly) ----
   //! Waits for the next record batch in order; false when the scan is exhausted.  The batch stays valid (its slot is
@@ -395,6 +399,8 @@ class ArrowScan : public ScanBase {
     };
     std::vector<KeyBound> keys;              // mi_scan_group_aggregate: not empty
     DeviceBuffer d_table;                    // K10's scan-wide table (device::GroupTableAt): lives as long as the call
+    uint32_t hash_max_groups = 0;            // mi_scan_hash_aggregate: not 0, and `keys` holds its one key
+    DeviceBuffer d_hash;                     // K11's table and collect arrays (HashBufferBytes): lives as long as the call
     DeviceBuffer d_windows;                  // what group_windows writes for the record batch in flight (device::GroupWindowsAt)
     DeviceBuffer d_acc;                      // aggmerge::Partial per aggregate: lives as long as the call
     DeviceBuffer d_partials;                 // partials[window][aggregate] of the record batch in flight (one stream: in order)
@@ -403,7 +409,7 @@ class ArrowScan : public ScanBase {
     std::vector<HipEvent> events;            // timed: {before agg_windows, between, after agg_combine} per record batch
   } aggn;
   // (the methods from here to DrainAggregates are scan_aggregate.cpp's)
-  //! agg_windows + agg_combine (with keys: group_windows + group_combine) over the slot's decoded vectors and selection
+  //! agg_windows + agg_combine (with keys: group_windows + group_combine, or hash_group_rows) over the slot's decoded vectors and selection
   //! vectors, behind the filter on the compute stream
   void EnqueueAggregates(Slot& s);
   //! aggn over the slot's decoded vectors as the launches take it: the aggregates, the keys when there are any, and -- the
@@ -459,6 +465,7 @@ class MultiDeviceScan : public ScanBase {
                   const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, mi_sum_product_result* out) override;
   void Aggregate(const std::vector<AggSpec>& specs, AggResult* out) override;
   void GroupAggregate(const std::vector<std::string>& keys, const std::vector<AggSpec>& specs, GroupResult* out) override;
+  void HashAggregate(const std::string& key, const std::vector<AggSpec>& specs, uint32_t max_groups, GroupResult* out) override;
   double Progress() override;
   void Stats(mi_scan_stats* out) override;
 

@@ -377,7 +377,7 @@ typedef struct mi_col_task {
                                    * base_stream_reader.cpp:24-29) */
 #define MI_ST_BAD_RUN_ENDS 512u   /* run ends not positive and strictly increasing, or short of the array (FULL validation) */
 #define MI_ST_SEL_RANGE 1024u     /* aggregates: a selection index names no row of its 2048-row window (skipped, never read) */
-#define MI_ST_GROUP_LIMIT 2048u   /* GROUP BY: more than MI_GROUP_WINDOW_LIMIT distinct keys in a window or MI_MAX_GROUPS in a scan */
+#define MI_ST_GROUP_LIMIT 2048u   /* GROUP BY: more than MI_GROUP_WINDOW_LIMIT distinct keys in a window or MI_MAX_GROUPS in a scan; hash GROUP BY: more than max_groups */
 #define MI_ST_GROUP_KEY_LONG 4096u /* GROUP BY: a selected row's VARCHAR / BLOB key is longer than 12 bytes */
 #define MI_ST_BAD_UNION_TAG 8192u  /* union: a type id is negative or names no member ("Arrow union tag out of range") */
 #define MI_ST_BAD_UNION_OFFSET 16384u /* dense union: an offset is negative or past its member array (FULL validation) */
@@ -1112,6 +1112,45 @@ int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int
 /* Debug and measurement facility, the counterpart of mi_aggregate_counters: launches of group_windows / group_combine by this
  * process so far, and their device time summed over the calls of mi_scan_group_aggregate that ran with MI_AGG_TIMING=1. */
 int mi_group_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, double* windows_ms, double* combine_ms);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Hash GROUP BY for MANY groups (an ABI extension, beside mi_scan_group_aggregate, which keeps its limits):
+ *   SELECT k, agg_1 .. agg_n FROM scan WHERE <the filter that was set> GROUP BY k
+ * with ONE key column, 1 <= n <= MI_MAX_AGGREGATES and up to `max_groups` (1 .. MI_MAX_HASH_GROUPS) distinct keys among the
+ * selected rows (`group by l_orderkey`, `l_suppkey`, `l_partkey`).  The groups live in a hash table in HBM that every
+ * workgroup inserts into with atomics; its size is a function of max_groups and n alone:
+ *   slots = max(64, the power of two >= 2 * max_groups);   bytes = 32 + 8 * slots + 24 * (slots + 2) * n
+ * plus max_groups * (12 + 32 * n) bytes for the collected result (max_groups = 2^24, n = 1: 1 GiB and 0.7 GiB).
+ * The key is a top-level column the scan decodes to an integer-like vector of 1 / 2 / 4 / 8 bytes (the integers, BOOLEAN as
+ * its byte, DATE, TIME / TIMESTAMP, DECIMAL(<=18)); rows whose key is NULL form one group.  MI_ENOTSUP, naming the column and
+ * pointing at mi_scan_group_aggregate, which takes them for few groups: a 16-byte key (HUGEINT, DECIMAL(19..38), UUID) and a
+ * VARCHAR / BLOB key; MI_ENOTSUP as in mi_scan_group_aggregate: FLOAT / DOUBLE, nested, dictionary-encoded, union and constant
+ * key columns.  (Several key columns are not expressible in this call.)
+ * The aggregates are those of mi_scan_aggregate with their classes, NULL rule (count == 0) and arithmetic, restricted to the
+ * ones whose merge is exact in any order: COUNT(*), COUNT, SUM / SUM_PRODUCT / SUM_EXPR over integer-like columns (128-bit,
+ * wrapping), MIN / MAX over columns of 1 .. 8 bytes, FLOAT / DOUBLE included (canonical bits).  MI_ENOTSUP with the column's
+ * name: a floating-point SUM / SUM_PRODUCT / SUM_EXPR (the table adds in arrival order: the sum would differ from run to
+ * run) and MIN / MAX of a 16-byte column (there is no 128-bit atomic).
+ * More distinct keys than max_groups: MI_ENOTSUP with a message that names max_groups.  The result is as
+ * mi_scan_group_aggregate's with n_keys = 1: one row per group that has a selected row, keys of kind MI_GROUP_KEY_INT128,
+ * ascending, NULLS LAST -- a function of the data alone.  More groups than `capacity`: *n_groups is set and the call fails
+ * with MI_EINVAL.  Call right after bind; the call projects its columns itself, honours the filter that was set, ignores
+ * mi_scan_options.filter_compact and drains the scan.  With rank / world every rank returns its share's groups; a
+ * multi-device scan merges its devices' group lists itself by key, in device order (max_groups bounds the merged list too). */
+#define MI_MAX_HASH_GROUPS 16777216
+int mi_scan_hash_aggregate(mi_scan* s, const char* key_column, const mi_agg_spec* aggs, int32_t n_aggs, int32_t max_groups,
+                           mi_group_key_value* out_keys /* [capacity] */, mi_agg_value* out_values /* [capacity * n_aggs] */,
+                           int32_t capacity, int32_t* n_groups, int64_t* rows_scanned, int64_t* rows_selected);
+/* The kernel-level entry, the counterpart of mi_group_aggregate_vectors, with the same sel / sel_count contract (counts
+ * clamped; an index past its window skipped, MI_EINVAL through MI_ST_SEL_RANGE).  `key`: one column of class
+ * MI_GROUP_KEY_CLASS_SIGNED / _UNSIGNED; the two 16-byte classes are MI_ENOTSUP. */
+int mi_hash_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* key, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel,
+                              const uint32_t* sel_count, int64_t nrows, int32_t max_groups, mi_group_key_value* out_keys,
+                              mi_agg_value* out_values, int32_t capacity, int32_t* n_groups, void* stream);
+/* Debug and measurement facility, the counterpart of mi_group_aggregate_counters: launches of hash_group_rows /
+ * hash_group_collect by this process so far, and their device time summed over the calls of mi_scan_hash_aggregate and
+ * mi_hash_aggregate_vectors that ran with MI_AGG_TIMING=1. */
+int mi_hash_aggregate_counters(int64_t* rows_launches, int64_t* collect_launches, double* rows_ms, double* collect_ms);
 
 #ifdef __cplusplus
 }

@@ -105,11 +105,12 @@ void AggTimingTotals(double out_ms[2]) {
 const ScanColumn& ArrowScan::AggregateColumn(const std::string& name, const std::string& what) const {
   auto it = std::find_if(all_columns.begin(), all_columns.end(), [&](const ScanColumn& sc) { return sc.name == name; });
   if (it == all_columns.end()) throw InvalidInputException(what + ": Field '" + name + "' does not exist in IPC file schema");
-  if (it->is_constant()) throw NotImplementedException(what + " on the constant column '" + name + "' is not computed in the scan");
+  const std::string typed = "'" + name + "' (" + it->field.DuckType() + ")";   // every refusal names the column and its DuckDB type
+  if (it->is_constant()) throw NotImplementedException(what + " on the constant column " + typed + " is not computed in the scan");
   std::string why;
-  if (!it->field.Supported(&why)) throw NotImplementedException("Column '" + name + "': " + why + " is not decoded by the MI355X scan path yet");
+  if (!it->field.Supported(&why)) throw NotImplementedException(what + " on column " + typed + ": " + why + " is not decoded by the MI355X scan path yet");
   if (it->field.has_dictionary || ValueField(it->field).has_dictionary)
-    throw NotImplementedException(what + " on the dictionary-encoded column '" + name + "' is not computed in the scan");
+    throw NotImplementedException(what + " on the dictionary-encoded column " + typed + " is not computed in the scan");
   // a union's vector is a tag vector over member vectors: no aggregate (COUNT included) and no GROUP BY key reads that tree
   if (it->field.type == MI_AT_UNION)
     throw NotImplementedException(what + " on the union column '" + name + "' (" + it->field.DuckType() + ") is not computed in the scan");
@@ -174,7 +175,7 @@ void ArrowScan::BindAggregateSpecs(const std::vector<AggSpec>& specs, const char
       const bool sums = sp.op == aggmerge::kOpSum || sp.op == aggmerge::kOpSumProduct;
       if (b.cls == aggmerge::kClassAny || (sums && b.cls == aggmerge::kClassWide))
         throw NotImplementedException(std::string(AggOpName(sp.op)) + " on column '" + sp.a + "' (" + ca.field.DuckType() + "): SUM takes integers, DATE, TIME / "
-                                      "TIMESTAMP, DECIMAL(<=18), FLOAT and DOUBLE columns, MIN / MAX those and HUGEINT / DECIMAL(19..38)");
+                                      "TIMESTAMP, DECIMAL(<=18), FLOAT and DOUBLE columns, MIN / MAX those and HUGEINT / DECIMAL(19..38) / UUID");
       if (sp.op == aggmerge::kOpSumProduct) {
         const ScanColumn& cb = FactorColumn(sp.b, sp.op, &b.cls_b);
         SameFamily(sp.op, ca, b.cls, cb, b.cls_b);
@@ -276,7 +277,7 @@ int32_t GroupKeyClassOf(const ScanColumn& c) {
     case FilterValueClass::kWide: return groupkey::kKeyWide;
     default: break;
   }
-  if (IsStringKind(kind)) return groupkey::kKeyString;
+  if (IsStringKind(kind) || kind == MI_K_STRVIEW) return groupkey::kKeyString;   // (a decoded string view is a string_t row as the others are)
   if (kind == MI_K_BOOL || kind == MI_K_BOOL8) return groupkey::kKeyUnsigned;
   if (IsIntegerLike(kind, w, vf, /*allow_bool*/ false)) return vf.type == MI_AT_INT && !vf.is_signed ? groupkey::kKeyUnsigned : groupkey::kKeySigned;
   return 0;
@@ -359,7 +360,7 @@ void ArrowScan::GroupAggregate(const std::vector<std::string>& keys, const std::
     kb.cls = GroupKeyClassOf(c);
     if (kb.cls == 0)
       throw NotImplementedException("GROUP BY on column '" + name + "' (" + c.field.DuckType() + ") stays above the scan: a key is an integer, BOOLEAN, DATE, TIME / "
-                                    "TIMESTAMP, DECIMAL, HUGEINT, VARCHAR or BLOB column");
+                                    "TIMESTAMP, DECIMAL, HUGEINT, UUID, VARCHAR or BLOB column");
     kb.col = SlotOf(&proj, name);
     aggn.keys.push_back(kb);
     out->kinds.push_back(groupkey::KindOfClass(kb.cls));

@@ -1060,13 +1060,14 @@ int mi_aggregate_counters(int64_t* window_launches, int64_t* combine_launches, d
  * a general hash aggregate.  The aggregates, their classes, their NULL rule and their arithmetic are exactly those of
  * mi_scan_aggregate, per group.
  * Key columns are top-level columns the scan decodes to an integer-like vector of 1 / 2 / 4 / 8 bytes (the integers, BOOLEAN
- * as its byte, DATE, TIME / TIMESTAMP, DECIMAL(<=18)), to a 16-byte integer (HUGEINT, DECIMAL(19..38)) or to VARCHAR / BLOB.
+ * as its byte, DATE, TIME / TIMESTAMP, DECIMAL(<=18)), to a 16-byte integer (HUGEINT, DECIMAL(19..38), UUID) or to VARCHAR /
+ * BLOB (utf8 / binary with 32- or 64-bit offsets, fixed-size binary, string views).
  * Every key value is normalised to 16 bytes plus a NULL bit: integers sign- or zero-extended to 128 bits; a string to its
  * inline image (uint32 length, then the bytes, the padding behind them masked to zero by the kernel).  A string key of
  * more than 12 bytes in a selected row makes the call fail with MI_ENOTSUP ("a VARCHAR / BLOB group key longer than 12
  * bytes stays above the scan"); rows the filter dropped are never looked at.  A NULL key is a value of its own (NULLs group
  * together, the bytes under a NULL are ignored); '' and NULL differ, 'a' and 'a\0' differ.
- * MI_ENOTSUP at bind, naming the column: FLOAT / DOUBLE, INTERVAL, nested, string-view, dictionary-encoded and constant
+ * MI_ENOTSUP at bind, naming the column and its type: FLOAT / DOUBLE, INTERVAL, nested, dictionary-encoded and constant
  * (filename / hive) key columns.  MI_EINVAL: no key or more than MI_MAX_GROUP_KEYS, a key column named twice, an unknown
  * column.  More groups than a limit allows: MI_ENOTSUP ("GROUP BY with more than ... groups stays above the scan").
  * The result is one row per group that has a selected row (a group whose every aggregate is NULL included), sorted

@@ -428,36 +428,62 @@ void VectorExprOf(const char* api, const mi_agg_vector_spec& spec, device::AggDe
   }
 }
 
-//! the vector specs of the call `api` as the launchers take them: prog (zeroed by the caller), the expressions of its
-//! SUM_EXPR aggregates in *table with *exprs pointing at it (else NULL), and each aggregate's class appended to `classes` (when given)
-void VectorProgramOf(const char* api, const mi_agg_vector_spec* aggs, int32_t n_aggs, device::AggProgram* prog, device::AggExprTable* table,
-                     const device::AggExprTable** exprs, std::vector<int32_t>* classes) {
-  auto column = [](const mi_agg_column& c) {
-    device::AggColumnDev d;
-    d.data = c.data;
-    d.validity = static_cast<const uint64_t*>(c.validity);
-    d.width = c.width;
-    d.cls = c.value_class;
-    return d;
-  };
-  prog->n_aggs = n_aggs;
-  *exprs = nullptr;
-  for (int32_t i = 0; i < n_aggs; i++) {
-    device::AggDescDev& d = prog->aggs[i];
-    d.op = aggs[i].op;
-    if (aggs[i].op == MI_AGG_SUM_EXPR) {
-      if (!*exprs) {
-        std::memset(table, 0, sizeof(*table));
-        *exprs = table;
-      }
-      VectorExprOf(api, aggs[i], &d, &table->exprs[i]);
-    } else {
-      d.a = column(aggs[i].a);
-      d.b = column(aggs[i].b);
-    }
-    if (classes) classes->push_back(d.a.cls);
+//! What a vector call makes of its arguments: the program as the launchers take it (exprs: NULL without a SUM_EXPR), each
+//! aggregate's operation, and the result with its kinds and classes
+struct VectorCall {
+  device::GroupProgram prog = {};
+  device::AggExprTable table;
+  const device::AggExprTable* exprs = nullptr;
+  std::vector<int32_t> ops;
+  GroupResult r;
+
+  void Key(const mi_group_key_column& c, int32_t kind) {
+    device::GroupKeyColumnDev& k = prog.keys[prog.n_keys++];
+    k.data = c.data;
+    k.validity = static_cast<const uint64_t*>(c.validity);
+    k.width = c.width;
+    k.cls = c.key_class;
+    r.kinds.push_back(kind);
   }
-}
+  //! the vector specs of the call `api` names in its messages; what is left to check is the *ProgramIsValid of its kernels
+  void Aggregates(const char* api, const mi_agg_vector_spec* aggs, int32_t n_aggs) {
+    auto column = [](const mi_agg_column& c) {
+      device::AggColumnDev d;
+      d.data = c.data;
+      d.validity = static_cast<const uint64_t*>(c.validity);
+      d.width = c.width;
+      d.cls = c.value_class;
+      return d;
+    };
+    prog.aggs.n_aggs = n_aggs;
+    for (int32_t i = 0; i < n_aggs; i++) {
+      device::AggDescDev& d = prog.aggs.aggs[i];
+      d.op = aggs[i].op;
+      if (aggs[i].op == MI_AGG_SUM_EXPR) {
+        if (!exprs) {
+          std::memset(&table, 0, sizeof(table));
+          exprs = &table;
+        }
+        VectorExprOf(api, aggs[i], &d, &table.exprs[i]);
+      } else {
+        d.a = column(aggs[i].a);
+        d.b = column(aggs[i].b);
+      }
+      ops.push_back(d.op);
+      r.classes.push_back(d.a.cls);
+    }
+  }
+  //! the call's one batch through a run of `mode` (what the scan gives every record batch): the groups come out sorted
+  void Run(mi_ctx* ctx, AggMode mode, uint32_t max_groups, bool count_time, const mi_sel_t* sel, const uint32_t* sel_count, int64_t nrows, void* stream) {
+    ctx->ctx->Bind();
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
+    AggRun run(mode, prog.n_keys, r.key_cls, ops, r.classes, max_groups, count_time);
+    run.Begin(s);
+    run.Batch(prog, exprs, sel, sel_count, nrows, s);
+    run.Finish(s, &r);
+    if (prog.n_keys) SortGroups(&r);
+  }
+};
 }  // namespace
 
 int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_aggs, const mi_sel_t* sel, const uint32_t* sel_count,
@@ -468,33 +494,13 @@ int mi_aggregate_vectors(mi_ctx* ctx, const mi_agg_vector_spec* aggs, int32_t n_
       throw InvalidInputException("mi_aggregate_vectors takes 1 to " + std::to_string(MI_MAX_AGGREGATES) + " aggregates, not " + std::to_string(n_aggs));
     if ((sel == nullptr) != (sel_count == nullptr)) throw InvalidInputException("mi_aggregate_vectors: sel and sel_count go together");
     if (nrows < 0) throw InvalidInputException("mi_aggregate_vectors: negative row count");
-    device::AggProgram prog;
-    std::memset(&prog, 0, sizeof(prog));
-    device::AggExprTable exprs_table;
-    const device::AggExprTable* exprs;
-    VectorProgramOf("mi_aggregate_vectors", aggs, n_aggs, &prog, &exprs_table, &exprs, nullptr);
-    if (!device::AggProgramIsValid(prog, exprs))
+    VectorCall v;
+    v.Aggregates("mi_aggregate_vectors", aggs, n_aggs);
+    if (!device::AggProgramIsValid(v.prog.aggs, v.exprs))
       throw InvalidInputException("mi_aggregate_vectors: an operation, value class or width that does not fit (SUM takes integers of width 1 / 2 / 4 / 8 "
                                   "or floats of width 4 / 8, MIN / MAX also width 16, a product two integers or two floats)");
-    ctx->ctx->Bind();
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
-    const int64_t n_windows = (nrows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
-    const size_t n = static_cast<size_t>(n_aggs);
-    DeviceBuffer d_partials((static_cast<size_t>(n_windows) * n + n) * sizeof(aggmerge::Partial));   // [window][aggregate], then the accumulators
-    aggmerge::Partial* partials = d_partials.get<aggmerge::Partial>();
-    aggmerge::Partial* acc = partials + static_cast<size_t>(n_windows) * n;
-    MI_HIP_CHECK(hipMemsetAsync(acc, 0, n * sizeof(aggmerge::Partial), s));
-    MI_HIP_CHECK(device::LaunchAggWindows(prog, sel, sel_count, nrows, partials, s, exprs));
-    MI_HIP_CHECK(device::LaunchAggCombine(prog, partials, n_windows, acc, s, exprs));
-    std::vector<aggmerge::Partial> host(n);
-    MI_HIP_CHECK(hipMemcpyAsync(host.data(), acc, n * sizeof(aggmerge::Partial), hipMemcpyDeviceToHost, s));
-    MI_HIP_CHECK(hipStreamSynchronize(s));
-    uint32_t flags = 0;
-    for (size_t i = 0; i < n; i++) {
-      FillAggValue(prog.aggs[i].op, prog.aggs[i].a.cls, host[i], &out[i]);
-      flags |= static_cast<uint32_t>(host[i].flags);
-    }
-    ThrowForStatus(flags);
+    v.Run(ctx, AggMode::kPlain, 0, /*count_time*/ false, sel, sel_count, nrows, stream);
+    for (size_t i = 0; i < v.ops.size(); i++) FillAggValue(v.ops[i], v.r.classes[i], v.r.values[i], &out[i]);
   });
 }
 
@@ -510,38 +516,14 @@ int mi_group_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* keys, int
       throw InvalidInputException("mi_group_aggregate_vectors takes 1 to " + std::to_string(MI_MAX_AGGREGATES) + " aggregates, not " + std::to_string(n_aggs));
     if ((sel == nullptr) != (sel_count == nullptr)) throw InvalidInputException("mi_group_aggregate_vectors: sel and sel_count go together");
     if (nrows < 0 || capacity < 0) throw InvalidInputException("mi_group_aggregate_vectors: negative row count or capacity");
-    device::GroupProgram prog;
-    std::memset(&prog, 0, sizeof(prog));
-    prog.n_keys = n_keys;
-    GroupResult r;
-    for (int32_t k = 0; k < n_keys; k++) {
-      prog.keys[k].data = keys[k].data;
-      prog.keys[k].validity = static_cast<const uint64_t*>(keys[k].validity);
-      prog.keys[k].width = keys[k].width;
-      prog.keys[k].cls = keys[k].key_class;
-      r.kinds.push_back(groupkey::KindOfClass(keys[k].key_class));
-    }
-    device::AggExprTable exprs_table;
-    const device::AggExprTable* exprs;
-    VectorProgramOf("mi_group_aggregate_vectors", aggs, n_aggs, &prog.aggs, &exprs_table, &exprs, &r.classes);
-    std::vector<int32_t> ops;
-    for (int32_t i = 0; i < n_aggs; i++) ops.push_back(aggs[i].op);
-    if (!device::GroupProgramIsValid(prog, exprs))
+    VectorCall v;
+    for (int32_t k = 0; k < n_keys; k++) v.Key(keys[k], groupkey::KindOfClass(keys[k].key_class));
+    v.Aggregates("mi_group_aggregate_vectors", aggs, n_aggs);
+    if (!device::GroupProgramIsValid(v.prog, v.exprs))
       throw InvalidInputException("mi_group_aggregate_vectors: a key class, operation, value class or width that does not fit (keys: signed / unsigned of width "
                                   "1 / 2 / 4 / 8, wide or string of width 16; aggregates as mi_aggregate_vectors takes them)");
-    ctx->ctx->Bind();
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
-    const int64_t n_windows = (nrows + MI_VECTOR_SIZE - 1) / MI_VECTOR_SIZE;
-    const size_t table_bytes = (device::GroupTableBytes(n_keys, n_aggs) + 15) & ~static_cast<size_t>(15);
-    DeviceBuffer d_all(table_bytes + device::GroupWindowsBytes(n_windows, n_keys, n_aggs) + 16);   // the table, then the windows' records
-    const device::GroupTableDev table = device::GroupTableAt(d_all.get(), n_keys, n_aggs);
-    const device::GroupWindowsOut win = device::GroupWindowsAt(d_all.get() + table_bytes, n_windows, n_keys, n_aggs);
-    MI_HIP_CHECK(device::GroupTableClear(d_all.get(), n_keys, n_aggs, s));
-    MI_HIP_CHECK(device::LaunchGroupWindows(prog, sel, sel_count, nrows, win, s, exprs));
-    MI_HIP_CHECK(device::LaunchGroupCombine(prog, win, n_windows, table, s, exprs));
-    ReadGroupTable(d_all.get(), n_keys, n_aggs, s, &r);
-    SortGroups(&r);
-    FillGroupOutputs(r, ops, out_keys, out_values, capacity, n_groups);
+    v.Run(ctx, AggMode::kGrouped, 0, /*count_time*/ false, sel, sel_count, nrows, stream);
+    FillGroupOutputs(v.r, v.ops, out_keys, out_values, capacity, n_groups);
   });
 }
 
@@ -556,51 +538,17 @@ int mi_hash_aggregate_vectors(mi_ctx* ctx, const mi_group_key_column* key, const
     if ((sel == nullptr) != (sel_count == nullptr)) throw InvalidInputException("mi_hash_aggregate_vectors: sel and sel_count go together");
     if (nrows < 0 || capacity < 0) throw InvalidInputException("mi_hash_aggregate_vectors: negative row count or capacity");
     CheckHashMaxGroups("mi_hash_aggregate_vectors", max_groups);
-    device::GroupProgram prog;
-    std::memset(&prog, 0, sizeof(prog));
-    prog.n_keys = 1;
-    prog.keys[0].data = key->data;
-    prog.keys[0].validity = static_cast<const uint64_t*>(key->validity);
-    prog.keys[0].width = key->width;
-    prog.keys[0].cls = key->key_class;
     if (key->key_class == MI_GROUP_KEY_CLASS_WIDE || key->key_class == MI_GROUP_KEY_CLASS_STRING) RefuseHashKeyClass("the key column", key->key_class);
-    GroupResult r;
-    r.kinds.push_back(groupkey::kKindInt128);
-    r.key_cls = key->key_class;
-    device::AggExprTable exprs_table;
-    const device::AggExprTable* exprs;
-    VectorProgramOf("mi_hash_aggregate_vectors", aggs, n_aggs, &prog.aggs, &exprs_table, &exprs, &r.classes);
-    std::vector<int32_t> ops;
-    for (int32_t i = 0; i < n_aggs; i++) {
-      ops.push_back(aggs[i].op);
-      RefuseHashAggregate("aggregate " + std::to_string(i), aggs[i].op, r.classes[static_cast<size_t>(i)]);
-    }
-    if (!device::HashGroupProgramIsValid(prog, exprs))
+    VectorCall v;
+    v.Key(*key, groupkey::kKindInt128);
+    v.r.key_cls = key->key_class;
+    v.Aggregates("mi_hash_aggregate_vectors", aggs, n_aggs);
+    for (int32_t i = 0; i < n_aggs; i++) RefuseHashAggregate("aggregate " + std::to_string(i), aggs[i].op, v.r.classes[static_cast<size_t>(i)]);
+    if (!device::HashGroupProgramIsValid(v.prog, v.exprs))
       throw InvalidInputException("mi_hash_aggregate_vectors: a key class, operation, value class or width that does not fit (key: signed / unsigned of width "
                                   "1 / 2 / 4 / 8; aggregates as mi_aggregate_vectors takes them, without floating-point sums and 16-byte MIN / MAX)");
-    ctx->ctx->Bind();
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->ctx->stream;
-    const uint32_t mg = static_cast<uint32_t>(max_groups);
-    DeviceBuffer d_all(HashBufferBytes(mg, n_aggs));
-    ClearHashBuffer(prog, d_all.get(), mg, s);
-    const char* timing = std::getenv("MI_AGG_TIMING");
-    const bool timed = timing && timing[0] == '1';
-    HipEvent begin, end;
-    if (timed) {
-      begin = HipEvent::CreateTimed();
-      end = HipEvent::CreateTimed();
-      MI_HIP_CHECK(hipEventRecord(begin, s));
-    }
-    MI_HIP_CHECK(device::LaunchHashGroupRows(prog, sel, sel_count, nrows, device::HashTableAt(d_all.get(), mg, n_aggs), s, exprs));
-    if (timed) MI_HIP_CHECK(hipEventRecord(end, s));
-    CollectHashGroups(prog, d_all.get(), mg, s, &r);   // (waits for the stream)
-    if (timed && nrows > 0) {
-      float ms = 0;
-      MI_HIP_CHECK(hipEventElapsedTime(&ms, begin, end));
-      AddHashTiming(0, ms);
-    }
-    SortGroups(&r);
-    FillGroupOutputs(r, ops, out_keys, out_values, capacity, n_groups);
+    v.Run(ctx, AggMode::kHash, static_cast<uint32_t>(max_groups), /*count_time*/ true, sel, sel_count, nrows, stream);
+    FillGroupOutputs(v.r, v.ops, out_keys, out_values, capacity, n_groups);
   });
 }
 

@@ -16,6 +16,7 @@
 #include <cstring>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // __forceinline__
 #define MI_KEY_FN __host__ __device__ __forceinline__
 #else
 #define MI_KEY_FN inline

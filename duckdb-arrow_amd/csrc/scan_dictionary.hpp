@@ -11,6 +11,7 @@
 
 #include "batch_slice.hpp"
 #include "engine.hpp"
+#include "scan_column.hpp"
 
 namespace miarrow {
 
@@ -41,8 +42,6 @@ struct DictState : DictHostValues {
   int32_t kind = 0, out_width = 0;
   std::map<size_t, std::shared_ptr<void>> match_maps;   // filter leaf -> device byte per entry: 0 no, 1 yes, 2 NULL
 };
-
-inline bool IsStringKind(int32_t kind) { return kind == MI_K_STR32 || kind == MI_K_STR64 || kind == MI_K_FIXED_BINARY; }
 
 //! The value kinds a dictionary may have: its values are decoded as ONE flat task, so value types that need more than
 //! {validity, buffer 1, buffer 2} (string views: a table of variadic buffers; lists / structs: child nodes) are not among them

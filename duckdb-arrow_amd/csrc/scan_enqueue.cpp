@@ -210,12 +210,12 @@ void ArrowScan::RefuseAbsentAggregateColumns(const Source& src) const {
     if (c >= 0 && src.out_to_file_column[static_cast<size_t>(c)] < 0)
       throw InvalidInputException("aggregate column '" + out_columns[static_cast<size_t>(c)].name + "' is absent from a file of the scan");
   };
-  for (const auto& a : aggn.aggs) {
+  for (const auto& a : aggn.plan.aggs) {
     present(a.col_a);
     present(a.col_b);
     for (const auto& f : a.factors) present(f.col);
   }
-  for (const auto& k : aggn.keys)
+  for (const auto& k : aggn.plan.keys)
     if (src.out_to_file_column[static_cast<size_t>(k.col)] < 0)
       throw InvalidInputException("GROUP BY column '" + out_columns[static_cast<size_t>(k.col)].name + "' is absent from a file of the scan");
 }

@@ -24,17 +24,6 @@
 
 namespace miarrow {
 
-FilterValueClass FilterClassOf(const ArrowField& field) {
-  const ArrowField& vf = ValueField(field);
-  int32_t kind, w;
-  int64_t param;
-  if (!vf.Plan(&kind, &param, &w, /*value_only*/ true)) return FilterValueClass::kOther;
-  if (vf.type == MI_AT_FLOAT && (w == 4 || w == 8)) return w == 4 ? FilterValueClass::kFloat32 : FilterValueClass::kFloat64;
-  if (vf.type == MI_AT_DECIMAL && kind == MI_K_COPY && w == 16) return FilterValueClass::kWide;
-  if (kind == MI_K_UUID) return FilterValueClass::kWide;   // hugeint_t whose signed order is the order of the text
-  return FilterValueClass::kOther;
-}
-
 namespace {
 using wide_t = __int128;
 constexpr wide_t kWideMax = static_cast<wide_t>(~static_cast<unsigned __int128>(0) >> 1), kWideMin = -kWideMax - 1;

@@ -15,8 +15,9 @@
 //   scan_readahead.{hpp,cpp}   ReadAhead: producer threads, their queues and pinned staging buffers (host code only)
 //   scan_filter.cpp            pushed-down predicates: normalisation, binding to the scan's columns, constants in HBM,
 //                              the per-batch FilterProgram
-//   scan_aggregate.{hpp,cpp}   the fused aggregates (mi_scan_aggregate, mi_scan_group_aggregate): their types, the methods
-//                              below that bind, enqueue and drain them, their C ABI
+//   scan_column.hpp            ScanColumn and what its Arrow field says about its values (host code only)
+//   scan_aggregate.{hpp,cpp}   the fused aggregates: the methods below that enqueue and drain them, their C ABI, over the
+//                              units agg_bind (host code only), agg_result (host code only) and agg_run
 //   scan_enqueue.cpp           what a record batch costs the GPU: stage A and stage B of ArrowScan as named steps, the K8
 //                              staging, the helpers both stages share
 //   scan_k8.{hpp,cpp}          the K8 scratch arena as data: layout, pinned tables, launch arguments (host code only)
@@ -44,26 +45,6 @@
 #include "scan_readahead.hpp"
 
 namespace miarrow {
-
-struct ScanColumn {
-  std::string name;
-  ArrowField field;           // arrow field of the first file that has it
-  bool is_filename = false;   // `filename` option (README.md:104-107)
-  bool is_hive = false;       // hive partition key
-  std::string hive_key;
-  //! one value per file, made on the host: never read from a file, decoded or filtered on the GPU
-  bool is_constant() const { return is_filename || is_hive; }
-};
-
-//! a run-end encoded column is filtered on its flat vector: what matters is the field of its values
-inline const ArrowField& ValueField(const ArrowField& f) { return f.type == MI_AT_RUN_END && f.children.size() == 2 ? f.children[1] : f; }
-//! Columns a range comparison / the fused aggregate reads as integers: integers, DATE, TIME / TIMESTAMP, DECIMAL(<= 18)
-//! -- and booleans where `allow_bool` -- by their transcode plan
-inline bool IsIntegerLike(int32_t kind, int32_t width, const ArrowField& f, bool allow_bool) {
-  return (kind == MI_K_COPY || kind == MI_K_DEC128 || kind == MI_K_DATE64 || kind == MI_K_MUL_I32 || kind == MI_K_MUL_I64 ||
-          kind == MI_K_DIV_I64 || kind == MI_K_NARROW || (allow_bool && (kind == MI_K_BOOL || kind == MI_K_BOOL8))) &&
-         (width == 1 || width == 2 || width == 4 || width == 8) && f.type != MI_AT_FLOAT;
-}
 
 //! One leaf of a pushed-down predicate after normalisation (scan_filter.cpp): every comparison on an integer-like column
 //! is an inclusive range (optionally negated), plus IS [NOT] NULL and IN-lists.
@@ -101,9 +82,6 @@ using FilterCnf = std::vector<std::vector<FilterLeaf>>;
 FilterCnf NormaliseFilter(const mi_filter_node* nodes, int32_t n_nodes, int32_t root, const std::vector<ScanColumn>* columns = nullptr);  // scan_filter.cpp
 //! what likematch::Compile answered -> nothing, or the refusal mi_scan_set_filter and mi_filter_like_match share (`column` may be empty)
 void CheckPattern(int compiled, int32_t op, const std::string& column);
-//! what a column's values are compared as by a pushed-down filter
-enum class FilterValueClass { kOther, kFloat32, kFloat64, kWide };
-FilterValueClass FilterClassOf(const ArrowField& field);
 
 //! A pushed-down filter bound to the columns of a scan (ArrowScan::Init)
 struct BoundFilter {
@@ -380,50 +358,22 @@ class ArrowScan : public ScanBase {
     DeviceBuffer d_acc;                    // unsigned long long {sum lo, sum hi, rows selected}
     int64_t rows_scanned = 0;
   } agg;
-  // fused aggregates (mi_scan_aggregate): a state of its own beside `agg`
+  // fused aggregates (mi_scan_aggregate and its grouped forms): a state of its own beside `agg`
   struct AggregateState {
     bool on = false;
-    struct Bound {
-      int32_t op = 0, cls = 0;
-      int32_t col_a = -1, col_b = -1;        // output columns
-      int32_t cls_b = 0;
-      struct Factor {
-        int32_t col = -1, cls = 0;             // output column (-1: a constant), its class
-        uint64_t mul = 0, add = 0;             // as device::AggFactorDev takes them
-      };
-      std::vector<Factor> factors;             // kOpSumExpr; col_a is then the first column factor's column
-    };
-    std::vector<Bound> aggs;
-    struct KeyBound {
-      int32_t col = -1, cls = 0;             // output column, groupkey::kKey*
-    };
-    std::vector<KeyBound> keys;              // mi_scan_group_aggregate: not empty
-    DeviceBuffer d_table;                    // K10's scan-wide table (device::GroupTableAt): lives as long as the call
-    uint32_t hash_max_groups = 0;            // mi_scan_hash_aggregate: not 0, and `keys` holds its one key
-    DeviceBuffer d_hash;                     // K11's table and collect arrays (HashBufferBytes): lives as long as the call
-    DeviceBuffer d_windows;                  // what group_windows writes for the record batch in flight (device::GroupWindowsAt)
-    DeviceBuffer d_acc;                      // aggmerge::Partial per aggregate: lives as long as the call
-    DeviceBuffer d_partials;                 // partials[window][aggregate] of the record batch in flight (one stream: in order)
+    BoundAggregates plan;                    // what the call reads, over the slots of its projection = the output columns
     int64_t rows_scanned = 0;
-    bool timed = false;                      // MI_AGG_TIMING=1: HIP events around every launch
-    std::vector<HipEvent> events;            // timed: {before agg_windows, between, after agg_combine} per record batch
+    std::unique_ptr<AggRun> run;             // the device side: lives as long as the call
   } aggn;
   // (the methods from here to DrainAggregates are scan_aggregate.cpp's)
-  //! agg_windows + agg_combine (with keys: group_windows + group_combine, or hash_group_rows) over the slot's decoded vectors and selection
-  //! vectors, behind the filter on the compute stream
+  //! the driver of the three calls: DrainAggregates, then the run's read-back; *out is sorted when the plan has keys
+  void RunAggregates(BoundAggregates plan, GroupResult* out);
+  //! the run's launches over the slot's decoded vectors and selection vectors, behind the filter on the compute stream
   void EnqueueAggregates(Slot& s);
-  //! aggn over the slot's decoded vectors as the launches take it: the aggregates, the keys when there are any, and -- the
-  //! return value tells -- the expressions of the kOpSumExpr aggregates
+  //! aggn.plan over the slot's decoded vectors as the launches take it; true: `exprs` holds the kOpSumExpr aggregates' expressions
   bool FillAggregatePrograms(const Slot& s, device::GroupProgram* gprog, device::AggExprTable* exprs) const;
-  //! bind-time validation shared by Aggregate and GroupAggregate: a column an aggregate (or GROUP BY, `what`) may read
-  const ScanColumn& AggregateColumn(const std::string& name, const std::string& what) const;
-  //! ... and a factor of SUM_PRODUCT / SUM_EXPR (`op`): such a column of a class a product takes, which goes to *cls
-  const ScanColumn& FactorColumn(const std::string& name, int32_t op, int32_t* cls) const;
-  //! validates `specs` into aggn.aggs and adds the columns they read to `proj`
-  void BindAggregateSpecs(const std::vector<AggSpec>& specs, const char* api, std::vector<std::string>* proj);
-  //! runs the scan over `proj` with aggn.on: `begin` after Init (allocates the accumulators), then every record batch;
-  //! returns the selected rows once the stream is idle and adds the launches' device time to `timing_ns` (MI_AGG_TIMING=1)
-  int64_t DrainAggregates(const std::vector<std::string>& proj, const std::function<void()>& begin, std::atomic<int64_t>* timing_ns);
+  //! runs the scan over aggn.plan.projection with aggn.on: the run's Begin after Init, then every record batch; returns the selected rows
+  int64_t DrainAggregates();
   // constant columns (filename / hive): 2048 string_t each per source, host
   std::map<std::pair<int32_t, size_t>, std::vector<mi_string_t>> const_vectors;
   std::mutex const_mu;
